@@ -8,10 +8,16 @@ on synthetic 800x800 ray batches.  Workload at every N: BASELINE.json configs[1]
 `sample_pavillon_16` model, carried as a data fixture, random-init fallback if absent).
 
   python bench.py --gpus 1 --steps 30 --warmup 5
+  python bench.py --gpus 1 --steps 30 --warmup 5 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (see README / DESIGN.md for the field meanings).
+Rank 0 prints ONE JSON line (see README / DESIGN.md for the field meanings).  A plain run sets up, warms up, times
+--steps steps and prints the line (at N > 1 the render-only phase A stays: it is the line's fallback if the exchange
+hangs).  --full also runs every measurement beside the headline: the CPU baseline and the quality check against the
+oracle, the sustained-MFMA probe, the speed / exact / guarded / split-frame modes and, at N > 1, the per-rank MFMA probe
+and the alternative exchange paths; each can still be left out with its --no-* option.  --dump-outputs DIR writes what
+the last timed step computed (rank 0): rgba.npy [h,w,4] and, without an exchange, rgb.npy [h,w,3], both float32.
 """
 import argparse
 import json
@@ -168,6 +174,25 @@ def cpu_baseline(model_dir, w, h, pose, rot, budget_s=10.0):
             "sample": "%d of %d image rows (%d rays, %.2f samples/ray) of the same frame in %.1f s: %d processes x %d threads, "
                       "numpy + %s fp32, %d host cores available" % (rows_done, h, rows_done * w, spp, wall, P, T, backend, avail)}, \
         res, (row0, rows), O.psnr
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, h, w, **arrays):
+    """--dump-outputs: each array ([h*w, C] or [h, w, C]) as out_dir/<name>.npy, float32, shape [h, w, C].  Should the total exceed
+    64 MB, every array keeps the same fixed, seeded sample of pixels instead ([k, C]), and pixel_index.npy says which."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float32).reshape(h * w, -1) for k, v in arrays.items()}
+    per_pixel = sum(a.shape[1] for a in arrays.values()) * 4
+    if per_pixel * h * w > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(h * w, size=(DUMP_MAX_BYTES - 4096) // (per_pixel + 8), replace=False))      # (4 KB: .npy headers)
+        np.save(os.path.join(out_dir, "pixel_index.npy"), idx.astype(np.float64))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+    else:
+        arrays = {k: a.reshape(h, w, -1) for k, a in arrays.items()}
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
 
 
 def free_port():
@@ -372,6 +397,8 @@ def run_peer(args):
         per_dev[v // P] += st.total_samples / max(frames, 1)
     if args.dump_image:
         np.save(args.dump_image, image.numpy().reshape(h, w, 4))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, h, w, rgba=image.numpy())
     mean_s = sum(per_dev) / len(per_dev)
     rec = {"metric": "FPS at %dx%d" % (w, h), "value": args.steps / dt, "unit": "frames/s", "n_gpus": n, "steps": args.steps, "warmup": args.warmup,
            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": args.precision,
@@ -434,7 +461,17 @@ def main():
     ap.add_argument("--watchdog", type=float, default=float(os.environ.get("ADANERF_BENCH_WATCHDOG_S", "600")),
                     help="seconds after which a run that is stuck (a collective that never returns) prints the line it has and exits; 0: off")
     ap.add_argument("--dump-image", default=None, help="rank 0 writes the last frame's RGBA8 image [h,w,4] as .npy (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as DIR/<name>.npy in float32: rgba [h,w,4] (the assembled frame) and, "
+                         "without an exchange, rgb [h,w,3]; the inputs are the same from run to run, so two builds can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline (CPU baseline + quality check, sustained-MFMA probe, speed / exact / "
+                         "guarded / split-frame modes; N > 1: per-rank MFMA probe, alternative exchange paths).  Off: the run does only what "
+                         "the headline needs")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_sustained_probe = args.no_speed_mode = args.no_exact_mode = True
+        args.no_guarded_mode = args.no_split_mode = args.no_alternatives = True
     if args.sampling is None:
         args.sampling = "split"      # DESIGN 1, the default rule: exact by construction unless guarded is >= 8 % faster in this very run (4-5 %)
 
@@ -843,6 +880,11 @@ def main():
 
     if rank == 0 and args.dump_image:
         np.save(args.dump_image, (images[state["last"]] if use_dist else outs[0][0][:h * w]).cpu().numpy().reshape(h, w, 4))
+    if rank == 0 and args.dump_outputs:      # what the last timed step computed, before any extra measurement renders again
+        if use_dist:
+            dump_outputs(args.dump_outputs, h, w, rgba=images[state["last"]].cpu().numpy())
+        else:
+            dump_outputs(args.dump_outputs, h, w, rgba=outs[0][0][:h * w].cpu().numpy(), rgb=rgb[:h * w].cpu().numpy())
 
     ms_per_step = dt / args.steps * 1e3
     fps = args.steps / dt

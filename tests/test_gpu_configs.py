@@ -270,6 +270,26 @@ def test_bench_rccl_branch_world_size_one(tmp_path):
     assert np.array_equal(np.load(one), np.load(dist1))
 
 
+def test_bench_plain_run_dumps_the_last_timed_frame(tmp_path):
+    """A plain bench line (no --full) times exactly --steps steps and measures nothing beside the headline; --dump-outputs writes the
+    last timed frame: rgba.npy = the RGBA8 frame --dump-image writes, rgb.npy its float colours.  A second run writes the same arrays."""
+    dumps = []
+    for k in range(2):
+        img, d = str(tmp_path / ("img%d.npy" % k)), str(tmp_path / ("out%d" % k))
+        p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1", "--dump-image", img, "--dump-outputs", d],
+                           cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        rec = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+        assert rec["steps"] == 4 and rec["ms_per_step"] > 0 and abs(rec["value"] * rec["ms_per_step"] - 1e3) < 1e-6
+        assert rec["cpu_baseline"] is None and rec["guarded_mode"] is None and rec["speed_mode"] is None and rec["split_frame_mode"] is None
+        assert "sustained_peak" not in rec["roofline"]
+        rgba, rgb = np.load(os.path.join(d, "rgba.npy")), np.load(os.path.join(d, "rgb.npy"))
+        assert rgba.dtype == rgb.dtype == np.float32 and rgba.shape == (800, 800, 4) and rgb.shape == (800, 800, 3)
+        assert np.array_equal(rgba, np.load(img).astype(np.float32)) and np.isfinite(rgb).all()
+        dumps.append((rgba, rgb))
+    assert all(np.array_equal(a, b) for a, b in zip(*dumps))
+
+
 # ---------------------------------------------------------------------------------------------
 # secondary outputs of the compositing step (depth_map = sum w z, acc_map = sum w)
 # ---------------------------------------------------------------------------------------------

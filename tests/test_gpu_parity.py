@@ -1366,7 +1366,8 @@ def test_bench_dry_run_and_per_rank_diagnostics(tmp_path):
     x = rec["exchange"]
     assert x["error"] is None and x["payloads_intact"] is True and len(x["ms"]) == 3 and x["payload_bytes_per_rank"] == 400 * 800 * 4
     assert rec["distinct_devices"] == 1      # both ranks on the one GPU here; N on a real node
-    b = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-alternatives"], cwd=root, env=env, capture_output=True, text=True, timeout=900)
+    b = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-alternatives", "--full"], cwd=root, env=env, capture_output=True,
+                       text=True, timeout=900)
     assert b.returncode == 0, b.stderr[-2000:]
     rec = json.loads([ln for ln in b.stdout.splitlines() if ln.startswith("{")][-1])
     sh = rec["shards"]
@@ -1612,7 +1613,7 @@ def test_bench_two_ranks_share_one_gpu(tmp_path, mode):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     one, two = str(tmp_path / "one.npy"), str(tmp_path / "two.npy")
     common = ["--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
-    a = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--dump-image", one] + common, cwd=root,
+    a = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--dump-image", one, "--full"] + common, cwd=root,
                        capture_output=True, text=True, timeout=600)
     assert a.returncode == 0, a.stderr[-2000:]
     env = dict(os.environ, ADANERF_BENCH_DIST_BACKEND="gloo", ADANERF_BENCH_ONE_DEVICE="1")
@@ -1653,7 +1654,7 @@ def test_bench_plain_python_launches_itself(tmp_path):
     env = dict(os.environ, ADANERF_BENCH_DIST_BACKEND="gloo", ADANERF_BENCH_ONE_DEVICE="1")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    b = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--dump-image", two],
+    b = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full", "--dump-image", two],
                        cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert b.returncode == 0, b.stderr[-3000:]
     assert "torch.distributed.run" in b.stderr

@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 O=gpurun_out/${ROUND:-r06}_bench_all; mkdir -p $O
 # GUARDED=1 run ...: the line also carries guarded_mode (the opt-in guarded selection measured beside the headline, and what --sampling auto picks)
-run() { n=$1; shift; g=--no-guarded-mode; [ "${GUARDED:-0}" = "1" ] && g=; python bench.py --no-speed-mode --no-exact-mode $g --no-split-mode "$@" 2>/dev/null | tail -1 > $O/$n.json; python - "$O/$n.json" "$n" <<'PY'
+run() { n=$1; shift; g=--no-guarded-mode; [ "${GUARDED:-0}" = "1" ] && g=; python bench.py --full --no-speed-mode --no-exact-mode $g --no-split-mode "$@" 2>/dev/null | tail -1 > $O/$n.json; python - "$O/$n.json" "$n" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
 q = d.get("quality") or {}

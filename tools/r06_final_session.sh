@@ -2,7 +2,7 @@
 # Round 6, final session on ONE box: GPU test suite, default bench line, every workload, kernel stats + PMC passes, multi-context stress, N = 8 projection.
 cd "$(dirname "$0")/.."; O=gpurun_out/r06_final; mkdir -p $O
 python -m pytest tests -m gpu -q > $O/r06_pytest_gpu_final.log 2>&1; tail -3 $O/r06_pytest_gpu_final.log
-python bench.py > $O/r06_bench_default.json 2> $O/r06_bench_default.err; python - <<'PY'
+python bench.py --full > $O/r06_bench_default.json 2> $O/r06_bench_default.err; python - <<'PY'
 import json
 r = json.loads(open("gpurun_out/r06_final/r06_bench_default.json").read().strip().splitlines()[-1])
 print("default:", round(r["value"], 1), "FPS", {k: round(v, 3) for k, v in r["stage_ms_per_frame"].items()}, "frac", round(r["roofline"]["frac"], 3), "of sustained", round(r["roofline"].get("frac_of_sustained") or 0, 3),
