@@ -630,6 +630,9 @@ int occupancy_grid(adanerf_ctx* c, K kernel, int threads, int* out) {
 int calibrate_guard(adanerf_ctx* c, int n_poses, uint32_t seed, bool install, float* max_diff, float* max_pair);
 int ensure_guard_band(adanerf_ctx* c);
 
+// the sampling net has a split-precision packing: not with raySampleInput on the run-time-shaped kernels, not above width 256 (pack.cpp)
+bool has_split_sampling(const adanerf_ctx* c) { return (!c->generic0 || c->ray_samples == 0) && c->topo0.width != kWideWidth; }
+
 // a sampling net of another topology / layout on the split-precision run-time-shaped kernel (else: the fp32 one)
 bool generic_split_sampling(const adanerf_ctx* c) {
   return c->generic0 && c->sampling_mode != ADANERF_SAMPLING_FP32 && c->ray_samples == 0 && c->net0_split.w.p != nullptr;
@@ -1099,10 +1102,11 @@ int launch_shade_mlp(adanerf_ctx* c, const float* d_rays, const uint32_t* d_key,
     const bool st = tune::kGenericStaged;
     const bool enc104 = enc == kEnc10_4;      // else the catch-all 16-band layout
     const int nb_wg = !st ? 1 : topo.width == 64 ? gen_blocks<64>() : topo.width == 128 ? (enc104 ? gen_blocks<128, 10>() : gen_blocks<128, kMaxBands>())
-                                                                                         : gen_blocks<256>();
+                                : topo.width == 256 ? gen_blocks<256>() : gen_blocks<512>();
     const int per_wg = 128 * nb_wg;
     const int tiles = (max_samples + per_wg - 1) / per_wg;
-    const uint32_t bias_cap = topo.width == 64 ? gen_bias_cap<64>() : topo.width == 128 ? gen_bias_cap<128>() : gen_bias_cap<256>();
+    const uint32_t bias_cap = topo.width == 64 ? gen_bias_cap<64>() : topo.width == 128 ? gen_bias_cap<128>()
+                              : topo.width == 256 ? gen_bias_cap<256>() : gen_bias_cap<512>();
     if (st && a.net.n_bias > bias_cap)      // cannot happen for depth <= 8 (pack.hpp kMaxDepth): the kernel keeps the whole table in LDS
       return fail(c, ADANERF_EUNSUPPORTED, "shading network: bias table exceeds the kernel's LDS capacity");
     int& grid16 = c->shade_gen16_grid[coarse ? 1 : 0][prec == ADANERF_PREC_BF16 ? 0 : 1];
@@ -1125,7 +1129,8 @@ int launch_shade_mlp(adanerf_ctx* c, const float* d_rays, const uint32_t* d_key,
   do {                                                             \
     if (topo.width == 64) ADN_GEN16(ET, FPv, FDv, 64);             \
     else if (topo.width == 128) ADN_GEN16(ET, FPv, FDv, 128);      \
-    else ADN_GEN16(ET, FPv, FDv, 256);                             \
+    else if (topo.width == 256) ADN_GEN16(ET, FPv, FDv, 256);      \
+    else ADN_GEN16(ET, FPv, FDv, 512);                             \
   } while (0)
     if (prec == ADANERF_PREC_BF16) {
       if (enc == kEnc10_4) ADN_GEN16_W(Bf16, 10, 4);
@@ -1141,7 +1146,8 @@ int launch_shade_mlp(adanerf_ctx* c, const float* d_rays, const uint32_t* d_key,
   } else if (generic) {
     const int enc = coarse ? enc_layout(c->fp0, c->fd0, false) : c->enc1;
     if (!gen_grid) HIP_TRY(c, shade_mlp_gen_grid(c->info.compute_units, enc, topo.width, &gen_grid));
-    const int tiles = (max_samples + 127) / 128;
+    const int per_wg = topo.width == kWideWidth ? 64 : 128;      // the wide form runs 16-sample blocks
+    const int tiles = (max_samples + per_wg - 1) / per_wg;
     HIP_TRY(c, launch_shade_mlp_gen(a, gen, enc, topo.width, std::min(tiles, gen_grid), c->stream));
   } else if (prec == ADANERF_PREC_FP32) {
     if (!c->shade_grid[2]) HIP_TRY(c, shade_mlp_f32_grid(c->info.compute_units, &c->shade_grid[2]));
@@ -1322,8 +1328,9 @@ static int create_on(adanerf_ctx* c, const char* model_dir, const adanerf_option
       return bail(ADANERF_EIO, "model0.onnx has " + std::to_string(p0.topo.bins) + " outputs, config.ini says multiDepthFeatures = " + std::to_string(ms.bins));
     c->topo0 = p0.topo;
     c->generic0 = !p0.topo.is_default(false) || c->enc0 == kEncMax;
-    // the split-precision packing: the ring-streamed kernel's for the 8 x 256 net, the run-time-shaped kernel's otherwise (not with raySampleInput)
-    if ((!c->generic0 || c->ray_samples == 0) && !pack_sampling_net(n0, sh, Elem::F16_SPLIT, &p0s, &err)) return bail(ADANERF_EIO, "model0.onnx: " + err);
+    // the split-precision packing: the ring-streamed kernel's for the 8 x 256 net, the run-time-shaped kernel's otherwise (not with raySampleInput,
+    // not above width 256: such nets run the fp32 kernel in every sampling mode)
+    if (has_split_sampling(c) && !pack_sampling_net(n0, sh, Elem::F16_SPLIT, &p0s, &err)) return bail(ADANERF_EIO, "model0.onnx: " + err);
   }
   c->sampling_mode = opt->sampling_mode;
   c->model_dir = model_dir;
@@ -1344,11 +1351,11 @@ static int create_on(adanerf_ctx* c, const char* model_dir, const adanerf_option
     if (opt->precision == ADANERF_PREC_FP32) p1 = std::move(probe);
     else if (!pack_shading_net(c->net1_host, sh, elem_of(opt->precision), &p1, &err)) return bail(ADANERF_EIO, "model1.onnx: " + err);
   }
-  // the run-time-shaped kernels are instantiated for these widths (k_generic_f32.hip.hpp); the packer pads any width <= 256 up to one of them
-  auto width_ok = [](int w) { return w == 64 || w == 128 || w == 256; };
-  if (c->genericc && !width_ok(c->topoc.width)) return bail(ADANERF_EUNSUPPORTED, "model0.onnx: layer width " + std::to_string(c->topoc.width) + " (64, 128 or 256 supported)");
-  if (c->generic0 && !width_ok(c->topo0.width)) return bail(ADANERF_EUNSUPPORTED, "model0.onnx: layer width " + std::to_string(c->topo0.width) + " (64, 128 or 256 supported)");
-  if (c->generic1 && !width_ok(c->topo1.width)) return bail(ADANERF_EUNSUPPORTED, "model1.onnx: layer width " + std::to_string(c->topo1.width) + " (64, 128 or 256 supported)");
+  // the run-time-shaped kernels are instantiated for these widths (k_generic_f32.hip.hpp); the packer pads any width <= 512 up to one of them
+  auto width_ok = [](int w) { return w == 64 || w == 128 || w == 256 || w == kWideWidth; };
+  if (c->genericc && !width_ok(c->topoc.width)) return bail(ADANERF_EUNSUPPORTED, "model0.onnx: layer width " + std::to_string(c->topoc.width) + " (64, 128, 256 or 512 supported)");
+  if (c->generic0 && !width_ok(c->topo0.width)) return bail(ADANERF_EUNSUPPORTED, "model0.onnx: layer width " + std::to_string(c->topo0.width) + " (64, 128, 256 or 512 supported)");
+  if (c->generic1 && !width_ok(c->topo1.width)) return bail(ADANERF_EUNSUPPORTED, "model1.onnx: layer width " + std::to_string(c->topo1.width) + " (64, 128, 256 or 512 supported)");
 
   // ---- device ----
   int n_dev = 0;
@@ -1381,7 +1388,7 @@ static int create_on(adanerf_ctx* c, const char* model_dir, const adanerf_option
     c->genc = GenericTopo{c->topoc.depth, c->topoc.cat_mask, 0, 0, nullptr, 0.f};
   } else {
     if ((rc = upload_net(c, p0, &c->net0))) return bail(rc, c->err);
-    if ((!c->generic0 || c->ray_samples == 0) && (rc = upload_net(c, p0s, &c->net0_split))) return bail(rc, c->err);
+    if (has_split_sampling(c) && (rc = upload_net(c, p0s, &c->net0_split))) return bail(rc, c->err);
   }
   if (c->ray_samples > 0) {
     if ((rc = dev_alloc(c, &c->rsi_z, ms.rsi_z.size() * sizeof(float)))) return bail(rc, c->err);

@@ -1,5 +1,5 @@
 // SURVEY 8f N4, second half: both networks in any exportable topology (sampling net of 2..8 layers, NeRF trunk of 1..8 layers, width
-// 64 / 128 / 256, skips at any layers or none, src/models.py:18-82, 199-277) and any encoding layout on the 16-bit MFMA pipe.
+// 64 / 128 / 256, shading also 512, skips at any layers or none, src/models.py:18-82, 199-277) and any encoding layout on the 16-bit MFMA pipe.
 // The specialised 8 x 256 kernels stage one fragment stream through an LDS ring whose chunk positions are compile-time
 // constants of that topology.  Here the layer table is a run-time argument: a run-time loop over the hidden layers with the layer's
 // tiles and k-steps unrolled, and the weights staged per output tile through two LDS buffers shared by the workgroup (TileStage below;
@@ -314,13 +314,15 @@ __device__ __forceinline__ void layer_16_staged(TileStage& st, float (&br)[16], 
 // in LDS and no bias registers they fit: 0.758 -> 0.709 ms at 6 x 128); width 256 runs two blocks with the whole 512-register file,
 // as the 8 x 256 kernel does.  The catch-all 16-band layout parks 7 KiB of encoding per block in LDS: at width 128 two blocks would
 // leave room for one workgroup only, so it keeps one block there (tuning.hpp).
+// Width 512 (shading only: the sampling net of that width runs the wide fp32 form) keeps one block per wave at one workgroup per CU.
 template <int W, int FP = 10>
 constexpr int gen_blocks() {
-  return W == 64 ? 2 : W == 128 ? (FP <= 10 ? tune::kGenericBlocks128 : 1) : tune::kGenericBlocks256;
+  return W == 64 ? 2 : W == 128 ? (FP <= 10 ? tune::kGenericBlocks128 : 1) : W == 256 ? tune::kGenericBlocks256 : tune::kGenericBlocks512;
 }
 template <int W, int FP = 10>
 constexpr int gen_occupancy() {
-  return W == 64 ? (FP <= 10 ? tune::kGenericOcc64 : 2) : W == 128 ? (FP <= 10 ? tune::kGenericOcc128 : 2) : (FP <= 10 ? tune::kGenericOcc256 : 1);
+  return W == 64 ? (FP <= 10 ? tune::kGenericOcc64 : 2) : W == 128 ? (FP <= 10 ? tune::kGenericOcc128 : 2)
+                 : W == 256 ? (FP <= 10 ? tune::kGenericOcc256 : 1) : tune::kGenericOcc512;
 }
 
 // A5 + A6 for any shading-net topology on the 16-bit engine, weights staged per tile.  Workgroup = 4 waves x NB x 32 samples.
@@ -336,6 +338,7 @@ __global__ __launch_bounds__(256, OCC) void shade_mlp16_gen_staged_kernel(ShadeA
   // ... except where it would cost a resident workgroup: width 64 on the 16-band layout fills the CU's 160 KB with two workgroups as it is
   constexpr bool LDSB = !(W == 64 && FP > 10);
   __shared__ __attribute__((aligned(1024))) char stage_mem[BIAS_AT + (LDSB ? gen_bias_cap<W>() * 4 : 0)];
+  static_assert(sizeof(stage_mem) <= 160 * 1024, "staged shading kernel: LDS beyond the CU's 160 KiB");
   typedef __attribute__((address_space(3))) u32x4* lds_u32x4_wptr;
   const int lane = lane_id();
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);

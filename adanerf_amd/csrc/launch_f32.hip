@@ -56,6 +56,14 @@ hipError_t launch_shade_mlp_f32(const ShadeArgs& a, int grid, hipStream_t stream
 
 
 hipError_t launch_sample_mlp_gen(const SampleArgs& a, const GenericTopo& t, int enc, int width, unsigned grid, hipStream_t stream) {
+  if (width == kWideWidth) {      // 16-ray blocks: 64 rays per workgroup (grid: the caller's, counted in 128-ray workgroups)
+    const dim3 gw((a.n_rays + 63) / 64);
+    if (t.ray_samples > 0) return hipErrorInvalidValue;      // the packer refuses raySampleInput at this width
+    if (enc == kEnc10_4) hipLaunchKernelGGL((sample_mlp_gen_wide_kernel<10, 4>), gw, dim3(256), 0, stream, a, t);
+    else if (enc == kEnc2_2) hipLaunchKernelGGL((sample_mlp_gen_wide_kernel<2, 2>), gw, dim3(256), 0, stream, a, t);
+    else hipLaunchKernelGGL((sample_mlp_gen_wide_kernel<kMaxBands, kMaxBands>), gw, dim3(256), 0, stream, a, t);
+    return hipGetLastError();
+  }
 #define ADN_GEN_S(W)                                                                                                             \
   if (width == W) {                                                                                                              \
     if (enc == kEnc10_4) hipLaunchKernelGGL((sample_mlp_gen_kernel<10, 4, W>), dim3(grid), dim3(256), 0, stream, a, t);          \
@@ -75,6 +83,9 @@ hipError_t shade_mlp_gen_grid(int compute_units, int enc, int width, int* grid) 
   if (width == W) e = enc == kEnc10_4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, shade_mlp32_gen_kernel<10, 4, W>, 256, 0)   \
                                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, shade_mlp32_gen_kernel<kMaxBands, kMaxBands, W>, 256, 0);
   ADN_GEN_G(64) ADN_GEN_G(128) ADN_GEN_G(256)
+  if (width == kWideWidth)
+    e = enc == kEnc10_4 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, shade_mlp32_gen_wide_kernel<10, 4>, 256, 0)
+                        : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, shade_mlp32_gen_wide_kernel<kMaxBands, kMaxBands>, 256, 0);
 #undef ADN_GEN_G
   if (e != hipSuccess) return e;
   *grid = (per_cu < 1 ? 1 : per_cu) * compute_units;
@@ -89,6 +100,11 @@ hipError_t launch_shade_mlp_gen(const ShadeArgs& a, const GenericTopo& t, int en
     return hipGetLastError();                                                                                                    \
   }
   ADN_GEN_L(64) ADN_GEN_L(128) ADN_GEN_L(256)
+  if (width == kWideWidth) {      // 64 samples per workgroup and pass
+    if (enc == kEnc10_4) hipLaunchKernelGGL((shade_mlp32_gen_wide_kernel<10, 4>), dim3(grid), dim3(256), 0, stream, a, t);
+    else hipLaunchKernelGGL((shade_mlp32_gen_wide_kernel<kMaxBands, kMaxBands>), dim3(grid), dim3(256), 0, stream, a, t);
+    return hipGetLastError();
+  }
 #undef ADN_GEN_L
   return hipErrorInvalidValue;
 }

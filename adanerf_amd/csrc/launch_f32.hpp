@@ -17,7 +17,9 @@ hipError_t launch_sample_mlp_f32(const SampleArgs& a, bool full, unsigned grid, 
 hipError_t shade_mlp_f32_grid(int compute_units, int* grid);
 hipError_t launch_shade_mlp_f32(const ShadeArgs& a, int grid, hipStream_t stream);
 
-// Generic-topology kernels (k_generic_f32.hip.hpp): width 64 / 128 / 256, run-time depth / skip / raySampleInput.
+// Generic-topology kernels (k_generic_f32.hip.hpp): width 64 / 128 / 256, run-time depth / skip / raySampleInput; width 512 (kWideWidth)
+// in the wide form: 16-sample blocks, 64 rays / samples per workgroup (the launchers size the sampling grid themselves; the shading
+// caller counts its tiles in 64 samples), no raySampleInput.
 // enc: slot layout of the positional encodings the network was packed with -- kEnc10_4, kEnc2_2 (sampling nets only) or
 // kEncMax (the catch-all kMaxBands-band layout: any posEncArgs).  hipErrorInvalidValue for a width / layout without an instantiation.
 enum { kEnc10_4 = 0, kEnc2_2 = 1, kEncMax = 2 };

@@ -48,6 +48,16 @@ ADN_HD inline int pe_col(int F, int q, int h, int FL = 0) {
   return -1;
 }
 
+// ---- wide form (hidden width 512, fp32 only: k_generic_f32.hip.hpp, the *_wide kernels) -----------------------------------------
+// v_mfma_f32_16x16x4_f32 on 16-sample blocks: lane l = (j = l & 15 sample, g = l >> 4 group) holds, for output tile m (16 rows),
+// rows 4 g + r, r = 0..3, so group g owns the slots q = 4 m + r that stand for features
+//     act_feature_wide(q, g) = 16 (q >> 2) + 4 g + (q & 3),
+// W / 4 slots per lane (128 at W = 512, half of the 32x32x2 form's W / 2).  k-step q takes slot q of every group (B = 1 VGPR).
+// An encoding's slots: slot q of group g is the 32-row form's slot 2 q + (g >> 1) of lane-half g & 1 (pe_slots(F) / 2 per group).
+constexpr int kWideWidth = 512;
+ADN_HD inline int act_feature_wide(int q, int g) { return 16 * (q >> 2) + 4 * g + (q & 3); }
+ADN_HD inline int pe_col_wide(int F, int q, int g, int FL = 0) { return pe_col(F, 2 * q + (g >> 1), g & 1, FL); }
+
 constexpr int kBins = 128;   // multiDepthFeatures
 
 }  // namespace adanerf

@@ -70,6 +70,8 @@ struct VLayer {
   std::vector<float> w;            // [rows][cols]
   std::vector<float> b;            // [rows]
   std::vector<int> col_h0, col_h1; // per slot: source column for lane-half 0 / 1 (-1 = zero)
+  bool wide = false;               // the wide fp32 form (layout.hpp act_feature_wide): 16-row tiles, slots per lane group in col_g
+  std::vector<int> col_g[4];
 };
 
 const Tensor* find(const TensorMap& m, const std::string& k, std::string* err) {
@@ -105,6 +107,14 @@ void init_layer(VLayer* L, int rows_padded, int cols) {
 void add_pe_slots(VLayer* L, int F, int col_base, int FL = 0) {
   if (FL <= 0) FL = F;
   int n = pe_slots(FL);
+  if (L->wide) {
+    for (int q = 0; q < n / 2; ++q)
+      for (int g = 0; g < 4; ++g) {
+        const int c = pe_col_wide(F, q, g, FL);
+        L->col_g[g].push_back(c < 0 ? -1 : col_base + c);
+      }
+    return;
+  }
   for (int q = 0; q < n; ++q) {
     int c0 = pe_col(F, q, 0, FL), c1 = pe_col(F, q, 1, FL);
     L->col_h0.push_back(c0 < 0 ? -1 : col_base + c0);
@@ -115,6 +125,14 @@ void add_pe_slots(VLayer* L, int F, int col_base, int FL = 0) {
 // n_features: the (padded) width the kernels run; n_real: the network's own width -- features beyond it are padding (zero column)
 void add_act_slots(VLayer* L, int n_features, int col_base, int n_real = -1) {
   if (n_real < 0) n_real = n_features;
+  if (L->wide) {
+    for (int q = 0; q < n_features / 4; ++q)
+      for (int g = 0; g < 4; ++g) {
+        const int f = act_feature_wide(q, g);
+        L->col_g[g].push_back(f < n_real ? col_base + f : -1);
+      }
+    return;
+  }
   int n = n_features / 2;   // slots per lane-half
   for (int q = 0; q < n; ++q) {
     const int f0 = act_feature(q, 0), f1 = act_feature(q, 1);
@@ -123,11 +141,11 @@ void add_act_slots(VLayer* L, int n_features, int col_base, int n_real = -1) {
   }
 }
 
-// The kernels are instantiated for hidden widths 64 / 128 / 256.  A network of any other width W <= 256 (the reference's layerWidth is
+// The kernels are instantiated for hidden widths 64 / 128 / 256 / 512.  A network of any other width W <= 512 (the reference's layerWidth is
 // free, src/models.py:18-82, 199-250) runs as the next of those with zero rows / zero bias appended to every hidden layer: a padded unit
 // is relu(0) = 0 (the feature layer has no activation: 0 as well) and feeds zero columns -- the results are those of the W-wide network
 // bit for bit in fp32, and to the engine's usual accuracy in 16 bits (the extra products are exact zeros).
-int pad_width(int w) { return w <= 64 ? 64 : (w <= 128 ? 128 : (w <= 256 ? 256 : 0)); }
+int pad_width(int w) { return w <= 64 ? 64 : (w <= 128 ? 128 : (w <= 256 ? 256 : (w <= kWideWidth ? kWideWidth : 0))); }
 
 // ---- scaled packing of bf16 shading nets (PackedNet::relu_scaled) --------------------------------------------------------------------
 // Source column c of a layer holds x_c 2^-ce[c] with |x_c| <= cb[c] (true scale).  The layer's outputs are bounded row by row,
@@ -170,7 +188,35 @@ void pe_col_scale(int n_cols, double identity_bound, std::vector<double>* cb, st
   }
 }
 
+// the wide fp32 form: fragments [m][s4][lane][4] of 16-row tiles, lane = (i = lane & 15 row, g = lane >> 4 group), slot q = 4 s4 + e of
+// group g; bias blocks [m][g][4] (feature 16 m + 4 g + r)
+void emit_wide(const VLayer& L, PackedNet* out) {
+  const int QS = static_cast<int>(L.col_g[0].size());
+  const int steps = QS / 4;
+  const int MT = L.rows / 16;
+  out->w_off.push_back(static_cast<uint32_t>(out->weights.size() / 16));
+  out->b_off.push_back(static_cast<uint32_t>(out->bias.size()));
+  out->slots.push_back(QS);
+  out->mtiles.push_back(MT);
+  const size_t base = out->weights.size();
+  out->weights.resize(base + static_cast<size_t>(MT) * steps * 64 * 16);
+  uint8_t* dst = out->weights.data() + base;
+  for (int m = 0; m < MT; ++m)
+    for (int s = 0; s < steps; ++s)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int row = 16 * m + (lane & 15), g = lane >> 4;
+        for (int e = 0; e < 4; ++e) {
+          const int col = L.col_g[g][4 * s + e];
+          const float v = (col >= 0) ? L.w[static_cast<size_t>(row) * L.cols + col] : 0.f;
+          std::memcpy(dst + ((static_cast<size_t>(m) * steps + s) * 64 + lane) * 16 + 4 * e, &v, 4);
+        }
+      }
+  for (int m = 0; m < MT; ++m)
+    for (int f = 0; f < 16; ++f) out->bias.push_back(L.b[16 * m + f]);      // [m][g][r] = feature 16 m + 4 g + r
+}
+
 void emit(const VLayer& L, Elem elem, PackedNet* out) {
+  if (L.wide) return emit_wide(L, out);
   const int G = (elem == Elem::F32) ? 4 : 8;          // slots per 16-byte fragment element group
   const int QS = static_cast<int>(L.col_h0.size());
   const int steps = QS / G;
@@ -279,7 +325,15 @@ bool pack_sampling_net(const TensorMap& net0, const NetShape& sh, Elem elem, Pac
   T.width = pad_width(Wr);                                       // ... and the width it runs at
   T.real_width = Wr;
   T.ray_samples = sh.ray_samples;
-  if (Wr < 1 || T.width == 0) return fail(err, "sampling net: width " + std::to_string(Wr) + " (1 .. 256 supported)");
+  if (Wr < 1 || T.width == 0) return fail(err, "sampling net: width " + std::to_string(Wr) + " (1 .. 512 supported)");
+  // wider than 256: the exact fp32 engine in its wide form only.  A split-precision kernel would hold hi and lo parts of input and output,
+  // 4 x W / 4 = 512 registers per lane at W = 512 (the plain 16-bit kernel exists for 8 x 256 only)
+  const bool wide = T.width == kWideWidth;
+  if (wide && elem != Elem::F32)
+    return fail(err, "sampling net: width " + std::to_string(Wr) + " > 256 runs on the fp32 engine only (the 16-bit sampling kernels would need "
+                     "512 registers per lane at width 512)");
+  if (wide && sh.ray_samples > 0)
+    return fail(err, "sampling net: raySampleInput is not supported with a width > 256 (" + std::to_string(Wr) + ")");
   // plain 16-bit fragments: the ring-streamed kernel of the 8 x 256 / 10-4 or 2-2 net only; the (hi, lo') split pairs pack for any
   // topology and layout without raySampleInput (k_generic16.hip.hpp); raySampleInput is fp32 only (K-major block, emit_ray_samples)
   const bool special = T.is_default(false) && !sh.lp0 && !sh.ld0;
@@ -298,6 +352,7 @@ bool pack_sampling_net(const TensorMap& net0, const NetShape& sh, Elem elem, Pac
     }
     VLayer L;
     init_layer(&L, (i == T.depth - 1) ? kBins : T.width, k);      // hidden layers: rows padded to the width the kernels run
+    L.wide = wide;
     if (!set_rows(&L, 0, W, B, k, err, "layers." + std::to_string(i))) return false;
     // multiDepthFeatures = D < 128: the selection kernels work on 128 values per ray; the bins the network does not have get zero
     // weights and a bias no threshold, arg-max or softmax ever picks (-1e30: exp() of it is 0, a sigmoid of it 0)
@@ -326,8 +381,10 @@ bool pack_shading_net(const TensorMap& net1, const NetShape& sh, Elem elem, Pack
   const int Wr = find(net1, "pts_linears.0.weight", err)->rows();   // exists: depth >= 1.  The network's own width W ...
   T.width = pad_width(Wr);                                          // ... and the width it runs at (pad_width)
   T.real_width = Wr;
-  if (Wr < 2 || T.width == 0) return fail(err, "shading net: width " + std::to_string(Wr) + " (2 .. 256 supported)");
+  if (Wr < 2 || T.width == 0) return fail(err, "shading net: width " + std::to_string(Wr) + " (2 .. 512 supported)");
   const int Wd = T.width, Wh = Wr / 2;      // views_linears.0 has W // 2 rows (src/models.py:236)
+  const bool wide = Wd == kWideWidth && elem == Elem::F32;      // fp32 at width 512: the wide form (16-row tiles); 16 bits keep the 32-row form
+  const int tail = wide ? 16 : 32;      // rows of the alpha tile behind the feature rows / of the rgb tile
   // bf16: scaled packing (scale_layer) -- h_bound / h_exp describe the trunk's current activations
   const bool scaled = elem == Elem::BF16 && scale_bf16;
   out->relu_scaled = scaled;
@@ -355,6 +412,7 @@ bool pack_shading_net(const TensorMap& net1, const NetShape& sh, Elem elem, Pack
     }
     VLayer L;
     init_layer(&L, Wd, k);
+    L.wide = wide;
     if (!set_rows(&L, 0, W, B, k, err, nm)) return false;
     if (i == 0) {
       add_pe_slots(&L, sh.fp1, 0, sh.lp1);
@@ -384,7 +442,8 @@ bool pack_shading_net(const TensorMap& net1, const NetShape& sh, Elem elem, Pack
     const Tensor* BA = find(net1, "alpha_linear.bias", err);
     if (!WF || !BF || !WA || !BA) return false;
     VLayer L;
-    init_layer(&L, Wd + 32, Wr);
+    init_layer(&L, Wd + tail, Wr);
+    L.wide = wide;
     if (!set_rows(&L, 0, WF, BF, Wr, err, "feature_linear")) return false;
     if (WF->rows() != Wr || WA->rows() != 1) {
       if (err) *err = "feature_linear/alpha_linear: unexpected row count";
@@ -412,6 +471,7 @@ bool pack_shading_net(const TensorMap& net1, const NetShape& sh, Elem elem, Pack
     }
     VLayer L;
     init_layer(&L, Wd / 2, Wr + n_dir);
+    L.wide = wide;
     if (!set_rows(&L, 0, W, B, Wr + n_dir, err, "views_linears.0")) return false;
     add_act_slots(&L, Wd, 0, Wr);
     add_pe_slots(&L, sh.fd1, Wr, sh.ld1);
@@ -433,7 +493,8 @@ bool pack_shading_net(const TensorMap& net1, const NetShape& sh, Elem elem, Pack
       return false;
     }
     VLayer L;
-    init_layer(&L, 32, Wh);
+    init_layer(&L, tail, Wh);
+    L.wide = wide;
     if (!set_rows(&L, 0, W, B, Wh, err, "rgb_linear")) return false;
     add_act_slots(&L, Wd / 2, 0, Wh);
     if (scaled) {      // no activation: rgb leaves the kernel times 2^v_exp

@@ -17,7 +17,7 @@ constexpr float kSplitScale = 2048.0f;
 // src/models.py:18-82, 199-250; the viewer takes it from the ONNX graph as well, not from config.ini).
 struct NetTopology {
   int depth = 8;           // Linear layers of the trunk (sampling net: all of them)
-  int width = 256;         // hidden width the kernels run: 64 / 128 / 256 (the network's own width padded with zero units, pack.cpp pad_width)
+  int width = 256;         // hidden width the kernels run: 64 / 128 / 256 / 512 (the network's own width padded with zero units, pack.cpp pad_width)
   int real_width = 256;    // the network's own hidden width W
   int skip = -1;           // NeRF trunk: the first entry of the reference's `skips` (layer skip + 1 takes cat([input_pts, h])); -1 = none
   int cat_mask = 0;        // ... all of them: bit l set <=> layer l takes cat([input_pts, h]) (one bit per skip: the NeRF class accepts a list)
@@ -29,7 +29,7 @@ constexpr float kAbsentBin = -1.0e30f;      // bias of the output rows a samplin
 constexpr int kMaxDepth = 8;    // w_off / b_off tables hold depth + 3 entries (kMaxLayers = 12)
 
 // One packed network: every layer's A fragments back to back plus the per-tile bias blocks.
-//   fp32 engine   : float  w[layer][m][s4][lane][4]   (slot q = 4 s4 + e)
+//   fp32 engine   : float  w[layer][m][s4][lane][4]   (slot q = 4 s4 + e; width 512: 16-row tiles m, bias [m][g][4], layout.hpp act_feature_wide)
 //   16-bit engine : uint16 w[layer][m][s ][lane][8]   (slot q = 8 s  + e)
 //   split engine  : uint16 w[layer][m][s ][part][lane][8], part 0 = hi, 1 = lo' 
 //   bias          : float  b[layer][m][h][16]         (feature 32m + 8(r>>2) + 4h + (r&3))
@@ -68,12 +68,13 @@ struct NetShape {
 
 // layers.{0..D-1}.{weight,bias}: [dir PE | pos PE | raySampleInput points] -> W x (D-1) -> 128  (src/models.py:18-82,183-195).
 // Every shipped config is 8 x 256 without extra points; other depths (2..8) / widths (any W <= 256, run zero-padded to 64 / 128 / 256) pack
-// for Elem::F32 and as split pairs; the raySampleInput input for Elem::F32 only (the generic fp32-MFMA kernels).
+// for Elem::F32 and as split pairs; the raySampleInput input for Elem::F32 only (the generic fp32-MFMA kernels).  257 <= W <= 512: Elem::F32
+// only (the wide form), without raySampleInput.
 bool pack_sampling_net(const TensorMap& net0, const NetShape& shape, Elem elem, PackedNet* out, std::string* err);
 
 // pts_linears.{0..D-1}, feature_linear(+alpha_linear as row W), views_linears.0, rgb_linear
-// (src/models.py:199-277).  Layer order in the blob: 0..D-1, feature+alpha, views, rgb.  Any topology (any W <= 256, run zero-padded to
-// 64 / 128 / 256; D in 1..8, skips anywhere) and encoding layout packs for every element type (16-bit: k_generic16.hip.hpp).
+// (src/models.py:199-277).  Layer order in the blob: 0..D-1, feature+alpha, views, rgb.  Any topology (any W <= 512, run zero-padded to
+// 64 / 128 / 256 / 512 -- fp32 at 512 in the wide form; D in 1..8, skips anywhere) and encoding layout packs for every element type (16-bit: k_generic16.hip.hpp).
 bool pack_shading_net(const TensorMap& net1, const NetShape& shape, Elem elem, PackedNet* out, std::string* err, bool scale_bf16 = true);
 // (scale_bf16 = false: the bf16 blob WITHOUT the per-layer powers of two -- no kernel consumes it; the CPU test replays it next to the scaled one)
 

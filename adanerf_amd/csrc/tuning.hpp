@@ -31,6 +31,8 @@ constexpr int kShadeGuardStep = 2;                                    // k-step 
 constexpr bool kGenericStaged = true;                // weights of an output tile staged through LDS once per workgroup (false: layer_16x3_direct, the baseline)
 constexpr int kGenericBlocks128 = 2, kGenericBlocks256 = 2;           // 32-sample blocks per wave of the staged shading kernel at that width
 constexpr int kGenericOcc64 = 2, kGenericOcc128 = 2, kGenericOcc256 = 1;      // workgroups per CU asked of the compiler
+// width 512 (16-bit shading only): one block per wave -- hA + hB = 128 + 136 registers, what two blocks of width 256 hold -- one workgroup per CU
+constexpr int kGenericBlocks512 = 1, kGenericOcc512 = 1;
 constexpr int kGenericSpread = 1;                    // a tile's conversions spread over the next tile's k-steps: 1 = width 256 only (r04_variants_generic_spread.log)
 constexpr bool kGenericBiasDirect = true;            // a tile's bias block read from the LDS table straight into its accumulators
 constexpr int kGenericAhead = 4;                     // fragments a wave requests from LDS ahead of the k-step that consumes them

@@ -93,7 +93,7 @@ enum {
 };
 /* Sampling nets of another topology / encoding layout (run-time-shaped kernels): ADANERF_SAMPLING_FP32 runs the exact fp32
  * kernel, every other mode the split-precision one (same arithmetic as ADANERF_SAMPLING_SPLIT_FP16; no plain-fp16 pass);
- * with raySampleInput always the fp32 kernel. */
+ * with raySampleInput always the fp32 kernel.  Sampling nets wider than 256 run the fp32 kernel in every mode (its wide form). */
 
 /* sample placement (config.ini rayMarchSampler[1]) */
 enum {
@@ -485,7 +485,9 @@ int adanerf_host_parse_model(const char* model_dir, const adanerf_options* opt, 
  *                (precision 4, net 1 only: the bf16 blob without that scaling, for tests -- no kernel consumes it.)
  * The shading net packs in every precision for every topology.  A sampling net other than 8 x 256 with a 10-4 / 2-2 encoding
  * packs for ADANERF_PREC_FP32 (run-time-shaped fp32 kernel) and, without raySampleInput, as split pairs (3: run-time-shaped
- * split-precision kernel); the plain 16-bit precisions -- and the split pairs with raySampleInput -- return ADANERF_EIO with a message. */
+ * split-precision kernel); the plain 16-bit precisions -- and the split pairs with raySampleInput -- return ADANERF_EIO with a message.
+ * Hidden widths up to 512 pack (zero-padded); a net wider than 256 packs for ADANERF_PREC_FP32 in the wide form (16-row tiles: records
+ * hold slots per lane group and 16-row tiles), a sampling net that wide for ADANERF_PREC_FP32 only, without raySampleInput. */
 int adanerf_host_pack_weights(const char* model_dir, int32_t net, int32_t precision, void* weights_out,
                               size_t* weights_bytes, float* bias_out, size_t* bias_floats, int32_t* layer_out,
                               int32_t* n_layers);
