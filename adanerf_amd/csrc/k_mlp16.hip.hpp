@@ -269,13 +269,11 @@ __device__ __forceinline__ void ws_start(WStream<CF, RS, LPW, NR>& st, const voi
   for (int i = 0; i < NR; ++i) st.R[i] = lds_read128(st.rd_next + i * 1024);
 }
 
-// ReLU on the raw bits: max(int(x), 0) is +0.0 for every negative float and the identity for positive
-// ones -- one v_max_i32, no canonicalising v_max_f32 pair.
-__device__ __forceinline__ float relu_bits(float x) {
-  int i = __builtin_bit_cast(int, x);
-  i = i > 0 ? i : 0;
-  return __builtin_bit_cast(float, i);
-}
+// ReLU that keeps a NaN of either sign: IEEE 754-2019 maximum(x, +0) -- one v_maximum3_f32 on gfx950, like the v_max_i32 on the raw bits
+// it replaces.  A NaN must survive: an activation that left the fp16 range turns into inf - inf in the next layer, the NaN can carry the
+// sign bit, and max(int(x), 0) made it a silent 0 -- the ray's outputs stayed finite and adanerf_stats.sampling_overflow never saw it
+// (tests/test_gpu_mlp_engines.py test_sampling_fp16_range_contract).
+__device__ __forceinline__ float relu_keep_nan(float x) { return __builtin_elementwise_maximum(x, 0.0f); }
 
 template <class ET, int F>
 __device__ __forceinline__ void pe_pack(const float x[3], int h, uint32_t* out) {
@@ -367,13 +365,19 @@ __device__ __forceinline__ void epilogue_quad_16(const f32x16& acc, int m, int g
     out[8 * m + 2 * g + 1] = q1;
     return;
   }
-  // convert first, then ReLU on the packed pair: max(int16, 0) clears every negative bf16/f16
-  // (one v_cvt_pk + one v_pk_max_i16 per two values)
+  // convert first, then ReLU on the packed pair (one v_cvt_pk + one packed max per two values): fp16 takes IEEE 754-2019 maximum, which
+  // keeps a NaN of either sign (relu_keep_nan: an fp16 overflow must reach the outputs); max(int16, 0) clears every negative bf16
   uint32_t p0 = ET::pack(acc[4 * g + 0], acc[4 * g + 1]), p1 = ET::pack(acc[4 * g + 2], acc[4 * g + 3]);
   if (RELU) {
-    const s16x2 z = {0, 0};
-    p0 = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, p0), z));
-    p1 = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, p1), z));
+    if constexpr (std::is_same_v<ET, Fp16>) {
+      const f16x2 z = {static_cast<_Float16>(0.f), static_cast<_Float16>(0.f)};
+      p0 = __builtin_bit_cast(uint32_t, __builtin_elementwise_maximum(__builtin_bit_cast(f16x2, p0), z));
+      p1 = __builtin_bit_cast(uint32_t, __builtin_elementwise_maximum(__builtin_bit_cast(f16x2, p1), z));
+    } else {
+      const s16x2 z = {0, 0};
+      p0 = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, p0), z));
+      p1 = __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(s16x2, p1), z));
+    }
   }
   out[8 * m + 2 * g + 0] = p0;
   out[8 * m + 2 * g + 1] = p1;

@@ -40,7 +40,7 @@ __device__ __forceinline__ void epilogue_pair_16x3(const f32x16& acc, const f32x
     out_f32[16 * m + 2 * pi] = v0;
     out_f32[16 * m + 2 * pi + 1] = v1;
   } else {
-    split_pack(relu_bits(v0), relu_bits(v1), &out_hi[8 * m + pi], &out_lo[8 * m + pi]);
+    split_pack(relu_keep_nan(v0), relu_keep_nan(v1), &out_hi[8 * m + pi], &out_lo[8 * m + pi]);
   }
 }
 
