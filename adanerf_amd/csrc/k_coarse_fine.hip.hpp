@@ -71,7 +71,7 @@ __global__ __launch_bounds__(kFineRaysPerBlock) void fine_sample_kernel(const fl
     double s = 0.0;
     for (int k = 0; k < nc; ++k) {
       const float dist = __fmul_rn((k + 1 < nc) ? __fsub_rn(zc[k + 1], zc[k]) : 1e10f, dn);
-      const float al = __fsub_rn(1.0f, expf(-__fmul_rn(fmaxf(raw[k].w, 0.f), dist)));
+      const float al = __fsub_rn(1.0f, expf(-__fmul_rn(relu_keep_nan_f32(raw[k].w), dist)));
       const float wt = __fmul_rn(al, static_cast<float>(T));
       T *= static_cast<double>(__fadd_rn(__fsub_rn(1.0f, al), 1e-10f));
       if (k >= 1 && k + 1 < nc) {

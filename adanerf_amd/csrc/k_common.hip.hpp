@@ -335,6 +335,10 @@ __device__ __forceinline__ int wave_incl_sum_dpp_i32(int v) {
 
 __device__ __forceinline__ float sigmoidf_dev(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// torch.relu on a density: 0 for x <= 0, and a NaN stays a NaN (fmaxf(NaN, 0) is 0: a ray with a NaN density would come out as
+// empty space instead of non-finite)
+__device__ __forceinline__ float relu_keep_nan_f32(float x) { return (x > 0.f || x != x) ? x : 0.f; }
+
 __device__ __forceinline__ int mbcnt64(uint64_t mask) {
   return __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(mask >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(mask), 0));
 }

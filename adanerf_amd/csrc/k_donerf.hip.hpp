@@ -95,7 +95,7 @@ __global__ __launch_bounds__(256) void composite_classic_kernel(const float4* __
     const float4 v = raw[o + k];
     const float zn = (k + 1 < n) ? sample_z[o + k + 1] : 0.f;
     const float dist = __fmul_rn((k + 1 < n) ? __fsub_rn(zn, zk) : 1e10f, dn);
-    const float al = __fsub_rn(1.0f, expf(-__fmul_rn(fmaxf(v.w, 0.f), dist)));
+    const float al = __fsub_rn(1.0f, expf(-__fmul_rn(relu_keep_nan_f32(v.w), dist)));
     const float wt = __fmul_rn(al, T);
     cr = __fadd_rn(cr, __fmul_rn(wt, sigmoidf_dev(v.x)));
     cg = __fadd_rn(cg, __fmul_rn(wt, sigmoidf_dev(v.y)));
@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void composite_classic_wave_kernel(const float
       v = raw[o + k];
       zk = sample_z[o + k];
       const float dist = __fmul_rn((k + 1 < n) ? __fsub_rn(sample_z[o + k + 1], zk) : 1e10f, dn);
-      al = __fsub_rn(1.0f, expf(-__fmul_rn(fmaxf(v.w, 0.f), dist)));
+      al = __fsub_rn(1.0f, expf(-__fmul_rn(relu_keep_nan_f32(v.w), dist)));
     }
     const float f = (k < n) ? __fadd_rn(__fsub_rn(1.0f, al), 1e-10f) : 1.0f;
     const float p = wave_incl_prod_dpp_f32(f);

@@ -428,7 +428,10 @@ int adanerf_sample_from_coarse(adanerf_ctx* ctx, const float* d_raw_coarse, cons
 int adanerf_composite_classic(adanerf_ctx* ctx, const float* d_raw, const float* d_sample_z, const float* d_rays,
                               int32_t n_rays, int32_t n, float* d_rgb_out, void* d_rgba8_out);
 
-/* Per-ray front-to-back compositing: c = sigmoid(raw.rgb), a = sigmoid(raw.a) * w. */
+/* Per-ray front-to-back compositing: c = sigmoid(raw.rgb), a = sigmoid(raw.a) * w.  Ray r composites the d_ray_counts[r] samples
+ * from d_ray_offsets[r] on; any layout is accepted (the compactor's ray-major one takes a staged fast path with the same result, bit
+ * for bit).  Contract: in a context with num_samples > 32 one wave composites a ray and every lane holds two samples, so
+ * d_ray_counts[r] must not exceed the context's num_samples (at most 128); samples beyond 128 are not read. */
 int adanerf_composite(adanerf_ctx* ctx, const float* d_raw, const float* d_sample_w,
                       const int32_t* d_ray_offsets, const int32_t* d_ray_counts, int32_t n_rays,
                       float* d_rgb_out, void* d_rgba8_out);
