@@ -142,6 +142,11 @@ struct adanerf_ctx {
   float* aux_acc = nullptr;
   float* aux_disp = nullptr;         // adanerf_set_disp_output
   DevBuf disp_scratch;               // [2, batch] depth / accumulation of the batch when the caller asked for disparity only
+  // adanerf_flip: filter tables of the last pixels-per-degree value, per-tile sums, the mean; grown on demand
+  DevBuf flip_tab, flip_partial, flip_mean;
+  double flip_ppd = 0.0;             // what flip_tab holds (0: nothing yet)
+  FlipParams flip_params{};
+  bool flip_lds_raised = false;      // flip_kernel may use more than 64 KB of dynamic LDS
   hipEvent_t peer_event = nullptr;   // adanerf_gather_to: orders the destination stream behind the copy
   uint64_t peer_tried = 0;           // bit d: peer access to device d has been requested once
 };
@@ -1252,6 +1257,159 @@ int launch_composite(adanerf_ctx* c, const float* d_raw, const float* d_w, const
   return ADANERF_OK;
 }
 
+// ---- FLIP (adanerf_flip): tables and constants of src/util/flip_loss.py for one pixels-per-degree value, built in fp64 and rounded
+// to fp32 where the reference rounds (torch.Tensor(g)) ----
+
+constexpr double kFlipPi = 3.14159265358979323846;
+constexpr double kFlipDefaultPpd = 0.7 * (3840 / 0.7) * (kFlipPi / 180);      // flip_loss.py:55
+constexpr double kFlipPpdMin = 10.0, kFlipPpdMax = 140.0;
+
+// generate_spatial_filter (flip_loss.py:112-154): a1 sqrt(pi / b1) exp(-pi^2 z / b1) + a2 sqrt(pi / b2) exp(-pi^2 z / b2), normalised by its own sum
+void flip_spatial_filter(double ppd, int r, double a1, double b1, double a2, double b2, float* out) {
+  const int n = 2 * r + 1;
+  const double dx = 1.0 / ppd;
+  std::vector<double> g(static_cast<size_t>(n) * n);
+  double sum = 0.0;
+  for (int y = -r; y <= r; ++y)
+    for (int x = -r; x <= r; ++x) {
+      const double z = (x * dx) * (x * dx) + (y * dx) * (y * dx);
+      const double v = a1 * std::sqrt(kFlipPi / b1) * std::exp(-(kFlipPi * kFlipPi) * z / b1) + a2 * std::sqrt(kFlipPi / b2) * std::exp(-(kFlipPi * kFlipPi) * z / b2);
+      g[static_cast<size_t>(y + r) * n + (x + r)] = v;
+      sum += v;
+    }
+  for (size_t i = 0; i < g.size(); ++i) out[i] = static_cast<float>(g[i] / sum);
+}
+
+// feature_detection (flip_loss.py:213-240): first (edge) or second (point) x derivative of a Gaussian; the table goes to fp32, then the
+// positive and the negative weights are normalised separately, in fp32
+void flip_feature_filter(double sd, int r, bool point, float* out) {
+  const int n = 2 * r + 1;
+  std::vector<double> g(static_cast<size_t>(n) * n);
+  double neg = 0.0, pos = 0.0;
+  for (int y = -r; y <= r; ++y)
+    for (int x = -r; x <= r; ++x) {
+      const double e = std::exp(-static_cast<double>(x * x + y * y) / (2 * sd * sd));
+      const double v = point ? (static_cast<double>(x * x) / (sd * sd) - 1) * e : -static_cast<double>(x) * e;
+      g[static_cast<size_t>(y + r) * n + (x + r)] = v;
+      if (v < 0) neg -= v;
+      if (v > 0) pos += v;
+    }
+  const float fneg = static_cast<float>(neg), fpos = static_cast<float>(pos);
+  for (size_t i = 0; i < g.size(); ++i) {
+    const float v = static_cast<float>(g[i]);
+    out[i] = v < 0.0f ? v / fneg : v / fpos;
+  }
+}
+
+// linear RGB -> hunt-adjusted L*a*b* in fp64 (the two primaries behind cmax, flip_loss.py:82-84)
+void flip_hunt_lab64(const double A[9], const double illum[3], const double rgb[3], double lab[3]) {
+  double f[3];
+  for (int i = 0; i < 3; ++i) {
+    const double t = (A[3 * i] * rgb[0] + A[3 * i + 1] * rgb[1] + A[3 * i + 2] * rgb[2]) / illum[i];
+    const double delta = 6.0 / 29.0;
+    f[i] = t > 0.00885 ? std::pow(t, 1.0 / 3.0) : t / (3 * delta * delta) + 4.0 / 29.0;
+  }
+  lab[0] = 116 * f[1] - 16;
+  lab[1] = 0.01 * lab[0] * (500 * (f[0] - f[1]));
+  lab[2] = 0.01 * lab[0] * (200 * (f[1] - f[2]));
+}
+
+int flip_prepare(adanerf_ctx* c, double ppd) {
+  if (c->flip_tab.p && c->flip_ppd == ppd) return ADANERF_OK;
+  const int rc = static_cast<int>(std::ceil(3 * std::sqrt(0.04 / (2 * kFlipPi * kFlipPi)) * ppd));      // the largest scale parameter is BY's 0.04
+  const double sd = 0.5 * 0.082 * ppd;
+  const int rf = static_cast<int>(std::ceil(3 * sd));
+  if (rc < 1 || rf < 1 || rc > kFlipMaxRadius || rf > kFlipMaxRadius)
+    return fail(c, ADANERF_EINVAL, "adanerf_flip: filter radius outside 1.." + std::to_string(kFlipMaxRadius) + " at this pixels_per_degree");
+  const size_t nc = static_cast<size_t>(2 * rc + 1) * (2 * rc + 1), nf = static_cast<size_t>(2 * rf + 1) * (2 * rf + 1);
+  std::vector<float> tab(3 * nc + 2 * nf);
+  flip_spatial_filter(ppd, rc, 1, 0.0047, 0, 1e-5, tab.data());
+  flip_spatial_filter(ppd, rc, 1, 0.0053, 0, 1e-5, tab.data() + nc);
+  flip_spatial_filter(ppd, rc, 34.1, 0.04, 13.5, 0.025, tab.data() + 2 * nc);
+  flip_feature_filter(sd, rf, false, tab.data() + 3 * nc);
+  flip_feature_filter(sd, rf, true, tab.data() + 3 * nc + nf);
+
+  FlipParams& p = c->flip_params;
+  p = FlipParams{};
+  p.rc = rc;
+  p.rf = rf;
+  p.halo = std::max(rc, rf);
+  // flip_loss.py:264-272 (D65); the reference holds the matrix in fp32 and inverts that
+  const double frac[9] = {10135552.0 / 24577794, 8788810.0 / 24577794, 4435075.0 / 24577794, 2613072.0 / 12288897, 8788810.0 / 12288897,
+                          887015.0 / 12288897,   1425312.0 / 73733382, 8788810.0 / 73733382, 70074185.0 / 73733382};
+  double A[9], inv[9], illum[3];
+  for (int i = 0; i < 9; ++i) A[i] = p.rgb2xyz[i] = static_cast<float>(frac[i]);
+  const double det = A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6]) + A[2] * (A[3] * A[7] - A[4] * A[6]);
+  inv[0] = (A[4] * A[8] - A[5] * A[7]) / det;
+  inv[1] = (A[2] * A[7] - A[1] * A[8]) / det;
+  inv[2] = (A[1] * A[5] - A[2] * A[4]) / det;
+  inv[3] = (A[5] * A[6] - A[3] * A[8]) / det;
+  inv[4] = (A[0] * A[8] - A[2] * A[6]) / det;
+  inv[5] = (A[2] * A[3] - A[0] * A[5]) / det;
+  inv[6] = (A[3] * A[7] - A[4] * A[6]) / det;
+  inv[7] = (A[1] * A[6] - A[0] * A[7]) / det;
+  inv[8] = (A[0] * A[4] - A[1] * A[3]) / det;
+  for (int i = 0; i < 9; ++i) p.xyz2rgb[i] = static_cast<float>(inv[i]);
+  for (int i = 0; i < 3; ++i) p.illum[i] = static_cast<float>(illum[i] = A[3 * i] + A[3 * i + 1] + A[3 * i + 2]);
+  p.lab_div = static_cast<float>(3 * (6.0 / 29.0) * (6.0 / 29.0));
+  p.lab_add = static_cast<float>(4.0 / 29.0);
+  // cmax = HyAB(green, blue) ^ qc in fp64; redistribute_errors' scalars (pc = 0.4, pt = 0.95) go to fp32 as torch applies them
+  const double green[3] = {0, 1, 0}, blue[3] = {0, 0, 1};
+  double lg[3], lb[3];
+  flip_hunt_lab64(A, illum, green, lg);
+  flip_hunt_lab64(A, illum, blue, lb);
+  const double cmax = std::pow(std::fabs(lg[0] - lb[0]) + std::sqrt((lg[1] - lb[1]) * (lg[1] - lb[1]) + (lg[2] - lb[2]) * (lg[2] - lb[2])), 0.7);
+  const double pccmax = 0.4 * cmax;
+  p.pccmax = static_cast<float>(pccmax);
+  p.lo_scale = static_cast<float>(0.95 / pccmax);
+  p.hi_div = static_cast<float>(cmax - pccmax);
+  p.pt = static_cast<float>(0.95);
+  p.one_minus_pt = static_cast<float>(1.0 - 0.95);
+  p.inv_sqrt2 = static_cast<float>(1 / std::sqrt(2.0));
+
+  int rc_ = dev_alloc(c, &c->flip_tab, tab.size() * sizeof(float));
+  if (rc_) return rc_;
+  c->flip_ppd = 0.0;
+  HIP_TRY(c, hipMemcpyAsync(c->flip_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // `tab` leaves scope
+  c->flip_ppd = ppd;
+  return ADANERF_OK;
+}
+
+int launch_flip(adanerf_ctx* c, const float* d_test, const float* d_ref, int width, int height, double ppd, float* d_map, float* mean_out) {
+  int rc = flip_prepare(c, ppd);
+  if (rc) return rc;
+  FlipParams p = c->flip_params;
+  p.tiles_x = (width + kFlipTile - 1) / kFlipTile;
+  const int tiles = p.tiles_x * ((height + kFlipTile - 1) / kFlipTile);
+  if ((rc = dev_alloc(c, &c->flip_partial, static_cast<size_t>(tiles) * sizeof(double)))) return rc;
+  if ((rc = dev_alloc(c, &c->flip_mean, sizeof(float)))) return rc;
+  p.test = d_test;
+  p.ref = d_ref;
+  p.map = d_map;
+  p.partial = reinterpret_cast<double*>(c->flip_partial.p);
+  p.tab = reinterpret_cast<const float*>(c->flip_tab.p);
+  p.width = width;
+  p.height = height;
+  const int S = kFlipTile + 2 * p.halo;
+  const size_t lds = static_cast<size_t>(6) * S * S * sizeof(float);      // >= 24 KB: also holds the 2 KB reduction tree
+  if (lds > 64 * 1024 && !c->flip_lds_raised) {
+    constexpr int Smax = kFlipTile + 2 * kFlipMaxRadius;
+    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(flip_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 6 * Smax * Smax * static_cast<int>(sizeof(float))));
+    c->flip_lds_raised = true;
+  }
+  hipLaunchKernelGGL(flip_kernel, dim3(tiles), dim3(kFlipThreads), lds, c->stream, p);
+  HIP_TRY(c, hipGetLastError());
+  hipLaunchKernelGGL(flip_mean_kernel, dim3(1), dim3(kFlipThreads), 0, c->stream, reinterpret_cast<const double*>(c->flip_partial.p), tiles,
+                     static_cast<double>(width) * height, reinterpret_cast<float*>(c->flip_mean.p));
+  HIP_TRY(c, hipGetLastError());
+  if (mean_out) {
+    HIP_TRY(c, hipMemcpyAsync(mean_out, c->flip_mean.p, sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return ADANERF_OK;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1508,7 +1666,7 @@ int adanerf_destroy(adanerf_ctx* c) {
                     &c->ztab, &c->rays, &c->oracle, &c->ray_offsets, &c->ray_counts, &c->selbin, &c->selw, &c->block_total,
                     &c->block_offset, &c->total, &c->sample_key, &c->sample_w, &c->raw, &c->sample_z, &c->rsi_z,
                     &c->netc[0].w, &c->netc[0].b, &c->netc[1].w, &c->netc[1].b, &c->netc[2].w, &c->netc[2].b, &c->ztab_coarse, &c->raw_coarse, &c->key_coarse,
-                    &c->guard_mask, &c->refine_list, &c->guard_probe, &c->disp_scratch};
+                    &c->guard_mask, &c->refine_list, &c->guard_probe, &c->disp_scratch, &c->flip_tab, &c->flip_partial, &c->flip_mean};
   for (DevBuf* b : bufs) dev_free(b);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   delete c;
@@ -2120,6 +2278,23 @@ int adanerf_gather_to(adanerf_ctx* dst, void* d_dst, adanerf_ctx* src, const voi
   BIND(dst);
   HIP_TRY(c, hipStreamWaitEvent(dst->stream, src->peer_event, 0));
   return ADANERF_OK;
+}
+
+int adanerf_flip(adanerf_ctx* c, const float* d_test_rgb, const float* d_ref_rgb, int32_t width, int32_t height, float pixels_per_degree,
+                 float* d_error_map, float* mean_out) {
+  if (!c) return ADANERF_EINVAL;
+  if (!d_test_rgb || !d_ref_rgb) return fail(c, ADANERF_EINVAL, "adanerf_flip: NULL image");
+  if (width < 1 || height < 1) return fail(c, ADANERF_EINVAL, "adanerf_flip: width and height must be >= 1");
+  if (static_cast<int64_t>(width) * height > (1ll << 30)) return fail(c, ADANERF_EINVAL, "adanerf_flip: width * height exceeds 2^30");
+  const double ppd = pixels_per_degree <= 0.f ? kFlipDefaultPpd : static_cast<double>(pixels_per_degree);
+  if (!(ppd >= kFlipPpdMin && ppd <= kFlipPpdMax)) {      // also a NaN; a filter is never truncated to fit
+    char msg[160];
+    std::snprintf(msg, sizeof(msg), "adanerf_flip: pixels_per_degree %.6g outside the supported %.0f..%.0f (<= 0 selects the reference's %.4f)",
+                  ppd, kFlipPpdMin, kFlipPpdMax, kFlipDefaultPpd);
+    return fail(c, ADANERF_EINVAL, msg);
+  }
+  BIND(c);
+  return launch_flip(c, d_test_rgb, d_ref_rgb, width, height, ppd, d_error_map, mean_out);
 }
 
 int adanerf_probe_mfma(adanerf_ctx* c, int32_t operands, int32_t f16, float target_ms, float* tflops, float* clock_mhz) {

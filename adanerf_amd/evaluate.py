@@ -1,8 +1,11 @@
 """Image evaluation over a DONeRF-style dataset directory with the MI355X renderer -- the counterpart of the
 reference's ``src/evaluate.py`` "images" evaluation (``generate_data`` :164-342: render every test view, MSE /
-PSNR against the ground-truth PNG, mean samples per ray) for an exported model directory.
+PSNR against the ground-truth PNG, mean samples per ray) for an exported model directory.  ``--metrics psnr flip`` adds the
+reference's second default metric (``metrics = ["flip", "psnr"]`` :613-615): the mean FLIP error of ``generate_flip_data``
+(:120-145 over ``src/util/flip_loss.py``), computed on the GPU by ``adanerf_flip`` from the frame that is still in device memory.
 
     python -m adanerf_amd.evaluate <model_dir> <dataset_dir> [--set test] [--out DIR] [--video out.y4m] [--precision bf16]
+                                   [--metrics psnr flip]
 
 Dataset layout (src/datasets.py:146-213, 361-365, 480-542): ``dataset_info.json`` (``resolution``,
 ``camera_angle_x``, ``view_cell_center``, ``view_cell_size`` ...), ``transforms_<set>.json`` with
@@ -67,7 +70,13 @@ def psnr_from_mse(mse: float) -> float:
 
 def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: Optional[str] = None,
              precision: str = "bf16", batch_size: int = -1, max_frames: int = 0, quiet: bool = False,
-             video: Optional[str] = None, fps: int = 30):
+             video: Optional[str] = None, fps: int = 30, metrics=("psnr",)):
+    """metrics: "psnr" (always reported where a ground-truth image exists) and / or "flip": each record gains ``flip``, the summary
+    ``mean_flip``, and with out_dir the error map is written as an 8-bit greyscale ``%05d_flip.png``."""
+    unknown = sorted(set(metrics) - {"psnr", "flip"})
+    if unknown:
+        raise ValueError("unknown metrics %s (known: psnr, flip)" % unknown)
+    want_flip = "flip" in metrics
     meta, frames = load_dataset(dataset_dir, set_name)
     if max_frames > 0:
         frames = frames[:max_frames]
@@ -80,6 +89,8 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
         if out_dir:
             os.makedirs(out_dir, exist_ok=True)
         vid = Y4mWriter(video, w, h, fps) if video else None
+        d_ref = r.empty((w * h, 3), np.float32) if want_flip else None
+        d_map = r.empty((w * h,), np.float32) if want_flip and out_dir else None
         for i, fr in enumerate(frames):
             r.set_camera(fr["pose"], fr["rot"])
             rgb, rgba, st = r.render_numpy()
@@ -91,6 +102,11 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                 ref = gt[:, :, :3].astype(np.float32).reshape(-1, 3) / 255.0        # datasets.py:286-287
                 mse = float(np.mean((rgb.astype(np.float64) - ref) ** 2))
                 rec.update(mse=mse, psnr=psnr_from_mse(mse))
+                if want_flip:       # the rendered frame is still on the device (render_numpy); argument order of src/evaluate.py:144
+                    rec.update(flip=r.flip_device(r._o_rgb, d_ref.upload(ref), w, h, error_map=d_map))
+                    if d_map is not None:
+                        fm = np.nan_to_num(d_map.numpy().reshape(h, w), nan=1.0)      # the map lies in [0, 1]
+                        write_png(os.path.join(out_dir, "%05d_flip.png" % i), np.clip(np.rint(fm * 255.0), 0, 255).astype(np.uint8))
             if out_dir:
                 write_png(os.path.join(out_dir, "%05d.png" % i), rgba[:, :3].reshape(h, w, 3))
             if vid:
@@ -106,6 +122,8 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                    mean_ms=float(np.mean([x["ms"] for x in results])) if results else 0.0)
     if with_gt:
         summary.update(mean_psnr=float(np.mean([x["psnr"] for x in with_gt])), mean_mse=float(np.mean([x["mse"] for x in with_gt])))
+        if want_flip:
+            summary.update(mean_flip=float(np.mean([x["flip"] for x in with_gt])))
     return summary, results
 
 
@@ -120,8 +138,11 @@ def main(argv=None):
     ap.add_argument("--max-frames", type=int, default=0)
     ap.add_argument("--video", default=None, help="also write the rendered frames as an uncompressed .y4m video")
     ap.add_argument("--fps", type=int, default=30)
+    ap.add_argument("--metrics", nargs="+", default=["psnr"], choices=["psnr", "flip"],
+                    help="flip: also the mean FLIP error per frame (and, with --out, its map as %%05d_flip.png)")
     a = ap.parse_args(argv)
-    summary, _ = evaluate(a.model_dir, a.dataset_dir, a.set, a.out, a.precision, a.batch_size, a.max_frames, video=a.video, fps=a.fps)
+    summary, _ = evaluate(a.model_dir, a.dataset_dir, a.set, a.out, a.precision, a.batch_size, a.max_frames, video=a.video, fps=a.fps,
+                          metrics=tuple(a.metrics))
     print(json.dumps(summary))
 
 

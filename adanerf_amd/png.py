@@ -1,5 +1,5 @@
 """Minimal PNG codec on zlib (no imageio / cv2 in this image): 8-bit gray / RGB / RGBA, non-interlaced,
-all five scanline filters on read; RGB or RGBA, filter 0 on write.  Enough for DONeRF dataset images
+all five scanline filters on read; gray, RGB or RGBA, filter 0 on write.  Enough for DONeRF dataset images
 (reference loader: src/datasets.py:275-287, imageio.imread(...)[:, :, :3] / 255)."""
 import struct
 import zlib
@@ -65,11 +65,13 @@ def read_png(path: str) -> np.ndarray:
 
 
 def write_png(path: str, img: np.ndarray) -> None:
-    """uint8 [h, w, 3|4] -> PNG (filter 0, zlib level 6)."""
+    """uint8 [h, w, 3|4] (or [h, w] / [h, w, 1]: greyscale) -> PNG (filter 0, zlib level 6)."""
     img = np.ascontiguousarray(img, dtype=np.uint8)
+    if img.ndim == 2:
+        img = img[:, :, None]
     h, w, c = img.shape
-    if c not in (3, 4):
-        raise ValueError("write_png expects RGB or RGBA")
+    if c not in (1, 3, 4):
+        raise ValueError("write_png expects gray, RGB or RGBA")
     raw = np.zeros((h, w * c + 1), dtype=np.uint8)
     raw[:, 1:] = img.reshape(h, w * c)
 
@@ -78,6 +80,6 @@ def write_png(path: str, img: np.ndarray) -> None:
 
     with open(path, "wb") as f:
         f.write(_SIG)
-        f.write(chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2 if c == 3 else 6, 0, 0, 0)))
+        f.write(chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, {1: 0, 3: 2, 4: 6}[c], 0, 0, 0)))
         f.write(chunk(b"IDAT", zlib.compress(raw.tobytes(), 6)))
         f.write(chunk(b"IEND", b""))

@@ -68,7 +68,7 @@ EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_las
            "adanerf_render", "adanerf_set_aux_outputs", "adanerf_set_disp_output", "adanerf_assemble_strips", "adanerf_sync", "adanerf_set_stream", "adanerf_set_profiling",
            "adanerf_collect_stats", "adanerf_ray_features", "adanerf_sample_mlp",
            "adanerf_compact", "adanerf_compact_guarded", "adanerf_calibrate_guard", "adanerf_guard_calibration_file", "adanerf_shade_features", "adanerf_shade_mlp", "adanerf_shade_mlp_z", "adanerf_sample_pdf", "adanerf_sample_uniform", "adanerf_shade_mlp_coarse", "adanerf_sample_from_coarse",
-           "adanerf_composite", "adanerf_composite_classic", "adanerf_copy_result_sampling_network",
+           "adanerf_composite", "adanerf_composite_classic", "adanerf_copy_result_sampling_network", "adanerf_flip",
            "adanerf_render_oracle", "adanerf_gather_to", "adanerf_probe_mfma", "adanerf_malloc",
            "adanerf_free", "adanerf_memcpy_h2d", "adanerf_memcpy_d2h", "adanerf_get_buffer"]
 
@@ -117,6 +117,7 @@ def load_library(path: Optional[str] = None):
     lib.adanerf_sample_from_coarse.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
     lib.adanerf_composite_classic.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
     lib.adanerf_copy_result_sampling_network.argtypes = [vp, vp, i32, vp]
+    lib.adanerf_flip.argtypes = [vp, vp, vp, i32, i32, C.c_float, vp, C.POINTER(C.c_float)]
     lib.adanerf_render_oracle.argtypes = [vp, vp]
     lib.adanerf_gather_to.argtypes = [vp, vp, vp, vp, C.c_size_t]
     lib.adanerf_probe_mfma.argtypes = [vp, i32, i32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
@@ -360,13 +361,54 @@ class NeuralRenderer:
         self._check(self.lib.adanerf_copy_result_sampling_network(self.handle, _ptr(oracle), n_rays, _ptr(rgba8_out)))
 
     def render_numpy(self):
-        """Convenience for tests/tools: renders and returns (rgb fp32 [R,3], rgba8 [R,4], Stats)."""
+        """Convenience for tests/tools: renders and returns (rgb fp32 [R,3], rgba8 [R,4], Stats).  The device copies stay in
+        ``_o_rgb`` / ``_o_rgba`` until the next call (the evaluator scores the frame from there)."""
         n = self.info.rays_local
         if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
             self._o_rgb = self.empty((n, 3), np.float32)
             self._o_rgba = self.empty((n, 4), np.uint8)
         st = self.render(self._o_rgba, self._o_rgb, stats=True)
         return self._o_rgb.numpy(), self._o_rgba.numpy(), st
+
+    # -- image metrics -----------------------------------------------------------------------------
+    def flip_device(self, test_rgb, ref_rgb, width: int, height: int, pixels_per_degree: Optional[float] = None, error_map=None,
+                    mean: bool = True) -> Optional[float]:
+        """FLIP of two device images ([height*width, 3] fp32 sRGB, the layout of render()'s rgb_out) as the reference's evaluation
+        computes it (src/evaluate.py:120-145 over src/util/flip_loss.py).  error_map: optional device [height*width] fp32.  Returns the
+        mean error (synchronous); with mean=False nothing is read back and the map is complete after sync().  pixels_per_degree None:
+        the reference's 67.02."""
+        m = C.c_float(0)
+        self._check(self.lib.adanerf_flip(self.handle, _ptr(test_rgb), _ptr(ref_rgb), width, height,
+                                          0.0 if pixels_per_degree is None else float(pixels_per_degree), _ptr(error_map),
+                                          C.byref(m) if mean else None))
+        return float(m.value) if mean else None
+
+    def flip(self, test_rgb, ref_rgb, width: Optional[int] = None, height: Optional[int] = None, pixels_per_degree: Optional[float] = None,
+             return_map: bool = False):
+        """FLIP of two host images: numpy [h, w, 3], or [h*w, 3] with width / height given (default: this renderer's frame).  Returns
+        the mean, or (mean, map [h, w] fp32) with return_map."""
+        t, r = np.asarray(test_rgb, dtype=np.float32), np.asarray(ref_rgb, dtype=np.float32)
+        if t.shape != r.shape:
+            raise ValueError("flip: images differ in shape: %s and %s" % (t.shape, r.shape))
+        if t.ndim == 3 and t.shape[2] == 3:
+            h, w = t.shape[:2]
+            if (width not in (None, w)) or (height not in (None, h)):
+                raise ValueError("flip: %dx%d images, width / height say %sx%s" % (w, h, width, height))
+        elif t.ndim == 2 and t.shape[1] == 3:
+            w, h = width or self.settings.width, height or self.settings.height
+            if w * h != t.shape[0]:
+                raise ValueError("flip: %d pixels are not %d x %d" % (t.shape[0], w, h))
+        else:
+            raise ValueError("flip: expected [h, w, 3] or [h*w, 3], got %s" % (t.shape,))
+        bufs = [DeviceArray(self, (h * w, 3), np.float32).upload(t.reshape(-1, 3)), DeviceArray(self, (h * w, 3), np.float32).upload(r.reshape(-1, 3))]
+        if return_map:
+            bufs.append(DeviceArray(self, (h * w,), np.float32))
+        try:
+            mean = self.flip_device(bufs[0], bufs[1], w, h, pixels_per_degree, bufs[2] if return_map else None)
+            return (mean, bufs[2].numpy().reshape(h, w)) if return_map else mean
+        finally:
+            for b in bufs:
+                b.free()
 
     def sync(self):
         self._check(self.lib.adanerf_sync(self.handle))

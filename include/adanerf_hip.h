@@ -24,6 +24,8 @@
  *   adanerf_shade_mlp                    contexts[1]->executeV2 (src/imagegenerator.cpp:336-344)
  *   adanerf_composite                    copyResultRaymarchAdaptiveMultDepth
  *                                        (include/cuda/adanerf_cuda_kernels.cuh:30-32)
+ *   adanerf_flip                         generate_flip_data (src/evaluate.py:120-145 of the reference's PyTorch tree) over
+ *                                        FLIP.compute_flip (src/util/flip_loss.py:61-105)
  *
  * Numerics follow the reference's PyTorch path (src/evaluate.py over nerf_raymarch_common.py /
  * features.py / models.py) wherever it disagrees with the viewer.
@@ -435,6 +437,27 @@ int adanerf_composite_classic(adanerf_ctx* ctx, const float* d_raw, const float*
 int adanerf_composite(adanerf_ctx* ctx, const float* d_raw, const float* d_sample_w,
                       const int32_t* d_ray_offsets, const int32_t* d_ray_counts, int32_t n_rays,
                       float* d_rgb_out, void* d_rgba8_out);
+
+/* ---- image metrics ---- */
+
+/* FLIP (Andersson et al. 2020) between two images as the reference's evaluation computes it (src/evaluate.py:120-145 over
+ * src/util/flip_loss.py:61-105): both images to YCxCz (sRGB clamped to [0, 1] first); colour pipeline = contrast-sensitivity filters
+ * A / RG / BY (replicate padding) -> clamped linear RGB -> L*a*b* -> Hunt adjustment -> HyAB ^ 0.7 -> redistribute_errors (pc 0.4,
+ * pt 0.95, cmax computed in fp64); feature pipeline = edge and point detectors on (Y + 16) / 116 in x and transposed;
+ * map = dE_c ^ (1 - dE_f) per pixel (IEEE pow: 0 ^ 0 = 1), mean = its average.  The metric is symmetric in the two images.
+ *   d_test_rgb, d_ref_rgb  [height*width,3] fp32, row-major, sRGB: the layout of adanerf_render's d_rgb_f32_out; values outside
+ *                          [0, 1] are clamped as the reference clamps them, a NaN reaches every map pixel within the filter radius
+ *                          and the mean
+ *   width, height          of the two images; independent of the context's frame size; width * height <= 2^30
+ *   pixels_per_degree      <= 0 selects the reference's 0.7 * (3840 / 0.7) * pi / 180 = 67.02; supported: 10 .. 140 (filter radii up to
+ *                          19 / 18 pixels); anything else returns ADANERF_EINVAL -- a filter is never truncated
+ *   d_error_map            [height*width] fp32 or NULL
+ *   mean_out               host pointer or NULL; non-NULL makes the call synchronous, with NULL the map is complete after adanerf_sync()
+ * Runs on the context's stream; filter tables and per-tile sums live in context-owned scratch, grown on demand and freed by
+ * adanerf_destroy.  One fused kernel per 32 x 32 tile plus a fixed-order reduction (no floating-point atomics): the same inputs give the
+ * same bits. */
+int adanerf_flip(adanerf_ctx* ctx, const float* d_test_rgb, const float* d_ref_rgb, int32_t width, int32_t height,
+                 float pixels_per_degree, float* d_error_map, float* mean_out);
 
 /* ---- measurement hook (bench.py's roofline) ---- */
 
