@@ -9,7 +9,7 @@ CSRC = os.path.join(HERE, "csrc")
 HOST = os.path.join(HERE, "host")
 LIBDIR = os.path.join(HERE, "lib")
 BINDIR = os.path.join(HERE, "bin")
-LIB_SOURCES = ["adanerf_hip.hip", "launch_f32.hip", "format.cpp", "pack.cpp"]
+LIB_SOURCES = ["adanerf_hip.hip", "launch_f32.hip", "model_setup.cpp", "guard_record.cpp", "flip_tables.cpp", "format.cpp", "pack.cpp"]
 _INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
 
 

@@ -10,7 +10,6 @@
 
 namespace adanerf {
 
-constexpr int kMaxCoarse = 128;      // coarse samples per ray (their depths are a table, like the 128 bins)
 constexpr int kFineRaysPerBlock = 64;
 
 // Rays as RayMarchFromPoses makes them without a SpherePosDir in front (src/features.py:417-428): origin = the camera

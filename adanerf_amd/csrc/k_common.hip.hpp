@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include "layout.hpp"
 #include "pack.hpp"
+#include "params.hpp"   // RayGenParams, ShadeParams, kNorm*: the plain structs the host fills
 
 namespace adanerf {
 
@@ -29,34 +30,6 @@ struct NetParams {
   uint32_t n_bias;           // floats in `bias` (the run-time-shaped kernels copy the whole table to LDS once per workgroup)
   float out_scale[2];        // shading nets: factors that take the kernel's alpha / rgb outputs back to the network's own scale (exact
                              // powers of two; 1 unless the bf16 packing scaled the layers: pack.hpp PackedNet::out_exp)
-};
-
-// Everything ray generation needs (A1 + A2).  Doubles mirror the float64 numpy ray table of
-// src/util/raygeneration.py:10-26.
-struct RayGenParams {
-  double start_x, x_pp, start_y, y_pp, focal;
-  int32_t w, h;
-  int32_t strip_rows, world, rank;     // round-robin strip sharding of image rows
-  int32_t use_ndc;
-  float rot[9];                        // row-major c2w
-  float pos[3];
-  float center[3];
-  float rad2;                          // ||view_cell_size/2||^2
-  float ndc_sw, ndc_sh;                // -1/(W/(2 focal)), -1/(H/(2 focal))
-};
-
-// rayMarchNormalization (src/nerf_raymarch_common.py:195-244)
-enum { kNormNone = 0, kNormInverseSqrtDistCentered = 1, kNormCentered = 2, kNormMaxDepth = 3, kNormMaxDepthCentered = 4, kNormLogCentered = 5,
-       kNormInverseDistCentered = 6 };
-
-struct ShadeParams {
-  float center[3];                     // view_cell_center, or rayMarchNormalizationCenter when the config sets three values
-  float max_depth;
-  float sqrt_max_depth;
-  int32_t normalize;                   // kNorm*
-  int32_t unit_dir;                    // 1: PE(dir/|dir|) (NDC), 0: PE(dir) as received
-  float log_max_depth_p1;              // math.log(max_depth + 1): kNormLogCentered
-  const float* ztab;                   // [128] world depth per bin
 };
 
 // ------------------------------------------------------------------------------------------

@@ -11,11 +11,6 @@ namespace adanerf {
 // DONeRF inverse-CDF sampler (FromClassifiedDepth) + classic sigma/delta compositing
 // ------------------------------------------------------------------------------------------
 
-struct DepthMap {          // warped depth t in [0,1] -> world depth (src/util/depth_transformations.py:37-58)
-  float d0, d1;
-  int32_t log_transform;   // 1: (d1-d0+1)^t - 1 + d0, 0: t (d1-d0) + d0
-};
-
 // wave sums / scans: the DPP forms of k_common.hip.hpp (see there for why not __shfl)
 __device__ __forceinline__ float wave_sum_f32(float v) { return wave_sum_dpp_f32(v); }
 __device__ __forceinline__ float wave_incl_scan_f32(float v, int) { return wave_incl_sum_dpp_f32(v); }

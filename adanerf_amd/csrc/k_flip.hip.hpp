@@ -7,7 +7,7 @@
 // evaluated from LDS as direct 2-D convolutions, the error map is written, and the workgroup leaves one partial sum (fp64, LDS tree
 // in a fixed order).  flip_mean_kernel adds the partial sums in a fixed order: no floating-point atomics, so the mean is reproducible
 // bit for bit.  Filter tables and radii arrive at run time (they depend on pixels per degree); the host builds them in fp64 as the
-// reference does (adanerf_hip.hip flip_prepare).  Every clamp and maximum keeps a NaN, as torch.clamp / torch.max do (fminf / fmaxf
+// reference does (flip_tables.cpp).  Every clamp and maximum keeps a NaN, as torch.clamp / torch.max do (fminf / fmaxf
 // would drop it); lane exchanges: none.
 #pragma once
 #include "k_common.hip.hpp"
@@ -16,24 +16,6 @@ namespace adanerf {
 
 constexpr int kFlipTile = 32;          // output tile edge; 256 threads, thread (tx, ty) owns pixels (tx, ty + 8 k), k = 0..3
 constexpr int kFlipThreads = 256;
-constexpr int kFlipMaxRadius = 19;     // colour radius at 140 pixels per degree: (32 + 38)^2 x 6 planes x 4 B = 117.6 KB of the CU's 160 KB
-
-struct FlipParams {
-  const float* test;     // [h*w,3] sRGB
-  const float* ref;      // [h*w,3] sRGB
-  float* map;            // [h*w] or null
-  double* partial;       // [tiles] one sum per workgroup
-  const float* tab;      // A, RG, BY [(2 rc + 1)^2] each, then edge, point [(2 rf + 1)^2] each (x direction; y is the transpose)
-  int32_t width, height, tiles_x;
-  int32_t rc, rf, halo;  // filter radii of the colour / feature pipeline; halo = max of the two
-  float rgb2xyz[9];      // flip_loss.py:264-272, fp32 as torch.Tensor holds it
-  float xyz2rgb[9];      // its inverse
-  float illum[3];        // A (1,1,1)
-  float lab_div, lab_add;          // 3 (6/29)^2, 4/29
-  float pccmax, lo_scale, hi_div;  // redistribute_errors: pc cmax, pt / (pc cmax), cmax - pc cmax
-  float pt, one_minus_pt;
-  float inv_sqrt2;
-};
 
 __device__ __forceinline__ float flip_clamp01(float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); }      // NaN stays NaN
 

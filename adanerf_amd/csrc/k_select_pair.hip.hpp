@@ -49,9 +49,6 @@ __host__ __device__ inline uint32_t audit_bits(int period, int phase, int seg) {
   return pattern << ((phase + seg) & (period - 1));
 }
 
-// src/nerf_raymarch_common.py:624-630 / 686-690: BCEWithLogitsLoss -> sigmoid, CrossEntropyLoss[Weighted] -> softmax over the bins
-constexpr int kOracleRaw = 0, kOracleSigmoid = 1, kOracleSoftmax = 2;
-
 // SelectOut::guard_eps for a bound eps on the raw outputs (host side; see pair_select)
 inline float guard_band_of(int transform, float eps) {
   return transform == kOracleSigmoid ? 0.25f * eps : (transform == kOracleSoftmax ? 1.01f * (__builtin_expf(2.0f * eps) - 1.0f) : eps);

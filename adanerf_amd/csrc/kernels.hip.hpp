@@ -1,5 +1,5 @@
 // gfx950 (CDNA4, wave64) kernels of the AdaNeRF per-frame hot path.  Device code only; the C ABI
-// in adanerf_hip.hip launches these.  Stage map:
+// in adanerf_hip.hip launches these (the fp32-MFMA ones through launch_f32.hip).  The plain structs the host fills are in params.hpp.  Stage map:
 //   A1+A2+A3  sample_mlp_kernel      ray gen -> sphere exit -> oracle PE -> 8-layer sampling MLP (fp32 MFMA)
 //   A4        select_kernel / scan_blocks_kernel / expand_kernel   top-N + threshold, deterministic compaction
 //   A5+A6     shade_mlp16_kernel / shade_mlp32_kernel   fused PE + 8x256 shading MLP (bf16/f16/f32 MFMA)

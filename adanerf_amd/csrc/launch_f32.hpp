@@ -4,28 +4,25 @@
 // split-precision sampling kernel) and that option slows these two down (fp32 sampling 5.3 -> 9.6 ms, fp32 shading
 // 60 -> 67 ms): their accumulators belong in AGPRs.
 #pragma once
-#include <hip/hip_runtime.h>
+#include "launch.hpp"
 
 namespace adanerf {
 struct SampleArgs;
 struct ShadeArgs;
 struct GenericTopo;
 
-// sample_mlp_kernel<10,4> (full = true) or <2,2>; grid = ceil(n_rays / 128) workgroups of 256 threads
-hipError_t launch_sample_mlp_f32(const SampleArgs& a, bool full, unsigned grid, hipStream_t stream);
-// persistent grid of shade_mlp32_kernel<10,4> for a device with `compute_units` CUs
-hipError_t shade_mlp_f32_grid(int compute_units, int* grid);
-hipError_t launch_shade_mlp_f32(const ShadeArgs& a, int grid, hipStream_t stream);
+// sample_mlp_kernel<10,4> (enc = kEnc10_4) or <2,2> (kEnc2_2); grid = ceil(n_rays / 128) workgroups of 256 threads
+hipError_t launch_sample_mlp_f32(const SampleArgs& a, int enc, unsigned grid, hipStream_t stream);
+// shade_mlp32_kernel<10,4> over `tiles` 128-sample tiles on its persistent grid
+hipError_t launch_shade_mlp_f32(GridCache& gc, const ShadeArgs& a, int tiles, hipStream_t stream);
 
 // Generic-topology kernels (k_generic_f32.hip.hpp): width 64 / 128 / 256, run-time depth / skip / raySampleInput; width 512 (kWideWidth)
-// in the wide form: 16-sample blocks, 64 rays / samples per workgroup (the launchers size the sampling grid themselves; the shading
+// in the wide form: 16-sample blocks, 64 rays / samples per workgroup (the sampling launcher sizes that grid itself; the shading
 // caller counts its tiles in 64 samples), no raySampleInput.
-// enc: slot layout of the positional encodings the network was packed with -- kEnc10_4, kEnc2_2 (sampling nets only) or
-// kEncMax (the catch-all kMaxBands-band layout: any posEncArgs).  hipErrorInvalidValue for a width / layout without an instantiation.
-enum { kEnc10_4 = 0, kEnc2_2 = 1, kEncMax = 2 };
+// enc: slot layout of the positional encodings the network was packed with (params.hpp) -- kEnc10_4, kEnc2_2 (sampling nets only) or
+// kEncMax.  hipErrorInvalidValue for a width / layout without an instantiation.
 hipError_t launch_sample_mlp_gen(const SampleArgs& a, const GenericTopo& t, int enc, int width, unsigned grid, hipStream_t stream);
-hipError_t shade_mlp_gen_grid(int compute_units, int enc, int width, int* grid);
-hipError_t launch_shade_mlp_gen(const ShadeArgs& a, const GenericTopo& t, int enc, int width, int grid, hipStream_t stream);
+hipError_t launch_shade_mlp_gen(GridCache& gc, const ShadeArgs& a, const GenericTopo& t, int enc, int width, int tiles, hipStream_t stream);
 
 // Measurement hook (k_probe.hip.hpp; include/adanerf_hip.h adanerf_probe_mfma): register-only v_mfma_f32_32x32x16_{bf16,f16} loops on every
 // CU for ~target_ms, operands 0 zero / 1 constant / 2 random / 3 relu-like, two accumulator chains per wave and one wave per SIMD (the

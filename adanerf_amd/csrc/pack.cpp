@@ -300,7 +300,7 @@ void emit_ray_samples(const VLayer& L, int A, int fp, int col_base, PackedNet* o
 
 }  // namespace
 
-// what every caller's NetShape must satisfy before any arithmetic on it (adanerf_create checks the same in setup_model; the host-only entry
+// what every caller's NetShape must satisfy before any arithmetic on it (adanerf_create checks the same in model_setup.cpp setup_model; the host-only entry
 // point adanerf_host_pack_weights builds its shape straight from config.ini): band counts the slot layouts exist for, raySampleInput in range
 static bool shape_ok(const NetShape& sh, std::string* err) {
   for (int f : {sh.fp0, sh.fd0, sh.fp1, sh.fd1})

@@ -33,7 +33,7 @@ void spit(const std::string& p, const std::vector<uint8_t>& b) {
   f.write(reinterpret_cast<const char*>(b.data()), static_cast<std::streamsize>(b.size()));
 }
 
-// the calls adanerf_create / adanerf_host_pack_weights make on a model directory (adanerf_hip.hip: setup_model, create); returns the
+// the calls adanerf_create / adanerf_host_pack_weights make on a model directory (model_setup.cpp: setup_model; adanerf_hip.hip: create_on); returns the
 // number of networks packed (0 = refused)
 int load_and_pack(const std::string& dir, std::string* why) {
   Config cfg;

@@ -285,7 +285,7 @@ def run_fine(r, raw, rays, n, tot_n, what):
 
 
 def coarse_table32(sc):
-    """The context's coarse depth table, computed independently of any kernel output: the host's fp32 arithmetic (adanerf_hip.hip:
+    """The context's coarse depth table, computed independently of any kernel output: the host's fp32 arithmetic (model_setup.cpp:
     torch.linspace's two-sided form + 0.5 / Nc, near (1 - t) + far t, the linear depth transform), which the library compiles without
     contraction, restated operation by operation"""
     F = np.float32

@@ -62,6 +62,10 @@ def test_dependency_list_is_the_include_closure():
     every_header = {f for f in os.listdir(csrc) if f.endswith((".hpp", ".h"))}
     assert every_header <= set(B.LIB_DEPS), "headers in csrc/ that no translation unit includes: %s" % sorted(every_header - set(B.LIB_DEPS))
     assert not any(f.startswith("x_") for f in os.listdir(csrc)), "experiment-only headers belong in tools/experiments/"
+    for src in B.LIB_SOURCES:      # device code stays in the two .hip units the ISA tests below compile
+        if src.endswith(".cpp"):
+            reached = [d for d in B.include_closure([src]) if d.endswith(".hip.hpp")]
+            assert not reached, "%s reaches device headers: %s" % (src, reached)
     h0 = B.source_hash()
     assert re.fullmatch(r"[0-9a-f]{16}", h0)
 
@@ -1246,9 +1250,9 @@ def test_host_loader_under_sanitizers_on_mutated_model_directories(tmp_path):
 
 
 def test_host_only_entry_points_under_sanitizers(tmp_path):
-    """tools/host_abi_sanitize.sh: the library's own host code (both .hip translation units compiled --cuda-host-only, format.cpp, pack.cpp)
+    """tools/host_abi_sanitize.sh: the library's own host code (both .hip translation units compiled --cuda-host-only, the five .cpp ones as they are)
     with -fsanitize=address,undefined, and adanerf_host_parse_model / _depth_table / _pack_weights called through the C ABI on 200 randomly
-    damaged model directories (tests/host_abi_fuzz.cpp).  Covers what the g++ harness above cannot: setup_model, i.e. every check
+    damaged model directories (tests/host_abi_fuzz.cpp).  Covers what the g++ harness above cannot: setup_model (csrc/model_setup.cpp), i.e. every check
     adanerf_create makes on config.ini / dataset_info.txt, and the shape adanerf_host_pack_weights derives from them (round 6: a saturated
     raySampleInput overflowed an int in the packer there)."""
     import shutil
