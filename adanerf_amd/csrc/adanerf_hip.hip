@@ -71,6 +71,7 @@ struct adanerf_ctx {
   bool guard_ev_pending = false;
   int guard_viol_seen = 0;
   int guard_mism_seen = 0;
+  bool guard_ev_stale = false;           // the copy in flight was taken under another (N, threshold): it must not widen the band in force
   int guard_widened = 0;
   uint32_t guard_frame = 0;              // frames rendered in guarded mode: the audit's rotating phase
   int debug_guard = 0;                   // $ADANERF_DEBUG_GUARD at create (measurement knobs, bit 0: no whole-row monitor; bits 1 / 2: which plain-fp16 sampling kernel)
@@ -92,7 +93,7 @@ struct adanerf_ctx {
   DevBuf overflow;                // int32 counter: rays whose oracle values came out non-finite
   PackedDev net1[3];              // shading net per precision (packed lazily)
   TensorMap net1_host;
-  DevBuf ztab;
+  DevBuf ztab;                    // [2][128]: the sampler's bin centres, the dense mode's depths (depth_table); ms.sp.ztab is the one in force
   // vanilla NeRF (ADANERF_SAMPLER_COARSE_FINE): model0.onnx is a NeRF net as well, evaluated at n_coarse uniform depths
   PackedDev netc[3];              // coarse net per precision (packed lazily)
   NetTopology topoc;
@@ -148,11 +149,10 @@ int hip_rc(adanerf_ctx* c, hipError_t e, const char* what) {
 
 int dev_alloc(adanerf_ctx* c, DevBuf* b, size_t bytes) {
   if (b->bytes >= bytes && b->p) return ADANERF_OK;
+  void* grown = nullptr;      // before the old one goes: a failed growth leaves the buffer usable
+  if (bytes) HIP_TRY(c, hipMalloc(&grown, bytes));
   if (b->p) HIP_TRY(c, hipFree(b->p));
-  b->p = nullptr;
-  b->bytes = 0;
-  if (bytes == 0) return ADANERF_OK;
-  HIP_TRY(c, hipMalloc(&b->p, bytes));
+  b->p = grown;
   b->bytes = bytes;
   return ADANERF_OK;
 }
@@ -193,6 +193,7 @@ int ensure_batch_buffers(adanerf_ctx* c, int n_rays, int n_max) {
   if (n_rays <= c->cap_rays && n_max <= c->cap_nmax) return ADANERF_OK;
   n_rays = std::max(n_rays, c->cap_rays);
   n_max = std::max(n_max, c->cap_nmax);
+  if (c->cap_rays > 0) HIP_TRY(c, hipStreamSynchronize(c->stream));      // growth frees buffers that enqueued frames may still use
   const size_t R = static_cast<size_t>(n_rays), S = R * static_cast<size_t>(n_max);
   const size_t nblk = (R + 31) / 32;     // segment totals: per 64 rays (select_kernel) or per 32 (pair selection)
   int rc;
@@ -554,6 +555,36 @@ int ensure_guard_band(adanerf_ctx* c) {
   return calibrate_guard(c, ADANERF_GUARD_CALIB_POSES, 1u, true, &d, &dp);
 }
 
+// The guarded selection's band belongs to (model, N, threshold): the state of a context before its first guarded frame -- bounds from
+// the options if they give any, else 0 = the key's calibration record or a measurement at that frame (ensure_guard_band); the audit
+// starts over.  The counters adanerf_stats documents as "since create" (and the device's running maxima behind them) go on; the per-frame
+// count of re-evaluated rays does not: only a fused guarded frame writes it, and the new pair may have none (cleared in stream order, so
+// the frames already enqueued still report theirs).
+int reset_guard_band(adanerf_ctx* c) {
+  if (c->sampling_mode == ADANERF_SAMPLING_GUARDED)      // first: the one step that can fail
+    HIP_TRY(c, hipMemsetAsync(reinterpret_cast<int32_t*>(c->total.p) + kTotalRefined, 0, sizeof(int32_t), c->stream));
+  const adanerf_options& opt = c->opt;
+  c->guard_eps = opt.guard_eps > 0.f ? opt.guard_eps : 0.f;
+  c->guard_eps_pair = (c->guard_eps > 0.f && opt.guard_eps_pair > 0.f) ? std::min(opt.guard_eps_pair, 2.0f * c->guard_eps) : 2.0f * c->guard_eps;
+  c->ms.info.guard_eps = c->guard_eps;
+  c->ms.info.guard_eps_pair = c->guard_eps_pair;
+  c->ms.info.guard_calib_source = c->guard_eps > 0.f ? ADANERF_GUARD_FROM_OPTIONS : ADANERF_GUARD_FROM_NONE;
+  c->ms.info.guard_calib_poses = 0;
+  c->guard_frame = 0;
+  c->guard_ev_stale = c->guard_ev_pending;
+  return ADANERF_OK;
+}
+
+// Context state that follows from the (N, threshold) select_samples left in ms.info: adanerf_create and adanerf_set_selection both end
+// here.  Buffer capacities follow the largest N the context has held (ensure_batch_buffers never shrinks); row strides, the selection
+// path, the compositing kernel and the calibration record's key are read off ms.info at every launch.
+int apply_selection(adanerf_ctx* c) {
+  if (int rc = ensure_batch_buffers(c, c->ms.info.batch_rays, c->ms.info.num_samples)) return rc;
+  if (int rc = reset_guard_band(c)) return rc;
+  c->ms.sp.ztab = reinterpret_cast<const float*>(c->ztab.p) + (c->ms.info.dense ? kBins : 0);
+  return ADANERF_OK;
+}
+
 constexpr int kShadeWaves = 8;   // one 8-wave workgroup per CU (two independent 4-wave workgroups measured 4.2-5.7 ms vs 3.8)
 
 int launch_shade_mlp(adanerf_ctx* c, const float* d_rays, const uint32_t* d_key, const int32_t* d_total, int max_samples, int prec,
@@ -660,7 +691,7 @@ int launch_composite(adanerf_ctx* c, const float* d_raw, const float* d_w, const
     aux.depth = d_depth;
     aux.acc = d_acc;
     aux.sample_key = d_key;      // null in dense mode: the bin of sample i is i & 127
-    aux.ztab = reinterpret_cast<const float*>(c->ztab.p);
+    aux.ztab = c->ms.sp.ztab;
   }
   if (c->ms.info.num_samples > 32)   // long rays (dense mode): one wave per ray, coalesced
     hipLaunchKernelGGL(composite_wave_kernel, dim3((n_rays + 3) / 4), dim3(256), 0, c->stream, reinterpret_cast<const float4*>(d_raw), d_w,
@@ -796,13 +827,8 @@ static int create_on(adanerf_ctx* c, const char* model_dir, const adanerf_option
   c->sampling_mode = opt->sampling_mode;
   c->model_dir = model_dir;
   if (const char* dbg = std::getenv("ADANERF_DEBUG_GUARD")) c->debug_guard = std::atoi(dbg);
-  c->guard_eps = opt->guard_eps > 0.f ? opt->guard_eps : 0.f;      // 0: the model's calibration record, or calibrated before the first guarded frame
-  c->guard_eps_pair = (c->guard_eps > 0.f && opt->guard_eps_pair > 0.f) ? std::min(opt->guard_eps_pair, 2.0f * c->guard_eps) : 2.0f * c->guard_eps;
   c->guard_audit_period = opt->guard_audit_period == 0 ? ADANERF_GUARD_AUDIT_PERIOD : std::max(opt->guard_audit_period, 0);
-  c->ms.info.guard_eps = c->guard_eps;
-  c->ms.info.guard_eps_pair = c->guard_eps_pair;
   c->ms.info.guard_audit_period = c->sampling_mode == ADANERF_SAMPLING_GUARDED ? c->guard_audit_period : 0;
-  c->ms.info.guard_calib_source = c->guard_eps > 0.f ? ADANERF_GUARD_FROM_OPTIONS : ADANERF_GUARD_FROM_NONE;
   if (c->sampling_mode == ADANERF_SAMPLING_GUARDED) c->model0_hash = fnv1a64_file(join_path(model_dir, "model0.onnx"));
   {   // topology of the shading net first (fp32 packing accepts every supported topology)
     PackedNet probe;
@@ -832,11 +858,13 @@ static int create_on(adanerf_ctx* c, const char* model_dir, const adanerf_option
   if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess) return bail(ADANERF_EDEVICE, "hipStreamCreate failed");
   c->stream = c->own_stream;
 
-  rc = dev_alloc(c, &c->ztab, kBins * sizeof(float));
+  rc = dev_alloc(c, &c->ztab, 2 * kBins * sizeof(float));
   if (rc) return bail(rc, c->err);
-  if (hipMemcpy(c->ztab.p, ms.ztab.data(), kBins * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+  float ztabs[2 * kBins];
+  depth_table(ms, false, ztabs);
+  depth_table(ms, true, ztabs + kBins);
+  if (hipMemcpy(c->ztab.p, ztabs, sizeof(ztabs), hipMemcpyHostToDevice) != hipSuccess)
     return bail(ADANERF_EDEVICE, "ztab upload failed");
-  c->ms.sp.ztab = reinterpret_cast<const float*>(c->ztab.p);
   if (c->ms.coarse_fine) {
     if ((rc = upload_net(c, p0, &c->netc[opt->precision]))) return bail(rc, c->err);
     if ((rc = dev_alloc(c, &c->ztab_coarse, kMaxCoarse * sizeof(float)))) return bail(rc, c->err);
@@ -861,7 +889,7 @@ static int create_on(adanerf_ctx* c, const char* model_dir, const adanerf_option
   if ((rc = dev_alloc(c, &c->overflow, 64))) return bail(rc, c->err);
   if (hipMemset(c->overflow.p, 0, 64) != hipSuccess) return bail(ADANERF_EDEVICE, "hipMemset failed");
   if ((rc = upload_net(c, p1, &c->net1[opt->precision]))) return bail(rc, c->err);
-  if ((rc = ensure_batch_buffers(c, c->ms.info.batch_rays, c->ms.info.num_samples))) return bail(rc, c->err);
+  if ((rc = apply_selection(c))) return bail(rc, c->err);
   *out = c;
   return ADANERF_OK;
 }
@@ -905,6 +933,31 @@ int adanerf_set_camera(adanerf_ctx* c, const float pos[3], const float rot[9]) {
   }
   std::memcpy(c->ms.rg.pos, pos, 3 * sizeof(float));
   std::memcpy(c->ms.rg.rot, rot, 9 * sizeof(float));
+  return ADANERF_OK;
+}
+
+int adanerf_set_selection(adanerf_ctx* c, int32_t num_samples, float threshold) {
+  BIND(c);
+  if (std::isnan(threshold)) return fail(c, ADANERF_EINVAL, "threshold is not a number (a negative value keeps the one in force)");
+  if (threshold >= 0.f && c->ms.info.sampler_mode != ADANERF_SAMPLER_ADAPTIVE)
+    return fail(c, ADANERF_EUNSUPPORTED, "this model's sampler takes no threshold (adanerf_create ignores options.threshold for it): pass a negative one");
+  ModelSetup& ms = c->ms;
+  const adanerf_info was = ms.info;
+  const ModelSetup::PosBound was_bound = ms.pos_bound;
+  const int was_n = ms.sel_n;
+  const float was_thr = ms.sel_thr;
+  std::vector<float> was_ztab = ms.ztab;
+  std::string err;
+  if (int rc = select_samples(&ms, num_samples, threshold, &err)) return fail(c, rc, err);
+  if (ms.info.num_samples == was.num_samples && ms.info.threshold == was.threshold) return ADANERF_OK;      // the pair in force: band and audit go on
+  if (int rc = apply_selection(c)) {      // the buffers could not grow: back to the pair that renders
+    ms.info = was;
+    ms.pos_bound = was_bound;
+    ms.sel_n = was_n;
+    ms.sel_thr = was_thr;
+    ms.ztab = std::move(was_ztab);
+    return rc;
+  }
   return ADANERF_OK;
 }
 
@@ -1205,6 +1258,12 @@ void poll_guard(adanerf_ctx* c) {
   std::memcpy(&seen, &c->guard_host[kSeenMax], sizeof(seen));
   std::memcpy(&pair, &c->guard_host[kSeenPair], sizeof(pair));
   const int viol = c->guard_host[kSeenViolations], mism = c->guard_host[kSeenAuditMismatch];
+  if (c->guard_ev_stale) {      // frames of the (N, threshold) before adanerf_set_selection: counted, but their band is gone
+    c->guard_ev_stale = false;
+    c->guard_viol_seen = std::max(c->guard_viol_seen, viol);
+    c->guard_mism_seen = std::max(c->guard_mism_seen, mism);
+    return;
+  }
   bool widened = false;
   if (viol > c->guard_viol_seen) {
     c->guard_viol_seen = viol;

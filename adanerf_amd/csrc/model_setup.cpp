@@ -126,17 +126,11 @@ int setup_model_unguarded(const char* model_dir, const adanerf_options* opt, Mod
     if (cf.losses[0] != "NeRFWeightMultiplicationLoss") ms->mult_mode = 0;   // no oracle weights in compositing
   }
 
-  int n_max = opt->num_samples > 0 ? opt->num_samples : cf.numRaymarchSamples.back();
-  float thr = opt->threshold >= 0.f ? opt->threshold : cf.adaptiveSamplingThreshold;
-  if (pdf_mode || coarse_fine) thr = 1.0f;   // unused by the inverse-CDF samplers; any positive value keeps the bin-centre depth table
   if (coarse_fine) {
-    // numRaymarchSamples = [Nc, Nf] (options.num_samples overrides Nf); every ray carries Nc + Nf samples through model1
+    // numRaymarchSamples = [Nc, Nf]; every ray carries Nc + Nf samples through model1 (select_samples)
     ms->n_coarse = cf.numRaymarchSamples[0];
     if (ms->n_coarse < 3 || ms->n_coarse > kMaxCoarse) return bad(ADANERF_EINVAL, "coarse/fine: numRaymarchSamples[0] must be in 3..128");
-    if (n_max < 1 || ms->n_coarse + n_max > 1024) return bad(ADANERF_EINVAL, "coarse/fine: numRaymarchSamples[1] must be >= 1 and Nc + Nf <= 1024");
-    n_max += ms->n_coarse;
   }
-  if (thr < 0.f) return bad(ADANERF_EUNSUPPORTED, "adaptiveSamplingThreshold < 0 is unsupported on the adaptive path (as in the reference)");
   // multiDepthFeatures = [D0, D1]: D0 outputs of the sampling network, D1 depth cells of the sampler (cell_size = 1 / D1); the
   // reference needs them equal (it indexes cells by output position).  D < 128 runs on 128-wide rows padded with absent bins
   // (pack.cpp); only the adaptive sampler with a threshold takes it -- dense mode and the inverse-CDF sampler walk all 128 bins.
@@ -144,11 +138,6 @@ int setup_model_unguarded(const char* model_dir, const adanerf_options* opt, Mod
   if (!cf.multiDepthFeatures.empty() && cf.multiDepthFeatures.front() != cf.multiDepthFeatures.back() && !coarse_fine)
     return bad(ADANERF_EUNSUPPORTED, "multiDepthFeatures entries differ: the sampler's cells are the sampling network's outputs");
   if (ms->bins < 1 || ms->bins > kBins) return bad(ADANERF_EUNSUPPORTED, "multiDepthFeatures must be in 1..128");
-  if (ms->bins != kBins && (pdf_mode || coarse_fine || thr == 0.f))
-    return bad(ADANERF_EUNSUPPORTED, "multiDepthFeatures != 128 is supported with the adaptive sampler and a threshold > 0 only");
-  if (ms->bins != kBins && n_max > ms->bins) return bad(ADANERF_EINVAL, "numRaymarchSamples exceeds multiDepthFeatures");
-  if (thr == 0.f && n_max != kBins) return bad(ADANERF_EUNSUPPORTED, "adaptiveSamplingThreshold == 0 (dense) requires numRaymarchSamples == 128");
-  if (!coarse_fine && (n_max < 1 || n_max > kBins)) return bad(ADANERF_EINVAL, "numRaymarchSamples must be in 1..128");
   if (opt->precision < 0 || opt->precision > 2) return bad(ADANERF_EINVAL, "precision must be ADANERF_PREC_{BF16,FP16,FP32}");
   if (opt->sampling_mode < 0 || opt->sampling_mode > 3) return bad(ADANERF_EINVAL, "sampling_mode must be ADANERF_SAMPLING_{SPLIT_FP16,FP32,FP16,GUARDED}");
   if (!(opt->guard_eps <= 1.0f)) return bad(ADANERF_EINVAL, "guard_eps must be <= 1 (<= 0 selects the default)");
@@ -174,15 +163,9 @@ int setup_model_unguarded(const char* model_dir, const adanerf_options* opt, Mod
   const int R = I.rays_local;
   if (static_cast<int64_t>(w) * h >= (1ll << 25)) return bad(ADANERF_EINVAL, "width*height must be < 2^25");
   I.batch_rays = (opt->batch_rays <= 0) ? std::max(R, 1) : std::min(opt->batch_rays, std::max(R, 1));
-  // sample offsets, keys and totals are int32 on the device
-  if (static_cast<int64_t>(I.batch_rays) * n_max > 0x7fffffffll)
-    return bad(ADANERF_EINVAL, "batch_rays * num_samples exceeds 2^31 - 1; use a smaller batch (-bs)");
   I.n_in0 = (ms->ray_samples * 3 + 3) * (2 * ms->fp0 + 1) + 3 + 6 * ms->fd0;     // src/features.py:738-740
   if (coarse_fine) I.n_in0 = 6 + 6 * (ms->fp0 + ms->fd0);                          // src/features.py:622
   I.n_in1 = 6 + 6 * (ms->fp1 + ms->fd1);
-  I.num_samples = n_max;
-  I.threshold = thr;
-  I.dense = thr == 0.f;
   I.use_ndc = ndc;
   I.sampler_mode = coarse_fine ? ADANERF_SAMPLER_COARSE_FINE : (pdf_mode ? ADANERF_SAMPLER_PDF : ADANERF_SAMPLER_ADAPTIVE);
   I.num_samples_coarse = ms->n_coarse;
@@ -248,27 +231,7 @@ int setup_model_unguarded(const char* model_dir, const adanerf_options* opt, Mod
     const float d0 = cf.depthRange[0], d1 = cf.depthRange[1];
     ms->rsi_z.push_back(ms->dm.log_transform ? powf(static_cast<float>(static_cast<double>(d1) - d0 + 1.0), t) - 1.0f + d0 : t * (d1 - d0) + d0);
   }
-  // ---- depth table: world depth of each of the 128 bins (A4/A5) ----
-  ms->ztab.resize(kBins);
-  const float znear = cf.zNear.empty() ? 0.001f : cf.zNear.back();
-  const float zfar = cf.zFar.empty() ? 1.0f : cf.zFar.back();
   const float d0 = cf.depthRange[0], d1 = cf.depthRange[1];
-  for (int k = 0; k < kBins; ++k) {
-    float t;
-    if (thr == 0.f) {
-      // src/nerf_raymarch_common.py:708-720: t = linspace(0,1,N+1)[:-1] + .5/N; z = near(1-t) + far t
-      float u = static_cast<float>(k) * (1.0f / kBins) + 0.5f / kBins;
-      t = znear * (1.0f - u) + zfar * u;
-    } else {
-      t = (static_cast<float>(k) + 0.5f) * (1.0f / static_cast<float>(ms->bins));   // (k + .5) * cell_size, cell_size = 1 / multiDepthFeatures, :726-741
-    }
-    float z;
-    if (ndc) z = t;                                            // ...NoDepthRange: :796-851
-    else if (cf.depthTransform == "log")                       // util/depth_transformations.py:37-48
-      z = powf(static_cast<float>(static_cast<double>(d1) - d0 + 1.0), t) - 1.0f + d0;
-    else z = t * (d1 - d0) + d0;                               // :57-58
-    ms->ztab[k] = z;
-  }
   // coarse/fine: LinearlySpacedZNearZFar.generate (src/nerf_raymarch_common.py:310-325): t = linspace(0,1,Nc+1)[:-1] + 0.5/Nc,
   // near (1-t) + far t with zNear[0] / zFar[0], then depth_transform.to_world over the depth range
   for (int k = 0; k < ms->n_coarse; ++k) {
@@ -281,29 +244,92 @@ int setup_model_unguarded(const char* model_dir, const adanerf_options* opt, Mod
     ms->ztab_coarse.push_back(cf.depthTransform == "log" ? powf(static_cast<float>(static_cast<double>(d1) - d0 + 1.0), zw) - 1.0f + d0
                                                          : zw * (d1 - d0) + d0);
   }
-  // bf16 shading nets are packed scaled (pack.cpp scale_layer): every ReLU layer carries a power of two that keeps its activations <= 1 for
-  // encoding inputs whose identity slots stay below kPosIdentityBound (positions) -- a scene whose sample positions can exceed it is refused here
-  // rather than clamped silently.  Positions: camera inside the view cell, samples up to the far end of the depth range along a unit ray.
-  if (opt->precision == ADANERF_PREC_BF16) {
-    double zmax = std::max<double>(std::fabs(cf.depthRange[1]), std::fabs(cf.max_depth));
-    for (float z : ms->ztab) zmax = std::max<double>(zmax, std::fabs(z));
-    for (float z : ms->ztab_coarse) zmax = std::max<double>(zmax, std::fabs(z));
+  // what bounds the sample positions of a bf16 shading net apart from the depth table in force (select_samples adds that and checks)
+  {
     double cmax = 0.0, off = 0.0;
     for (int i = 0; i < 3; ++i) {
       cmax = std::max<double>(cmax, std::fabs(cf.viewcellCenter[i]));
       off = std::max<double>(off, std::fabs(static_cast<double>(sp.center[i]) - cf.viewcellCenter[i]));
     }
     ModelSetup::PosBound& pb = ms->pos_bound;
-    pb.active = !ndc;
+    pb.active = opt->precision == ADANERF_PREC_BF16 && !ndc;
     pb.normalize = sp.normalize;
     pb.cmax = cmax;
-    pb.zmax = zmax;
     pb.off = off;
     pb.M = std::max<double>(cf.max_depth, 1e-30);
     pb.rad = rad;
     for (int i = 0; i < 3; ++i) pb.center[i] = cf.viewcellCenter[i];
-    double bound = pb.at(0.5 * rad);      // a camera inside the view cell
-    if (ndc) bound = 64.0;      // NDC cube [-1, 1]^3 for rays inside the frustum (positions o' + t d', t in [0, 1])
+  }
+  // ---- everything that follows from (N, threshold) ----
+  ms->sel_n = cf.numRaymarchSamples.back();
+  ms->sel_thr = cf.adaptiveSamplingThreshold;
+  return select_samples(ms, opt->num_samples, opt->threshold, err);
+}
+
+void depth_table(const ModelSetup& ms, bool dense, float* ztab128) {
+  const Config& cf = ms.cfg;
+  const float znear = cf.zNear.empty() ? 0.001f : cf.zNear.back();
+  const float zfar = cf.zFar.empty() ? 1.0f : cf.zFar.back();
+  const float d0 = cf.depthRange[0], d1 = cf.depthRange[1];
+  for (int k = 0; k < kBins; ++k) {
+    float t;
+    if (dense) {
+      // src/nerf_raymarch_common.py:708-720: t = linspace(0,1,N+1)[:-1] + .5/N; z = near(1-t) + far t
+      float u = static_cast<float>(k) * (1.0f / kBins) + 0.5f / kBins;
+      t = znear * (1.0f - u) + zfar * u;
+    } else {
+      t = (static_cast<float>(k) + 0.5f) * (1.0f / static_cast<float>(ms.bins));   // (k + .5) * cell_size, cell_size = 1 / multiDepthFeatures, :726-741
+    }
+    float z;
+    if (ms.info.use_ndc) z = t;                                // ...NoDepthRange: :796-851
+    else if (cf.depthTransform == "log")                       // util/depth_transformations.py:37-48
+      z = powf(static_cast<float>(static_cast<double>(d1) - d0 + 1.0), t) - 1.0f + d0;
+    else z = t * (d1 - d0) + d0;                               // :57-58
+    ztab128[k] = z;
+  }
+}
+
+int select_samples(ModelSetup* ms, int32_t num_samples, float threshold, std::string* err) {
+  auto bad = [&](int code, const std::string& msg) {
+    *err = msg;
+    return code;
+  };
+  const Config& cf = ms->cfg;
+  adanerf_info& I = ms->info;
+  const bool coarse_fine = ms->coarse_fine, pdf_mode = I.sampler_mode == ADANERF_SAMPLER_PDF;
+  const int n_req = num_samples > 0 ? num_samples : ms->sel_n;
+  const float thr_req = threshold >= 0.f ? threshold : ms->sel_thr;
+  int n_max = n_req;
+  float thr = thr_req;
+  if (pdf_mode || coarse_fine) thr = 1.0f;   // unused by the inverse-CDF samplers; any positive value keeps the bin-centre depth table
+  if (coarse_fine) {
+    // numRaymarchSamples = [Nc, Nf] (num_samples overrides Nf); every ray carries Nc + Nf samples through model1
+    if (n_max < 1 || ms->n_coarse + n_max > 1024) return bad(ADANERF_EINVAL, "coarse/fine: numRaymarchSamples[1] must be >= 1 and Nc + Nf <= 1024");
+    n_max += ms->n_coarse;
+  }
+  if (thr < 0.f) return bad(ADANERF_EUNSUPPORTED, "adaptiveSamplingThreshold < 0 is unsupported on the adaptive path (as in the reference)");
+  if (ms->bins != kBins && (pdf_mode || coarse_fine || thr == 0.f))
+    return bad(ADANERF_EUNSUPPORTED, "multiDepthFeatures != 128 is supported with the adaptive sampler and a threshold > 0 only");
+  if (ms->bins != kBins && n_max > ms->bins) return bad(ADANERF_EINVAL, "numRaymarchSamples exceeds multiDepthFeatures");
+  if (thr == 0.f && n_max != kBins) return bad(ADANERF_EUNSUPPORTED, "adaptiveSamplingThreshold == 0 (dense) requires numRaymarchSamples == 128");
+  if (!coarse_fine && (n_max < 1 || n_max > kBins)) return bad(ADANERF_EINVAL, "numRaymarchSamples must be in 1..128");
+  // sample offsets, keys and totals are int32 on the device
+  if (static_cast<int64_t>(I.batch_rays) * n_max > 0x7fffffffll)
+    return bad(ADANERF_EINVAL, "batch_rays * num_samples exceeds 2^31 - 1; use a smaller batch (-bs)");
+  // ---- depth table: world depth of each of the 128 bins (A4/A5) ----
+  std::vector<float> ztab(kBins);
+  depth_table(*ms, thr == 0.f, ztab.data());
+  // bf16 shading nets are packed scaled (pack.cpp scale_layer): every ReLU layer carries a power of two that keeps its activations <= 1 for
+  // encoding inputs whose identity slots stay below kPosIdentityBound (positions) -- a scene whose sample positions can exceed it is refused here
+  // rather than clamped silently.  Positions: camera inside the view cell, samples up to the far end of the depth range along a unit ray.
+  ModelSetup::PosBound pb = ms->pos_bound;
+  if (I.precision == ADANERF_PREC_BF16) {
+    double zmax = std::max<double>(std::fabs(cf.depthRange[1]), std::fabs(cf.max_depth));
+    for (float z : ztab) zmax = std::max<double>(zmax, std::fabs(z));
+    for (float z : ms->ztab_coarse) zmax = std::max<double>(zmax, std::fabs(z));
+    pb.zmax = zmax;
+    double bound = pb.at(0.5 * pb.rad);      // a camera inside the view cell
+    if (I.use_ndc) bound = 64.0;      // NDC cube [-1, 1]^3 for rays inside the frustum (positions o' + t d', t in [0, 1])
     if (!(bound <= kPosIdentityBound)) {
       char msg[256];
       std::snprintf(msg, sizeof(msg), "sample positions of this scene can reach %.3g after rayMarchNormalization: beyond the %.0f the bf16 shading path's "
@@ -311,6 +337,14 @@ int setup_model_unguarded(const char* model_dir, const adanerf_options* opt, Mod
       return bad(ADANERF_EUNSUPPORTED, msg);
     }
   }
+  // nothing above has touched *ms: a refused pair leaves it as it was
+  ms->sel_n = n_req;
+  ms->sel_thr = thr_req;
+  ms->pos_bound = pb;
+  ms->ztab = std::move(ztab);
+  I.num_samples = n_max;
+  I.threshold = thr;
+  I.dense = thr == 0.f;
   return ADANERF_OK;
 }
 

@@ -49,7 +49,9 @@ struct ModelSetup {
   int fp0 = 10, fd0 = 4, fp1 = 10, fd1 = 4;
   int ray_samples = 0;
   std::vector<float> rsi_z;
-  std::vector<float> ztab;
+  std::vector<float> ztab;       // depth table in force: bin centres, or the dense mode's t-values at threshold 0 (depth_table)
+  int sel_n = 0;                 // N and threshold as stated by the config or the last caller who overrode them (coarse/fine: Nf): what
+  float sel_thr = 0.f;           // "keep" means to select_samples
   int bins = 128;                 // multiDepthFeatures: depth cells of the adaptive sampler (src/nerf_raymarch_common.py:675-677, 726-727)
   DepthMap dm{};
   bool coarse_fine = false;
@@ -63,6 +65,14 @@ struct ModelSetup {
 // (tests/host_sanitize_fuzz.cpp runs the loader itself under ASan / UBSan on mutated directories).
 int setup_model(const char* model_dir, const adanerf_options* opt, ModelSetup* ms, std::string* err);
 int setup_model_unguarded(const char* model_dir, const adanerf_options* opt, ModelSetup* ms, std::string* err);
+
+// Everything a context derives from (N, threshold) on the host, for adanerf_create and adanerf_set_selection alike: resolves the pair
+// (num_samples <= 0 / threshold < 0 keep what is in force), validates it against the model and the batch size, and fills
+// info.num_samples / .threshold / .dense, ztab and pos_bound.zmax.  On failure *ms is unchanged.  Needs every model-derived field
+// of *ms (setup_model calls it last).
+int select_samples(ModelSetup* ms, int32_t num_samples, float threshold, std::string* err);
+// world depth of each of the 128 bins: the sampler's cell centres, or (dense) the dense mode's uniform t-values
+void depth_table(const ModelSetup& ms, bool dense, float* ztab128);
 
 // slot layout of an encoding pair (kEnc*, params.hpp): any pair but 10-4 (both networks) and 2-2 (sampling network) is packed into
 // the catch-all kMaxBands layout and runs on the run-time-shaped kernels

@@ -5,7 +5,11 @@ reference's second default metric (``metrics = ["flip", "psnr"]`` :613-615): the
 (:120-145 over ``src/util/flip_loss.py``), computed on the GPU by ``adanerf_flip`` from the frame that is still in device memory.
 
     python -m adanerf_amd.evaluate <model_dir> <dataset_dir> [--set test] [--out DIR] [--video out.y4m] [--precision bf16]
-                                   [--metrics psnr flip]
+                                   [--metrics psnr flip] [--sweep-thresholds T ...] [--sweep-samples N ...]
+
+``--sweep-thresholds`` / ``--sweep-samples`` render the set once per (N, threshold) of their cross product on ONE context
+(``NeuralRenderer.set_selection``: an AdaNeRF network is trained once and rendered at any sample budget) -- the two axes of a quality
+table; the summary gains ``sweep``, ``--out DIR`` writes into ``DIR/n<N>_t<threshold>/``.
 
 Dataset layout (src/datasets.py:146-213, 361-365, 480-542): ``dataset_info.json`` (``resolution``,
 ``camera_angle_x``, ``view_cell_center``, ``view_cell_size`` ...), ``transforms_<set>.json`` with
@@ -13,6 +17,7 @@ Dataset layout (src/datasets.py:146-213, 361-365, 480-542): ``dataset_info.json`
 [:3, 3], rotation = [:3, :3]), images ``<file_path>.png``.
 """
 import argparse
+import itertools
 import json
 import math
 import os
@@ -68,11 +73,22 @@ def psnr_from_mse(mse: float) -> float:
     return float("inf") if mse == 0 else 10.0 * math.log10(1.0 / mse)
 
 
+def sweep_dir_name(num_samples: int, threshold: float) -> str:
+    """Sub-directory of --out for one setting of a sweep: n<N>_t<threshold>, the threshold as %g prints it (n8_t0.1, n128_t0)."""
+    return "n%d_t%g" % (num_samples, threshold)
+
+
 def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: Optional[str] = None,
              precision: str = "bf16", batch_size: int = -1, max_frames: int = 0, quiet: bool = False,
-             video: Optional[str] = None, fps: int = 30, metrics=("psnr",)):
+             video: Optional[str] = None, fps: int = 30, metrics=("psnr",), sweep_thresholds=None, sweep_samples=None):
     """metrics: "psnr" (always reported where a ground-truth image exists) and / or "flip": each record gains ``flip``, the summary
-    ``mean_flip``, and with out_dir the error map is written as an 8-bit greyscale ``%05d_flip.png``."""
+    ``mean_flip``, and with out_dir the error map is written as an 8-bit greyscale ``%05d_flip.png``.
+
+    sweep_thresholds / sweep_samples (lists; either may be None = the model's own value): the set is rendered once per (N, threshold) of
+    their cross product, N outermost, all on the one context.  The summary is then ``{"frames": n, "sweep": [...]}`` with one
+    ``{num_samples, threshold, mean_psnr, mean_mse, mean_samples_per_ray, mean_ms[, mean_flip]}`` per setting (what a plain run of a
+    model with that setting reports), the records of all settings follow each other and carry ``num_samples`` / ``threshold``, and
+    out_dir gets one sub-directory per setting (sweep_dir_name)."""
     unknown = sorted(set(metrics) - {"psnr", "flip"})
     if unknown:
         raise ValueError("unknown metrics %s (known: psnr, flip)" % unknown)
@@ -86,37 +102,59 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
         if abs(r.info.fov - meta["fov"]) > 1e-4 and not quiet:
             print("warning: dataset camera_angle_x %.6f differs from the model's fov %.6f (the model's is used)" %
                   (meta["fov"], r.info.fov), file=sys.stderr)
-        if out_dir:
-            os.makedirs(out_dir, exist_ok=True)
         vid = Y4mWriter(video, w, h, fps) if video else None
         d_ref = r.empty((w * h, 3), np.float32) if want_flip else None
         d_map = r.empty((w * h,), np.float32) if want_flip and out_dir else None
-        for i, fr in enumerate(frames):
-            r.set_camera(fr["pose"], fr["rot"])
-            rgb, rgba, st = r.render_numpy()
-            rec = dict(frame=i, image=fr["image"], samples_per_ray=st.total_samples / float(w * h), ms=st.ms_total)
-            if os.path.exists(fr["image"]):
-                gt = read_png(fr["image"])
-                if gt.shape[0] != h or gt.shape[1] != w:
-                    raise ValueError("%s: expected %dx%d, got %dx%d" % (fr["image"], w, h, gt.shape[1], gt.shape[0]))
-                ref = gt[:, :, :3].astype(np.float32).reshape(-1, 3) / 255.0        # datasets.py:286-287
-                mse = float(np.mean((rgb.astype(np.float64) - ref) ** 2))
-                rec.update(mse=mse, psnr=psnr_from_mse(mse))
-                if want_flip:       # the rendered frame is still on the device (render_numpy); argument order of src/evaluate.py:144
-                    rec.update(flip=r.flip_device(r._o_rgb, d_ref.upload(ref), w, h, error_map=d_map))
-                    if d_map is not None:
-                        fm = np.nan_to_num(d_map.numpy().reshape(h, w), nan=1.0)      # the map lies in [0, 1]
-                        write_png(os.path.join(out_dir, "%05d_flip.png" % i), np.clip(np.rint(fm * 255.0), 0, 255).astype(np.uint8))
+
+        def render_set(out_dir, extra):
+            """one pass over the set at the selection in force -> its records"""
+            recs: List[dict] = []
             if out_dir:
-                write_png(os.path.join(out_dir, "%05d.png" % i), rgba[:, :3].reshape(h, w, 3))
-            if vid:
-                vid.add(rgba[:, :3].reshape(h, w, 3))
-            results.append(rec)
-            if not quiet:
-                print("frame %d: %s" % (i, ", ".join("%s=%s" % (k, ("%.4f" % v) if isinstance(v, float) else v)
-                                                      for k, v in rec.items() if k not in ("frame", "image"))))
+                os.makedirs(out_dir, exist_ok=True)
+            for i, fr in enumerate(frames):
+                r.set_camera(fr["pose"], fr["rot"])
+                rgb, rgba, st = r.render_numpy()
+                rec = dict(extra, frame=i, image=fr["image"], samples_per_ray=st.total_samples / float(w * h), ms=st.ms_total)
+                if os.path.exists(fr["image"]):
+                    gt = read_png(fr["image"])
+                    if gt.shape[0] != h or gt.shape[1] != w:
+                        raise ValueError("%s: expected %dx%d, got %dx%d" % (fr["image"], w, h, gt.shape[1], gt.shape[0]))
+                    ref = gt[:, :, :3].astype(np.float32).reshape(-1, 3) / 255.0        # datasets.py:286-287
+                    mse = float(np.mean((rgb.astype(np.float64) - ref) ** 2))
+                    rec.update(mse=mse, psnr=psnr_from_mse(mse))
+                    if want_flip:       # the rendered frame is still on the device (render_numpy); argument order of src/evaluate.py:144
+                        rec.update(flip=r.flip_device(r._o_rgb, d_ref.upload(ref), w, h, error_map=d_map))
+                        if d_map is not None:
+                            fm = np.nan_to_num(d_map.numpy().reshape(h, w), nan=1.0)      # the map lies in [0, 1]
+                            write_png(os.path.join(out_dir, "%05d_flip.png" % i), np.clip(np.rint(fm * 255.0), 0, 255).astype(np.uint8))
+                if out_dir:
+                    write_png(os.path.join(out_dir, "%05d.png" % i), rgba[:, :3].reshape(h, w, 3))
+                if vid:
+                    vid.add(rgba[:, :3].reshape(h, w, 3))
+                recs.append(rec)
+                if not quiet:
+                    print("frame %d: %s" % (i, ", ".join("%s=%s" % (k, ("%.4f" % v) if isinstance(v, float) else v)
+                                                          for k, v in rec.items() if k not in ("frame", "image"))))
+            return recs
+
+        sweep = []
+        if sweep_thresholds or sweep_samples:
+            for n, t in itertools.product(sweep_samples or [None], sweep_thresholds or [None]):
+                info = r.set_selection(n, t)
+                key = dict(num_samples=int(info.num_samples), threshold=float(info.threshold) if t is None else float(t))
+                recs = render_set(os.path.join(out_dir, sweep_dir_name(**key)) if out_dir else None, key)
+                sweep.append(dict(key, **{k: v for k, v in summarise(recs, want_flip).items() if k != "frames"}))
+                results.extend(recs)
+        else:
+            results = render_set(out_dir, {})
         if vid:
             vid.close()
+    if sweep:
+        return dict(frames=len(frames), sweep=sweep), results
+    return summarise(results, want_flip), results
+
+
+def summarise(results: List[dict], want_flip: bool) -> dict:
     with_gt = [x for x in results if "psnr" in x]
     summary = dict(frames=len(results), mean_samples_per_ray=float(np.mean([x["samples_per_ray"] for x in results])) if results else 0.0,
                    mean_ms=float(np.mean([x["ms"] for x in results])) if results else 0.0)
@@ -124,10 +162,10 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
         summary.update(mean_psnr=float(np.mean([x["psnr"] for x in with_gt])), mean_mse=float(np.mean([x["mse"] for x in with_gt])))
         if want_flip:
             summary.update(mean_flip=float(np.mean([x["flip"] for x in with_gt])))
-    return summary, results
+    return summary
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("model_dir")
     ap.add_argument("dataset_dir")
@@ -140,9 +178,17 @@ def main(argv=None):
     ap.add_argument("--fps", type=int, default=30)
     ap.add_argument("--metrics", nargs="+", default=["psnr"], choices=["psnr", "flip"],
                     help="flip: also the mean FLIP error per frame (and, with --out, its map as %%05d_flip.png)")
-    a = ap.parse_args(argv)
+    ap.add_argument("--sweep-thresholds", nargs="+", type=float, default=None, metavar="T",
+                    help="render the set once per threshold (x --sweep-samples) on one context; summary gains `sweep`, --out gets n<N>_t<T>/")
+    ap.add_argument("--sweep-samples", nargs="+", type=int, default=None, metavar="N",
+                    help="render the set once per sample budget N (x --sweep-thresholds)")
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     summary, _ = evaluate(a.model_dir, a.dataset_dir, a.set, a.out, a.precision, a.batch_size, a.max_frames, video=a.video, fps=a.fps,
-                          metrics=tuple(a.metrics))
+                          metrics=tuple(a.metrics), sweep_thresholds=a.sweep_thresholds, sweep_samples=a.sweep_samples)
     print(json.dumps(summary))
 
 

@@ -1,5 +1,6 @@
 #include "inputhandler.h"
 
+#include <cstdlib>
 #include <cstring>
 #include <sstream>
 #include <string>
@@ -66,6 +67,20 @@ bool InputHandler::replay(const char* line) {
       if (tok == "b+") buttonDown(Button::LEFT, x, y);
       else if (tok == "b-") buttonUp(Button::LEFT, x, y);
       else mouseMove(x, y);
+    } else if (tok == "n" || tok == "thr") {
+      // one value, read whole: "n 8", "thr 0.15"; the library validates the pair when the frame is rendered
+      std::string val;
+      if (!(in >> val)) return false;
+      char* end = nullptr;
+      if (tok == "n") {
+        const long n = std::strtol(val.c_str(), &end, 10);
+        if (end == val.c_str() || *end != 0 || n < 1 || n > 1 << 20) return false;
+        renderer.setSelection(static_cast<int>(n), -1.f);
+      } else {
+        const float t = std::strtof(val.c_str(), &end);
+        if (end == val.c_str() || *end != 0 || !(t >= 0.f)) return false;
+        renderer.setSelection(0, t);
+      }
     } else if ((tok[0] == '+' || tok[0] == '-') && tok.size() > 1) {
       Key k;
       if (!key_of(tok.substr(1), &k)) return false;

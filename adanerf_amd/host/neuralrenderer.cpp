@@ -170,6 +170,19 @@ bool NeuralRenderer::init() {
 bool NeuralRenderer::render() {
   float rot[9];
   camera.getRotMatrix(rot);
+  if (selection_pending) {      // script tokens "n" / "thr": every context (--gpus / --sub-shares) gets the same pair before this frame
+    selection_pending = false;
+    std::vector<adanerf_ctx*> all(1, ctx);
+    all.insert(all.end(), peers.begin(), peers.end());
+    for (adanerf_ctx* c : all)
+      if (adanerf_set_selection(c, want_samples, want_threshold) != ADANERF_OK) {
+        err = adanerf_last_error(c);
+        return false;
+      }
+    want_samples = 0;
+    want_threshold = -1.f;
+    adanerf_get_info(ctx, &info_);
+  }
   if (adanerf_set_camera(ctx, camera.getPosition(), rot) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;
@@ -215,6 +228,7 @@ bool NeuralRenderer::render() {
                   << ", fc2: " << st.ms_compact / f << ", rm: " << st.ms_composite / f
                   << ", avg samples ppx: " << st.total_samples * world / f / settings.total_size
                   << " (total: " << static_cast<long long>(st.total_samples * world / f) << ")"
+                  << ", N: " << info_.num_samples << ", thr: " << info_.threshold
                   << ", frames: " << sample_count << ", gpus: " << peers.size() + 1 << " (stage times: GPU 0's share)" << std::endl;
       }
     }
@@ -246,6 +260,7 @@ bool NeuralRenderer::render() {
               << ", fc2: " << s_fc2 / logging_interval << ", rm: " << s_rm / logging_interval
               << ", avg samples ppx: " << s_num_total_samples / static_cast<double>(logging_interval) / settings.total_size
               << " (total: " << s_num_total_samples / logging_interval << ")"
+              << ", N: " << info_.num_samples << ", thr: " << info_.threshold
               << ", frames: " << sample_count << ", frame ms: " << s_total / logging_interval << std::endl;
     s_inference1 = s_inference2 = s_fc2 = s_rm = s_total = 0;
     s_num_total_samples = 0;

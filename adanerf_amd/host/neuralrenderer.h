@@ -19,6 +19,17 @@ class NeuralRenderer {
   bool render();                     // one frame; logs every 100 frames like imagegenerator.cpp:379-393
   void switchRenderOracle() { render_oracle = !render_oracle; }   // neuralrenderer.h: the 'O' key toggle
   bool renderingOracle() const { return render_oracle; }
+  // sample budget N / selection threshold from the next frame on (n <= 0, thr < 0: keep); reaches every context in render()
+  void setSelection(int n, float thr) {
+    if (n > 0) want_samples = n;
+    if (thr >= 0.f) want_threshold = thr;
+    selection_pending = true;
+  }
+  bool pendingSelection(int* n, float* thr) const {      // what the next frame will ask of the library (0 / < 0: keep)
+    *n = want_samples;
+    *thr = want_threshold;
+    return selection_pending;
+  }
   int batchesPerFrame() const;       // ceil(rays / batch_rays)
   bool writeImageToFile();           // out.bmp in the model directory (neuralrenderer.cpp:184-222)
   const adanerf_info& info() const { return info_; }
@@ -35,6 +46,9 @@ class NeuralRenderer {
   void* d_frame = nullptr;           // uchar4 [h*w]
   std::string err;
   bool render_oracle = false;
+  bool selection_pending = false;    // setSelection since the last frame
+  int want_samples = 0;
+  float want_threshold = -1.f;
   // 100-frame running sums
   int logging_interval = 100, sample_count = 0;
   double s_inference1 = 0, s_inference2 = 0, s_fc2 = 0, s_rm = 0, s_total = 0;

@@ -12,6 +12,8 @@ const char* Settings::usage() {
          "               [--yaw DEG] [--pitch DEG]\n"
          "               [--samples N] [--threshold T] [--oracle]\n"
          "               [--script FILE] [--log-camera] [--dry-run]     input replay: one line of events per frame\n"
+         "                                                              (+w -w ... b+ x y  b- x y  m x y; n <int> / thr <float>:\n"
+         "                                                              sample budget N / threshold from that frame on)\n"
          "               [--gpus N] [--same-device] [--sub-shares P]\n";
 }
 

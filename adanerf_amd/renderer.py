@@ -64,7 +64,7 @@ class Stats(C.Structure):
                 ("guard_audit_mismatch", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
-EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_last_error", "adanerf_abi_version", "adanerf_struct_sizes", "adanerf_set_camera",
+EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_last_error", "adanerf_abi_version", "adanerf_struct_sizes", "adanerf_set_camera", "adanerf_set_selection",
            "adanerf_render", "adanerf_set_aux_outputs", "adanerf_set_disp_output", "adanerf_assemble_strips", "adanerf_sync", "adanerf_set_stream", "adanerf_set_profiling",
            "adanerf_collect_stats", "adanerf_ray_features", "adanerf_sample_mlp",
            "adanerf_compact", "adanerf_compact_guarded", "adanerf_calibrate_guard", "adanerf_guard_calibration_file", "adanerf_shade_features", "adanerf_shade_mlp", "adanerf_shade_mlp_z", "adanerf_sample_pdf", "adanerf_sample_uniform", "adanerf_shade_mlp_coarse", "adanerf_sample_from_coarse",
@@ -91,6 +91,7 @@ def load_library(path: Optional[str] = None):
     lib.adanerf_last_error.argtypes = [vp]
     lib.adanerf_last_error.restype = C.c_char_p
     lib.adanerf_set_camera.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    lib.adanerf_set_selection.argtypes = [vp, i32, C.c_float]
     lib.adanerf_render.argtypes = [vp, vp, vp, C.POINTER(Stats)]
     lib.adanerf_assemble_strips.argtypes = [vp, vp, vp]
     lib.adanerf_set_aux_outputs.argtypes = [vp, vp, vp]
@@ -330,6 +331,15 @@ class NeuralRenderer:
         r = np.ascontiguousarray(rot_c2w, dtype=np.float32).reshape(9)
         self._check(self.lib.adanerf_set_camera(self.handle, p.ctypes.data_as(C.POINTER(C.c_float)),
                                                 r.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def set_selection(self, num_samples: Optional[int] = None, threshold: Optional[float] = None) -> "Info":
+        """The sample budget N and / or the selection threshold for the frames rendered from now on (None keeps the one in force); the
+        context is then what one constructed with these values would be, without reloading the model (adanerf_set_selection).
+        threshold 0 is the dense mode and needs num_samples 128.  Refreshes and returns ``self.info``.  A ``sampling="auto"`` choice made
+        at construction is not re-measured: the mode chosen for the first pair stays."""
+        self._check(self.lib.adanerf_set_selection(self.handle, 0 if num_samples is None else int(num_samples),
+                                                   -1.0 if threshold is None else float(threshold)))
+        return self.refresh_info()
 
     def render(self, rgba8_out=None, rgb_out=None, stats: bool = False) -> Optional[Stats]:
         """One frame into caller-owned device buffers ([rays_local] uchar4 / [rays_local,3] fp32).

@@ -10,6 +10,8 @@
  *                                        RayMarchFromPoses::create (src/featureset.cpp:67-140),
  *                                        ImageGenerator::load/initEngine (src/imagegenerator.cpp:84-226)
  *   adanerf_set_camera                   Camera::UpdateFeatureRot/getPosition (src/camera.cpp:143-201)
+ *   adanerf_set_selection                numRaymarchSamples / adaptiveSamplingThreshold: members of RayMarchFromPoses, handed to
+ *                                        updateRayMarchFromPosesAdaptive on every call (src/featureset.cpp:80,153)
  *   adanerf_render                       ImageGenerator::inference, 2-context adaptive branch
  *                                        (src/imagegenerator.cpp:282-394) as called from
  *                                        NeuralRenderer::render (src/neuralrenderer.cpp:146-182)
@@ -263,6 +265,25 @@ int adanerf_struct_sizes(int32_t sizes_out[3]);
  * returns ADANERF_EUNSUPPORTED and leaves the previous camera in place -- render such poses with an fp16 / fp32 context.  NDC scenes
  * (useNDC) assume rays inside the frustum of the recorded cameras (positions in the NDC cube); that is not checked per pose. */
 int adanerf_set_camera(adanerf_ctx* ctx, const float pos[3], const float rot_c2w[9]);
+
+/* The sample budget N and the selection threshold of a live context: the quality / speed dial of an AdaNeRF network, which is trained
+ * once and rendered at any budget.  num_samples <= 0 keeps the N in force, threshold < 0 the threshold in force (the convention of
+ * adanerf_options).  The resulting pair is validated by the code adanerf_create runs on options.num_samples / .threshold, with its
+ * error codes and messages (threshold 0 is the dense mode and needs num_samples == 128); a NaN threshold is ADANERF_EINVAL.  Afterwards
+ * the context is what a new context created with these two options would be: same frames, same buffers, same adanerf_info
+ * (num_samples / threshold / dense).  On failure nothing has changed.
+ *   ADANERF_SAMPLER_PDF / _COARSE_FINE: adanerf_create ignores options.threshold for these samplers, so a threshold >= 0 returns
+ *   ADANERF_EUNSUPPORTED; num_samples is the N (coarse/fine: Nf) that options.num_samples overrides.
+ *   Ordering is that of adanerf_set_camera: the adanerf_render / adanerf_render_oracle calls issued afterwards see the new pair, frames
+ *   already enqueued keep theirs (both values reach the kernels by value).  Device memory is allocated only when N exceeds the largest N
+ *   the context has held, never released before adanerf_destroy, and the stream is synchronised only then (before the smaller buffers
+ *   are freed); adanerf_render never allocates for it.  The adanerf_stats counters documented as "since create" keep counting.
+ *   ADANERF_SAMPLING_GUARDED: the band belongs to (model, N, threshold).  A change leaves the context where a new guarded context is
+ *   before its first guarded frame -- bounds from options.guard_eps if given, else from the new pair's calibration record
+ *   (adanerf_guard_calibration_file names it), else calibrated at the next guarded frame; adanerf_info.guard_calib_source and the audit's
+ *   phase start over; a band widened under the old pair is not carried along.  A call that changes neither value leaves all of this
+ *   alone.  Outside the fused selection's domain (N > 16, threshold 0) the mode runs the split-precision engine alone, as after create. */
+int adanerf_set_selection(adanerf_ctx* ctx, int32_t num_samples, float threshold);
 
 /* Renders this context's rays.  d_rgba8_out: [rays_local] uchar4 (A=255), row-major over the shard's
  * rows -- for shard_world==1 that is the whole image, pixel (x,y) at y*w+x.  d_rgb_f32_out: optional
