@@ -585,6 +585,21 @@ int apply_selection(adanerf_ctx* c) {
   return ADANERF_OK;
 }
 
+// Context state that follows from the (width, height) frame_geometry left in ms.info / ms.rg: adanerf_set_frame_size ends here (create
+// goes through apply_selection, whose buffer call sees the same batch).  Capacities follow the largest batch the context has held; the
+// caller's per-ray outputs were sized for `was_rays` rays.  The guard band belongs to (model, N, threshold) and stays; its audit starts over.
+int apply_frame_size(adanerf_ctx* c, int was_rays) {
+  const size_t B = static_cast<size_t>(c->ms.info.batch_rays);
+  if (int rc = ensure_batch_buffers(c, c->ms.info.batch_rays, c->ms.info.num_samples)) return rc;
+  if (c->disp_scratch.p && c->disp_scratch.bytes < B * 2 * sizeof(float)) {      // adanerf_render would grow it: not with frames in flight
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (int rc = dev_alloc(c, &c->disp_scratch, B * 2 * sizeof(float))) return rc;
+  }
+  if (c->ms.info.rays_local != was_rays) c->aux_depth = c->aux_acc = c->aux_disp = nullptr;
+  c->guard_frame = 0;
+  return ADANERF_OK;
+}
+
 constexpr int kShadeWaves = 8;   // one 8-wave workgroup per CU (two independent 4-wave workgroups measured 4.2-5.7 ms vs 3.8)
 
 int launch_shade_mlp(adanerf_ctx* c, const float* d_rays, const uint32_t* d_key, const int32_t* d_total, int max_samples, int prec,
@@ -959,6 +974,49 @@ int adanerf_set_selection(adanerf_ctx* c, int32_t num_samples, float threshold) 
     return rc;
   }
   return ADANERF_OK;
+}
+
+int adanerf_set_frame_size(adanerf_ctx* c, int32_t width, int32_t height) {
+  BIND(c);
+  ModelSetup& ms = c->ms;
+  const int w = width > 0 ? width : ms.info.width, h = height > 0 ? height : ms.info.height;
+  if (w == ms.info.width && h == ms.info.height) return ADANERF_OK;      // the size in force: buffers, outputs and the audit go on
+  const adanerf_info was = ms.info;
+  const RayGenParams was_rg = ms.rg;
+  std::string err;
+  if (int rc = frame_geometry(&ms, &c->opt, w, h, &err)) return fail(c, rc, err);
+  if (int rc = apply_frame_size(c, was.rays_local)) {      // the buffers could not grow: back to the size that renders
+    ms.info = was;
+    ms.rg = was_rg;
+    return rc;
+  }
+  c->opt.width = w;
+  c->opt.height = h;
+  return ADANERF_OK;
+}
+
+int adanerf_present(adanerf_ctx* c, const void* d_src_rgba8, int32_t src_w, int32_t src_h, void* d_dst_rgba8, int32_t dst_w, int32_t dst_h,
+                    int32_t flags) {
+  if (!c) return ADANERF_EINVAL;
+  if (!d_src_rgba8 || !d_dst_rgba8) return fail(c, ADANERF_EINVAL, "adanerf_present: NULL image");
+  if (src_w < 1 || src_h < 1 || dst_w < 1 || dst_h < 1 || src_w > kPresentMaxSide || src_h > kPresentMaxSide || dst_w > kPresentMaxSide ||
+      dst_h > kPresentMaxSide)
+    return fail(c, ADANERF_EINVAL, "adanerf_present: every side must be in 1.." + std::to_string(kPresentMaxSide));
+  constexpr int32_t kFilters = ADANERF_PRESENT_NEAREST | ADANERF_PRESENT_LINEAR;
+  if ((flags & ~(ADANERF_PRESENT_FLIP_Y | kFilters)) || (flags & kFilters) == kFilters)
+    return fail(c, ADANERF_EINVAL, "adanerf_present: flags must be ADANERF_PRESENT_FLIP_Y with at most one of _NEAREST / _LINEAR");
+  const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src_rgba8), d0 = reinterpret_cast<uintptr_t>(d_dst_rgba8);
+  const uintptr_t s1 = s0 + static_cast<size_t>(src_w) * src_h * 4, d1 = d0 + static_cast<size_t>(dst_w) * dst_h * 4;
+  if ((s0 | d0) & 3) return fail(c, ADANERF_EINVAL, "adanerf_present: images must be 4-byte aligned (uchar4)");
+  if (s0 < d1 && d0 < s1) return fail(c, ADANERF_EINVAL, "adanerf_present: source and destination overlap");
+  BIND(c);
+  const bool linear = (flags & kFilters) ? (flags & ADANERF_PRESENT_LINEAR) != 0 : dst_w > src_w;      // the reference's rule
+  const uint64_t den = 8ull * static_cast<uint64_t>(dst_w) * static_cast<uint64_t>(dst_h);               // 2 D E
+  const int threads = (1 + (dst_w + 3) / 4) * dst_h;
+  hipLaunchKernelGGL(present_kernel, dim3((threads + 255) / 256), dim3(256), 0, c->stream, static_cast<const uchar4*>(d_src_rgba8),
+                     static_cast<uchar4*>(d_dst_rgba8), src_w, src_h, dst_w, dst_h, linear ? 1 : 0, (flags & ADANERF_PRESENT_FLIP_Y) ? 1 : 0,
+                     static_cast<uint32_t>((d0 >> 2) & 3), den, ~0ull / den);
+  HIP_RETURN(c, hipGetLastError());
 }
 
 int adanerf_sync(adanerf_ctx* c) {

@@ -5,6 +5,7 @@
 //   A5+A6     shade_mlp16_kernel / shade_mlp32_kernel   fused PE + 8x256 shading MLP (bf16/f16/f32 MFMA)
 //   A7        composite_kernel       sigmoid + alpha * oracle weight, front-to-back
 //   N1        flip_kernel / flip_mean_kernel   FLIP error map and mean of an image pair (the evaluator's second metric)
+//   N3        present_kernel         the frame at the window's size (the viewer's blit: linear / nearest, y flip)
 // plus explicit-feature debug kernels (ray_features_kernel, shade_features_kernel) that materialise
 // what the reference launchers wrote to memory, for parity tests only.
 // The code lives in one header per stage; this file includes them all.
@@ -19,3 +20,4 @@
 #include "k_coarse_fine.hip.hpp"
 #include "k_composite.hip.hpp"
 #include "k_flip.hip.hpp"
+#include "k_present.hip.hpp"

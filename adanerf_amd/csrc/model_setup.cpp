@@ -147,22 +147,10 @@ int setup_model_unguarded(const char* model_dir, const adanerf_options* opt, Mod
     if (ap > 32 || (ap > 0 && (ap & (ap - 1)) != 0)) return bad(ADANERF_EINVAL, "guard_audit_period must be a power of two <= 32 (0: default, < 0: off)");
   }
 
-  // ---- info / ray generation constants (A1: src/util/raygeneration.py:10-26, float64) ----
-  const int w = opt->width, h = opt->height;
+  // ---- info; everything that follows from (width, height): frame_geometry ----
   adanerf_info& I = ms->info;
   I.abi_version = ADANERF_ABI_VERSION;
-  I.width = w;
-  I.height = h;
   I.compute_units = 0;
-  const int world = opt->shard_world > 0 ? opt->shard_world : 1;
-  const int rank = opt->shard_rank;
-  if (rank < 0 || rank >= world) return bad(ADANERF_EINVAL, "shard_rank out of range");
-  const int strip_rows = opt->strip_rows > 0 ? opt->strip_rows : 8;
-  I.rays_local = rows_of_rank(h, strip_rows, world, rank) * w;
-  I.rays_local_max = rows_of_rank(h, strip_rows, world, 0) * w;
-  const int R = I.rays_local;
-  if (static_cast<int64_t>(w) * h >= (1ll << 25)) return bad(ADANERF_EINVAL, "width*height must be < 2^25");
-  I.batch_rays = (opt->batch_rays <= 0) ? std::max(R, 1) : std::min(opt->batch_rays, std::max(R, 1));
   I.n_in0 = (ms->ray_samples * 3 + 3) * (2 * ms->fp0 + 1) + 3 + 6 * ms->fd0;     // src/features.py:738-740
   if (coarse_fine) I.n_in0 = 6 + 6 * (ms->fp0 + ms->fd0);                          // src/features.py:622
   I.n_in1 = 6 + 6 * (ms->fp1 + ms->fd1);
@@ -171,23 +159,8 @@ int setup_model_unguarded(const char* model_dir, const adanerf_options* opt, Mod
   I.num_samples_coarse = ms->n_coarse;
   I.precision = opt->precision;
   I.fov = static_cast<float>(cf.fov);
-  const double fov = cf.fov;
-  const double focal = 0.5 * w / std::tan(0.5 * fov);   // src/datasets.py:182
-  I.focal = static_cast<float>(focal);
-  const double x_dist = std::tan(fov / 2) * focal;
-  const double y_dist = x_dist * (static_cast<double>(h) / w);
-  const double x_pp = x_dist / (w / 2.0), y_pp = y_dist / (h / 2.0);
+  if (int rc = frame_geometry(ms, opt, opt->width, opt->height, err)) return rc;
   RayGenParams& g = ms->rg;
-  g.start_x = -(x_dist - x_pp / 2);
-  g.x_pp = x_pp;
-  g.start_y = -(y_dist - y_pp / 2);
-  g.y_pp = y_pp;
-  g.focal = focal;
-  g.w = w;
-  g.h = h;
-  g.strip_rows = strip_rows;
-  g.world = world;
-  g.rank = rank;
   g.use_ndc = ndc;
   double r2 = 0;
   for (int i = 0; i < 3; ++i) {
@@ -200,8 +173,6 @@ int setup_model_unguarded(const char* model_dir, const adanerf_options* opt, Mod
   const double rad = std::sqrt(r2);
   g.rad2 = static_cast<float>(rad * rad);
   I.view_cell_radius = static_cast<float>(rad);
-  g.ndc_sw = static_cast<float>(-1.0 / (w / (2.0 * focal)));
-  g.ndc_sh = static_cast<float>(-1.0 / (h / (2.0 * focal)));
   const float ident[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   std::memcpy(g.rot, ident, sizeof(ident));
   for (int i = 0; i < 3; ++i) g.pos[i] = g.center[i];
@@ -264,6 +235,52 @@ int setup_model_unguarded(const char* model_dir, const adanerf_options* opt, Mod
   ms->sel_n = cf.numRaymarchSamples.back();
   ms->sel_thr = cf.adaptiveSamplingThreshold;
   return select_samples(ms, opt->num_samples, opt->threshold, err);
+}
+
+int frame_geometry(ModelSetup* ms, const adanerf_options* opt, int w, int h, std::string* err) {
+  auto bad = [&](int code, const std::string& msg) {
+    *err = msg;
+    return code;
+  };
+  if (w <= 0 || h <= 0) return bad(ADANERF_EINVAL, "width/height must be positive");
+  const int world = opt->shard_world > 0 ? opt->shard_world : 1;
+  const int rank = opt->shard_rank;
+  if (rank < 0 || rank >= world) return bad(ADANERF_EINVAL, "shard_rank out of range");
+  const int strip_rows = opt->strip_rows > 0 ? opt->strip_rows : 8;
+  if (static_cast<int64_t>(w) * h >= (1ll << 25)) return bad(ADANERF_EINVAL, "width*height must be < 2^25");
+  const int R = rows_of_rank(h, strip_rows, world, rank) * w;
+  const int batch = (opt->batch_rays <= 0) ? std::max(R, 1) : std::min(opt->batch_rays, std::max(R, 1));
+  // sample offsets, keys and totals are int32 on the device (select_samples checks the same product for a new N; 0: no N yet)
+  if (static_cast<int64_t>(batch) * ms->info.num_samples > 0x7fffffffll)
+    return bad(ADANERF_EINVAL, "batch_rays * num_samples exceeds 2^31 - 1; use a smaller batch (-bs)");
+  // nothing above has touched *ms: a refused size leaves it as it was
+  adanerf_info& I = ms->info;
+  I.width = w;
+  I.height = h;
+  I.rays_local = R;
+  I.rays_local_max = rows_of_rank(h, strip_rows, world, 0) * w;
+  I.batch_rays = batch;
+  // ray generation constants (A1: src/util/raygeneration.py:10-26, float64)
+  const double fov = ms->cfg.fov;
+  const double focal = 0.5 * w / std::tan(0.5 * fov);   // src/datasets.py:182
+  I.focal = static_cast<float>(focal);
+  const double x_dist = std::tan(fov / 2) * focal;
+  const double y_dist = x_dist * (static_cast<double>(h) / w);
+  const double x_pp = x_dist / (w / 2.0), y_pp = y_dist / (h / 2.0);
+  RayGenParams& g = ms->rg;
+  g.start_x = -(x_dist - x_pp / 2);
+  g.x_pp = x_pp;
+  g.start_y = -(y_dist - y_pp / 2);
+  g.y_pp = y_pp;
+  g.focal = focal;
+  g.w = w;
+  g.h = h;
+  g.strip_rows = strip_rows;
+  g.world = world;
+  g.rank = rank;
+  g.ndc_sw = static_cast<float>(-1.0 / (w / (2.0 * focal)));
+  g.ndc_sh = static_cast<float>(-1.0 / (h / (2.0 * focal)));
+  return ADANERF_OK;
 }
 
 void depth_table(const ModelSetup& ms, bool dense, float* ztab128) {

@@ -71,6 +71,12 @@ int setup_model_unguarded(const char* model_dir, const adanerf_options* opt, Mod
 // info.num_samples / .threshold / .dense, ztab and pos_bound.zmax.  On failure *ms is unchanged.  Needs every model-derived field
 // of *ms (setup_model calls it last).
 int select_samples(ModelSetup* ms, int32_t num_samples, float threshold, std::string* err);
+// Everything a context derives from (width, height) on the host, for adanerf_create and adanerf_set_frame_size alike: validates the
+// size against the shard geometry and batch size of *opt (and the N in force, if there is one yet) and fills info.width / .height /
+// .rays_local / .rays_local_max / .batch_rays / .focal and the image half of rg (pixel pitch, start, focal, strips, NDC scales); the
+// camera and the view cell in rg stay.  batch_rays comes from opt->batch_rays, the value the caller asked for, never from the clamped
+// info.batch_rays.  On failure *ms is unchanged.  Needs ms->cfg.
+int frame_geometry(ModelSetup* ms, const adanerf_options* opt, int w, int h, std::string* err);
 // world depth of each of the 128 bins: the sampler's cell centres, or (dense) the dense mode's uniform t-values
 void depth_table(const ModelSetup& ms, bool dense, float* ztab128);
 

@@ -5,11 +5,14 @@ reference's second default metric (``metrics = ["flip", "psnr"]`` :613-615): the
 (:120-145 over ``src/util/flip_loss.py``), computed on the GPU by ``adanerf_flip`` from the frame that is still in device memory.
 
     python -m adanerf_amd.evaluate <model_dir> <dataset_dir> [--set test] [--out DIR] [--video out.y4m] [--precision bf16]
-                                   [--metrics psnr flip] [--sweep-thresholds T ...] [--sweep-samples N ...]
+                                   [--metrics psnr flip] [--sweep-thresholds T ...] [--sweep-samples N ...] [--sweep-scales S ...]
 
 ``--sweep-thresholds`` / ``--sweep-samples`` render the set once per (N, threshold) of their cross product on ONE context
 (``NeuralRenderer.set_selection``: an AdaNeRF network is trained once and rendered at any sample budget) -- the two axes of a quality
-table; the summary gains ``sweep``, ``--out DIR`` writes into ``DIR/n<N>_t<threshold>/``.
+table; the summary gains ``sweep``, ``--out DIR`` writes into ``DIR/n<N>_t<threshold>/``.  ``--sweep-scales`` is the third axis, the
+resolution: the set is rendered at ``round(w S) x round(h S)`` on the same context (``NeuralRenderer.set_frame_size``), presented to the
+dataset's ``w x h`` on the GPU (``adanerf_present``, the viewer's blit) and scored from that 8-bit image / 255; sub-directories gain
+``_s<scale>``.
 
 Dataset layout (src/datasets.py:146-213, 361-365, 480-542): ``dataset_info.json`` (``resolution``,
 ``camera_angle_x``, ``view_cell_center``, ``view_cell_size`` ...), ``transforms_<set>.json`` with
@@ -73,14 +76,20 @@ def psnr_from_mse(mse: float) -> float:
     return float("inf") if mse == 0 else 10.0 * math.log10(1.0 / mse)
 
 
-def sweep_dir_name(num_samples: int, threshold: float) -> str:
-    """Sub-directory of --out for one setting of a sweep: n<N>_t<threshold>, the threshold as %g prints it (n8_t0.1, n128_t0)."""
-    return "n%d_t%g" % (num_samples, threshold)
+def sweep_dir_name(num_samples: int, threshold: float, scale: Optional[float] = None) -> str:
+    """Sub-directory of --out for one setting of a sweep: n<N>_t<threshold>, the threshold as %g prints it (n8_t0.1, n128_t0); with
+    --sweep-scales n<N>_t<threshold>_s<scale> (n8_t0.1_s0.5)."""
+    return "n%d_t%g" % (num_samples, threshold) + ("" if scale is None else "_s%g" % scale)
+
+
+def scaled_size(w: int, h: int, scale: float):
+    """The render size of one --sweep-scales entry: round(w S) x round(h S), at least 1 x 1."""
+    return max(1, int(round(w * scale))), max(1, int(round(h * scale)))
 
 
 def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: Optional[str] = None,
              precision: str = "bf16", batch_size: int = -1, max_frames: int = 0, quiet: bool = False,
-             video: Optional[str] = None, fps: int = 30, metrics=("psnr",), sweep_thresholds=None, sweep_samples=None):
+             video: Optional[str] = None, fps: int = 30, metrics=("psnr",), sweep_thresholds=None, sweep_samples=None, sweep_scales=None):
     """metrics: "psnr" (always reported where a ground-truth image exists) and / or "flip": each record gains ``flip``, the summary
     ``mean_flip``, and with out_dir the error map is written as an 8-bit greyscale ``%05d_flip.png``.
 
@@ -88,10 +97,16 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     their cross product, N outermost, all on the one context.  The summary is then ``{"frames": n, "sweep": [...]}`` with one
     ``{num_samples, threshold, mean_psnr, mean_mse, mean_samples_per_ray, mean_ms[, mean_flip]}`` per setting (what a plain run of a
     model with that setting reports), the records of all settings follow each other and carry ``num_samples`` / ``threshold``, and
-    out_dir gets one sub-directory per setting (sweep_dir_name)."""
+    out_dir gets one sub-directory per setting (sweep_dir_name).
+
+    sweep_scales (list or None): innermost axis of the same cross product.  Each setting renders at scaled_size(w, h, S), presents the
+    frame to w x h on the device and scores THAT image (uint8 / 255, also at S = 1: the entries of one table are measured alike);
+    samples_per_ray counts per rendered ray; entries and records carry ``scale``; frames written to out_dir / video are the presented ones."""
     unknown = sorted(set(metrics) - {"psnr", "flip"})
     if unknown:
         raise ValueError("unknown metrics %s (known: psnr, flip)" % unknown)
+    if sweep_scales and not all(s > 0 for s in sweep_scales):
+        raise ValueError("sweep_scales must be positive, got %s" % (list(sweep_scales),))
     want_flip = "flip" in metrics
     meta, frames = load_dataset(dataset_dir, set_name)
     if max_frames > 0:
@@ -105,16 +120,21 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
         vid = Y4mWriter(video, w, h, fps) if video else None
         d_ref = r.empty((w * h, 3), np.float32) if want_flip else None
         d_map = r.empty((w * h,), np.float32) if want_flip and out_dir else None
+        d_pres = r.empty((w * h, 3), np.float32) if want_flip and sweep_scales else None
 
-        def render_set(out_dir, extra):
-            """one pass over the set at the selection in force -> its records"""
+        def render_set(out_dir, extra, scale=None):
+            """one pass over the set at the selection (and, with a scale, the frame size) in force -> its records"""
+            rw, rh = (w, h) if scale is None else (r.info.width, r.info.height)
             recs: List[dict] = []
             if out_dir:
                 os.makedirs(out_dir, exist_ok=True)
             for i, fr in enumerate(frames):
                 r.set_camera(fr["pose"], fr["rot"])
                 rgb, rgba, st = r.render_numpy()
-                rec = dict(extra, frame=i, image=fr["image"], samples_per_ray=st.total_samples / float(w * h), ms=st.ms_total)
+                if scale is not None:      # the frame as a w x h window shows it, filtered on the device
+                    rgba = r.present(w, h).reshape(-1, 4)
+                    rgb = rgba[:, :3].astype(np.float32) / 255.0
+                rec = dict(extra, frame=i, image=fr["image"], samples_per_ray=st.total_samples / float(rw * rh), ms=st.ms_total)
                 if os.path.exists(fr["image"]):
                     gt = read_png(fr["image"])
                     if gt.shape[0] != h or gt.shape[1] != w:
@@ -123,7 +143,8 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                     mse = float(np.mean((rgb.astype(np.float64) - ref) ** 2))
                     rec.update(mse=mse, psnr=psnr_from_mse(mse))
                     if want_flip:       # the rendered frame is still on the device (render_numpy); argument order of src/evaluate.py:144
-                        rec.update(flip=r.flip_device(r._o_rgb, d_ref.upload(ref), w, h, error_map=d_map))
+                        d_test = r._o_rgb if scale is None else d_pres.upload(rgb)
+                        rec.update(flip=r.flip_device(d_test, d_ref.upload(ref), w, h, error_map=d_map))
                         if d_map is not None:
                             fm = np.nan_to_num(d_map.numpy().reshape(h, w), nan=1.0)      # the map lies in [0, 1]
                             write_png(os.path.join(out_dir, "%05d_flip.png" % i), np.clip(np.rint(fm * 255.0), 0, 255).astype(np.uint8))
@@ -138,11 +159,14 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
             return recs
 
         sweep = []
-        if sweep_thresholds or sweep_samples:
-            for n, t in itertools.product(sweep_samples or [None], sweep_thresholds or [None]):
+        if sweep_thresholds or sweep_samples or sweep_scales:
+            for n, t, sc in itertools.product(sweep_samples or [None], sweep_thresholds or [None], sweep_scales or [None]):
                 info = r.set_selection(n, t)
                 key = dict(num_samples=int(info.num_samples), threshold=float(info.threshold) if t is None else float(t))
-                recs = render_set(os.path.join(out_dir, sweep_dir_name(**key)) if out_dir else None, key)
+                if sc is not None:
+                    r.set_frame_size(*scaled_size(w, h, sc))
+                    key["scale"] = float(sc)
+                recs = render_set(os.path.join(out_dir, sweep_dir_name(**key)) if out_dir else None, key, sc)
                 sweep.append(dict(key, **{k: v for k, v in summarise(recs, want_flip).items() if k != "frames"}))
                 results.extend(recs)
         else:
@@ -182,13 +206,16 @@ def build_parser():
                     help="render the set once per threshold (x --sweep-samples) on one context; summary gains `sweep`, --out gets n<N>_t<T>/")
     ap.add_argument("--sweep-samples", nargs="+", type=int, default=None, metavar="N",
                     help="render the set once per sample budget N (x --sweep-thresholds)")
+    ap.add_argument("--sweep-scales", nargs="+", type=float, default=None, metavar="S",
+                    help="render the set once per scale S of the dataset's resolution (x the other sweeps) on the same context, present it "
+                         "to the full size on the GPU and score that 8-bit image; entries gain `scale`, --out directories _s<S>")
     return ap
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
     summary, _ = evaluate(a.model_dir, a.dataset_dir, a.set, a.out, a.precision, a.batch_size, a.max_frames, video=a.video, fps=a.fps,
-                          metrics=tuple(a.metrics), sweep_thresholds=a.sweep_thresholds, sweep_samples=a.sweep_samples)
+                          metrics=tuple(a.metrics), sweep_thresholds=a.sweep_thresholds, sweep_samples=a.sweep_samples, sweep_scales=a.sweep_scales)
     print(json.dumps(summary))
 
 

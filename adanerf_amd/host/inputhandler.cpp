@@ -81,6 +81,17 @@ bool InputHandler::replay(const char* line) {
         if (end == val.c_str() || *end != 0 || !(t >= 0.f)) return false;
         renderer.setSelection(0, t);
       }
+    } else if (tok == "size") {
+      // two values, each read whole: "size 400 300"; the library validates the size when the frame is rendered
+      long v[2];
+      for (long& x : v) {
+        std::string val;
+        if (!(in >> val)) return false;
+        char* end = nullptr;
+        x = std::strtol(val.c_str(), &end, 10);
+        if (end == val.c_str() || *end != 0 || x < 1 || x > 1 << 16) return false;
+      }
+      renderer.setFrameSize(static_cast<int>(v[0]), static_cast<int>(v[1]));
     } else if ((tok[0] == '+' || tok[0] == '-') && tok.size() > 1) {
       Key k;
       if (!key_of(tok.substr(1), &k)) return false;

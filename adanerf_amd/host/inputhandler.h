@@ -21,7 +21,8 @@ class InputHandler {
   bool quitRequested() const { return quit; }
   // one script line = the events in front of one frame: "+w" "-w" (key down / up: w a s d q e o f esc), "b+ x y" / "b- x y"
   // (left button), "m x y" (mouse position), "n <int>" / "thr <float>" (sample budget N / selection threshold from this line's frame
-  // on: NeuralRenderer::setSelection); returns false on a malformed line
+  // on: NeuralRenderer::setSelection), "size <W> <H>" (frame size from this line's frame on, the window size stays:
+  // NeuralRenderer::setFrameSize); returns false on a malformed line
   bool replay(const char* line);
 
  private:

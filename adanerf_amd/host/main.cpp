@@ -51,7 +51,7 @@ int main(int argc, char* argv[]) {
     if (settings.log_camera)
       std::printf("camera %d pos %.9g %.9g %.9g yaw %.9g pitch %.9g view %s\n", f, camera.pos[0], camera.pos[1], camera.pos[2],
                   camera.yaw, camera.pitch, neural_renderer.renderingOracle() ? "oracle" : "image");
-    if (!settings.dry_run && !neural_renderer.render()) {
+    if (!(settings.dry_run ? neural_renderer.applyFrameSize() : neural_renderer.render())) {
       std::cout << "render failed: " << neural_renderer.error() << std::endl;
       return -1;
     }

@@ -16,6 +16,7 @@ NeuralRenderer::~NeuralRenderer() {
   if (ctx) {
     if (d_gathered) adanerf_free(ctx, d_gathered);
     if (d_frame) adanerf_free(ctx, d_frame);
+    if (d_window) adanerf_free(ctx, d_window);
     adanerf_destroy(ctx);
   }
 }
@@ -30,7 +31,7 @@ static adanerf_options options_of(const Settings& settings) {
   std::memset(&opt, 0, sizeof(opt));
   opt.width = static_cast<int32_t>(settings.width);
   opt.height = static_cast<int32_t>(settings.height);
-  opt.batch_rays = static_cast<int32_t>(settings.batch_size);
+  opt.batch_rays = settings.batch_request;      // the library clamps it to the frame (Settings::batch_size), again at every size
   opt.num_samples = settings.num_samples;
   opt.threshold = settings.threshold;
   opt.sampling_mode = (settings.sampling == "split" || settings.sampling == "auto") ? ADANERF_SAMPLING_SPLIT_FP16 : (settings.sampling == "fp32" ? ADANERF_SAMPLING_FP32
@@ -91,7 +92,7 @@ bool NeuralRenderer::init() {
   std::memset(&opt, 0, sizeof(opt));
   opt.width = static_cast<int32_t>(settings.width);
   opt.height = static_cast<int32_t>(settings.height);
-  opt.batch_rays = static_cast<int32_t>(settings.batch_size);
+  opt.batch_rays = settings.batch_request;      // the library clamps it to the frame (Settings::batch_size), again at every size
   opt.device_id = 0;
   opt.precision = settings.precision == "fp32" ? ADANERF_PREC_FP32 : (settings.precision == "fp16" ? ADANERF_PREC_FP16 : ADANERF_PREC_BF16);
   opt.num_samples = settings.num_samples;
@@ -139,23 +140,13 @@ bool NeuralRenderer::init() {
     else peers.push_back(c);
   }
   adanerf_get_info(ctx, &info_);
-  if (adanerf_malloc(ctx, static_cast<size_t>(info_.width) * info_.height * 4, &d_frame) != ADANERF_OK) {
+  world_ = world;
+  strip_rows_ = strip_rows;
+  if (!allocFrameBuffers()) return false;
+  if (settings.write_window &&
+      adanerf_malloc(ctx, static_cast<size_t>(settings.window_width) * settings.window_height * 4, &d_window) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;
-  }
-  if (world > 1) {
-    const size_t payload = static_cast<size_t>(info_.rays_local_max) * 4;
-    if (adanerf_malloc(ctx, payload * world, &d_gathered) != ADANERF_OK) {
-      err = adanerf_last_error(ctx);
-      return false;
-    }
-    d_payload.assign(world, nullptr);
-    d_payload[0] = d_gathered;     // rank 0 renders straight into its slot
-    for (int rank = 1; rank < world; ++rank)
-      if (adanerf_malloc(peers[rank - 1], payload, &d_payload[rank]) != ADANERF_OK) {
-        err = adanerf_last_error(peers[rank - 1]);
-        return false;
-      }
   }
   camera.setPosition(info_.view_cell_center);   // Camera::init: pos = view-cell centre (camera.cpp:49)
   camera.setViewCell(info_.view_cell_size);
@@ -167,9 +158,71 @@ bool NeuralRenderer::init() {
   return true;
 }
 
+bool NeuralRenderer::allocFrameBuffers() {
+  if (d_frame && adanerf_free(ctx, d_frame) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+  d_frame = nullptr;
+  if (adanerf_malloc(ctx, static_cast<size_t>(info_.width) * info_.height * 4, &d_frame) != ADANERF_OK) {
+    err = adanerf_last_error(ctx);
+    return false;
+  }
+  if (world_ > 1) {
+    const size_t payload = static_cast<size_t>(info_.rays_local_max) * 4;
+    if (d_gathered && adanerf_free(ctx, d_gathered) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+    d_gathered = nullptr;
+    if (adanerf_malloc(ctx, payload * world_, &d_gathered) != ADANERF_OK) {
+      err = adanerf_last_error(ctx);
+      return false;
+    }
+    d_payload.resize(world_, nullptr);
+    d_payload[0] = d_gathered;     // rank 0 renders straight into its slot
+    for (int rank = 1; rank < world_; ++rank) {
+      if (d_payload[rank] && adanerf_free(peers[rank - 1], d_payload[rank]) != ADANERF_OK) return err = adanerf_last_error(peers[rank - 1]), false;
+      d_payload[rank] = nullptr;
+      if (adanerf_malloc(peers[rank - 1], payload, &d_payload[rank]) != ADANERF_OK) {
+        err = adanerf_last_error(peers[rank - 1]);
+        return false;
+      }
+    }
+  }
+  return true;
+}
+
+// script token "size": every context (--gpus / --sub-shares) gets the same frame size before this frame, the frame buffers follow;
+// the window size stays.  Without a device (--dry-run) the model directory is parsed again at the new size: the same validation.
+bool NeuralRenderer::applyFrameSize() {
+  if (!size_pending) return true;
+  size_pending = false;
+  const int w = want_width, h = want_height;
+  if (!ctx) {
+    Settings at = settings;
+    at.width = static_cast<unsigned>(w);
+    at.height = static_cast<unsigned>(h);
+    const adanerf_options opt = options_of(at);
+    if (adanerf_host_parse_model(settings.model_path.c_str(), &opt, &info_) != ADANERF_OK) return err = adanerf_last_error(nullptr), false;
+  } else {
+    // a live context keeps its strip height: the rows of the new size must split into those strips over the shares as evenly as at start
+    if (world_ > 1 && (h % strip_rows_ != 0 || (h / strip_rows_) % world_ != 0)) {
+      err = "size " + std::to_string(w) + " x " + std::to_string(h) + ": " + std::to_string(h) + " rows do not split into strips of " +
+            std::to_string(strip_rows_) + " rows over " + std::to_string(world_) + " shares";
+      return false;
+    }
+    std::vector<adanerf_ctx*> all(1, ctx);
+    all.insert(all.end(), peers.begin(), peers.end());
+    for (adanerf_ctx* c : all)
+      if (adanerf_set_frame_size(c, w, h) != ADANERF_OK) return err = adanerf_last_error(c), false;
+    adanerf_get_info(ctx, &info_);
+    if (!allocFrameBuffers()) return false;
+  }
+  settings.width = static_cast<unsigned>(info_.width);
+  settings.height = static_cast<unsigned>(info_.height);
+  settings.total_size = settings.width * settings.height;
+  return true;
+}
+
 bool NeuralRenderer::render() {
   float rot[9];
   camera.getRotMatrix(rot);
+  if (!applyFrameSize()) return false;
   if (selection_pending) {      // script tokens "n" / "thr": every context (--gpus / --sub-shares) gets the same pair before this frame
     selection_pending = false;
     std::vector<adanerf_ctx*> all(1, ctx);
@@ -193,7 +246,7 @@ bool NeuralRenderer::render() {
       return false;
     }
     sample_count++;
-    return settings.write_images ? writeImageToFile() : true;
+    return writeImageToFile();
   }
   adanerf_stats st;
   std::memset(&st, 0, sizeof(st));
@@ -228,11 +281,11 @@ bool NeuralRenderer::render() {
                   << ", fc2: " << st.ms_compact / f << ", rm: " << st.ms_composite / f
                   << ", avg samples ppx: " << st.total_samples * world / f / settings.total_size
                   << " (total: " << static_cast<long long>(st.total_samples * world / f) << ")"
-                  << ", N: " << info_.num_samples << ", thr: " << info_.threshold
+                  << ", N: " << info_.num_samples << ", thr: " << info_.threshold << ", size: " << info_.width << "x" << info_.height
                   << ", frames: " << sample_count << ", gpus: " << peers.size() + 1 << " (stage times: GPU 0's share)" << std::endl;
       }
     }
-    return settings.write_images ? writeImageToFile() : true;
+    return writeImageToFile();
   }
   if (adanerf_render(ctx, d_frame, nullptr, &st) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
@@ -260,25 +313,36 @@ bool NeuralRenderer::render() {
               << ", fc2: " << s_fc2 / logging_interval << ", rm: " << s_rm / logging_interval
               << ", avg samples ppx: " << s_num_total_samples / static_cast<double>(logging_interval) / settings.total_size
               << " (total: " << s_num_total_samples / logging_interval << ")"
-              << ", N: " << info_.num_samples << ", thr: " << info_.threshold
+              << ", N: " << info_.num_samples << ", thr: " << info_.threshold << ", size: " << info_.width << "x" << info_.height
               << ", frames: " << sample_count << ", frame ms: " << s_total / logging_interval << std::endl;
     s_inference1 = s_inference2 = s_fc2 = s_rm = s_total = 0;
     s_num_total_samples = 0;
   }
-  if (settings.write_images) return writeImageToFile();
-  return true;
+  return writeImageToFile();
 }
 
+// -w: the frame at its render size, exactly as before; --write-window: the frame as the viewer's blit would show it in a window of
+// -ws W H (interoprenderbuffer.cpp:87), presented on the device
 bool NeuralRenderer::writeImageToFile() {
-  const int w = static_cast<int>(settings.width), h = static_cast<int>(settings.height);
+  if (settings.write_images && !writeBmp("out.bmp", d_frame, static_cast<int>(settings.width), static_cast<int>(settings.height))) return false;
+  if (!settings.write_window) return true;
+  const int ww = static_cast<int>(settings.window_width), wh = static_cast<int>(settings.window_height);
+  if (adanerf_present(ctx, d_frame, static_cast<int>(settings.width), static_cast<int>(settings.height), d_window, ww, wh, 0) != ADANERF_OK) {
+    err = adanerf_last_error(ctx);
+    return false;
+  }
+  return writeBmp("out_window.bmp", d_window, ww, wh);
+}
+
+bool NeuralRenderer::writeBmp(const std::string& name, const void* d_image, int w, int h) {
   std::vector<unsigned char> image(static_cast<size_t>(w) * h * 4);
-  if (adanerf_memcpy_d2h(ctx, image.data(), d_frame, image.size()) != ADANERF_OK) {
+  if (adanerf_memcpy_d2h(ctx, image.data(), d_image, image.size()) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;
   }
   std::string path = settings.model_path;
   if (!path.empty() && path.back() != '/') path += '/';
-  path += "out.bmp";
+  path += name;
   std::ofstream fout(path, std::ios::binary);
   if (!fout) {
     err = "cannot write " + path;

@@ -30,8 +30,20 @@ class NeuralRenderer {
     *thr = want_threshold;
     return selection_pending;
   }
+  // frame size from the next frame on ("size W H"); the window size stays.  Reaches every context in render()
+  void setFrameSize(int w, int h) {
+    want_width = w;
+    want_height = h;
+    size_pending = true;
+  }
+  bool pendingFrameSize(int* w, int* h) const {      // what the next frame will ask of the library
+    *w = want_width;
+    *h = want_height;
+    return size_pending;
+  }
+  bool applyFrameSize();             // a pending setFrameSize, now: render() calls it; --dry-run calls it in render()'s place (host only)
   int batchesPerFrame() const;       // ceil(rays / batch_rays)
-  bool writeImageToFile();           // out.bmp in the model directory (neuralrenderer.cpp:184-222)
+  bool writeImageToFile();           // out.bmp in the model directory (neuralrenderer.cpp:184-222); --write-window: out_window.bmp too
   const adanerf_info& info() const { return info_; }
   const std::string& error() const { return err; }
 
@@ -44,11 +56,17 @@ class NeuralRenderer {
   void* d_gathered = nullptr;        // rank 0: uchar4 [N][rays_local_max]
   adanerf_info info_{};
   void* d_frame = nullptr;           // uchar4 [h*w]
+  void* d_window = nullptr;          // --write-window: uchar4 [window_height*window_width], the frame as adanerf_present shows it
+  int world_ = 1, strip_rows_ = 8;   // share layout chosen at init; a live context keeps its strip height
+  bool allocFrameBuffers();          // d_frame, d_gathered, d_payload for the size in info_ (again after a size change)
+  bool writeBmp(const std::string& name, const void* d_image, int w, int h);
   std::string err;
   bool render_oracle = false;
   bool selection_pending = false;    // setSelection since the last frame
   int want_samples = 0;
   float want_threshold = -1.f;
+  bool size_pending = false;         // setFrameSize since the last frame
+  int want_width = 0, want_height = 0;
   // 100-frame running sums
   int logging_interval = 100, sample_count = 0;
   double s_inference1 = 0, s_inference2 = 0, s_fc2 = 0, s_rm = 0, s_total = 0;

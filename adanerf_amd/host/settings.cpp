@@ -8,12 +8,14 @@
 const char* Settings::usage() {
   return "Usage: adanerf [modelPath] [-s|--size W H] [-ws|--windowSize W H] [-bs|--batchSize N]\n"
          "               [-nb|--numberOfBatches N] [-w|--writeImages] [-d|--debug]\n"
+         "               [--write-window]     also write the frame presented at the window size (-ws): out_window.bmp\n"
          "               [--frames N] [--precision bf16|fp16|fp32] [--sampling auto|guarded|split|fp32|fp16]\n"
          "               [--yaw DEG] [--pitch DEG]\n"
          "               [--samples N] [--threshold T] [--oracle]\n"
          "               [--script FILE] [--log-camera] [--dry-run]     input replay: one line of events per frame\n"
          "                                                              (+w -w ... b+ x y  b- x y  m x y; n <int> / thr <float>:\n"
-         "                                                              sample budget N / threshold from that frame on)\n"
+         "                                                              sample budget N / threshold from that frame on;\n"
+         "                                                              size <W> <H>: frame size from that frame on, the window stays)\n"
          "               [--gpus N] [--same-device] [--sub-shares P]\n";
 }
 
@@ -50,6 +52,8 @@ bool Settings::init(int argc, char** argv, std::string* err) {
       n_batches = static_cast<unsigned>(std::max(1, std::atoi(argv[++i])));
     } else if (a == "-w" || a == "--writeImages") {
       write_images = true;
+    } else if (a == "--write-window") {
+      write_window = true;
     } else if (a == "-d" || a == "--debug") {
       is_debug = true;
     } else if (a == "--frames") {
@@ -109,6 +113,10 @@ bool Settings::init(int argc, char** argv, std::string* err) {
     *err = "size must be positive";
     return false;
   }
+  if (ws_used && (window_width == 0 || window_height == 0)) {
+    *err = "window size must be positive";
+    return false;
+  }
   total_size = width * height;
   if (sampling.empty()) sampling = "split";      // exact by construction; guarded / fp16 are opt-in (the default rule)
   if (!ws_used) {
@@ -118,5 +126,6 @@ bool Settings::init(int argc, char** argv, std::string* err) {
   // settings.cpp:38-46
   batch_size = static_cast<unsigned>(std::ceil(total_size / static_cast<float>(n_batches)));
   if (bs_used) batch_size = batch_arg <= 0 ? total_size : std::min(static_cast<unsigned>(batch_arg), total_size);
+  batch_request = bs_used ? std::max(batch_arg, 0) : (n_batches > 1 ? static_cast<int>(batch_size) : 0);
   return true;
 }

@@ -7,9 +7,12 @@ class Settings {
  public:
   std::string model_path = "sample/";
   unsigned int width = 800, height = 800, total_size = 640000;
-  unsigned int window_width = 800, window_height = 800;   // accepted, unused (headless)
+  unsigned int window_width = 800, window_height = 800;   // -ws: the size --write-window presents the frame at (default: the frame size)
   unsigned int batch_size = 640000;
+  int batch_request = 0;        // what adanerf_options.batch_rays gets: -bs as given (not clamped to the first frame size, so that a
+                                // "size" token re-derives the batch from it), -nb's share of the first frame, 0: the whole frame
   bool write_images = false;
+  bool write_window = false;    // --write-window: also write the frame presented at the window size (out_window.bmp beside out.bmp)
   bool is_debug = false;        // -d: accepted, headless is always "debug" (no GL interop)
   // headless extras (not in the reference)
   int frames = 100;             // --frames: frames to render before exiting

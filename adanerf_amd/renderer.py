@@ -24,6 +24,8 @@ _PREC = {"bf16": PREC_BF16, "fp16": PREC_FP16, "f16": PREC_FP16, "fp32": PREC_FP
 BUF_RAYS, BUF_ORACLE, BUF_RAY_OFFSETS, BUF_RAY_COUNTS, BUF_SAMPLE_KEY, BUF_SAMPLE_W, BUF_RAW, BUF_TOTAL, BUF_SAMPLE_Z, BUF_RAW_COARSE = range(10)
 SAMPLER_ADAPTIVE, SAMPLER_PDF, SAMPLER_COARSE_FINE = 0, 1, 2
 FLAG_KEEP_ORACLE, FLAG_WAVE_SELECT, FLAG_NO_GUARD_CACHE, FLAG_GUARD_AUDIT_FILL = 1, 2, 4, 8
+PRESENT_FLIP_Y, PRESENT_NEAREST, PRESENT_LINEAR = 1, 2, 4      # adanerf_present flags
+PRESENT_FILTERS = {None: 0, "nearest": PRESENT_NEAREST, "linear": PRESENT_LINEAR}
 ABI_VERSION = 4
 GUARD_FROM = {0: "none", 1: "options", 2: "record", 3: "calibration", 4: "monitor"}
 SAMPLING_MODES = {"split": 0, "fp16x3": 0, "fp32": 1, "fp16": 2, "guarded": 3}
@@ -64,7 +66,7 @@ class Stats(C.Structure):
                 ("guard_audit_mismatch", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
-EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_last_error", "adanerf_abi_version", "adanerf_struct_sizes", "adanerf_set_camera", "adanerf_set_selection",
+EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_last_error", "adanerf_abi_version", "adanerf_struct_sizes", "adanerf_set_camera", "adanerf_set_selection", "adanerf_set_frame_size", "adanerf_present",
            "adanerf_render", "adanerf_set_aux_outputs", "adanerf_set_disp_output", "adanerf_assemble_strips", "adanerf_sync", "adanerf_set_stream", "adanerf_set_profiling",
            "adanerf_collect_stats", "adanerf_ray_features", "adanerf_sample_mlp",
            "adanerf_compact", "adanerf_compact_guarded", "adanerf_calibrate_guard", "adanerf_guard_calibration_file", "adanerf_shade_features", "adanerf_shade_mlp", "adanerf_shade_mlp_z", "adanerf_sample_pdf", "adanerf_sample_uniform", "adanerf_shade_mlp_coarse", "adanerf_sample_from_coarse",
@@ -92,6 +94,8 @@ def load_library(path: Optional[str] = None):
     lib.adanerf_last_error.restype = C.c_char_p
     lib.adanerf_set_camera.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.adanerf_set_selection.argtypes = [vp, i32, C.c_float]
+    lib.adanerf_set_frame_size.argtypes = [vp, i32, i32]
+    lib.adanerf_present.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32]
     lib.adanerf_render.argtypes = [vp, vp, vp, C.POINTER(Stats)]
     lib.adanerf_assemble_strips.argtypes = [vp, vp, vp]
     lib.adanerf_set_aux_outputs.argtypes = [vp, vp, vp]
@@ -151,10 +155,25 @@ class Settings:
     number_of_batches: int = 1    # -nb (overridden by batch_size)
     write_images: bool = False
     is_debug: bool = True         # headless always
+    window_width: Optional[int] = None    # -ws: the size a frame is presented at (NeuralRenderer.present); None -> the frame size
+    window_height: Optional[int] = None   # at construction, as the viewer's Settings defaults it
+
+    def __post_init__(self):
+        if self.window_width is None:
+            self.window_width = self.width
+        if self.window_height is None:
+            self.window_height = self.height
 
     @property
     def total_size(self) -> int:
         return self.width * self.height
+
+    def requested_batch(self) -> int:
+        """What adanerf_options.batch_rays gets: -bs as given (the library clamps it to the frame, again at every set_frame_size), -nb's
+        share of the first frame, 0 for the whole frame."""
+        if self.batch_size and self.batch_size > 0:
+            return int(self.batch_size)
+        return self.resolved_batch() if self.number_of_batches > 1 else 0
 
     def resolved_batch(self) -> int:
         if self.batch_size and self.batch_size > 0:
@@ -267,7 +286,7 @@ class NeuralRenderer:
         self.settings = settings
         self.lib = load_library(lib_path)
         self.handle = None
-        self._opt = _Options(width=settings.width, height=settings.height, batch_rays=settings.resolved_batch(),
+        self._opt = _Options(width=settings.width, height=settings.height, batch_rays=settings.requested_batch(),
                              device_id=device_id, precision=_PREC[precision] if isinstance(precision, str) else int(precision),
                              num_samples=num_samples, threshold=threshold, shard_rank=shard_rank,
                              shard_world=shard_world, strip_rows=strip_rows,
@@ -278,6 +297,7 @@ class NeuralRenderer:
         self.info = Info()
         self.last_stats = Stats()
         self._own = []
+        self._last_frame = None       # (device rgba8, width, height) of the last render() that wrote one
 
     # -- lifecycle -------------------------------------------------------------------------------
     def init(self) -> bool:
@@ -341,11 +361,33 @@ class NeuralRenderer:
                                                    -1.0 if threshold is None else float(threshold)))
         return self.refresh_info()
 
+    def set_frame_size(self, width: Optional[int] = None, height: Optional[int] = None) -> "Info":
+        """The frame size for the frames rendered from now on (None keeps the value in force); the context is then what one constructed
+        with this size would be, without reloading the model (adanerf_set_frame_size).  ``settings.width / height`` follow, the window
+        size stays; the renderer's own output buffers (render_numpy) are made again at the next frame; device buffers the caller made
+        for the old size, the ones behind set_aux_outputs / set_disp_output included (the library drops those when rays_local
+        changes), are the caller's to re-make.  Refreshes and returns ``self.info``."""
+        self._check(self.lib.adanerf_set_frame_size(self.handle, 0 if width is None else int(width), 0 if height is None else int(height)))
+        self.refresh_info()
+        self.settings.width, self.settings.height = self.info.width, self.info.height
+        for name in ("_o_rgb", "_o_rgba"):
+            if hasattr(self, name):
+                a = getattr(self, name)
+                if self._last_frame is not None and self._last_frame[0] is a:
+                    self._last_frame = None
+                a.free()
+                self._own.remove(a)
+                delattr(self, name)
+        return self.info
+
     def render(self, rgba8_out=None, rgb_out=None, stats: bool = False) -> Optional[Stats]:
         """One frame into caller-owned device buffers ([rays_local] uchar4 / [rays_local,3] fp32).
         ``stats=True`` synchronises and returns the per-stage timing record."""
         st = Stats() if stats else None
         self._check(self.lib.adanerf_render(self.handle, _ptr(rgba8_out), _ptr(rgb_out), C.byref(st) if stats else None))
+        if rgba8_out is not None:      # what present() shows: whole frames only (a shard's rows wait for adanerf_assemble_strips)
+            whole = self.info.rays_local == self.info.width * self.info.height
+            self._last_frame = (rgba8_out, self.info.width, self.info.height) if whole else None
         if stats:
             self.last_stats = st
         return st
@@ -379,6 +421,32 @@ class NeuralRenderer:
             self._o_rgba = self.empty((n, 4), np.uint8)
         st = self.render(self._o_rgba, self._o_rgb, stats=True)
         return self._o_rgb.numpy(), self._o_rgba.numpy(), st
+
+    # -- the frame at the window's size ---------------------------------------------------------------
+    def present_device(self, src_rgba8, src_w: int, src_h: int, dst_rgba8, dst_w: int, dst_h: int, flip_y: bool = False,
+                       filter: Optional[str] = None):
+        """The viewer's blit from its render buffer to the window (interoprenderbuffer.cpp:87) on device images: row-major uchar4
+        [src_h*src_w] -> [dst_h*dst_w], on the context's stream (adanerf_present).  filter None: the reference's rule (linear if the
+        destination is wider than the source, else nearest); "nearest" / "linear" force one.  flip_y: rows bottom-up (BMP order)."""
+        if filter not in PRESENT_FILTERS:
+            raise ValueError("present: filter must be None, 'nearest' or 'linear', got %r" % (filter,))
+        self._check(self.lib.adanerf_present(self.handle, _ptr(src_rgba8), int(src_w), int(src_h), _ptr(dst_rgba8), int(dst_w), int(dst_h),
+                                             (PRESENT_FLIP_Y if flip_y else 0) | PRESENT_FILTERS[filter]))
+
+    def present(self, window_w: Optional[int] = None, window_h: Optional[int] = None, flip_y: bool = False,
+                filter: Optional[str] = None) -> np.ndarray:
+        """The last rendered frame (render_numpy, or a render() with an rgba8 buffer) at the window's size: uint8
+        [window_h, window_w, 4].  Default size: settings.window_width / window_height.  Whole frames only (shard_world 1)."""
+        if self._last_frame is None:
+            raise AdaNeRFError("present: no whole frame has been rendered into an rgba8 buffer yet (a shard's strips: assemble them, then present_device)")
+        src, w, h = self._last_frame
+        ww, wh = int(window_w or self.settings.window_width), int(window_h or self.settings.window_height)
+        dst = DeviceArray(self, (wh, ww, 4), np.uint8)
+        try:
+            self.present_device(src, w, h, dst, ww, wh, flip_y=flip_y, filter=filter)
+            return dst.numpy()
+        finally:
+            dst.free()
 
     # -- image metrics -----------------------------------------------------------------------------
     def flip_device(self, test_rgb, ref_rgb, width: int, height: int, pixels_per_degree: Optional[float] = None, error_map=None,

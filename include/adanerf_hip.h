@@ -12,6 +12,8 @@
  *   adanerf_set_camera                   Camera::UpdateFeatureRot/getPosition (src/camera.cpp:143-201)
  *   adanerf_set_selection                numRaymarchSamples / adaptiveSamplingThreshold: members of RayMarchFromPoses, handed to
  *                                        updateRayMarchFromPosesAdaptive on every call (src/featureset.cpp:80,153)
+ *   adanerf_set_frame_size               Settings::width / height (src/settings.cpp:20-33), fixed for the life of the viewer's NeuralRenderer
+ *   adanerf_present                      the blit from the render buffer to the window (src/interoprenderbuffer.cpp:87)
  *   adanerf_render                       ImageGenerator::inference, 2-context adaptive branch
  *                                        (src/imagegenerator.cpp:282-394) as called from
  *                                        NeuralRenderer::render (src/neuralrenderer.cpp:146-182)
@@ -285,6 +287,26 @@ int adanerf_set_camera(adanerf_ctx* ctx, const float pos[3], const float rot_c2w
  *   alone.  Outside the fused selection's domain (N > 16, threshold 0) the mode runs the split-precision engine alone, as after create. */
 int adanerf_set_selection(adanerf_ctx* ctx, int32_t num_samples, float threshold);
 
+/* The frame size of a live context: the third dial of a real-time viewer beside N and the threshold (a window resize, a dynamic-resolution
+ * step, a resolution-against-quality table).  Replaces Settings::width / height (src/settings.cpp:20-33), which are fixed for the life of
+ * the viewer's NeuralRenderer.  width <= 0 keeps the width in force, height <= 0 the height in force (the convention of
+ * adanerf_set_selection).  The resulting size is validated by the code adanerf_create runs on options.width / .height, with its error codes
+ * and messages (width * height < 2^25, batch_rays * num_samples <= 2^31 - 1).  Afterwards the context is what a new context created with
+ * the original options and this size would be: the same frames byte for byte, the same adanerf_info -- width, height, rays_local,
+ * rays_local_max, batch_rays, focal and everything else.  batch_rays is derived again from the options.batch_rays the caller asked for
+ * at create, not from the clamped adanerf_info.batch_rays; shard_rank / shard_world / strip_rows stay and are applied to the new height.
+ * On failure nothing has changed.  The model, the packed networks, N, the threshold and the camera in force stay.
+ *   Ordering is that of adanerf_set_camera: the calls issued afterwards see the new size, frames already enqueued keep theirs (the ray
+ *   generator's constants reach the kernels by value).  Buffer capacities follow the largest batch_rays x N the context has held: device
+ *   memory is allocated (new buffers first, then the old ones freed) only when the batch exceeds that, never released before
+ *   adanerf_destroy, and the stream is synchronised only then; a shrink allocates nothing, a call that changes neither value touches
+ *   nothing, and adanerf_render never allocates for it.
+ *   The caller-owned per-ray outputs of adanerf_set_aux_outputs / adanerf_set_disp_output were sized for the old rays_local: a call that
+ *   CHANGES rays_local resets all three to NULL (set them again for the new size); a call that does not change it leaves them.
+ *   ADANERF_SAMPLING_GUARDED: the band belongs to (model, N, threshold) and its calibration runs on its own 64 x 64 rays, so the bounds,
+ *   their source and pose count in adanerf_info stay; the audit's phase and fill cycle start over (frames do not depend on either). */
+int adanerf_set_frame_size(adanerf_ctx* ctx, int32_t width, int32_t height);
+
 /* Renders this context's rays.  d_rgba8_out: [rays_local] uchar4 (A=255), row-major over the shard's
  * rows -- for shard_world==1 that is the whole image, pixel (x,y) at y*w+x.  d_rgb_f32_out: optional
  * [rays_local,3] fp32 unclamped colour (parity output).  Either may be NULL.  stats != NULL makes
@@ -479,6 +501,29 @@ int adanerf_composite(adanerf_ctx* ctx, const float* d_raw, const float* d_sampl
  * same bits. */
 int adanerf_flip(adanerf_ctx* ctx, const float* d_test_rgb, const float* d_ref_rgb, int32_t width, int32_t height,
                  float pixels_per_degree, float* d_error_map, float* mean_out);
+
+/* adanerf_present flags */
+enum {
+  ADANERF_PRESENT_FLIP_Y = 1,  /* rows are written bottom-up: the reference's destination rectangle (GL's origin) and the BMP row order */
+  ADANERF_PRESENT_NEAREST = 2, /* force the nearest filter */
+  ADANERF_PRESENT_LINEAR = 4   /* force the linear filter; together with _NEAREST: ADANERF_EINVAL */
+};
+
+/* The frame at the window's size: the headless counterpart of the viewer's blit from its render buffer (-s W H) to the window (-ws W H),
+ * src/interoprenderbuffer.cpp:87 -- linear filtering on both axes if dst_w > src_w, nearest otherwise, as there.  With
+ * adanerf_set_frame_size this is dynamic resolution: a frame rendered at a reduced size reaches the caller at the window's size without
+ * leaving the device.
+ *   d_src_rgba8 [src_h*src_w] uchar4, d_dst_rgba8 [dst_h*dst_w] uchar4, both row-major and 4-byte aligned; every side in 1..16384; the
+ *   two ranges must not overlap.  Independent of the context's frame size (as adanerf_flip); runs on the context's stream.
+ *   flags: ADANERF_PRESENT_*; 0 gives a top-down image filtered by the rule above.
+ * GL leaves the rounding of a linear blit to the implementation; this library defines it in integers (the same bits on every call).
+ * Per axis, with D = 2 dst_w:  n = (2 x + 1) src_w - dst_w,  i0 = floor(n / D),  f = n - i0 D;  the taps are i0 and i0 + 1 clamped to the
+ * edge, their weights D - f and f (samples at pixel centres: equal sizes give the identity); y alike with E = 2 dst_h.  Per channel,
+ * alpha included, v = the sum of the four weighted taps and out = floor((2 v + D E) / (2 D E)).  Nearest takes pixel
+ * min(floor((2 x + 1) src_w / D), src_w - 1).  A NULL pointer, a side outside 1..16384, both filter flags, an unknown flag, a pointer
+ * that is not 4-byte aligned or overlapping ranges return ADANERF_EINVAL. */
+int adanerf_present(adanerf_ctx* ctx, const void* d_src_rgba8, int32_t src_w, int32_t src_h, void* d_dst_rgba8, int32_t dst_w,
+                    int32_t dst_h, int32_t flags);
 
 /* ---- measurement hook (bench.py's roofline) ---- */
 
