@@ -115,6 +115,8 @@ struct adanerf_ctx {
   float* aux_depth = nullptr;        // adanerf_set_aux_outputs: caller-owned [rays_local] buffers filled by adanerf_render
   float* aux_acc = nullptr;
   float* aux_disp = nullptr;         // adanerf_set_disp_output
+  const uint8_t* budget_n = nullptr;  // adanerf_set_budget_map: caller-owned [rays_local] per-ray N / threshold, read by the trim kernels of every render
+  const float* budget_thr = nullptr;
   DevBuf disp_scratch;               // [2, batch] depth / accumulation of the batch when the caller asked for disparity only
   // adanerf_flip: filter tables of the last pixels-per-degree value, per-tile sums, the mean; grown on demand
   DevBuf flip_tab, flip_partial, flip_mean;
@@ -259,6 +261,8 @@ bool generic_split_sampling(const adanerf_ctx* c) {
   return c->generic0 && c->sampling_mode != ADANERF_SAMPLING_FP32 && c->ms.ray_samples == 0 && c->net0_split.w.p != nullptr;
 }
 
+bool has_budget_map(const adanerf_ctx* c) { return c->budget_n != nullptr || c->budget_thr != nullptr; }
+
 // sel != nullptr: the adaptive selection runs in the kernel's epilogue (k_select_pair.hip.hpp) and d_oracle may be null
 int launch_sample_mlp(adanerf_ctx* c, int first_ray, int n_rays, float* d_oracle, float* d_rays, const SelectOut* sel = nullptr) {
   if (n_rays <= 0) return ADANERF_OK;
@@ -294,7 +298,8 @@ int launch_sample_mlp(adanerf_ctx* c, int first_ray, int n_rays, float* d_oracle
   }
   // Guarded two-precision selection: plain fp16 for every ray, then the split engine on the rays the guard band flagged.
   // Only where the selection is fused; otherwise this mode is the split-precision engine.
-  const bool guarded = c->sampling_mode == ADANERF_SAMPLING_GUARDED && sel != nullptr;
+  // Nor under a budget map: unrefined rays keep the fp16 engine's values in selw, and a trim by them would not be the exact selection.
+  const bool guarded = c->sampling_mode == ADANERF_SAMPLING_GUARDED && sel != nullptr && !has_budget_map(c);
   if (guarded) {
     // first guarded frame of a context created without a band: the model's record, or measure one
     if (int rc = c->guard_eps > 0.f ? 0 : ensure_guard_band(c)) return rc;
@@ -393,12 +398,29 @@ int launch_expand(adanerf_ctx* c, int n_rays, int n_max, int seg_shift, int32_t*
   HIP_RETURN(c, hipGetLastError());
 }
 
+// Per-ray budgets: the selection of the batch (counts, selbin, selw, segment totals per 2^seg_shift rays) trimmed to (n_r, thr_r) before
+// launch_expand (k_budget.hip.hpp).  The maps are indexed by local ray: ray 0 of the batch is entry map_first.
+struct BudgetMaps {
+  const uint8_t* n;
+  const float* thr;
+  int first;
+};
+
+int launch_trim(adanerf_ctx* c, const BudgetMaps& bm, int n_rays, int n_max, float thr, int seg_shift, int32_t* d_cnt) {
+  if (n_rays <= 0) return ADANERF_OK;
+  const bool per_thread = n_max <= kTrimThreadMaxN;
+  const dim3 grid(per_thread ? (n_rays + 255) / 256 : (n_rays + (1 << seg_shift) - 1) >> seg_shift);
+  hipLaunchKernelGGL(per_thread ? trim_rows_kernel : trim_rows_wave_kernel, grid, dim3(256), 0, c->stream, d_cnt, reinterpret_cast<uint8_t*>(c->selbin.p),
+                     reinterpret_cast<float*>(c->selw.p), bm.n, bm.thr, bm.first, n_rays, n_max, thr, seg_shift, reinterpret_cast<int32_t*>(c->block_total.p));
+  HIP_RETURN(c, hipGetLastError());
+}
+
 // the pair selection keeps its sorted candidate lists in registers: n_max <= kPairMaxN; ADANERF_FLAG_WAVE_SELECT forces the
 // wave-per-ray select_kernel (any n_max)
 bool use_pair_select(const adanerf_ctx* c, int n_max) { return n_max <= kPairMaxN && !(c->opt.flags & ADANERF_FLAG_WAVE_SELECT); }
 
 int launch_compact(adanerf_ctx* c, const float* d_oracle, int n_rays, int n_max, float thr, int32_t* d_off, int32_t* d_cnt,
-                   uint32_t* d_key, float* d_w, int32_t* d_total) {
+                   uint32_t* d_key, float* d_w, int32_t* d_total, const BudgetMaps* bm = nullptr) {
   if (n_rays <= 0) return ADANERF_OK;
   if (thr == 0.0f) {
     const size_t n = static_cast<size_t>(n_rays) * kBins;
@@ -409,12 +431,16 @@ int launch_compact(adanerf_ctx* c, const float* d_oracle, int n_rays, int n_max,
   if (use_pair_select(c, n_max)) {
     hipLaunchKernelGGL(select_rows_kernel, dim3((n_rays + 127) / 128), dim3(256), 0, c->stream, d_oracle, n_rays, select_out(c, n_max, thr, d_cnt),
                        static_cast<const int32_t*>(nullptr));
+    if (bm)
+      if (int rc = launch_trim(c, *bm, n_rays, n_max, thr, kPairSegShift, d_cnt)) return rc;
     return launch_expand(c, n_rays, n_max, kPairSegShift, d_off, d_cnt, d_key, d_w, d_total);
   }
   const int nblk = (n_rays + kSelRaysPerBlock - 1) / kSelRaysPerBlock;
   hipLaunchKernelGGL(select_kernel, dim3(nblk), dim3(256), 0, c->stream, d_oracle, n_rays, n_max, thr, c->ms.transform, d_cnt,
                      reinterpret_cast<uint8_t*>(c->selbin.p), reinterpret_cast<float*>(c->selw.p),
                      reinterpret_cast<int32_t*>(c->block_total.p));
+  if (bm)
+    if (int rc = launch_trim(c, *bm, n_rays, n_max, thr, kSelSegShift, d_cnt)) return rc;
   return launch_expand(c, n_rays, n_max, kSelSegShift, d_off, d_cnt, d_key, d_w, d_total);
 }
 
@@ -595,7 +621,11 @@ int apply_frame_size(adanerf_ctx* c, int was_rays) {
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (int rc = dev_alloc(c, &c->disp_scratch, B * 2 * sizeof(float))) return rc;
   }
-  if (c->ms.info.rays_local != was_rays) c->aux_depth = c->aux_acc = c->aux_disp = nullptr;
+  if (c->ms.info.rays_local != was_rays) {
+    c->aux_depth = c->aux_acc = c->aux_disp = nullptr;
+    c->budget_n = nullptr;      // the budget maps were sized for the old rays_local too
+    c->budget_thr = nullptr;
+  }
   c->guard_frame = 0;
   return ADANERF_OK;
 }
@@ -956,6 +986,8 @@ int adanerf_set_selection(adanerf_ctx* c, int32_t num_samples, float threshold) 
   if (std::isnan(threshold)) return fail(c, ADANERF_EINVAL, "threshold is not a number (a negative value keeps the one in force)");
   if (threshold >= 0.f && c->ms.info.sampler_mode != ADANERF_SAMPLER_ADAPTIVE)
     return fail(c, ADANERF_EUNSUPPORTED, "this model's sampler takes no threshold (adanerf_create ignores options.threshold for it): pass a negative one");
+  if (threshold == 0.f && has_budget_map(c))
+    return fail(c, ADANERF_EUNSUPPORTED, "threshold 0 (dense) keeps every bin: remove the budget map first (adanerf_set_budget_map with two NULLs)");
   ModelSetup& ms = c->ms;
   const adanerf_info was = ms.info;
   const ModelSetup::PosBound was_bound = ms.pos_bound;
@@ -1361,6 +1393,7 @@ int adanerf_render(adanerf_ctx* c, void* d_rgba8, float* d_rgb, adanerf_stats* s
   const int R = c->ms.info.rays_local, B = c->ms.info.batch_rays, N = c->ms.info.num_samples;
   const float thr = c->ms.info.threshold;
   const int n_batches = R > 0 ? (R + B - 1) / B : 0;
+  const bool budget = has_budget_map(c);      // adaptive sampler, threshold > 0 (adanerf_set_budget_map / adanerf_set_selection see to it)
   int rc = ensure_batch_buffers(c, std::min(B, std::max(R, 1)), N);
   if (rc) return rc;
   if (stats && c->profiling && c->events_used) {   // a synchronous call starts a fresh record
@@ -1421,16 +1454,20 @@ int adanerf_render(adanerf_ctx* c, void* d_rgba8, float* d_rgb, adanerf_stats* s
     const bool fused = !pdf && thr > 0.f && use_pair_select(c, N) && c->sampling_mode != ADANERF_SAMPLING_FP32 && (!c->generic0 || generic_split_sampling(c)) &&
                        !(c->opt.flags & ADANERF_FLAG_KEEP_ORACLE);
     const SelectOut so = select_out(c, N, thr, cnt);
+    const BudgetMaps bm{c->budget_n, c->budget_thr, first};
     if (!cfm && (rc = launch_sample_mlp(c, first, n, fused ? nullptr : oracle, rays, fused ? &so : nullptr))) return rc;
     if (ev && !cfm) HIP_TRY(c, hipEventRecord(ev[1], c->stream));
     float* sz = reinterpret_cast<float*>(c->sample_z.p);
     if (cfm) rc = ADANERF_OK;
     else if (pdf) rc = launch_sample_pdf(c, oracle, n, N, off, cnt, key, sw, sz, total);
-    else if (fused) rc = launch_expand(c, n, N, kPairSegShift, off, cnt, key, sw, total);
+    else if (fused) {
+      rc = budget ? launch_trim(c, bm, n, N, thr, kPairSegShift, cnt) : ADANERF_OK;
+      if (!rc) rc = launch_expand(c, n, N, kPairSegShift, off, cnt, key, sw, total);
+    }
     else if (thr == 0.f) {      // dense: implicit keys, the oracle buffer is the weight array (dense_offsets_kernel)
       hipLaunchKernelGGL(dense_offsets_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, off, cnt, total);
       HIP_TRY(c, hipGetLastError());
-    } else rc = launch_compact(c, oracle, n, N, thr, off, cnt, key, sw, total);
+    } else rc = launch_compact(c, oracle, n, N, thr, off, cnt, key, sw, total, budget ? &bm : nullptr);
     if (rc) return rc;
     const bool dense_implicit = !cfm && !pdf && !fused && thr == 0.f;
     const uint32_t* key_s = dense_implicit ? nullptr : key;
@@ -1461,8 +1498,9 @@ int adanerf_render(adanerf_ctx* c, void* d_rgba8, float* d_rgb, adanerf_stats* s
       c->events_used += 5;
     }
   }
-  if (c->sampling_mode == ADANERF_SAMPLING_GUARDED && c->guard_mask.p && n_batches > 0) ++c->guard_frame;      // the audit moves on
-  if (c->sampling_mode == ADANERF_SAMPLING_GUARDED && c->guard_mask.p && n_batches > 0 && !c->guard_ev_pending) {
+  // under a budget map the guarded mode renders as the split engine: no audit to move on, no monitor to read
+  if (c->sampling_mode == ADANERF_SAMPLING_GUARDED && c->guard_mask.p && n_batches > 0 && !budget) ++c->guard_frame;      // the audit moves on
+  if (c->sampling_mode == ADANERF_SAMPLING_GUARDED && c->guard_mask.p && n_batches > 0 && !budget && !c->guard_ev_pending) {
     if (!c->guard_host) {
       HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&c->guard_host), 8 * sizeof(int32_t)));
       std::memset(c->guard_host, 0, 8 * sizeof(int32_t));
@@ -1498,6 +1536,69 @@ int adanerf_set_disp_output(adanerf_ctx* c, float* d_disp_map) {
   BIND(c);
   c->aux_disp = d_disp_map;
   return ADANERF_OK;
+}
+
+int adanerf_set_budget_map(adanerf_ctx* c, const uint8_t* d_n_map, const float* d_thr_map) {
+  BIND(c);
+  if (d_n_map || d_thr_map) {
+    if (c->ms.coarse_fine || c->ms.info.sampler_mode != ADANERF_SAMPLER_ADAPTIVE)
+      return fail(c, ADANERF_EUNSUPPORTED, "per-ray budgets trim the adaptive selection: this model's sampler has none");
+    if (c->ms.info.dense) return fail(c, ADANERF_EUNSUPPORTED, "threshold 0 (dense) keeps every bin: there is no selection to trim");
+  }
+  // a guarded context renders as the split engine while a map is installed: the per-frame count of re-evaluated rays goes back to 0 in
+  // stream order (only a guarded frame writes it), as in reset_guard_band
+  if (c->sampling_mode == ADANERF_SAMPLING_GUARDED && (d_n_map || d_thr_map) && !has_budget_map(c) && c->total.p)
+    HIP_TRY(c, hipMemsetAsync(reinterpret_cast<int32_t*>(c->total.p) + kTotalRefined, 0, sizeof(int32_t), c->stream));
+  c->budget_n = d_n_map;
+  c->budget_thr = d_thr_map;
+  return ADANERF_OK;
+}
+
+int adanerf_foveate(adanerf_ctx* c, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* n, const float* thr,
+                    uint8_t* d_n_map, float* d_thr_map) {
+  if (!c) return ADANERF_EINVAL;
+  if (!std::isfinite(gaze_x) || !std::isfinite(gaze_y)) return fail(c, ADANERF_EINVAL, "adanerf_foveate: the gaze must be finite");
+  if (n_rings < 0 || n_rings > kFoveaMaxRings) return fail(c, ADANERF_EINVAL, "adanerf_foveate: n_rings must be in 0.." + std::to_string(kFoveaMaxRings));
+  if ((n_rings > 0 && !radius_px) || !n || !thr) return fail(c, ADANERF_EINVAL, "adanerf_foveate: NULL array");
+  FoveaParams f{};
+  for (int k = 0; k < n_rings; ++k) {
+    if (radius_px[k] < 0 || (k > 0 && radius_px[k] <= radius_px[k - 1]))
+      return fail(c, ADANERF_EINVAL, "adanerf_foveate: radii must be >= 0 and strictly ascending");
+    const uint64_t d = 2ull * static_cast<uint64_t>(radius_px[k]);
+    f.r2x4[k] = d * d;
+  }
+  for (int k = 0; k <= n_rings; ++k) {
+    if (n[k] < 0 || n[k] > 255) return fail(c, ADANERF_EINVAL, "adanerf_foveate: every n must be in 0..255");
+    if (std::isnan(thr[k])) return fail(c, ADANERF_EINVAL, "adanerf_foveate: a threshold is not a number");
+    f.n[k] = static_cast<uint8_t>(n[k]);
+    f.thr[k] = thr[k];
+  }
+  for (int k = n_rings; k < kFoveaMaxRings; ++k) {      // the slots behind the rings in use contain nothing and carry the outside entry
+    f.r2x4[k] = ~0ull;
+    f.n[k + 1] = f.n[n_rings];
+    f.thr[k + 1] = f.thr[n_rings];
+  }
+  // twice the gaze, to the nearest integer (ties to even); beyond +-2^31 half-pixels every pixel of any frame is equally far outside
+  auto half_px = [](float g) { return static_cast<int64_t>(std::lrintf(std::min(std::max(2.0f * g, -2147483648.0f), 2147483648.0f))); };
+  f.gx2 = half_px(gaze_x);
+  f.gy2 = half_px(gaze_y);
+  BIND(c);
+  const int R = c->ms.info.rays_local;
+  if (R <= 0 || (!d_n_map && !d_thr_map)) return ADANERF_OK;
+  hipLaunchKernelGGL(foveate_kernel, dim3((R + 255) / 256), dim3(256), 0, c->stream, c->ms.rg, f, R, d_n_map, d_thr_map);
+  HIP_RETURN(c, hipGetLastError());
+}
+
+int adanerf_compact_budget(adanerf_ctx* c, const float* d_oracle, int32_t n_rays, int32_t n_max, float thr, const uint8_t* d_n_map,
+                           const float* d_thr_map, int32_t* d_off, int32_t* d_cnt, uint32_t* d_key, float* d_w, int32_t* d_total) {
+  BIND(c);
+  if (!d_oracle || !d_off || !d_cnt || !d_key || !d_w || !d_total) return fail(c, ADANERF_EINVAL, "NULL buffer");
+  if (n_rays < 0 || n_max < 1 || n_max > kBins || !(thr > 0.f)) return fail(c, ADANERF_EINVAL, "n_rays/n_max/thr out of range (thr must be > 0: the dense mode selects nothing)");
+  if (static_cast<int64_t>(n_rays) >= (1ll << 25)) return fail(c, ADANERF_EINVAL, "n_rays must be < 2^25 per batch");
+  if (static_cast<int64_t>(n_rays) * n_max > 0x7fffffffll) return fail(c, ADANERF_EINVAL, "n_rays * n_max exceeds 2^31 - 1");
+  if (int rc = ensure_compact_scratch(c, n_rays, n_max)) return rc;
+  const BudgetMaps bm{d_n_map, d_thr_map, 0};
+  return launch_compact(c, d_oracle, n_rays, n_max, thr, d_off, d_cnt, d_key, d_w, d_total, &bm);
 }
 
 int adanerf_set_stream(adanerf_ctx* c, void* hip_stream) {

@@ -30,7 +30,7 @@ from typing import List, Optional
 import numpy as np
 
 from .png import read_png, write_png
-from .renderer import NeuralRenderer, Settings
+from .renderer import NeuralRenderer, Settings, parse_fovea
 
 
 def load_dataset(dataset_dir: str, set_name: str = "test"):
@@ -89,7 +89,7 @@ def scaled_size(w: int, h: int, scale: float):
 
 def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: Optional[str] = None,
              precision: str = "bf16", batch_size: int = -1, max_frames: int = 0, quiet: bool = False,
-             video: Optional[str] = None, fps: int = 30, metrics=("psnr",), sweep_thresholds=None, sweep_samples=None, sweep_scales=None):
+             video: Optional[str] = None, fps: int = 30, metrics=("psnr",), fovea=None, sweep_thresholds=None, sweep_samples=None, sweep_scales=None):
     """metrics: "psnr" (always reported where a ground-truth image exists) and / or "flip": each record gains ``flip``, the summary
     ``mean_flip``, and with out_dir the error map is written as an 8-bit greyscale ``%05d_flip.png``.
 
@@ -101,7 +101,13 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
 
     sweep_scales (list or None): innermost axis of the same cross product.  Each setting renders at scaled_size(w, h, S), presents the
     frame to w x h on the device and scores THAT image (uint8 / 255, also at S = 1: the entries of one table are measured alike);
-    samples_per_ray counts per rendered ray; entries and records carry ``scale``; frames written to out_dir / video are the presented ones."""
+    samples_per_ray counts per rendered ray; entries and records carry ``scale``; frames written to out_dir / video are the presented ones.
+
+    fovea (``R:N:T[,R:N:T...],N:T`` or what renderer.parse_fovea makes of it, or None): every frame is rendered with per-ray budgets around a
+    gaze at the centre of the rendered frame (radii in its pixels).  Records and summary keep their shape: PSNR / FLIP / samples per ray are
+    those of the foveated frames -- the quality-against-cost table of a foveation setting."""
+    if isinstance(fovea, str):
+        fovea = parse_fovea(fovea)
     unknown = sorted(set(metrics) - {"psnr", "flip"})
     if unknown:
         raise ValueError("unknown metrics %s (known: psnr, flip)" % unknown)
@@ -128,6 +134,8 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
             recs: List[dict] = []
             if out_dir:
                 os.makedirs(out_dir, exist_ok=True)
+            if fovea:      # again for every setting: a frame size that changes the ray count drops the maps
+                r.foveate((0.5 * rw, 0.5 * rh), fovea)
             for i, fr in enumerate(frames):
                 r.set_camera(fr["pose"], fr["rot"])
                 rgb, rgba, st = r.render_numpy()
@@ -209,13 +217,17 @@ def build_parser():
     ap.add_argument("--sweep-scales", nargs="+", type=float, default=None, metavar="S",
                     help="render the set once per scale S of the dataset's resolution (x the other sweeps) on the same context, present it "
                          "to the full size on the GPU and score that 8-bit image; entries gain `scale`, --out directories _s<S>")
+    ap.add_argument("--fovea", type=parse_fovea, default=None, metavar="R:N:T[,R:N:T...],N:T",
+                    help="per-ray sample budgets around a gaze at the image centre: rings (radius px : N : threshold), then the entry outside "
+                         "them; PSNR / FLIP / samples per ray are then those of the foveated frames")
     return ap
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
     summary, _ = evaluate(a.model_dir, a.dataset_dir, a.set, a.out, a.precision, a.batch_size, a.max_frames, video=a.video, fps=a.fps,
-                          metrics=tuple(a.metrics), sweep_thresholds=a.sweep_thresholds, sweep_samples=a.sweep_samples, sweep_scales=a.sweep_scales)
+                          metrics=tuple(a.metrics), sweep_thresholds=a.sweep_thresholds, sweep_samples=a.sweep_samples, sweep_scales=a.sweep_scales,
+                          fovea=a.fovea)
     print(json.dumps(summary))
 
 

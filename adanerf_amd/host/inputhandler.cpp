@@ -81,6 +81,17 @@ bool InputHandler::replay(const char* line) {
         if (end == val.c_str() || *end != 0 || !(t >= 0.f)) return false;
         renderer.setSelection(0, t);
       }
+    } else if (tok == "gaze") {
+      // two values, each read whole: "gaze 400.5 300"; pixels, may lie outside the frame
+      float v[2];
+      for (float& x : v) {
+        std::string val;
+        if (!(in >> val)) return false;
+        char* end = nullptr;
+        x = std::strtof(val.c_str(), &end);
+        if (end == val.c_str() || *end != 0 || !(x - x == 0.f)) return false;      // finite
+      }
+      renderer.setGaze(v[0], v[1]);
     } else if (tok == "size") {
       // two values, each read whole: "size 400 300"; the library validates the size when the frame is rendered
       long v[2];

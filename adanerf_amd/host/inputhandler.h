@@ -22,7 +22,8 @@ class InputHandler {
   // one script line = the events in front of one frame: "+w" "-w" (key down / up: w a s d q e o f esc), "b+ x y" / "b- x y"
   // (left button), "m x y" (mouse position), "n <int>" / "thr <float>" (sample budget N / selection threshold from this line's frame
   // on: NeuralRenderer::setSelection), "size <W> <H>" (frame size from this line's frame on, the window size stays:
-  // NeuralRenderer::setFrameSize); returns false on a malformed line
+  // NeuralRenderer::setFrameSize), "gaze <X> <Y>" (the --fovea gaze point in pixels from this line's frame on:
+  // NeuralRenderer::setGaze); returns false on a malformed line
   bool replay(const char* line);
 
  private:

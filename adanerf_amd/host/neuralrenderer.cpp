@@ -7,6 +7,12 @@
 #include <iostream>
 
 NeuralRenderer::~NeuralRenderer() {
+  for (size_t i = 0; i < d_fovea_n.size(); ++i) {
+    adanerf_ctx* c = i == 0 ? ctx : (i - 1 < peers.size() ? peers[i - 1] : nullptr);
+    if (!c) continue;
+    if (d_fovea_n[i]) adanerf_free(c, d_fovea_n[i]);
+    if (d_fovea_thr[i]) adanerf_free(c, d_fovea_thr[i]);
+  }
   for (size_t i = 0; i < peers.size(); ++i) {
     if (peers[i]) {
       if (i + 1 < d_payload.size() && d_payload[i + 1]) adanerf_free(peers[i], d_payload[i + 1]);
@@ -212,10 +218,41 @@ bool NeuralRenderer::applyFrameSize() {
       if (adanerf_set_frame_size(c, w, h) != ADANERF_OK) return err = adanerf_last_error(c), false;
     adanerf_get_info(ctx, &info_);
     if (!allocFrameBuffers()) return false;
+    fovea_pending = true;      // the maps belong to the old rays_local
   }
   settings.width = static_cast<unsigned>(info_.width);
   settings.height = static_cast<unsigned>(info_.height);
   settings.total_size = settings.width * settings.height;
+  return true;
+}
+
+// --fovea: every context (--gpus / --sub-shares) fills the maps of its own local rays from the gaze and installs them; again after a
+// "gaze" token and after a "size" token (the library drops the maps with the old rays_local).  Until a "gaze" token the gaze is the centre
+// of the frame in force.
+bool NeuralRenderer::applyFovea() {
+  if (settings.fovea_n.empty() || !fovea_pending || !ctx) return true;
+  fovea_pending = false;
+  if (!gaze_set) {
+    gaze_x = 0.5f * static_cast<float>(info_.width);
+    gaze_y = 0.5f * static_cast<float>(info_.height);
+  }
+  std::vector<adanerf_ctx*> all(1, ctx);
+  all.insert(all.end(), peers.begin(), peers.end());
+  d_fovea_n.resize(all.size(), nullptr);
+  d_fovea_thr.resize(all.size(), nullptr);
+  for (size_t i = 0; i < all.size(); ++i) {
+    adanerf_ctx* c = all[i];
+    adanerf_info in;
+    bool ok = adanerf_get_info(c, &in) == ADANERF_OK && adanerf_set_budget_map(c, nullptr, nullptr) == ADANERF_OK;
+    if (ok && d_fovea_n[i]) ok = adanerf_free(c, d_fovea_n[i]) == ADANERF_OK && adanerf_free(c, d_fovea_thr[i]) == ADANERF_OK;      // synchronises
+    d_fovea_n[i] = d_fovea_thr[i] = nullptr;
+    ok = ok && adanerf_malloc(c, static_cast<size_t>(in.rays_local), &d_fovea_n[i]) == ADANERF_OK &&
+         adanerf_malloc(c, static_cast<size_t>(in.rays_local) * sizeof(float), &d_fovea_thr[i]) == ADANERF_OK &&
+         adanerf_foveate(c, gaze_x, gaze_y, static_cast<int32_t>(settings.fovea_radius.size()), settings.fovea_radius.data(), settings.fovea_n.data(),
+                         settings.fovea_thr.data(), static_cast<uint8_t*>(d_fovea_n[i]), static_cast<float*>(d_fovea_thr[i])) == ADANERF_OK &&
+         adanerf_set_budget_map(c, static_cast<const uint8_t*>(d_fovea_n[i]), static_cast<const float*>(d_fovea_thr[i])) == ADANERF_OK;
+    if (!ok) return err = adanerf_last_error(c), false;
+  }
   return true;
 }
 
@@ -236,6 +273,7 @@ bool NeuralRenderer::render() {
     want_threshold = -1.f;
     adanerf_get_info(ctx, &info_);
   }
+  if (!applyFovea()) return false;
   if (adanerf_set_camera(ctx, camera.getPosition(), rot) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;

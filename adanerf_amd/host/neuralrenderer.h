@@ -41,6 +41,18 @@ class NeuralRenderer {
     *h = want_height;
     return size_pending;
   }
+  // --fovea: the gaze point from the next frame on (script token "gaze X Y", pixels); every context's maps are filled again in render()
+  void setGaze(float x, float y) {
+    gaze_x = x;
+    gaze_y = y;
+    gaze_set = true;
+    fovea_pending = true;
+  }
+  bool pendingGaze(float* x, float* y) const {      // what the next frame will ask of the library
+    *x = gaze_x;
+    *y = gaze_y;
+    return fovea_pending;
+  }
   bool applyFrameSize();             // a pending setFrameSize, now: render() calls it; --dry-run calls it in render()'s place (host only)
   int batchesPerFrame() const;       // ceil(rays / batch_rays)
   bool writeImageToFile();           // out.bmp in the model directory (neuralrenderer.cpp:184-222); --write-window: out_window.bmp too
@@ -65,6 +77,11 @@ class NeuralRenderer {
   bool selection_pending = false;    // setSelection since the last frame
   int want_samples = 0;
   float want_threshold = -1.f;
+  bool applyFovea();                 // --fovea: maps of every context filled for the gaze and the size in force, and installed
+  std::vector<void*> d_fovea_n, d_fovea_thr;   // per context (rank order): uint8 / float [rays_local] on that context's GPU
+  bool fovea_pending = true;         // the maps are to be filled before the next frame: at start, after "gaze", after "size"
+  bool gaze_set = false;             // a "gaze" token has moved it from the frame centre
+  float gaze_x = 0.f, gaze_y = 0.f;
   bool size_pending = false;         // setFrameSize since the last frame
   int want_width = 0, want_height = 0;
   // 100-frame running sums

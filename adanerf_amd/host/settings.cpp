@@ -12,11 +12,53 @@ const char* Settings::usage() {
          "               [--frames N] [--precision bf16|fp16|fp32] [--sampling auto|guarded|split|fp32|fp16]\n"
          "               [--yaw DEG] [--pitch DEG]\n"
          "               [--samples N] [--threshold T] [--oracle]\n"
+         "               [--fovea R:N:T[,R:N:T...],N:T]     per-ray budgets: rings around the gaze (radius px : N : threshold), then the\n"
+         "                                                  entry outside them; the gaze starts at the frame centre\n"
          "               [--script FILE] [--log-camera] [--dry-run]     input replay: one line of events per frame\n"
          "                                                              (+w -w ... b+ x y  b- x y  m x y; n <int> / thr <float>:\n"
          "                                                              sample budget N / threshold from that frame on;\n"
-         "                                                              size <W> <H>: frame size from that frame on, the window stays)\n"
+         "                                                              size <W> <H>: frame size from that frame on, the window stays;\n"
+         "                                                              gaze <X> <Y>: the --fovea gaze point, in pixels)\n"
          "               [--gpus N] [--same-device] [--sub-shares P]\n";
+}
+
+// R:N:T[,R:N:T...],N:T -- every field read whole; what adanerf_foveate would refuse is refused here, with the spec in the message
+bool Settings::parseFovea(const std::string& spec, std::vector<int>* radius, std::vector<int>* n, std::vector<float>* thr, std::string* err) {
+  auto bad = [&](const char* why) {
+    *err = "--fovea " + spec + ": " + why + " (expected R:N:T[,R:N:T...],N:T)";
+    return false;
+  };
+  radius->clear();
+  n->clear();
+  thr->clear();
+  std::vector<std::string> parts(1);
+  for (char ch : spec) {
+    if (ch == ',') parts.emplace_back();
+    else parts.back() += ch;
+  }
+  for (size_t k = 0; k < parts.size(); ++k) {
+    std::vector<std::string> f(1);
+    for (char ch : parts[k]) {
+      if (ch == ':') f.emplace_back();
+      else f.back() += ch;
+    }
+    const bool last = k + 1 == parts.size();
+    if (f.size() != (last ? 2u : 3u)) return bad(last ? "the last entry must be N:T" : "a ring must be R:N:T");
+    char* end = nullptr;
+    for (size_t j = 0; j + 1 < f.size(); ++j) {
+      const long v = std::strtol(f[j].c_str(), &end, 10);
+      if (end == f[j].c_str() || *end != 0) return bad("not an integer");
+      const bool is_radius = !last && j == 0;
+      if (is_radius && (v < 0 || v > 0x7fffffffl || (!radius->empty() && v <= radius->back()))) return bad("radii must be >= 0 and strictly ascending");
+      if (!is_radius && (v < 0 || v > 255)) return bad("N must be in 0..255");
+      (is_radius ? radius : n)->push_back(static_cast<int>(v));
+    }
+    const float t = std::strtof(f.back().c_str(), &end);
+    if (end == f.back().c_str() || *end != 0 || t != t) return bad("a threshold is not a number");
+    thr->push_back(t);
+  }
+  if (radius->size() > 8) return bad("at most 8 rings");
+  return true;
 }
 
 bool Settings::init(int argc, char** argv, std::string* err) {
@@ -89,6 +131,9 @@ bool Settings::init(int argc, char** argv, std::string* err) {
     } else if (a == "--sub-shares") {
       if (!need(i, 1)) return false;
       sub_shares = std::max(1, std::min(4, std::atoi(argv[++i])));
+    } else if (a == "--fovea") {
+      if (!need(i, 1)) return false;
+      if (!parseFovea(argv[++i], &fovea_radius, &fovea_n, &fovea_thr, err)) return false;
     } else if (a == "--oracle") {
       render_oracle = true;
     } else if (a == "--script") {

@@ -2,6 +2,7 @@
 // reference viewer (adanerf_real_time_viewer/src/main.cpp:19-50, src/settings.cpp:15-47).
 #pragma once
 #include <string>
+#include <vector>
 
 class Settings {
  public:
@@ -30,6 +31,12 @@ class Settings {
   std::string script;           // --script FILE: replay input events, one line per frame (inputhandler.h)
   bool log_camera = false;      // --log-camera: print position / yaw / pitch / view per frame
   bool dry_run = false;         // --dry-run: replay the script without a device (no rendering)
+  // --fovea R:N:T[,R:N:T...],N:T: per-ray sample budgets around a gaze point (adanerf_foveate): up to 8 rings, radius in whole pixels
+  // strictly ascending, each with the N (0..255, 0 = the context's) and threshold of the pixels inside it; the last entry is for the pixels
+  // outside every ring.  The gaze starts at the frame centre (script token `gaze X Y` moves it).  Empty fovea_n: no foveation
+  std::vector<int> fovea_radius, fovea_n;
+  std::vector<float> fovea_thr;
+  static bool parseFovea(const std::string& spec, std::vector<int>* radius, std::vector<int>* n, std::vector<float>* thr, std::string* err);
   bool render_oracle = false;   // --oracle: the viewer's 'O' key (inputhandler.cpp:76), sampling-network debug view
 
   // returns false and fills err on a malformed command line

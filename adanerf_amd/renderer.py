@@ -67,6 +67,7 @@ class Stats(C.Structure):
 
 
 EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_last_error", "adanerf_abi_version", "adanerf_struct_sizes", "adanerf_set_camera", "adanerf_set_selection", "adanerf_set_frame_size", "adanerf_present",
+           "adanerf_set_budget_map", "adanerf_foveate", "adanerf_compact_budget",
            "adanerf_render", "adanerf_set_aux_outputs", "adanerf_set_disp_output", "adanerf_assemble_strips", "adanerf_sync", "adanerf_set_stream", "adanerf_set_profiling",
            "adanerf_collect_stats", "adanerf_ray_features", "adanerf_sample_mlp",
            "adanerf_compact", "adanerf_compact_guarded", "adanerf_calibrate_guard", "adanerf_guard_calibration_file", "adanerf_shade_features", "adanerf_shade_mlp", "adanerf_shade_mlp_z", "adanerf_sample_pdf", "adanerf_sample_uniform", "adanerf_shade_mlp_coarse", "adanerf_sample_from_coarse",
@@ -95,6 +96,9 @@ def load_library(path: Optional[str] = None):
     lib.adanerf_set_camera.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.adanerf_set_selection.argtypes = [vp, i32, C.c_float]
     lib.adanerf_set_frame_size.argtypes = [vp, i32, i32]
+    lib.adanerf_set_budget_map.argtypes = [vp, vp, vp]
+    lib.adanerf_foveate.argtypes = [vp, C.c_float, C.c_float, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_float), vp, vp]
+    lib.adanerf_compact_budget.argtypes = [vp, vp, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp, vp]
     lib.adanerf_present.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32]
     lib.adanerf_render.argtypes = [vp, vp, vp, C.POINTER(Stats)]
     lib.adanerf_assemble_strips.argtypes = [vp, vp, vp]
@@ -223,6 +227,39 @@ def _ptr(x):
     if hasattr(x, "data_ptr"):      # torch tensor on the context's device
         return x.data_ptr()
     return int(x)
+
+
+FOVEA_MAX_RINGS = 8
+
+
+def parse_fovea(spec: str):
+    """``R:N:T[,R:N:T...],N:T`` -> [(R, N, T), ..., (N, T)]: concentric rings around the gaze (radius in whole pixels, strictly ascending,
+    at most 8), each with the sample budget N (0..255, 0 = the context's) and the threshold T of the pixels inside it, then the entry of
+    the pixels outside every ring.  The form adanerf_foveate / NeuralRenderer.foveate take.  ValueError on anything else."""
+    parts = [p.strip() for p in str(spec).split(",")]
+    if not parts or any(not p for p in parts):
+        raise ValueError("fovea %r: expected R:N:T[,R:N:T...],N:T" % (spec,))
+    out = []
+    for k, p in enumerate(parts):
+        f = p.split(":")
+        last = k == len(parts) - 1
+        if len(f) != (2 if last else 3):
+            raise ValueError("fovea %r: %r must be %s" % (spec, p, "N:T (the outside entry comes last)" if last else "R:N:T"))
+        try:
+            ints = [int(v) for v in f[:-1]]
+            t = float(f[-1])
+        except ValueError:
+            raise ValueError("fovea %r: %r is not %s" % (spec, p, "N:T" if last else "R:N:T")) from None
+        if t != t:
+            raise ValueError("fovea %r: a threshold is not a number" % (spec,))
+        if not 0 <= ints[-1] <= 255:
+            raise ValueError("fovea %r: N must be in 0..255" % (spec,))
+        if not last and (ints[0] < 0 or ints[0] >= 1 << 31 or (out and ints[0] <= out[-1][0])):
+            raise ValueError("fovea %r: radii must be >= 0 and strictly ascending" % (spec,))
+        out.append(tuple(ints) + (t,))
+    if len(out) - 1 > FOVEA_MAX_RINGS:
+        raise ValueError("fovea %r: at most %d rings" % (spec, FOVEA_MAX_RINGS))
+    return out
 
 
 def choose_sampling(settings, pos=None, rot_c2w=None, precision="bf16", frames: int = 6, warmup: int = 2, margin: float = DEFAULT_RULE_MARGIN, **kw):
@@ -370,6 +407,8 @@ class NeuralRenderer:
         self._check(self.lib.adanerf_set_frame_size(self.handle, 0 if width is None else int(width), 0 if height is None else int(height)))
         self.refresh_info()
         self.settings.width, self.settings.height = self.info.width, self.info.height
+        if hasattr(self, "_b_n") and self._b_n.shape[0] != self.info.rays_local:      # the library dropped the maps with the old rays_local
+            self._drop_budget_buffers()
         for name in ("_o_rgb", "_o_rgba"):
             if hasattr(self, name):
                 a = getattr(self, name)
@@ -379,6 +418,62 @@ class NeuralRenderer:
                 self._own.remove(a)
                 delattr(self, name)
         return self.info
+
+    # -- per-ray sample budgets ----------------------------------------------------------------------
+    def _drop_budget_buffers(self):
+        for name in ("_b_n", "_b_thr"):
+            if hasattr(self, name):
+                a = getattr(self, name)
+                a.free()
+                self._own.remove(a)
+                delattr(self, name)
+
+    def budget_buffers(self):
+        """The renderer's own device maps ([rays_local] uint8 N, [rays_local] fp32 threshold), made on first use and again after a frame
+        size that changes rays_local.  Fill them (upload, foveate_device) and install them with set_budget_map."""
+        n = self.info.rays_local
+        if not hasattr(self, "_b_n") or self._b_n.shape[0] != n:
+            self._drop_budget_buffers()
+            self._b_n = self.empty((n,), np.uint8)
+            self._b_thr = self.empty((n,), np.float32)
+        return self._b_n, self._b_thr
+
+    def set_budget_map(self, n_map=None, thr_map=None):
+        """Per-ray sample budgets for the frames rendered from now on (adanerf_set_budget_map): n_map [rays_local] uint8 (0 or above the
+        context's N: the context's N), thr_map [rays_local] fp32 (not above the context's threshold: the context's).  Each is a numpy array
+        (uploaded into the renderer's own buffer), a device buffer (the renderer's budget_buffers(), a DeviceArray, a pointer) or None (that
+        half follows the context); both None turns the feature off.  A frame size that changes rays_local removes the maps."""
+        own = self.budget_buffers() if any(isinstance(m, np.ndarray) for m in (n_map, thr_map)) else (None, None)
+        ptrs = []
+        for m, buf, dt in ((n_map, own[0], np.uint8), (thr_map, own[1], np.float32)):
+            if isinstance(m, np.ndarray):
+                if m.size != self.info.rays_local:
+                    raise ValueError("set_budget_map: %d entries for %d local rays" % (m.size, self.info.rays_local))
+                self.sync()      # frames in flight still read the buffer
+                buf.upload(m.reshape(-1).astype(dt, copy=False))
+                m = buf
+            ptrs.append(_ptr(m))
+        self._check(self.lib.adanerf_set_budget_map(self.handle, ptrs[0], ptrs[1]))
+
+    def foveate_device(self, gaze_xy, rings, n_map=None, thr_map=None) -> int:
+        """adanerf_foveate into device buffers (either may be None): rings as parse_fovea returns them, [(R, N, T), ..., (N, T)].
+        Returns the library's code (0, or ADANERF_EINVAL with nothing written) instead of raising: tests look at both."""
+        rings = [tuple(r) for r in rings]
+        nr = len(rings) - 1
+        radius = (C.c_int32 * max(nr, 1))(*[int(r[0]) for r in rings[:-1]])
+        n = (C.c_int32 * (nr + 1))(*[int(r[-2]) for r in rings])
+        thr = (C.c_float * (nr + 1))(*[float(r[-1]) for r in rings])
+        return self.lib.adanerf_foveate(self.handle, float(gaze_xy[0]), float(gaze_xy[1]), nr, radius, n, thr, _ptr(n_map), _ptr(thr_map))
+
+    def foveate(self, gaze_xy, rings):
+        """Foveated rendering from now on: fills the renderer's own maps from the gaze point (pixels) and the rings ([(R, N, T), ...,
+        (N, T)] or the string parse_fovea takes) on the device, then installs them.  Call again when the gaze moves or the frame size
+        changes; set_budget_map() removes them."""
+        if isinstance(rings, str):
+            rings = parse_fovea(rings)
+        n_map, thr_map = self.budget_buffers()
+        self._check(self.foveate_device(gaze_xy, rings, n_map, thr_map))
+        self._check(self.lib.adanerf_set_budget_map(self.handle, n_map.ptr, thr_map.ptr))
 
     def render(self, rgba8_out=None, rgb_out=None, stats: bool = False) -> Optional[Stats]:
         """One frame into caller-owned device buffers ([rays_local] uchar4 / [rays_local,3] fp32).
@@ -529,6 +624,10 @@ class NeuralRenderer:
     def compact(self, oracle, n_rays: int, n_max: int, thr: float, ray_offsets, ray_counts, sample_key, sample_w, total):
         self._check(self.lib.adanerf_compact(self.handle, _ptr(oracle), n_rays, n_max, thr, _ptr(ray_offsets),
                                              _ptr(ray_counts), _ptr(sample_key), _ptr(sample_w), _ptr(total)))
+
+    def compact_budget(self, oracle, n_rays: int, n_max: int, thr: float, n_map, thr_map, ray_offsets, ray_counts, sample_key, sample_w, total):
+        self._check(self.lib.adanerf_compact_budget(self.handle, _ptr(oracle), n_rays, n_max, thr, _ptr(n_map), _ptr(thr_map), _ptr(ray_offsets),
+                                                    _ptr(ray_counts), _ptr(sample_key), _ptr(sample_w), _ptr(total)))
 
     def compact_guarded(self, oracle_approx, oracle_exact, n_rays: int, n_max: int, thr: float, eps: float, ray_offsets, ray_counts,
                         sample_key, sample_w, total, refined, eps_pair: float = 0.0, audit_period: int = 0, audit_phase: int = 0, monitor=None,

@@ -284,7 +284,8 @@ int adanerf_set_camera(adanerf_ctx* ctx, const float pos[3], const float rot_c2w
  *   before its first guarded frame -- bounds from options.guard_eps if given, else from the new pair's calibration record
  *   (adanerf_guard_calibration_file names it), else calibrated at the next guarded frame; adanerf_info.guard_calib_source and the audit's
  *   phase start over; a band widened under the old pair is not carried along.  A call that changes neither value leaves all of this
- *   alone.  Outside the fused selection's domain (N > 16, threshold 0) the mode runs the split-precision engine alone, as after create. */
+ *   alone.  Outside the fused selection's domain (N > 16, threshold 0, or while a budget map is installed: adanerf_set_budget_map) the mode
+ *   runs the split-precision engine alone, as after create.  Threshold 0 is refused (ADANERF_EUNSUPPORTED) while a budget map is installed. */
 int adanerf_set_selection(adanerf_ctx* ctx, int32_t num_samples, float threshold);
 
 /* The frame size of a live context: the third dial of a real-time viewer beside N and the threshold (a window resize, a dynamic-resolution
@@ -301,8 +302,9 @@ int adanerf_set_selection(adanerf_ctx* ctx, int32_t num_samples, float threshold
  *   memory is allocated (new buffers first, then the old ones freed) only when the batch exceeds that, never released before
  *   adanerf_destroy, and the stream is synchronised only then; a shrink allocates nothing, a call that changes neither value touches
  *   nothing, and adanerf_render never allocates for it.
- *   The caller-owned per-ray outputs of adanerf_set_aux_outputs / adanerf_set_disp_output were sized for the old rays_local: a call that
- *   CHANGES rays_local resets all three to NULL (set them again for the new size); a call that does not change it leaves them.
+ *   The caller-owned per-ray buffers of adanerf_set_aux_outputs / adanerf_set_disp_output / adanerf_set_budget_map were sized for the old
+ *   rays_local: a call that CHANGES rays_local resets all five to NULL (set them again for the new size); a call that does not change it
+ *   leaves them.
  *   ADANERF_SAMPLING_GUARDED: the band belongs to (model, N, threshold) and its calibration runs on its own 64 x 64 rays, so the bounds,
  *   their source and pose count in adanerf_info stay; the audit's phase and fill cycle start over (frames do not depend on either). */
 int adanerf_set_frame_size(adanerf_ctx* ctx, int32_t width, int32_t height);
@@ -321,13 +323,45 @@ int adanerf_render(adanerf_ctx* ctx, void* d_rgba8_out, float* d_rgb_f32_out, ad
  *                                   depth_transform.from_world(.) of it otherwise (src/features.py:571-577); its disp_map:
  *                                   adanerf_set_disp_output
  *   d_acc_map   [rays_local] fp32   sum_k w_k (accumulated opacity)
- * with w_k the compositing weight of sample k (after accumulationMult).  Either may be NULL.  Caller-owned buffers. */
+ * with w_k the compositing weight of sample k (after accumulationMult).  Either may be NULL.  Caller-owned buffers; an
+ * adanerf_set_frame_size that changes rays_local resets them to NULL (as it does the maps of adanerf_set_budget_map). */
 int adanerf_set_aux_outputs(adanerf_ctx* ctx, float* d_depth_map, float* d_acc_map);
 
 /* The third secondary output of the reference's compositing (disp_map, src/nerf_raymarch_common.py:61 and :138):
  * d_disp_map [rays_local] fp32 = 1 / max(1e-10, depth_map / acc_map), filled by every adanerf_render until reset with NULL
  * (independent of adanerf_set_aux_outputs; a ray with acc_map == 0 gives NaN exactly as the reference's 0 / 0 does). */
 int adanerf_set_disp_output(adanerf_ctx* ctx, float* d_disp_map);
+
+/* Per-ray sample budgets: the budget dial of adanerf_set_selection per pixel -- full quality where the viewer looks, fewer samples in the
+ * periphery, a cheaper border under dynamic resolution, a caller-made importance mask.
+ *   d_n_map   [rays_local] uint8   N of the ray; 0 or a value above the context's N: the context's N
+ *   d_thr_map [rays_local] fp32    threshold of the ray; a value not above the context's threshold (a NaN too): the context's threshold
+ * both indexed by local ray as d_rgba8_out is, caller-owned, device memory.  Either may be NULL (that half follows the context); both NULL
+ * turns the feature off.  The N and the threshold in force are the cap and the floor, evaluated per render, so adanerf_set_selection needs
+ * no special case; device data is never "invalid".  Ray r then carries exactly the selection a context with (n_r, thr_r) makes for it:
+ * the selection rule keeps a prefix of one order (values descending, lower bin first), so it is a trim of the row the context's own
+ * selection wrote -- one small kernel between the selection and the compaction; shading and compositing consume counts and offsets and do
+ * not change.  After a render adanerf_stats.total_samples and ADANERF_BUF_RAY_COUNTS / _RAY_OFFSETS / _SAMPLE_KEY / _SAMPLE_W / _TOTAL
+ * describe the trimmed selection.
+ *   Ordering is that of adanerf_set_camera; the maps are read by the renders issued afterwards at the time their kernels run, so a caller
+ *   may rewrite them on the context's stream between frames.  adanerf_set_frame_size resets both to NULL when it changes rays_local.
+ *   ADANERF_EUNSUPPORTED, with nothing changed: a context with threshold 0 (dense), ADANERF_SAMPLER_PDF / _COARSE_FINE.  While a map is
+ *   installed adanerf_set_selection refuses threshold 0.
+ *   ADANERF_SAMPLING_GUARDED: unrefined rays hold the fp16 engine's values, and a trim by them would not be the exact selection, so while a
+ *   map is installed the context renders as an ADANERF_SAMPLING_SPLIT_FP16 context: no first pass, no audit, rays_refined 0.  The band,
+ *   its source and the audit's phase are left untouched; removing the map resumes guarded rendering. */
+int adanerf_set_budget_map(adanerf_ctx* ctx, const uint8_t* d_n_map, const float* d_thr_map);
+
+/* Fills budget maps for this context's local rays from a gaze point (pixels; pixel (x, y) has its centre at (x + 0.5, y + 0.5)) and
+ * n_rings concentric rings, in integers: gx2 = lrintf(2 gaze_x), gy2 alike (each clamped to +-2^31);
+ * q = (2 x + 1 - gx2)^2 + (2 y + 1 - gy2)^2; ring k contains the pixel iff q <= 4 radius_px[k]^2; the pixel gets (n[k], thr[k]) of the
+ * first ring that contains it, else entry n_rings ("outside").  Host arrays: radius_px[n_rings] whole pixels, strictly ascending;
+ * n[n_rings + 1] in 0..255; thr[n_rings + 1].  A gaze outside the image, zero rings and rings larger than the image are all legal.
+ * d_n_map [rays_local] uint8 / d_thr_map [rays_local] fp32: device buffers, either may be NULL.  Runs on the context's stream; it only
+ * fills buffers, installing them is adanerf_set_budget_map.  ADANERF_EINVAL, with nothing written: a NaN / infinite gaze, n_rings outside
+ * 0..8, radii negative or not strictly ascending, an n outside 0..255, a NaN thr. */
+int adanerf_foveate(adanerf_ctx* ctx, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* n,
+                    const float* thr, uint8_t* d_n_map, float* d_thr_map);
 
 /* De-interleaves the gathered shard payloads ([shard_world][rays_local_max] uchar4, rank-major)
  * into the full row-major image [h*w] uchar4. */
@@ -393,6 +427,13 @@ int adanerf_compact_guarded(adanerf_ctx* ctx, const float* d_oracle_approx, cons
                             int32_t n_max, float thr, float eps, float eps_pair, int32_t audit_period, int32_t audit_phase,
                             int32_t audit_fill_cap, int32_t audit_cycle, int32_t* d_ray_offsets, int32_t* d_ray_counts, uint32_t* d_sample_key, float* d_sample_w,
                             int32_t* d_total, int32_t* d_refined, uint32_t* d_monitor);
+
+/* adanerf_compact with per-ray budgets, for tests: the selection at (n_max, thr), then the trim of ray r to d_n_map[r] / d_thr_map[r] (the
+ * rules of adanerf_set_budget_map; either map may be NULL), then the compaction.  thr > 0.  Honours ADANERF_FLAG_WAVE_SELECT and
+ * n_max > 16 as adanerf_compact does.  Outputs as adanerf_compact. */
+int adanerf_compact_budget(adanerf_ctx* ctx, const float* d_oracle, int32_t n_rays, int32_t n_max, float thr, const uint8_t* d_n_map,
+                           const float* d_thr_map, int32_t* d_ray_offsets, int32_t* d_ray_counts, uint32_t* d_sample_key,
+                           float* d_sample_w, int32_t* d_total);
 
 /* Calibrates the band of ADANERF_SAMPLING_GUARDED for the loaded model: n_poses cameras drawn inside the view cell
  * (positions uniform in 90 % of it, any orientation; seeded), 64 x 64 rays covering the field of view each, through both the
