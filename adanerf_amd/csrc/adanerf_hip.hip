@@ -123,6 +123,7 @@ struct adanerf_ctx {
   double flip_ppd = 0.0;             // what flip_tab holds (0: nothing yet)
   FlipParams flip_params{};
   bool flip_lds_raised = false;      // flip_kernel may use more than 64 KB of dynamic LDS
+  DevBuf reproj_zbuf, reproj_holes;  // adanerf_reproject: [width*height] uint64 z-buffer, the hole count; grown on demand
   hipEvent_t peer_event = nullptr;   // adanerf_gather_to: orders the destination stream behind the copy
   uint64_t peer_tried = 0;           // bit d: peer access to device d has been requested once
 };
@@ -1049,6 +1050,55 @@ int adanerf_present(adanerf_ctx* c, const void* d_src_rgba8, int32_t src_w, int3
                      static_cast<uchar4*>(d_dst_rgba8), src_w, src_h, dst_w, dst_h, linear ? 1 : 0, (flags & ADANERF_PRESENT_FLIP_Y) ? 1 : 0,
                      static_cast<uint32_t>((d0 >> 2) & 3), den, ~0ull / den);
   HIP_RETURN(c, hipGetLastError());
+}
+
+int adanerf_reproject(adanerf_ctx* c, const void* d_src_rgba8, const float* d_src_depth_map, const float* d_src_acc_map, const float src_pos[3],
+                      const float src_rot_c2w[9], const float dst_pos[3], const float dst_rot_c2w[9], float acc_min, uint32_t hole_rgba8,
+                      int32_t flags, void* d_dst_rgba8, float* d_dst_depth, uint8_t* d_dst_mask, int32_t* holes_out) {
+  if (!c) return ADANERF_EINVAL;
+  if (!d_src_rgba8 || !d_src_depth_map || !d_src_acc_map || !d_dst_rgba8) return fail(c, ADANERF_EINVAL, "adanerf_reproject: NULL image");
+  if (!src_pos || !src_rot_c2w || !dst_pos || !dst_rot_c2w) return fail(c, ADANERF_EINVAL, "adanerf_reproject: NULL pose");
+  for (int k = 0; k < 9; ++k)
+    if (!std::isfinite(src_rot_c2w[k]) || !std::isfinite(dst_rot_c2w[k]) || (k < 3 && (!std::isfinite(src_pos[k]) || !std::isfinite(dst_pos[k]))))
+      return fail(c, ADANERF_EINVAL, "adanerf_reproject: a pose entry is not finite");
+  if (!(acc_min >= 0.f)) return fail(c, ADANERF_EINVAL, "adanerf_reproject: acc_min must be >= 0");      // also a NaN
+  if (flags & ~ADANERF_REPROJECT_FILL) return fail(c, ADANERF_EINVAL, "adanerf_reproject: flags must be 0 or ADANERF_REPROJECT_FILL");
+  const int w = c->ms.info.width, h = c->ms.info.height, n = w * h;
+  const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src_rgba8), d0 = reinterpret_cast<uintptr_t>(d_dst_rgba8);
+  if ((s0 | d0) & 3) return fail(c, ADANERF_EINVAL, "adanerf_reproject: colour images must be 4-byte aligned (uchar4)");
+  if (s0 < d0 + static_cast<size_t>(n) * 4 && d0 < s0 + static_cast<size_t>(n) * 4)      // the resolve pass reads the source colour while it writes
+    return fail(c, ADANERF_EINVAL, "adanerf_reproject: source and destination colour overlap");
+  if (c->ms.info.use_ndc) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_reproject: the depth_map of a useNDC model is NDC depth, not a distance along the ray");
+  if (c->ms.rg.world != 1) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_reproject: whole frames only (shard_world must be 1)");
+  BIND(c);
+  if (c->reproj_zbuf.bytes < static_cast<size_t>(n) * sizeof(uint64_t) || !c->reproj_holes.p) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // a warp in flight may still use the smaller z-buffer
+    if (int rc = dev_alloc(c, &c->reproj_zbuf, static_cast<size_t>(n) * sizeof(uint64_t))) return rc;
+    if (int rc = dev_alloc(c, &c->reproj_holes, 64)) return rc;
+  }
+  ReprojectParams p{};
+  p.g = c->ms.rg;
+  std::memcpy(p.g.pos, src_pos, 3 * sizeof(float));
+  std::memcpy(p.g.rot, src_rot_c2w, 9 * sizeof(float));
+  std::memcpy(p.dst_pos, dst_pos, 3 * sizeof(float));
+  std::memcpy(p.dst_rot, dst_rot_c2w, 9 * sizeof(float));
+  p.acc_min = acc_min;
+  p.origin_is_camera = c->ms.coarse_fine ? 1 : 0;      // what the render path writes to ADANERF_BUF_RAYS (camera_rays_kernel)
+  unsigned long long* zbuf = reinterpret_cast<unsigned long long*>(c->reproj_zbuf.p);
+  int32_t* holes = reinterpret_cast<int32_t*>(c->reproj_holes.p);
+  const dim3 grid((n + 255) / 256), block(256);
+  hipLaunchKernelGGL(reproject_clear_kernel, grid, block, 0, c->stream, zbuf, n, holes);
+  HIP_TRY(c, hipGetLastError());
+  hipLaunchKernelGGL(reproject_splat_kernel, grid, block, 0, c->stream, p, d_src_depth_map, d_src_acc_map, zbuf);
+  HIP_TRY(c, hipGetLastError());
+  hipLaunchKernelGGL(reproject_resolve_kernel, grid, block, 0, c->stream, zbuf, static_cast<const uint32_t*>(d_src_rgba8), w, h,
+                     (flags & ADANERF_REPROJECT_FILL) ? 1 : 0, hole_rgba8, static_cast<uint32_t*>(d_dst_rgba8), d_dst_depth, d_dst_mask, holes);
+  HIP_TRY(c, hipGetLastError());
+  if (holes_out) {
+    HIP_TRY(c, hipMemcpyAsync(holes_out, holes, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return ADANERF_OK;
 }
 
 int adanerf_sync(adanerf_ctx* c) {

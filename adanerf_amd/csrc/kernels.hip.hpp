@@ -7,6 +7,7 @@
 //   A7        composite_kernel       sigmoid + alpha * oracle weight, front-to-back
 //   N1        flip_kernel / flip_mean_kernel   FLIP error map and mean of an image pair (the evaluator's second metric)
 //   N3        present_kernel         the frame at the window's size (the viewer's blit: linear / nearest, y flip)
+//   N4        reproject_clear_kernel / reproject_splat_kernel / reproject_resolve_kernel   a rendered frame warped to another pose by its depth
 // plus explicit-feature debug kernels (ray_features_kernel, shade_features_kernel) that materialise
 // what the reference launchers wrote to memory, for parity tests only.
 // The code lives in one header per stage; this file includes them all.
@@ -23,3 +24,4 @@
 #include "k_flip.hip.hpp"
 #include "k_present.hip.hpp"
 #include "k_budget.hip.hpp"
+#include "k_reproject.hip.hpp"

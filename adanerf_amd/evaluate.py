@@ -6,6 +6,7 @@ reference's second default metric (``metrics = ["flip", "psnr"]`` :613-615): the
 
     python -m adanerf_amd.evaluate <model_dir> <dataset_dir> [--set test] [--out DIR] [--video out.y4m] [--precision bf16]
                                    [--metrics psnr flip] [--sweep-thresholds T ...] [--sweep-samples N ...] [--sweep-scales S ...]
+                                   [--reproject-stride K]
 
 ``--sweep-thresholds`` / ``--sweep-samples`` render the set once per (N, threshold) of their cross product on ONE context
 (``NeuralRenderer.set_selection``: an AdaNeRF network is trained once and rendered at any sample budget) -- the two axes of a quality
@@ -13,6 +14,10 @@ table; the summary gains ``sweep``, ``--out DIR`` writes into ``DIR/n<N>_t<thres
 resolution: the set is rendered at ``round(w S) x round(h S)`` on the same context (``NeuralRenderer.set_frame_size``), presented to the
 dataset's ``w x h`` on the GPU (``adanerf_present``, the viewer's blit) and scored from that 8-bit image / 255; sub-directories gain
 ``_s<scale>``.
+
+``--reproject-stride K`` renders the poses with ``i % K == 0`` and warps the others from the nearest rendered pose before them
+(``adanerf_reproject``, holes filled from their neighbours): what a host that renders every K-th frame shows in between, scored against
+the same ground truth.
 
 Dataset layout (src/datasets.py:146-213, 361-365, 480-542): ``dataset_info.json`` (``resolution``,
 ``camera_angle_x``, ``view_cell_center``, ``view_cell_size`` ...), ``transforms_<set>.json`` with
@@ -89,7 +94,8 @@ def scaled_size(w: int, h: int, scale: float):
 
 def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: Optional[str] = None,
              precision: str = "bf16", batch_size: int = -1, max_frames: int = 0, quiet: bool = False,
-             video: Optional[str] = None, fps: int = 30, metrics=("psnr",), fovea=None, sweep_thresholds=None, sweep_samples=None, sweep_scales=None):
+             video: Optional[str] = None, fps: int = 30, metrics=("psnr",), fovea=None, sweep_thresholds=None, sweep_samples=None, reproject_stride=None,
+             sweep_scales=None):
     """metrics: "psnr" (always reported where a ground-truth image exists) and / or "flip": each record gains ``flip``, the summary
     ``mean_flip``, and with out_dir the error map is written as an 8-bit greyscale ``%05d_flip.png``.
 
@@ -103,6 +109,12 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     frame to w x h on the device and scores THAT image (uint8 / 255, also at S = 1: the entries of one table are measured alike);
     samples_per_ray counts per rendered ray; entries and records carry ``scale``; frames written to out_dir / video are the presented ones.
 
+    reproject_stride (K >= 1 or None): the poses with i % K == 0 are rendered, every other pose is the nearest rendered frame before it
+    warped to that pose on the device (NeuralRenderer.reproject, fill on) and scored from the 8-bit result / 255.  Records gain ``warped``
+    and, for a warped frame, ``hole_fraction`` (pixels nothing reached, of w h) in place of samples_per_ray / ms; the summary gains
+    ``mean_psnr_rendered``, ``mean_psnr_warped``, ``mean_hole_fraction`` and, with "flip", ``mean_flip_rendered`` / ``mean_flip_warped``;
+    mean_samples_per_ray / mean_ms are those of the rendered frames.  At the dataset's resolution only (not with sweep_scales).
+
     fovea (``R:N:T[,R:N:T...],N:T`` or what renderer.parse_fovea makes of it, or None): every frame is rendered with per-ray budgets around a
     gaze at the centre of the rendered frame (radii in its pixels).  Records and summary keep their shape: PSNR / FLIP / samples per ray are
     those of the foveated frames -- the quality-against-cost table of a foveation setting."""
@@ -113,6 +125,11 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
         raise ValueError("unknown metrics %s (known: psnr, flip)" % unknown)
     if sweep_scales and not all(s > 0 for s in sweep_scales):
         raise ValueError("sweep_scales must be positive, got %s" % (list(sweep_scales),))
+    stride = int(reproject_stride) if reproject_stride is not None else 0
+    if reproject_stride is not None and stride < 1:
+        raise ValueError("reproject_stride must be >= 1, got %s" % (reproject_stride,))
+    if stride and sweep_scales:
+        raise ValueError("reproject_stride warps at the dataset's resolution: not together with sweep_scales")
     want_flip = "flip" in metrics
     meta, frames = load_dataset(dataset_dir, set_name)
     if max_frames > 0:
@@ -126,7 +143,9 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
         vid = Y4mWriter(video, w, h, fps) if video else None
         d_ref = r.empty((w * h, 3), np.float32) if want_flip else None
         d_map = r.empty((w * h,), np.float32) if want_flip and out_dir else None
-        d_pres = r.empty((w * h, 3), np.float32) if want_flip and sweep_scales else None
+        d_pres = r.empty((w * h, 3), np.float32) if want_flip and (sweep_scales or stride) else None
+        if stride:
+            r.enable_reprojection()
 
         def render_set(out_dir, extra, scale=None):
             """one pass over the set at the selection (and, with a scale, the frame size) in force -> its records"""
@@ -137,12 +156,20 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
             if fovea:      # again for every setting: a frame size that changes the ray count drops the maps
                 r.foveate((0.5 * rw, 0.5 * rh), fovea)
             for i, fr in enumerate(frames):
-                r.set_camera(fr["pose"], fr["rot"])
-                rgb, rgba, st = r.render_numpy()
-                if scale is not None:      # the frame as a w x h window shows it, filtered on the device
-                    rgba = r.present(w, h).reshape(-1, 4)
+                warped = bool(stride) and i % stride != 0
+                if warped:      # the last rendered frame at this pose: what a host that renders every K-th frame shows here
+                    rgba, _, holes = r.reproject(fr["pose"], fr["rot"])
                     rgb = rgba[:, :3].astype(np.float32) / 255.0
-                rec = dict(extra, frame=i, image=fr["image"], samples_per_ray=st.total_samples / float(rw * rh), ms=st.ms_total)
+                    rec = dict(extra, frame=i, image=fr["image"], warped=True, hole_fraction=holes / float(w * h))
+                else:
+                    r.set_camera(fr["pose"], fr["rot"])
+                    rgb, rgba, st = r.render_numpy()
+                    if scale is not None:      # the frame as a w x h window shows it, filtered on the device
+                        rgba = r.present(w, h).reshape(-1, 4)
+                        rgb = rgba[:, :3].astype(np.float32) / 255.0
+                    rec = dict(extra, frame=i, image=fr["image"], samples_per_ray=st.total_samples / float(rw * rh), ms=st.ms_total)
+                    if stride:
+                        rec.update(warped=False)
                 if os.path.exists(fr["image"]):
                     gt = read_png(fr["image"])
                     if gt.shape[0] != h or gt.shape[1] != w:
@@ -151,7 +178,7 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                     mse = float(np.mean((rgb.astype(np.float64) - ref) ** 2))
                     rec.update(mse=mse, psnr=psnr_from_mse(mse))
                     if want_flip:       # the rendered frame is still on the device (render_numpy); argument order of src/evaluate.py:144
-                        d_test = r._o_rgb if scale is None else d_pres.upload(rgb)
+                        d_test = r._o_rgb if scale is None and not warped else d_pres.upload(rgb)
                         rec.update(flip=r.flip_device(d_test, d_ref.upload(ref), w, h, error_map=d_map))
                         if d_map is not None:
                             fm = np.nan_to_num(d_map.numpy().reshape(h, w), nan=1.0)      # the map lies in [0, 1]
@@ -188,12 +215,21 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
 
 def summarise(results: List[dict], want_flip: bool) -> dict:
     with_gt = [x for x in results if "psnr" in x]
-    summary = dict(frames=len(results), mean_samples_per_ray=float(np.mean([x["samples_per_ray"] for x in results])) if results else 0.0,
-                   mean_ms=float(np.mean([x["ms"] for x in results])) if results else 0.0)
+    rendered = [x for x in results if not x.get("warped")]
+    summary = dict(frames=len(results), mean_samples_per_ray=float(np.mean([x["samples_per_ray"] for x in rendered])) if rendered else 0.0,
+                   mean_ms=float(np.mean([x["ms"] for x in rendered])) if rendered else 0.0)
     if with_gt:
         summary.update(mean_psnr=float(np.mean([x["psnr"] for x in with_gt])), mean_mse=float(np.mean([x["mse"] for x in with_gt])))
         if want_flip:
             summary.update(mean_flip=float(np.mean([x["flip"] for x in with_gt])))
+    if any("warped" in x for x in results):      # reproject_stride: the two kinds of frame apart (None: no such frame with a ground truth)
+        for kind, flag in (("rendered", False), ("warped", True)):
+            part = [x for x in with_gt if bool(x.get("warped")) == flag]
+            summary["mean_psnr_" + kind] = float(np.mean([x["psnr"] for x in part])) if part else None
+            if want_flip:
+                summary["mean_flip_" + kind] = float(np.mean([x["flip"] for x in part])) if part else None
+        holes = [x["hole_fraction"] for x in results if x.get("warped")]
+        summary["mean_hole_fraction"] = float(np.mean(holes)) if holes else 0.0
     return summary
 
 
@@ -217,6 +253,9 @@ def build_parser():
     ap.add_argument("--sweep-scales", nargs="+", type=float, default=None, metavar="S",
                     help="render the set once per scale S of the dataset's resolution (x the other sweeps) on the same context, present it "
                          "to the full size on the GPU and score that 8-bit image; entries gain `scale`, --out directories _s<S>")
+    ap.add_argument("--reproject-stride", type=int, default=None, metavar="K",
+                    help="render the poses with i %% K == 0 and warp the others from the nearest rendered pose before them (adanerf_reproject); "
+                         "the summary gains mean_psnr_rendered / mean_psnr_warped / mean_hole_fraction (and mean_flip_* with --metrics flip)")
     ap.add_argument("--fovea", type=parse_fovea, default=None, metavar="R:N:T[,R:N:T...],N:T",
                     help="per-ray sample budgets around a gaze at the image centre: rings (radius px : N : threshold), then the entry outside "
                          "them; PSNR / FLIP / samples per ray are then those of the foveated frames")
@@ -227,7 +266,7 @@ def main(argv=None):
     a = build_parser().parse_args(argv)
     summary, _ = evaluate(a.model_dir, a.dataset_dir, a.set, a.out, a.precision, a.batch_size, a.max_frames, video=a.video, fps=a.fps,
                           metrics=tuple(a.metrics), sweep_thresholds=a.sweep_thresholds, sweep_samples=a.sweep_samples, sweep_scales=a.sweep_scales,
-                          fovea=a.fovea)
+                          fovea=a.fovea, reproject_stride=a.reproject_stride)
     print(json.dumps(summary))
 
 

@@ -1,5 +1,6 @@
 #include "neuralrenderer.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
@@ -22,6 +23,8 @@ NeuralRenderer::~NeuralRenderer() {
   if (ctx) {
     if (d_gathered) adanerf_free(ctx, d_gathered);
     if (d_frame) adanerf_free(ctx, d_frame);
+    for (void* p : {d_depth, d_acc, d_warp})
+      if (p) adanerf_free(ctx, p);
     if (d_window) adanerf_free(ctx, d_window);
     adanerf_destroy(ctx);
   }
@@ -148,6 +151,10 @@ bool NeuralRenderer::init() {
   adanerf_get_info(ctx, &info_);
   world_ = world;
   strip_rows_ = strip_rows;
+  if (settings.reproject > 1 && (world > 1 || info_.use_ndc)) {
+    err = world > 1 ? "--reproject warps whole frames of one context; use it with --gpus 1" : "--reproject: the depth of a useNDC model is NDC depth";
+    return false;
+  }
   if (!allocFrameBuffers()) return false;
   if (settings.write_window &&
       adanerf_malloc(ctx, static_cast<size_t>(settings.window_width) * settings.window_height * 4, &d_window) != ADANERF_OK) {
@@ -170,6 +177,17 @@ bool NeuralRenderer::allocFrameBuffers() {
   if (adanerf_malloc(ctx, static_cast<size_t>(info_.width) * info_.height * 4, &d_frame) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;
+  }
+  d_shown = d_frame;
+  if (settings.reproject > 1) {      // the aux outputs belong to the frame size: the library drops them when rays_local changes
+    const size_t n = static_cast<size_t>(info_.width) * info_.height;
+    have_source = false;
+    for (void** p : {&d_depth, &d_acc, &d_warp}) {
+      if (*p && adanerf_free(ctx, *p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+      *p = nullptr;
+      if (adanerf_malloc(ctx, n * 4, p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+    }
+    if (adanerf_set_aux_outputs(ctx, static_cast<float*>(d_depth), static_cast<float*>(d_acc)) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
   }
   if (world_ > 1) {
     const size_t payload = static_cast<size_t>(info_.rays_local_max) * 4;
@@ -272,6 +290,7 @@ bool NeuralRenderer::render() {
     want_samples = 0;
     want_threshold = -1.f;
     adanerf_get_info(ctx, &info_);
+    have_source = false;      // a new selection shows from this frame on: render it
   }
   if (!applyFovea()) return false;
   if (adanerf_set_camera(ctx, camera.getPosition(), rot) != ADANERF_OK) {
@@ -284,8 +303,11 @@ bool NeuralRenderer::render() {
       return false;
     }
     sample_count++;
+    have_source = false;      // the debug view has no depth to warp
+    d_shown = d_frame;
     return writeImageToFile();
   }
+  if (settings.reproject > 1 && have_source && since_render + 1 < settings.reproject) return warp(rot);
   adanerf_stats st;
   std::memset(&st, 0, sizeof(st));
   if (!peers.empty()) {
@@ -345,27 +367,62 @@ bool NeuralRenderer::render() {
   s_total += st.ms_total;
   s_num_total_samples += st.total_samples;
   sample_count++;
-  if (sample_count % logging_interval == 0) {
-    // same fields as the reference's log line; fc1 (ray/oracle features) is fused into "Inference 1"
-    std::cout << "Inference 1:" << s_inference1 / logging_interval << ", 2:" << s_inference2 / logging_interval << " | fc1: 0"
-              << ", fc2: " << s_fc2 / logging_interval << ", rm: " << s_rm / logging_interval
-              << ", avg samples ppx: " << s_num_total_samples / static_cast<double>(logging_interval) / settings.total_size
-              << " (total: " << s_num_total_samples / logging_interval << ")"
-              << ", N: " << info_.num_samples << ", thr: " << info_.threshold << ", size: " << info_.width << "x" << info_.height
-              << ", frames: " << sample_count << ", frame ms: " << s_total / logging_interval << std::endl;
-    s_inference1 = s_inference2 = s_fc2 = s_rm = s_total = 0;
-    s_num_total_samples = 0;
+  s_rendered++;
+  if (settings.reproject > 1) {
+    std::memcpy(src_pos, camera.getPosition(), sizeof(src_pos));
+    std::memcpy(src_rot, rot, sizeof(src_rot));
+    have_source = true;
+    since_render = 0;
   }
+  d_shown = d_frame;
+  logInterval();
   return writeImageToFile();
+}
+
+// --reproject K: the last rendered frame at this frame's camera (adanerf_reproject, holes filled from their neighbours, the rest black)
+bool NeuralRenderer::warp(const float rot[9]) {
+  int32_t holes = 0;
+  if (adanerf_reproject(ctx, d_frame, static_cast<const float*>(d_depth), static_cast<const float*>(d_acc), src_pos, src_rot, camera.getPosition(), rot,
+                        0.5f, 0xFF000000u, ADANERF_REPROJECT_FILL, d_warp, nullptr, nullptr, &holes) != ADANERF_OK) {
+    err = adanerf_last_error(ctx);
+    return false;
+  }
+  since_render++;
+  sample_count++;
+  s_warped++;
+  s_holes += holes;
+  d_shown = d_warp;
+  logInterval();
+  return writeImageToFile();
+}
+
+void NeuralRenderer::logInterval() {
+  if (sample_count % logging_interval != 0) return;
+  // same fields as the reference's log line; fc1 (ray/oracle features) is fused into "Inference 1".  --reproject K > 1: the averages are
+  // over the rendered frames of the interval, and the line gains the holes per warped frame
+  const int rendered = settings.reproject > 1 ? std::max(s_rendered, 1) : logging_interval;
+  std::cout << "Inference 1:" << s_inference1 / rendered << ", 2:" << s_inference2 / rendered << " | fc1: 0"
+            << ", fc2: " << s_fc2 / rendered << ", rm: " << s_rm / rendered
+            << ", avg samples ppx: " << s_num_total_samples / static_cast<double>(rendered) / settings.total_size
+            << " (total: " << s_num_total_samples / rendered << ")"
+            << ", N: " << info_.num_samples << ", thr: " << info_.threshold << ", size: " << info_.width << "x" << info_.height
+            << ", frames: " << sample_count << ", frame ms: " << s_total / rendered;
+  if (settings.reproject > 1) std::cout << ", holes: " << s_holes / static_cast<double>(std::max(s_warped, 1)) << " (" << s_warped << " warped frames)";
+  std::cout << std::endl;
+  s_inference1 = s_inference2 = s_fc2 = s_rm = s_total = 0;
+  s_num_total_samples = 0;
+  s_holes = 0;
+  s_rendered = s_warped = 0;
 }
 
 // -w: the frame at its render size, exactly as before; --write-window: the frame as the viewer's blit would show it in a window of
 // -ws W H (interoprenderbuffer.cpp:87), presented on the device
 bool NeuralRenderer::writeImageToFile() {
-  if (settings.write_images && !writeBmp("out.bmp", d_frame, static_cast<int>(settings.width), static_cast<int>(settings.height))) return false;
+  const void* shown = d_shown ? d_shown : d_frame;
+  if (settings.write_images && !writeBmp("out.bmp", shown, static_cast<int>(settings.width), static_cast<int>(settings.height))) return false;
   if (!settings.write_window) return true;
   const int ww = static_cast<int>(settings.window_width), wh = static_cast<int>(settings.window_height);
-  if (adanerf_present(ctx, d_frame, static_cast<int>(settings.width), static_cast<int>(settings.height), d_window, ww, wh, 0) != ADANERF_OK) {
+  if (adanerf_present(ctx, shown, static_cast<int>(settings.width), static_cast<int>(settings.height), d_window, ww, wh, 0) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;
   }

@@ -68,6 +68,18 @@ class NeuralRenderer {
   void* d_gathered = nullptr;        // rank 0: uchar4 [N][rays_local_max]
   adanerf_info info_{};
   void* d_frame = nullptr;           // uchar4 [h*w]
+  // --reproject K > 1: depth_map / acc_map of the last rendered frame (the context's aux outputs), its pose, the warped frame
+  void* d_depth = nullptr;
+  void* d_acc = nullptr;
+  void* d_warp = nullptr;            // uchar4 [h*w]
+  const void* d_shown = nullptr;     // what the last frame presented: d_frame or d_warp (-w / --write-window write it)
+  bool have_source = false;          // d_frame, d_depth, d_acc and src_* describe one rendered frame of the size and selection in force
+  int since_render = 0;              // warped frames since it
+  float src_pos[3] = {0, 0, 0}, src_rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  bool warp(const float rot[9]);     // this frame = the source frame at the camera of the moment
+  void logInterval();                // the per-100-frame line of the single-context path
+  long long s_holes = 0;             // holes of the warped frames / rendered and warped frames of the running interval
+  int s_rendered = 0, s_warped = 0;
   void* d_window = nullptr;          // --write-window: uchar4 [window_height*window_width], the frame as adanerf_present shows it
   int world_ = 1, strip_rows_ = 8;   // share layout chosen at init; a live context keeps its strip height
   bool allocFrameBuffers();          // d_frame, d_gathered, d_payload for the size in info_ (again after a size change)

@@ -19,6 +19,8 @@ const char* Settings::usage() {
          "                                                              sample budget N / threshold from that frame on;\n"
          "                                                              size <W> <H>: frame size from that frame on, the window stays;\n"
          "                                                              gaze <X> <Y>: the --fovea gaze point, in pixels)\n"
+         "               [--reproject K]      of every K frames render the first and warp it to the camera of the next K - 1 (depth\n"
+         "                                    reprojection, holes filled from their neighbours); -w / --write-window write what was shown\n"
          "               [--gpus N] [--same-device] [--sub-shares P]\n";
 }
 
@@ -134,6 +136,15 @@ bool Settings::init(int argc, char** argv, std::string* err) {
     } else if (a == "--fovea") {
       if (!need(i, 1)) return false;
       if (!parseFovea(argv[++i], &fovea_radius, &fovea_n, &fovea_thr, err)) return false;
+    } else if (a == "--reproject") {
+      if (!need(i, 1)) return false;
+      char* end = nullptr;
+      const long k = std::strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end != 0 || k < 1 || k > 1000000) {
+        *err = "--reproject K: K must be an integer >= 1";
+        return false;
+      }
+      reproject = static_cast<int>(k);
     } else if (a == "--oracle") {
       render_oracle = true;
     } else if (a == "--script") {

@@ -37,6 +37,8 @@ class Settings {
   std::vector<int> fovea_radius, fovea_n;
   std::vector<float> fovea_thr;
   static bool parseFovea(const std::string& spec, std::vector<int>* radius, std::vector<int>* n, std::vector<float>* thr, std::string* err);
+  int reproject = 1;            // --reproject K: of every K frames the first is rendered, the next K - 1 are that frame warped to their own camera
+                                // (adanerf_reproject, fill on); 1: every frame is rendered
   bool render_oracle = false;   // --oracle: the viewer's 'O' key (inputhandler.cpp:76), sampling-network debug view
 
   // returns false and fills err on a malformed command line

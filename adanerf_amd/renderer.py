@@ -26,6 +26,7 @@ SAMPLER_ADAPTIVE, SAMPLER_PDF, SAMPLER_COARSE_FINE = 0, 1, 2
 FLAG_KEEP_ORACLE, FLAG_WAVE_SELECT, FLAG_NO_GUARD_CACHE, FLAG_GUARD_AUDIT_FILL = 1, 2, 4, 8
 PRESENT_FLIP_Y, PRESENT_NEAREST, PRESENT_LINEAR = 1, 2, 4      # adanerf_present flags
 PRESENT_FILTERS = {None: 0, "nearest": PRESENT_NEAREST, "linear": PRESENT_LINEAR}
+REPROJECT_FILL = 1                                             # adanerf_reproject flag
 ABI_VERSION = 4
 GUARD_FROM = {0: "none", 1: "options", 2: "record", 3: "calibration", 4: "monitor"}
 SAMPLING_MODES = {"split": 0, "fp16x3": 0, "fp32": 1, "fp16": 2, "guarded": 3}
@@ -66,7 +67,7 @@ class Stats(C.Structure):
                 ("guard_audit_mismatch", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
-EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_last_error", "adanerf_abi_version", "adanerf_struct_sizes", "adanerf_set_camera", "adanerf_set_selection", "adanerf_set_frame_size", "adanerf_present",
+EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_last_error", "adanerf_abi_version", "adanerf_struct_sizes", "adanerf_set_camera", "adanerf_set_selection", "adanerf_set_frame_size", "adanerf_present", "adanerf_reproject",
            "adanerf_set_budget_map", "adanerf_foveate", "adanerf_compact_budget",
            "adanerf_render", "adanerf_set_aux_outputs", "adanerf_set_disp_output", "adanerf_assemble_strips", "adanerf_sync", "adanerf_set_stream", "adanerf_set_profiling",
            "adanerf_collect_stats", "adanerf_ray_features", "adanerf_sample_mlp",
@@ -100,6 +101,8 @@ def load_library(path: Optional[str] = None):
     lib.adanerf_foveate.argtypes = [vp, C.c_float, C.c_float, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_float), vp, vp]
     lib.adanerf_compact_budget.argtypes = [vp, vp, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp, vp]
     lib.adanerf_present.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32]
+    fp = C.POINTER(C.c_float)
+    lib.adanerf_reproject.argtypes = [vp, vp, vp, vp, fp, fp, fp, fp, C.c_float, C.c_uint32, i32, vp, vp, vp, C.POINTER(i32)]
     lib.adanerf_render.argtypes = [vp, vp, vp, C.POINTER(Stats)]
     lib.adanerf_assemble_strips.argtypes = [vp, vp, vp]
     lib.adanerf_set_aux_outputs.argtypes = [vp, vp, vp]
@@ -335,6 +338,9 @@ class NeuralRenderer:
         self.last_stats = Stats()
         self._own = []
         self._last_frame = None       # (device rgba8, width, height) of the last render() that wrote one
+        self._pose = None             # (pos [3], rot [9]) of the last set_camera
+        self._rp_on = False           # enable_reprojection(): render_numpy keeps depth, acc and the pose of its frame
+        self._rp_frame = None         # (device rgba8, depth, acc, pos, rot, rays) of the last render_numpy since then
 
     # -- lifecycle -------------------------------------------------------------------------------
     def init(self) -> bool:
@@ -388,6 +394,7 @@ class NeuralRenderer:
         r = np.ascontiguousarray(rot_c2w, dtype=np.float32).reshape(9)
         self._check(self.lib.adanerf_set_camera(self.handle, p.ctypes.data_as(C.POINTER(C.c_float)),
                                                 r.ctypes.data_as(C.POINTER(C.c_float))))
+        self._pose = (p.copy(), r.copy())
 
     def set_selection(self, num_samples: Optional[int] = None, threshold: Optional[float] = None) -> "Info":
         """The sample budget N and / or the selection threshold for the frames rendered from now on (None keeps the one in force); the
@@ -409,6 +416,7 @@ class NeuralRenderer:
         self.settings.width, self.settings.height = self.info.width, self.info.height
         if hasattr(self, "_b_n") and self._b_n.shape[0] != self.info.rays_local:      # the library dropped the maps with the old rays_local
             self._drop_budget_buffers()
+        self._rp_frame = None      # a frame of the old size cannot be warped with the new size's ray generator
         for name in ("_o_rgb", "_o_rgba"):
             if hasattr(self, name):
                 a = getattr(self, name)
@@ -514,8 +522,62 @@ class NeuralRenderer:
         if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
             self._o_rgb = self.empty((n, 3), np.float32)
             self._o_rgba = self.empty((n, 4), np.uint8)
+        if self._rp_on:
+            self._reproject_buffers()
         st = self.render(self._o_rgba, self._o_rgb, stats=True)
+        if self._rp_on:
+            if self._pose is None:
+                raise AdaNeRFError("reprojection needs the pose of the frame: call set_camera before render_numpy")
+            self._rp_frame = (self._o_rgba, self._rp_depth, self._rp_acc, self._pose[0], self._pose[1], n)
         return self._o_rgb.numpy(), self._o_rgba.numpy(), st
+
+    # -- the last frame at the pose of the moment --------------------------------------------------------
+    def _reproject_buffers(self):
+        """the renderer's own aux outputs and warp destinations, made on first use and again after a frame size that changes rays_local
+        (the library drops the aux outputs then); installed as the context's aux outputs"""
+        n = self.info.rays_local
+        if not hasattr(self, "_rp_depth") or self._rp_depth.shape[0] != n:
+            for name in ("_rp_depth", "_rp_acc", "_rp_rgba", "_rp_mask"):
+                if hasattr(self, name):
+                    a = getattr(self, name)
+                    a.free()
+                    self._own.remove(a)
+            self._rp_depth, self._rp_acc = self.empty((n,), np.float32), self.empty((n,), np.float32)
+            self._rp_rgba, self._rp_mask = self.empty((n, 4), np.uint8), self.empty((n,), np.uint8)
+            self._rp_frame = None
+            self.set_aux_outputs(self._rp_depth, self._rp_acc)
+
+    def enable_reprojection(self):
+        """From now on render_numpy keeps what reproject() needs on the device: its RGBA8 frame, depth_map and acc_map in aux buffers of
+        the renderer's own (they replace any set_aux_outputs of the caller's) and the pose of the last set_camera.  Whole frames of
+        models without useNDC only (adanerf_reproject)."""
+        if self.info.use_ndc or self.info.rays_local != self.info.width * self.info.height:
+            raise AdaNeRFError("reprojection needs a whole frame of a model without useNDC")
+        self._rp_on = True
+        self._reproject_buffers()
+
+    def reproject_device(self, src_rgba8, src_depth, src_acc, src_pos, src_rot, dst_pos, dst_rot, dst_rgba8, dst_depth=None, dst_mask=None,
+                         acc_min: float = 0.5, hole_rgba8: int = 0xFF000000, fill: bool = True, holes: bool = True) -> Optional[int]:
+        """adanerf_reproject on device images of the context's frame size: the frame (uchar4, depth_map, acc_map) rendered at
+        (src_pos, src_rot) warped to (dst_pos, dst_rot) into dst_rgba8 and, if given, dst_depth (fp32) / dst_mask (uint8: 1 a source
+        pixel, 2 filled from a neighbour, 0 hole_rgba8).  Returns the number of holes (synchronous); with holes=False nothing is read
+        back and the outputs are complete after sync()."""
+        f = [np.ascontiguousarray(v, dtype=np.float32).reshape(k) for v, k in ((src_pos, 3), (src_rot, 9), (dst_pos, 3), (dst_rot, 9))]
+        fp = [v.ctypes.data_as(C.POINTER(C.c_float)) for v in f]
+        n = C.c_int32(0)
+        self._check(self.lib.adanerf_reproject(self.handle, _ptr(src_rgba8), _ptr(src_depth), _ptr(src_acc), fp[0], fp[1], fp[2], fp[3],
+                                               float(acc_min), int(hole_rgba8) & 0xFFFFFFFF, REPROJECT_FILL if fill else 0, _ptr(dst_rgba8),
+                                               _ptr(dst_depth), _ptr(dst_mask), C.byref(n) if holes else None))
+        return int(n.value) if holes else None
+
+    def reproject(self, dst_pos, dst_rot, fill: bool = True, acc_min: float = 0.5):
+        """The last render_numpy frame (after enable_reprojection) warped to the pose (dst_pos, dst_rot): returns (rgba8 [R,4] uint8,
+        mask [R] uint8, holes).  Holes come out opaque black.  The camera in force does not change."""
+        if self._rp_frame is None or self._rp_frame[5] != self.info.rays_local:
+            raise AdaNeRFError("reproject: no frame to warp -- enable_reprojection(), set_camera, then render_numpy")
+        rgba, depth, acc, pos, rot, _ = self._rp_frame
+        holes = self.reproject_device(rgba, depth, acc, pos, rot, dst_pos, dst_rot, self._rp_rgba, None, self._rp_mask, acc_min=acc_min, fill=fill)
+        return self._rp_rgba.numpy(), self._rp_mask.numpy(), holes
 
     # -- the frame at the window's size ---------------------------------------------------------------
     def present_device(self, src_rgba8, src_w: int, src_h: int, dst_rgba8, dst_w: int, dst_h: int, flip_y: bool = False,

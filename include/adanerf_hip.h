@@ -14,6 +14,8 @@
  *                                        updateRayMarchFromPosesAdaptive on every call (src/featureset.cpp:80,153)
  *   adanerf_set_frame_size               Settings::width / height (src/settings.cpp:20-33), fixed for the life of the viewer's NeuralRenderer
  *   adanerf_present                      the blit from the render buffer to the window (src/interoprenderbuffer.cpp:87)
+ *   adanerf_reproject                    none: the viewer presents the frame it rendered (src/neuralrenderer.cpp:146-182 ->
+ *                                        src/interoprenderbuffer.cpp:87); this stage sits in front of that step
  *   adanerf_render                       ImageGenerator::inference, 2-context adaptive branch
  *                                        (src/imagegenerator.cpp:282-394) as called from
  *                                        NeuralRenderer::render (src/neuralrenderer.cpp:146-182)
@@ -565,6 +567,48 @@ enum {
  * that is not 4-byte aligned or overlapping ranges return ADANERF_EINVAL. */
 int adanerf_present(adanerf_ctx* ctx, const void* d_src_rgba8, int32_t src_w, int32_t src_h, void* d_dst_rgba8, int32_t dst_w,
                     int32_t dst_h, int32_t flags);
+
+/* adanerf_reproject flags */
+enum { ADANERF_REPROJECT_FILL = 1 }; /* a destination pixel no source pixel lands in takes the farthest of its 8 neighbours' source pixels */
+
+/* Depth reprojection (timewarp): the last rendered frame warped to the pose of the moment, for a host whose display rate or pose latency
+ * must not follow the render rate (a head-tracked or 120 Hz host between two renders).  The viewer has no counterpart: NeuralRenderer::render
+ * (src/neuralrenderer.cpp:146-182) hands the frame it rendered to the blit of src/interoprenderbuffer.cpp:87, and this stage sits in
+ * front of that present step (adanerf_present may follow it).  Inputs are what one adanerf_render of this context wrote: the RGBA8 frame,
+ * the depth_map and acc_map of adanerf_set_aux_outputs, and the pose it was rendered at.
+ *   d_src_rgba8 [height*width] uchar4, d_src_depth_map / d_src_acc_map [height*width] fp32; src_pos / src_rot_c2w: the pose of that frame
+ *   dst_pos / dst_rot_c2w   the pose to warp to (conventions of adanerf_set_camera; the camera in force is neither read nor changed)
+ *   acc_min                 a source pixel with acc_map < acc_min has no surface ("far"); 0 is legal
+ *   hole_rgba8              colour of a destination pixel nothing reaches: the pixel's four bytes as a little-endian word (R lowest)
+ *   flags                   0 or ADANERF_REPROJECT_FILL
+ *   d_dst_rgba8 [height*width] uchar4; d_dst_depth [height*width] fp32 or NULL; d_dst_mask [height*width] uint8 or NULL
+ *   holes_out               host pointer or NULL: the number of pixels with mask 0; non-NULL makes the call synchronous (as mean_out of
+ *                           adanerf_flip), with NULL the outputs are complete after adanerf_sync()
+ * All images have the context's CURRENT frame size (the ray generator's constants belong to it) and are indexed as adanerf_render's
+ * output is; the colour images are 4-byte aligned.  d_dst_depth may be d_src_depth_map; the two colour images must not overlap.
+ * Definition (every operation a single rounded fp32 operation in this order; the same inputs give the same bits on every call):
+ *   splat, source pixel i = row*width + col: (nds, p) = this context's ray of that pixel at the source pose; o = p, the view-cell sphere
+ *   exit (ADANERF_SAMPLER_ADAPTIVE / _PDF), or src_pos (ADANERF_SAMPLER_COARSE_FINE) -- the origin in ADANERF_BUF_RAYS.  a = acc_map[i],
+ *   t = depth_map[i] / a.  The pixel is far if !(a >= acc_min), if t is not finite or if !(t > 0) (NaNs are far).  q = (o + nds t) - dst_pos
+ *   for a near pixel, q = nds for a far one (direction only: the sky follows the rotation alone).  v_k = (R[k] q_0 + R[3+k] q_1) + R[6+k] q_2
+ *   with R = dst_rot_c2w (its transpose applied), zc = -v_2; dropped unless zc is finite and > 0.  u = (focal v_0) / zc + 0.5 width,
+ *   vv = (focal (-v_1)) / zc + 0.5 height, focal = adanerf_info.focal (pixel pitch 1); dropped unless 0 <= u < width and 0 <= vv < height.
+ *   The pixel lands in (floor(u), floor(vv)) with the key (bits(zc) << 32 | i), bits = 0x7F800000 (+inf) for a far pixel; the smallest key
+ *   of a destination pixel wins (a 64-bit integer atomic minimum: nearest surface, lower source index on a tie; no floating-point atomics).
+ *   resolve, destination pixel j: with a winner, its source pixel's colour, mask 1, depth = the winner's zc (+inf for a far winner).
+ *   Without one and with ADANERF_REPROJECT_FILL: among the 8 neighbours' winners (never filled results) the LARGEST key -- the farthest
+ *   surface, the usual choice behind a disocclusion -- gives colour and depth, mask 2.  Otherwise hole_rgba8, depth 0, mask 0.
+ * What it does not do: a splat covers one pixel, so background can show through the cracks of a magnified foreground (a forward move);
+ * view-dependent colour stays that of the source pose; re-rendering only the holes would need a ray mask in the render path.
+ * Runs on the context's stream in three launches (clear, splat, resolve); the z-buffer and the hole count live in context-owned scratch,
+ * grown on demand (the stream is synchronised only then), never shrunk, freed by adanerf_destroy; adanerf_render never allocates them.
+ * ADANERF_EINVAL, with nothing written: a NULL source image, destination colour or pose; a pose entry that is not finite; acc_min NaN or
+ * negative; an unknown flag; a colour image that is not 4-byte aligned; destination colour overlapping the source colour.
+ * ADANERF_EUNSUPPORTED, with nothing written: a useNDC model (its depth_map is NDC depth); a context with shard_world != 1. */
+int adanerf_reproject(adanerf_ctx* ctx, const void* d_src_rgba8, const float* d_src_depth_map, const float* d_src_acc_map,
+                      const float src_pos[3], const float src_rot_c2w[9], const float dst_pos[3], const float dst_rot_c2w[9],
+                      float acc_min, uint32_t hole_rgba8, int32_t flags, void* d_dst_rgba8, float* d_dst_depth, uint8_t* d_dst_mask,
+                      int32_t* holes_out);
 
 /* ---- measurement hook (bench.py's roofline) ---- */
 
