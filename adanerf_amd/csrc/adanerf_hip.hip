@@ -1283,6 +1283,30 @@ int adanerf_composite(adanerf_ctx* c, const float* d_raw, const float* d_w, cons
   return launch_composite(c, d_raw, d_w, d_off, d_cnt, n_rays, d_rgb, d_rgba8);
 }
 
+int adanerf_composite_aux(adanerf_ctx* c, const float* d_raw, const float* d_w, const int32_t* d_off, const int32_t* d_cnt, const uint32_t* d_key,
+                          int32_t n_rays, float* d_rgb, void* d_rgba8, float* d_depth, float* d_acc) {
+  BIND(c);
+  if (!d_raw || !d_w || !d_off || !d_cnt || n_rays < 0) return fail(c, ADANERF_EINVAL, "bad argument");
+  if (!d_key && !c->ms.info.dense && (d_depth || d_acc))      // launch_composite would leave the maps unwritten
+    return fail(c, ADANERF_EINVAL, "adanerf_composite_aux: a depth or acc map needs d_sample_key unless the context is dense (threshold 0)");
+  return launch_composite(c, d_raw, d_w, d_off, d_cnt, n_rays, d_rgb, d_rgba8, d_key, d_depth, d_acc);
+}
+
+int adanerf_composite_classic_aux(adanerf_ctx* c, const float* d_raw, const float* d_z, const float* d_rays, int32_t n_rays, int32_t n,
+                                  float* d_rgb, void* d_rgba8, float* d_depth, float* d_acc) {
+  BIND(c);
+  if (!d_raw || !d_z || !d_rays || n_rays < 0 || n < 1) return fail(c, ADANERF_EINVAL, "bad argument");
+  return launch_composite_classic(c, d_raw, d_z, d_rays, n_rays, n, d_rgb, d_rgba8, d_depth, d_acc);
+}
+
+int adanerf_disp_map(adanerf_ctx* c, const float* d_depth, const float* d_acc, int32_t n, float* d_disp) {
+  BIND(c);
+  if (!d_depth || !d_acc || !d_disp || n < 0) return fail(c, ADANERF_EINVAL, "adanerf_disp_map: NULL buffer or n < 0");
+  if (n == 0) return ADANERF_OK;
+  hipLaunchKernelGGL(disp_map_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_depth, d_acc, n, d_disp);
+  HIP_RETURN(c, hipGetLastError());
+}
+
 namespace {
 
 constexpr size_t kMaxProfiledBatches = 1 << 16;

@@ -72,7 +72,7 @@ EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_las
            "adanerf_render", "adanerf_set_aux_outputs", "adanerf_set_disp_output", "adanerf_assemble_strips", "adanerf_sync", "adanerf_set_stream", "adanerf_set_profiling",
            "adanerf_collect_stats", "adanerf_ray_features", "adanerf_sample_mlp",
            "adanerf_compact", "adanerf_compact_guarded", "adanerf_calibrate_guard", "adanerf_guard_calibration_file", "adanerf_shade_features", "adanerf_shade_mlp", "adanerf_shade_mlp_z", "adanerf_sample_pdf", "adanerf_sample_uniform", "adanerf_shade_mlp_coarse", "adanerf_sample_from_coarse",
-           "adanerf_composite", "adanerf_composite_classic", "adanerf_copy_result_sampling_network", "adanerf_flip",
+           "adanerf_composite", "adanerf_composite_classic", "adanerf_composite_aux", "adanerf_composite_classic_aux", "adanerf_disp_map", "adanerf_copy_result_sampling_network", "adanerf_flip",
            "adanerf_render_oracle", "adanerf_gather_to", "adanerf_probe_mfma", "adanerf_malloc",
            "adanerf_free", "adanerf_memcpy_h2d", "adanerf_memcpy_d2h", "adanerf_get_buffer"]
 
@@ -128,6 +128,9 @@ def load_library(path: Optional[str] = None):
     lib.adanerf_shade_mlp_coarse.argtypes = [vp, vp, vp, vp, i32, i32, vp]
     lib.adanerf_sample_from_coarse.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
     lib.adanerf_composite_classic.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
+    lib.adanerf_composite_aux.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.adanerf_composite_classic_aux.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    lib.adanerf_disp_map.argtypes = [vp, vp, vp, i32, vp]
     lib.adanerf_copy_result_sampling_network.argtypes = [vp, vp, i32, vp]
     lib.adanerf_flip.argtypes = [vp, vp, vp, i32, i32, C.c_float, vp, C.POINTER(C.c_float)]
     lib.adanerf_render_oracle.argtypes = [vp, vp]
@@ -766,3 +769,17 @@ class NeuralRenderer:
     def composite(self, raw, sample_w, ray_offsets, ray_counts, n_rays: int, rgb_out=None, rgba8_out=None):
         self._check(self.lib.adanerf_composite(self.handle, _ptr(raw), _ptr(sample_w), _ptr(ray_offsets), _ptr(ray_counts),
                                                n_rays, _ptr(rgb_out), _ptr(rgba8_out)))
+
+    def composite_aux(self, raw, sample_w, ray_offsets, ray_counts, sample_key, n_rays: int, rgb_out=None, rgba8_out=None, depth_out=None,
+                      acc_out=None):
+        """composite that also writes depth_map / acc_map [n_rays] fp32; sample_key None: dense contexts only (bin = sample index & 127)"""
+        self._check(self.lib.adanerf_composite_aux(self.handle, _ptr(raw), _ptr(sample_w), _ptr(ray_offsets), _ptr(ray_counts), _ptr(sample_key),
+                                                   n_rays, _ptr(rgb_out), _ptr(rgba8_out), _ptr(depth_out), _ptr(acc_out)))
+
+    def composite_classic_aux(self, raw, sample_z, rays, n_rays: int, n: int, rgb_out=None, rgba8_out=None, depth_out=None, acc_out=None):
+        self._check(self.lib.adanerf_composite_classic_aux(self.handle, _ptr(raw), _ptr(sample_z), _ptr(rays), n_rays, n,
+                                                           _ptr(rgb_out), _ptr(rgba8_out), _ptr(depth_out), _ptr(acc_out)))
+
+    def disp_map(self, depth, acc, n: int, disp_out):
+        """disp_out[i] = 1 / max(1e-10, depth[i] / acc[i]) over n fp32 values (NaN stays NaN)"""
+        self._check(self.lib.adanerf_disp_map(self.handle, _ptr(depth), _ptr(acc), n, _ptr(disp_out)))

@@ -524,6 +524,26 @@ int adanerf_composite(adanerf_ctx* ctx, const float* d_raw, const float* d_sampl
                       const int32_t* d_ray_offsets, const int32_t* d_ray_counts, int32_t n_rays,
                       float* d_rgb_out, void* d_rgba8_out);
 
+/* adanerf_composite that also writes the secondary outputs of the step (src/nerf_raymarch_common.py:136-141): d_depth_out [n_rays]
+ * fp32 = sum w z and d_acc_out [n_rays] fp32 = sum w over the ray's samples, w the weight the colour is formed with (under
+ * accumulationMult = weights it carries the multiplier) and z the context's depth table at the bin of d_sample_key [S] (key & 127).
+ * Either map may be NULL and is then not touched; with both NULL this is adanerf_composite.  The colours are those of adanerf_composite,
+ * bit for bit.  d_sample_key may be NULL only in a dense context (threshold 0), where it means "bin = sample index & 127" (every ray
+ * carries all 128 bins in order); NULL in any other context with a map requested returns ADANERF_EINVAL and writes nothing. */
+int adanerf_composite_aux(adanerf_ctx* ctx, const float* d_raw, const float* d_sample_w, const int32_t* d_ray_offsets,
+                          const int32_t* d_ray_counts, const uint32_t* d_sample_key, int32_t n_rays, float* d_rgb_out, void* d_rgba8_out,
+                          float* d_depth_out, float* d_acc_out);
+
+/* adanerf_composite_classic that also writes depth_map = sum w z (z = d_sample_z of the sample) and acc_map = sum w
+ * (src/nerf_raymarch_common.py:60-62) into d_depth_out / d_acc_out [n_rays] fp32; either may be NULL and is then not touched. */
+int adanerf_composite_classic_aux(adanerf_ctx* ctx, const float* d_raw, const float* d_sample_z, const float* d_rays, int32_t n_rays,
+                                  int32_t n, float* d_rgb_out, void* d_rgba8_out, float* d_depth_out, float* d_acc_out);
+
+/* disp_map of src/nerf_raymarch_common.py:61 / :138 from the two maps above: d_disp_out[i] = 1 / max(1e-10, d_depth[i] / d_acc[i]),
+ * n fp32 values each, on the context's stream.  max is torch.max: the NaN of an empty ray (0 / 0) stays NaN.  n = 0 does nothing;
+ * a NULL pointer or n < 0 returns ADANERF_EINVAL. */
+int adanerf_disp_map(adanerf_ctx* ctx, const float* d_depth, const float* d_acc, int32_t n, float* d_disp_out);
+
 /* ---- image metrics ---- */
 
 /* FLIP (Andersson et al. 2020) between two images as the reference's evaluation computes it (src/evaluate.py:120-145 over

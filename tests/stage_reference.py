@@ -16,6 +16,13 @@ by a subtraction from 1: its absolute error is an ulp of 1 however small alpha i
 sum |w_k| does not see on a ray of small densities; there the floor is 2^-100 + mean_k |T_k|.  A component whose fp64 reference is
 not finite must be non-finite in the kernel's output; no finite ray is excluded.
 
+The depth and accumulation maps (acc = sum_k w_k, depth = sum_k w_k z_k, w_k the weight the colour is formed with: under mult weights
+it carries the multiplier) are compared in the same units: acc against `scale`, depth against scale max_k |z_k| over the ray's active
+samples (each term adds one rounding of w z), both with C_AUX[kind] in place of C[kind] and signed (multipliers in [-0.5, 1.8] make acc
+negative on some rays).  z_k = ztab[key_k & 127], the table from adanerf_host_depth_table -- nothing a kernel wrote.  The non-finite rule is
+the same.  C_AUX[kind] is twice the worst case of the fp32 emulations below against fp64 on the tests' own rows (MEASURED_AUX): the margin
+the samplers and the colour constants have, for the association differences of a DPP scan; what the device measures does not widen it.
+
 The samplers are compared by forward residual: the inverse CDF is ill-conditioned in empty bins, the CDF is not.  Every returned depth
 is mapped back in fp64 and the fp64 CDF there must equal the sample's u.  The bound is twice the largest residual of the fp32 numpy
 oracle on the same rows (sampler_bound); no sample is excluded.
@@ -42,6 +49,18 @@ MEASURED = {
     "classic_wave": dict(oracle=0.0677, device=0.0465),   # composite_classic_wave_kernel: n = 65 | n = 1024
 }
 C = {k: 2 * max(v["oracle"], v["device"]) for k, v in MEASURED.items()}
+
+# The maps: `emulation` is the larger of the depth and the acc worst case of composite32 / composite_classic32 (thread kinds: summed in
+# sample order, wave kinds: per lane, then across the wave) against fp64 on the GPU tests' rows, all multiplier modes, the dense layout
+# included; recomputed and compared with this table by test_stage_reference_cpu.py.  `device` is what an MI355X measured (the largest
+# worst_units of its stage_kernel_aux lines in profiles/stage_kernels_measured.log); it is stated, and does not enter the bound.
+MEASURED_AUX = {
+    "thread": dict(emulation=0.3100, device=0.2792),          # composite_kernel<256>: depth, N = 1 alpha
+    "wave": dict(emulation=0.4436, device=0.5682),            # composite_wave_kernel: acc, N = 64 alpha
+    "classic_thread": dict(emulation=0.0629, device=0.0654),  # composite_classic_kernel: acc, n = 2
+    "classic_wave": dict(emulation=0.0578, device=0.0487),    # composite_classic_wave_kernel: depth, n = 63
+}
+C_AUX = {k: 2 * v["emulation"] for k, v in MEASURED_AUX.items()}
 
 
 def sigmoid64(x):
@@ -117,7 +136,7 @@ def composite_units(K, ref, scale, n_samples):
     nonfinite_ok = bool((~np.isfinite(K2[~fin])).all())
     unit = (EPS * (np.asarray(n_samples, np.float64) + C0) * scale).reshape(-1, 1)
     with np.errstate(all="ignore"):
-        u = np.where(fin, np.abs(K2 - ref2) / unit, 0.0)
+        u = np.where(fin & (K2 != ref2), np.abs(K2 - ref2) / unit, 0.0)      # an empty ray's depth has unit 0: only exactly 0 passes
     u = np.where(fin & ~np.isfinite(K2), np.inf, u)          # a finite reference and a non-finite result: never inside a bound
     return u, nonfinite_ok
 
@@ -135,11 +154,74 @@ def check_composite(K, ref, scale, n_samples, kind, log=None, bound=None):
     return worst
 
 
-def composite32(raw, sample_w, off, cnt, mult, fault=None):
-    """fp32 emulation of the wave kernel's arithmetic (two 64-sample halves, the second scaled by the first's total) with its faults:
-    inclusive (product includes the sample's own factor), no_half_total, mult2_on_alpha"""
-    m = MULT[mult]
+def ray_zmax(z, off, cnt):
+    """max_k |z_k| over the active samples of each ray of an (offset, count) layout (0 for an empty ray); z [S]"""
     idx, act = gather(off, cnt)
+    return np.max(np.where(act, np.abs(np.asarray(z, np.float64)[idx]), 0.0), 1, initial=0.0)
+
+
+def check_aux(depth, acc, ref_depth, ref_acc, scale, zmax, n_samples, kind, log=None):
+    """The comparator of the two maps (either may be None: not requested); returns the worst cases (depth, acc) in the bound's units"""
+    worst = {}
+    for name, K, ref, sc in (("depth", depth, ref_depth, scale * zmax), ("acc", acc, ref_acc, scale)):
+        if K is None:
+            continue
+        u, ok = composite_units(K, ref, sc, n_samples)
+        worst[name] = float(u.max()) if u.size else 0.0
+        if log:
+            log(dict(kind=kind, map=name, worst_units=worst[name], bound=C_AUX[kind], rays=int(u.shape[0]), non_finite_rule=ok))
+        assert ok, "%s %s: a ray whose fp64 reference is not finite came out finite" % (kind, name)
+        assert worst[name] <= C_AUX[kind], "%s %s: worst ray %d is %.3g units of 2^-24 (n + %d) scale off fp64 (bound %.3g)" % (
+            kind, name, int(np.argmax(u.max(1))), worst[name], C0, C_AUX[kind])
+    return worst.get("depth", 0.0), worst.get("acc", 0.0)
+
+
+def _seq_sum(x):
+    return np.cumsum(x, 1, dtype=F32)[:, -1] if x.shape[1] else np.zeros(x.shape[0], F32)
+
+
+def _wave_sum(x):
+    """each lane adds its values (sample lane, lane + 64, ...) in order, then the wave sums the 64 lanes"""
+    R, n = x.shape
+    laps = max((n + 63) // 64, 1)
+    p = np.zeros((R, laps * 64), F32)
+    p[:, :n] = x
+    return np.sum(np.cumsum(p.reshape(R, laps, 64), 1, dtype=F32)[:, -1], 1, dtype=F32)
+
+
+def composite32(raw, sample_w, off, cnt, mult, fault=None, ztab=None, key=None, order="wave"):
+    """fp32 emulation of the wave kernel's arithmetic (two 64-sample halves, the second scaled by the first's total) with its faults:
+    inclusive (product includes the sample's own factor), no_half_total, mult2_on_alpha.  With a depth table `ztab` [128] (and `key` [S];
+    None: bin = sample index & 127) -> (rgb, depth, acc) with the maps as the kernels form them: products rounded, then summed per lane
+    and across the wave (order = "wave") or in sample order with a sequential transmittance (order = "seq": composite_kernel).  Faults of
+    the maps: z_by_index (the table looked up by index & 127 although a key is given), aux_without_mult (mult weights: the map's weight
+    lacks the multiplier), aux_second_half_unmasked (slots >= count of the second half contribute what lies there)"""
+    if ztab is None:
+        return _composite32(raw, sample_w, off, cnt, mult, fault, order)[0]
+    idx, act = gather(off, cnt)
+    S = raw.shape[0]
+    rgb, q, w_plain = _composite32(raw, sample_w, off, cnt, mult, fault, order)
+    if fault == "aux_second_half_unmasked":
+        k = np.arange(act.shape[1])[None, :]
+        act = act | (k >= 64)
+        idx = np.minimum(off[:, None].astype(np.int64) + k, S - 1)
+        _, q, w_plain = _composite32(raw, sample_w, off, cnt, mult, fault, order, idx, act)
+    if fault == "aux_without_mult":
+        q = w_plain
+    bins = (idx if (key is None or fault == "z_by_index") else np.asarray(key).astype(np.int64)[idx]) & 127
+    with np.errstate(all="ignore"):
+        z = np.where(act, np.asarray(ztab, F32)[bins], F32(0))
+        q = np.where(act, q, F32(0))
+        add = _seq_sum if order == "seq" else _wave_sum
+        return rgb, add((q * z).astype(F32)), add(q)
+
+
+def _composite32(raw, sample_w, off, cnt, mult, fault, order, idx=None, act=None):
+    """-> rgb, the samples' weights [R,n] (with the multiplier of mult weights), and without it"""
+    m = MULT[mult]
+    if idx is None:
+        idx, act = gather(off, cnt)
+    chunk = 64 if order == "wave" else max(act.shape[1], 1)
     with np.errstate(all="ignore"):
         s = (F32(1) / (F32(1) + np.exp(-raw[idx].astype(F32), dtype=F32))).astype(F32)
         wv = np.where(act, sample_w[idx].astype(F32), F32(0))
@@ -148,19 +230,21 @@ def composite32(raw, sample_w, off, cnt, mult, fault=None):
             al = (al * wv).astype(F32)
         f = np.where(act, (F32(1) - al) + F32(1e-10), F32(1)).astype(F32)
         T = np.ones_like(f)
-        for h in range(0, f.shape[1], 64):
-            p = np.cumprod(f[:, h:h + 64], 1, dtype=F32)
+        for h in range(0, f.shape[1], chunk):
+            p = np.cumprod(f[:, h:h + chunk], 1, dtype=F32)
             e = p if fault == "inclusive" else np.concatenate([np.ones_like(p[:, :1]), p[:, :-1]], 1)
             carry = np.ones_like(p[:, :1]) if (h == 0 or fault == "no_half_total") else np.prod(f[:, :h], 1, dtype=F32)[:, None]
-            T[:, h:h + 64] = carry * e
-        w = (al * T).astype(F32)
+            T[:, h:h + chunk] = carry * e
+        w = w_plain = (al * T).astype(F32)
         if m == 2 and fault != "mult2_on_alpha":
             w = (w * wv).astype(F32)
-        return np.sum(w[..., None] * np.where(act[..., None], s[..., :3], F32(0)), 1, dtype=F32).reshape(-1, 3)
+        return np.sum(w[..., None] * np.where(act[..., None], s[..., :3], F32(0)), 1, dtype=F32).reshape(-1, 3), w, w_plain
 
 
-def composite_classic32(raw, z, rays_d, fault=None):
-    """fp32 emulation of the classic wave kernel (64-sample laps, transmittance carried) with its faults: no_lap_carry, last_zero, no_relu"""
+def composite_classic32(raw, z, rays_d, fault=None, aux=False, order="wave"):
+    """fp32 emulation of the classic wave kernel (64-sample laps, transmittance carried) with its faults: no_lap_carry, last_zero, no_relu.
+    aux -> (rgb, depth, acc), the maps summed per lane over the laps and then across the wave (order = "wave") or in sample order
+    ("seq": composite_classic_kernel); their fault: classic_depth_next_z (z[k+1] in place of z[k], 0 after the last)"""
     raw, z, d = raw.astype(F32), z.astype(F32), rays_d.astype(F32)
     with np.errstate(all="ignore"):
         dn = np.sqrt(np.sum(d * d, -1, keepdims=True, dtype=F32))
@@ -177,7 +261,12 @@ def composite_classic32(raw, z, rays_d, fault=None):
             T[:, h:h + 64] = carry * e
         w = (al * T).astype(F32)
         s = (F32(1) / (F32(1) + np.exp(-raw[..., :3], dtype=F32))).astype(F32)
-        return np.sum(w[..., None] * s, 1, dtype=F32)
+        rgb = np.sum(w[..., None] * s, 1, dtype=F32)
+        if not aux:
+            return rgb
+        zz = np.concatenate([z[:, 1:], np.zeros_like(z[:, :1])], 1) if fault == "classic_depth_next_z" else z
+        add = _seq_sum if order == "seq" else _wave_sum
+        return rgb, add((w * zz).astype(F32)), add(w)
 
 
 # ---- c. RGBA8 -------------------------------------------------------------------------------------------------------------------------
@@ -417,7 +506,8 @@ NONFINITE = (np.nan, np.inf, -np.inf)
 def composite_inputs(seed, N, n_rays=192, nonfinite=True):
     """A base set of distinct rays in the compactor's layout: counts ragged in 0..N (count 0 rays between non-empty ones, full rays),
     saturating runs, rows of identical samples, oracle weights in [-0.5, 1.8], and a few rays carrying NaN / +-inf (finite_rays = False)
-    -> dict(raw [S,4], sw [S], off, cnt [R] int32, finite [R] bool)"""
+    -> dict(raw [S,4], sw [S], off, cnt [R] int32, finite [R] bool, key [S] uint32: ray << 7 | bin, the bins of a ray ascending and
+    distinct over 0..127 as the compactor produces them (drawn from a generator of their own: the other arrays are what they were))"""
     rng = np.random.default_rng(seed)
     cnt = rng.integers(0, N + 1, n_rays)
     cnt[:12] = [N, 0, N, 1 if N > 1 else N, 0, 0, N, max(N - 1, 0), min(64, N), min(65, N), min(63, N), N]
@@ -451,7 +541,52 @@ def composite_inputs(seed, N, n_rays=192, nonfinite=True):
             if r < n_rays and cnt[r] > 0:
                 sw[off[r] + cnt[r] // 2] = np.nan if r == 36 else np.inf
                 finite[r] = False
-    return dict(raw=raw, sw=sw, off=off, cnt=cnt, finite=finite)
+    krng = np.random.default_rng(seed + 7000000)
+    bins = np.concatenate([np.sort(krng.permutation(128)[:c]) for c in cnt] + [np.zeros(0, np.int64)])
+    key = ((ray.astype(np.uint32) << np.uint32(7)) | bins.astype(np.uint32)).astype(np.uint32)
+    return dict(raw=raw, sw=sw, off=off, cnt=cnt, finite=finite, key=key)
+
+
+def permuted(L, B):
+    """ray j of the long list is base ray (a j + c) mod B"""
+    return (7919 * np.arange(L, dtype=np.int64) + 17) % B
+
+
+def layout(c, ids, gap=None):
+    """The base rays `ids`, in that order, as a fresh (offset, count) layout: the compactor's without `gap`, with gap[i] unused slots
+    (NaN, key of all ones: nothing may read them) in front of ray i otherwise -> raw, sw, off, cnt, key"""
+    cnt = c["cnt"][ids].astype(np.int64)
+    g = np.zeros_like(cnt) if gap is None else np.asarray(gap, np.int64)
+    start = np.cumsum(cnt + g) - cnt
+    total = int(start[-1] + cnt[-1])
+    intra = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    src = np.repeat(c["off"][ids].astype(np.int64), cnt) + intra
+    dst = np.repeat(start, cnt) + intra
+    raw = np.full((max(total, 1), 4), np.nan, np.float32)
+    sw = np.full(max(total, 1), np.nan, np.float32)
+    key = np.full(max(total, 1), 0xFFFFFFFF, np.uint32)
+    raw[dst], sw[dst], key[dst] = c["raw"][src], c["sw"][src], c["key"][src]
+    return raw, sw, start.astype(np.int32), cnt.astype(np.int32), key
+
+
+def dense_layout(n_rays=1001):
+    """test_composite_dense_mode's rows: the 128-sample rays of composite_inputs(1128, 128), permuted, in the compactor's layout"""
+    c = composite_inputs(1128, 128)
+    ids = np.flatnonzero(c["cnt"] == 128)
+    raw, sw, off, cnt, key = layout(c, ids[permuted(n_rays, ids.size)])
+    return dict(raw=raw, sw=sw, off=off, cnt=cnt, key=key)
+
+
+def host_depth_table(lib, options_type, model_dir, num_samples, threshold):
+    """The context's depth table [128] from the host library (adanerf_host_depth_table: compared with the oracle in test_host_cpu.py)"""
+    import ctypes
+    lib.adanerf_host_depth_table.argtypes = [ctypes.c_char_p, ctypes.POINTER(options_type), ctypes.c_void_p]
+    o = options_type(width=8, height=8, batch_rays=0, device_id=0, precision=0, num_samples=num_samples, threshold=threshold, shard_rank=0,
+                     shard_world=1, strip_rows=8)
+    zt = np.zeros(128, F32)
+    rc = lib.adanerf_host_depth_table(model_dir.encode(), ctypes.byref(o), zt.ctypes.data)
+    assert rc == 0, lib.adanerf_last_error(None)
+    return zt
 
 
 def classic_inputs(seed, n, n_rays=96, nonfinite=True):

@@ -294,15 +294,19 @@ def test_bench_plain_run_dumps_the_last_timed_frame(tmp_path):
 # secondary outputs of the compositing step (depth_map = sum w z, acc_map = sum w)
 # ---------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("name", AUX_CASES + ["classroom_dense128"])
+@pytest.mark.parametrize("name", AUX_CASES + ["classroom_dense128"] + ["classroom_n8_aux@N%d" % n for n in (12, 24, 48)])
 def test_aux_outputs_match_oracle(name, tmp_path_factory):
     """adanerf_set_aux_outputs: adaptive (LDS-staged compositing kernel), dense (wave-per-ray kernel), FromClassifiedDepth
     (classic kernel), under each multiplier mode the fixtures carry; the oracle's values are pinned to the reference's
-    NeRFOutputDepth / NeRFWeightsOutput in tests/test_oracle_golden.py."""
+    NeRFOutputDepth / NeRFWeightsOutput in tests/test_oracle_golden.py.  name@N<n>: the fixture's model with num_samples = n at
+    40 x 32 rays, so that adanerf_render hands the key array to composite_kernel<128>, <64> and the adaptive composite_wave_kernel too."""
+    name, _, n_over = name.partition("@N")
     z, meta, sc = load_case(name)
     wts = case_weights(meta)
-    d = _dir(tmp_path_factory, sc, wts, "aux_" + name)
-    w, h = (40, 32) if sc.threshold == 0.0 and sc.sampler != "FromClassifiedDepth" else (112, 80)
+    if n_over:
+        sc = dataclasses.replace(sc, num_samples=int(n_over))
+    d = _dir(tmp_path_factory, sc, wts, "aux_" + name + n_over)
+    w, h = (40, 32) if n_over or (sc.threshold == 0.0 and sc.sampler != "FromClassifiedDepth") else (112, 80)
     ref = O.render_rays(O.generate_ray_directions(w, h, sc.fov), z["pose"], z["rot"], sc, wts, w, h, keep=True)
     with adanerf_amd.NeuralRenderer(adanerf_amd.Settings(d, w, h, batch_size=3000), precision="fp32") as r:
         r.set_camera(z["pose"], z["rot"])
@@ -311,6 +315,7 @@ def test_aux_outputs_match_oracle(name, tmp_path_factory):
         disp = r.empty((w * h,), np.float32)
         r.set_disp_output(disp)
         rgb, rgba, st = r.render_numpy()
+        assert not n_over or (r.info.num_samples == int(n_over) and not r.info.dense)
         dm, am = depth.numpy(), acc.numpy()
         # disp_map (src/nerf_raymarch_common.py:61 / :138) is a function of the two maps: exactly that function of what was written
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -329,7 +334,7 @@ def test_aux_outputs_match_oracle(name, tmp_path_factory):
     if "bins" in ref:                                       # adaptive: compare rays whose selection agrees (SURVEY "Hard parts")
         cnt_ok = np.isclose(np.abs(rgb - ref["rgb"]).max(axis=1), 0, atol=3e-4)
         same = cnt_ok
-        check_identical(same, "aux_outputs_" + name, residual_budget(w * h))      # oracle evaluated on this box: at most max(1, 1e-4 n) rays
+        check_identical(same, "aux_outputs_" + name + n_over, residual_budget(w * h))      # oracle evaluated on this box: at most max(1, 1e-4 n) rays
     if sc.sampler == "FromClassifiedDepth":
         # where a bin's probability mass is ~0 the inverse CDF is ill-conditioned and an occasional sample lands at the other
         # edge of an empty bin (see test_pdf_sampler_matches_reference): robust bounds, < 0.5 % of rays may deviate

@@ -8,7 +8,12 @@ tests/stage_reference.py, at the sizes where their dispatch branches and loop st
  b. position invariance, no tolerance: every occurrence of a base ray in a long permuted list (threads, waves, workgroups, grid laps,
     the staged and the direct path of composite_kernel) is bit-identical to its base-set result;
  c. RGBA8 bytes equal stage_reference.rgba8_of of the fp32 colours the same launch wrote, exactly;
- d. every launch writes into exact-size outputs between two 4 KiB canary regions.
+ d. every launch writes into exact-size outputs between two 4 KiB canary regions;
+ e. the depth and accumulation maps (adanerf_composite_aux / adanerf_composite_classic_aux) of every compositing launch above: against fp64
+    in the colour's units (stage_reference.check_aux, bound C_AUX: twice the fp32 emulation's worst case), signed, empty rays exactly 0;
+    requested alone or together they have the same bits, a map that is not requested is not touched, and the colours beside them are the
+    bits of the launch without maps; position invariance as in b.  The keys' bins ascend and differ from index & 127; the depth table
+    comes from the host library.  adanerf_disp_map: bit for bit its fp32 restatement on a list of edge pairs.
 
 Bounds: stage_reference.C (compositing, measured on an MI355X: profiles/stage_kernels_measured.log), twice the fp32 numpy oracle's
 residual on the same rows (samplers).  Models are written from the golden scenes; the networks do not matter here.
@@ -21,10 +26,13 @@ Kernels and the cases that reach them:
         each: 1, RB - 1, RB, RB + 1, 5 RB + 37 and zero rays; the compactor's layout (staged), a gapped and a reversed layout (direct),
         workgroups that span exactly cap and cap + 1 samples
     composite_wave_kernel            N = 33, 64, 65, 127, 128, threshold > 0, counts ragged in 0..N, and all counts = N;
-                                     test_composite_dense_mode (threshold 0, every count 128)
+                                     test_composite_dense_mode (threshold 0, every count 128; null key, key arange & 127, mirrored key)
+        every launch: without maps (the staged / direct loops), with depth, with acc, with both (composite_kernel's map loop)
   launch_composite_classic
     composite_classic_kernel         test_composite_classic[n] n = 1, 2, 31, 32
     composite_classic_wave_kernel    n = 33, 63, 64, 65, 128, 129, 192, 1024 (1 to 16 laps, whole and ragged last laps)
+  adanerf_disp_map
+    disp_map_kernel                  test_disp_map[n] n = 1, 255, 256, 257, 1000
   launch_sample_pdf
     pdf_sample_kernel                test_pdf_sampler[transform-depth] n = 1, 2, 8, 63, 64, 65, 200; three laps of its grid
   launch_sample_fine / launch_sample_uniform
@@ -40,6 +48,7 @@ import stage_reference as S
 from conftest import load_case, record
 
 import adanerf_amd
+from adanerf_amd import renderer as R
 
 pytestmark = pytest.mark.gpu
 
@@ -95,52 +104,73 @@ def same_bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
-def permuted(L, B):
-    """ray j of the long list is base ray (a j + c) mod B"""
-    return (7919 * np.arange(L, dtype=np.int64) + 17) % B
+permuted = S.permuted
+layout = S.layout
 
 
 def _log(kernel, **ctx):
     return lambda summary: record("stage_kernel", kernel=kernel, **ctx, **summary)
 
 
+def _log_aux(kernel, **ctx):
+    return lambda summary: record("stage_kernel_aux", kernel=kernel, **ctx, **summary)
+
+
+def untouched(g, what):
+    assert (g.body(what) == 0xA5).all(), what + ": written although it was not requested"
+
+
+def depth_table(r, model_dir):
+    """The context's depth table from the host library -- nothing a kernel wrote"""
+    return S.host_depth_table(r.lib, R._Options, model_dir, int(r.info.num_samples), float(r.info.threshold))
+
+
 # ---- adaptive compositing ------------------------------------------------------------------------------------------------------------------
 
-def layout(c, ids, gap=None):
-    """The base rays `ids`, in that order, as a fresh (offset, count) layout: the compactor's without `gap`, with gap[i] unused slots
-    (NaN: nothing may read them) in front of ray i otherwise"""
-    cnt = c["cnt"][ids].astype(np.int64)
-    g = np.zeros_like(cnt) if gap is None else np.asarray(gap, np.int64)
-    start = np.cumsum(cnt + g) - cnt
-    total = int(start[-1] + cnt[-1])
-    intra = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
-    src = np.repeat(c["off"][ids].astype(np.int64), cnt) + intra
-    dst = np.repeat(start, cnt) + intra
-    raw = np.full((max(total, 1), 4), np.nan, np.float32)
-    sw = np.full(max(total, 1), np.nan, np.float32)
-    raw[dst], sw[dst] = c["raw"][src], c["sw"][src]
-    return raw, sw, start.astype(np.int32), cnt.astype(np.int32)
-
-
-def run_composite(r, raw, sw, off, cnt, n, what):
+def run_composite(r, raw, sw, off, cnt, key, n, what, null_key=False):
+    """One layout through adanerf_composite and through adanerf_composite_aux with depth only, acc only and both: every colour output of
+    the four launches has the same bits, a map has the same bits whichever other map is requested, a map that is not requested is
+    not touched -> rgb, rgba8, depth, acc"""
     bufs = [r.to_device(np.ascontiguousarray(a)) for a in (raw, sw, off, cnt)]
+    d_key = None if null_key else r.to_device(np.ascontiguousarray(key))
     rgb, rgba = Guarded(r, n * 12), Guarded(r, n * 4)
     r.composite(*bufs, n, rgb.ptr, rgba.ptr)
     r.sync()
-    for b in bufs:
+    K, K8 = rgb.body(what + " rgb", np.float32).reshape(n, 3), rgba.body(what + " rgba8").reshape(n, 4)
+    maps = {}
+    for want in ("depth", "acc", "both"):
+        rgb, rgba, dm, am = Guarded(r, n * 12), Guarded(r, n * 4), Guarded(r, n * 4), Guarded(r, n * 4)
+        r.composite_aux(*bufs, d_key, n, rgb.ptr, rgba.ptr, dm.ptr if want != "acc" else None, am.ptr if want != "depth" else None)
+        r.sync()
+        w = "%s with %s" % (what, want)
+        assert same_bits(rgb.body(w + " rgb", np.float32).reshape(n, 3), K) and same_bits(rgba.body(w + " rgba8").reshape(n, 4), K8), \
+            w + ": the colours differ from those of adanerf_composite"
+        for name, g in (("depth", dm), ("acc", am)):
+            if want in (name, "both"):
+                maps.setdefault(name, []).append(g.body(w + " " + name, np.float32))
+            else:
+                untouched(g, w + " " + name)
+    for name, (alone, both) in maps.items():
+        assert same_bits(alone, both), "%s: %s alone differs from %s beside the other map" % (what, name, name)
+    for b in bufs + ([] if null_key else [d_key]):
         b.free()
-    return rgb.body(what + " rgb", np.float32).reshape(n, 3), rgba.body(what + " rgba8").reshape(n, 4)
+    return K, K8, maps["depth"][1], maps["acc"][1]
 
 
-def composite_checks(r, c, N, mult, kind, tag):
+def composite_checks(r, c, N, mult, kind, tag, ztab, null_key=False):
     B = c["cnt"].shape[0]
-    K, K8 = run_composite(r, c["raw"], c["sw"], c["off"], c["cnt"], B, tag)
-    ref, _, _, scale = S.composite64(c["raw"], c["sw"], c["off"], c["cnt"], mult)
+    K, K8, D, A = run_composite(r, c["raw"], c["sw"], c["off"], c["cnt"], c["key"], B, tag, null_key)
+    bins = (np.arange(c["raw"].shape[0]) if null_key else c["key"]) & 127
+    ref, ref_d, ref_a, scale = S.composite64(c["raw"], c["sw"], c["off"], c["cnt"], mult, z=ztab[bins])
     name = "composite_wave_kernel" if N > 32 else "composite_kernel<%d>" % (256 if N <= 9 else 128 if N <= 19 else 64)
     S.check_composite(K, ref, scale, c["cnt"], kind, log=_log(kind, instance=name, N=N, mult=mult, case=tag))
+    S.check_aux(D, A, ref_d, ref_a, scale, S.ray_zmax(ztab[bins], c["off"], c["cnt"]), c["cnt"], kind,
+                log=_log_aux(kind, instance=name, N=N, mult=mult, case=tag))
     assert np.array_equal(K8, S.rgba8_of(K)), tag + ": RGBA8 is not the contract's function of the fp32 colour"
-    assert (c["cnt"] > 0).any() and (K[c["cnt"] == 0] == 0).all()
-    return K, K8
+    empty = c["cnt"] == 0
+    assert (~empty).any() and (K[empty] == 0).all()
+    assert (D[empty].view(np.uint32) == 0).all() and (A[empty].view(np.uint32) == 0).all(), tag + ": an empty ray's maps are not +0.0"
+    return K, K8, D, A
 
 
 @pytest.mark.parametrize("mult", list(MULTS))
@@ -153,10 +183,12 @@ def test_composite(N, mult, mult_dirs):
     tag = "N%d_%s" % (N, mult)
     with adanerf_amd.NeuralRenderer(adanerf_amd.Settings(mult_dirs[mult], 8, 8), precision="fp32", num_samples=N, threshold=0.2) as r:
         assert r.info.num_samples == N and not r.info.dense
-        K, K8 = composite_checks(r, c, N, mult, kind, tag)
+        ztab = depth_table(r, mult_dirs[mult])
+        base = composite_checks(r, c, N, mult, kind, tag, ztab)
 
         def same(ids, got, what):
-            assert same_bits(got[0], K[ids]) and same_bits(got[1], K8[ids]), "%s %s: differs from the base set" % (tag, what)
+            for name, g, k in zip(("rgb", "rgba8", "depth", "acc"), got, base):
+                assert same_bits(g, k[ids]), "%s %s: %s differs from the base set" % (tag, what, name)
         counts = [1, RB - 1, RB, RB + 1, 5 * RB + 37] if kind == "thread" else [1, 3, 4, 5, 1001]
         ids = permuted(counts[-1], B)
         for n in counts:      # the compactor's layout: the staged path of composite_kernel
@@ -164,7 +196,7 @@ def test_composite(N, mult, mult_dirs):
         # gaps in front of every ray, and the base arrays walked backwards: the direct path
         gap = 1 + (np.arange(ids.size) % 5)
         same(ids, run_composite(r, *layout(c, ids, gap), ids.size, tag + " gapped"), "gapped")
-        same(np.arange(B)[::-1], run_composite(r, c["raw"], c["sw"], c["off"][::-1].copy(), c["cnt"][::-1].copy(), B, tag + " reversed"), "reversed")
+        same(np.arange(B)[::-1], run_composite(r, c["raw"], c["sw"], c["off"][::-1].copy(), c["cnt"][::-1].copy(), c["key"], B, tag + " reversed"), "reversed")
         # every count = N: workgroups of exactly cap = RB N samples (staged); one unused slot inside each: cap + 1 (direct)
         full = np.flatnonzero(c["finite"] & (c["cnt"] == N))
         ids = full[permuted(2 * RB + 1, full.size)]
@@ -172,36 +204,80 @@ def test_composite(N, mult, mult_dirs):
         gap = np.zeros(ids.size, np.int64)
         gap[1::RB] = 1
         same(ids, run_composite(r, *layout(c, ids, gap), ids.size, tag + " cap + 1"), "cap + 1")
-        # zero rays: nothing is written
-        rgb, rgba = Guarded(r, 12), Guarded(r, 4)
+        # zero rays: nothing is written; a map without a key outside the dense mode: refused, nothing is written
         bufs = [r.to_device(a) for a in (c["raw"], c["sw"], c["off"], c["cnt"])]
+        d_key = r.to_device(c["key"])
+        rgb, rgba = Guarded(r, 12), Guarded(r, 4)
         r.composite(*bufs, 0, rgb.ptr, rgba.ptr)
         r.sync()
-        assert (rgb.body(tag + " 0 rays") == 0xA5).all() and (rgba.body(tag + " 0 rays") == 0xA5).all()
+        untouched(rgb, tag + " 0 rays")
+        untouched(rgba, tag + " 0 rays")
+        out = [Guarded(r, 12), Guarded(r, 4), Guarded(r, 4), Guarded(r, 4)]
+        r.composite_aux(*bufs, d_key, 0, *[g.ptr for g in out])
+        r.sync()
+        for g in out:
+            untouched(g, tag + " 0 rays with maps")
+        for want in ((True, False), (False, True), (True, True)):
+            out = [Guarded(r, B * 12), Guarded(r, B * 4), Guarded(r, B * 4), Guarded(r, B * 4)]
+            with pytest.raises(adanerf_amd.AdaNeRFError, match="error -1: adanerf_composite_aux: .*d_sample_key"):
+                r.composite_aux(*bufs, None, B, out[0].ptr, out[1].ptr, out[2].ptr if want[0] else None, out[3].ptr if want[1] else None)
+            r.sync()
+            for g in out:
+                untouched(g, tag + " no key")
+        rgb, rgba = Guarded(r, B * 12), Guarded(r, B * 4)      # no map: the key is not needed
+        r.composite_aux(*bufs, None, B, rgb.ptr, rgba.ptr, None, None)
+        r.sync()
+        assert same_bits(rgb.body(tag + " no key, no map", np.float32).reshape(B, 3), base[0]) and same_bits(rgba.body(tag).reshape(B, 4), base[1])
 
 
 def test_composite_dense_mode(mult_dirs):
-    """threshold 0: every ray carries all 128 bins"""
-    c = S.composite_inputs(1128, 128)
-    ids = np.flatnonzero(c["cnt"] == 128)
-    raw, sw, off, cnt = layout(c, ids[permuted(1001, ids.size)])
-    c2 = dict(raw=raw, sw=sw, off=off, cnt=cnt)
+    """threshold 0: every ray carries all 128 bins; a null key is the key arange & 127, bit for bit"""
+    c2 = S.dense_layout()
+    n = c2["cnt"].shape[0]
     with adanerf_amd.NeuralRenderer(adanerf_amd.Settings(mult_dirs["alpha"], 8, 8), precision="fp32", num_samples=128, threshold=0.0) as r:
         assert r.info.dense and r.info.num_samples == 128
-        composite_checks(r, c2, 128, "alpha", "wave", "dense128")
+        ztab = depth_table(r, mult_dirs["alpha"])
+        assert np.array_equal(c2["key"] & 127, np.arange(c2["key"].shape[0], dtype=np.uint32) & 127)
+        null = composite_checks(r, c2, 128, "alpha", "wave", "dense128", ztab, null_key=True)
+        keyed = run_composite(r, c2["raw"], c2["sw"], c2["off"], c2["cnt"], c2["key"], n, "dense128 keyed")
+        for name, a, b in zip(("rgb", "rgba8", "depth", "acc"), null, keyed):
+            assert same_bits(a, b), "dense128: %s with a null key differs from the key arange & 127" % name
+        # a key that is given is used in the dense mode too: every bin mirrored
+        c3 = dict(c2, key=(c2["key"] & ~np.uint32(127)) | (np.uint32(127) - (c2["key"] & np.uint32(127))))
+        _, _, D, A = run_composite(r, c3["raw"], c3["sw"], c3["off"], c3["cnt"], c3["key"], n, "dense128 mirrored")
+        _, ref_d, ref_a, scale = S.composite64(c3["raw"], c3["sw"], c3["off"], c3["cnt"], "alpha", z=ztab[c3["key"] & 127])
+        S.check_aux(D, A, ref_d, ref_a, scale, S.ray_zmax(ztab[c3["key"] & 127], c3["off"], c3["cnt"]), c3["cnt"], "wave")
+        assert same_bits(A, null[3])
 
 
 # ---- classic compositing ---------------------------------------------------------------------------------------------------------------------
 
 def run_classic(r, c, ids, n, what):
-    R = len(ids)
+    """as run_composite: adanerf_composite_classic, and adanerf_composite_classic_aux with depth only, acc only and both"""
+    R_ = len(ids)
     bufs = [r.to_device(np.ascontiguousarray(c[k][ids])) for k in ("raw", "z", "rays")]
-    rgb, rgba = Guarded(r, R * 12), Guarded(r, R * 4)
-    r.composite_classic(*bufs, R, n, rgb.ptr, rgba.ptr)
+    rgb, rgba = Guarded(r, R_ * 12), Guarded(r, R_ * 4)
+    r.composite_classic(*bufs, R_, n, rgb.ptr, rgba.ptr)
     r.sync()
+    K, K8 = rgb.body(what + " rgb", np.float32).reshape(R_, 3), rgba.body(what + " rgba8").reshape(R_, 4)
+    maps = {}
+    for want in ("depth", "acc", "both"):
+        rgb, rgba, dm, am = Guarded(r, R_ * 12), Guarded(r, R_ * 4), Guarded(r, R_ * 4), Guarded(r, R_ * 4)
+        r.composite_classic_aux(*bufs, R_, n, rgb.ptr, rgba.ptr, dm.ptr if want != "acc" else None, am.ptr if want != "depth" else None)
+        r.sync()
+        w = "%s with %s" % (what, want)
+        assert same_bits(rgb.body(w + " rgb", np.float32).reshape(R_, 3), K) and same_bits(rgba.body(w + " rgba8").reshape(R_, 4), K8), \
+            w + ": the colours differ from those of adanerf_composite_classic"
+        for name, g in (("depth", dm), ("acc", am)):
+            if want in (name, "both"):
+                maps.setdefault(name, []).append(g.body(w + " " + name, np.float32))
+            else:
+                untouched(g, w + " " + name)
+    for name, (alone, both) in maps.items():
+        assert same_bits(alone, both), "%s: %s alone differs from %s beside the other map" % (what, name, name)
     for b in bufs:
         b.free()
-    return rgb.body(what + " rgb", np.float32).reshape(R, 3), rgba.body(what + " rgba8").reshape(R, 4)
+    return K, K8, maps["depth"][1], maps["acc"][1]
 
 
 @pytest.mark.parametrize("n", CLASSIC_N)
@@ -211,20 +287,76 @@ def test_composite_classic(n, mult_dirs):
     B = c["z"].shape[0]
     tag = "n%d" % n
     with adanerf_amd.NeuralRenderer(adanerf_amd.Settings(mult_dirs["alpha"], 8, 8), precision="fp32") as r:
-        K, K8 = run_classic(r, c, np.arange(B), n, tag)
-        ref, _, _, scale = S.composite_classic64(c["raw"], c["z"], c["rays"][:, 4:7])
-        S.check_composite(K, ref, scale, n, kind, log=_log(kind, instance="composite_classic_kernel" if n <= 32 else "composite_classic_wave_kernel", n=n, case=tag))
+        base = run_classic(r, c, np.arange(B), n, tag)
+        K, K8, D, A = base
+        ref, ref_d, ref_a, scale = S.composite_classic64(c["raw"], c["z"], c["rays"][:, 4:7])
+        instance = "composite_classic_kernel" if n <= 32 else "composite_classic_wave_kernel"
+        S.check_composite(K, ref, scale, n, kind, log=_log(kind, instance=instance, n=n, case=tag))
+        S.check_aux(D, A, ref_d, ref_a, scale, np.abs(c["z"].astype(np.float64)).max(1), n, kind, log=_log_aux(kind, instance=instance, n=n, case=tag))
         assert np.array_equal(K8, S.rgba8_of(K)), tag + ": RGBA8 is not the contract's function of the fp32 colour"
         counts = [1, 255, 256, 257, 777] if kind == "classic_thread" else [1, 3, 4, 5, 1001 if n <= 192 else 301]
         ids = permuted(counts[-1], B)
         for m in counts:
-            got, got8 = run_classic(r, c, ids[:m], n, "%s %d rays" % (tag, m))
-            assert same_bits(got, K[ids[:m]]) and same_bits(got8, K8[ids[:m]]), "%s %d rays: differs from the base set" % (tag, m)
-        rgb, rgba = Guarded(r, 12), Guarded(r, 4)
+            got = run_classic(r, c, ids[:m], n, "%s %d rays" % (tag, m))
+            for name, g, k in zip(("rgb", "rgba8", "depth", "acc"), got, base):
+                assert same_bits(g, k[ids[:m]]), "%s %d rays: %s differs from the base set" % (tag, m, name)
         bufs = [r.to_device(c[k]) for k in ("raw", "z", "rays")]
+        rgb, rgba = Guarded(r, 12), Guarded(r, 4)
         r.composite_classic(*bufs, 0, n, rgb.ptr, rgba.ptr)
         r.sync()
-        assert (rgb.body(tag + " 0 rays") == 0xA5).all() and (rgba.body(tag + " 0 rays") == 0xA5).all()
+        untouched(rgb, tag + " 0 rays")
+        untouched(rgba, tag + " 0 rays")
+        out = [Guarded(r, 12), Guarded(r, 4), Guarded(r, 4), Guarded(r, 4)]
+        r.composite_classic_aux(*bufs, 0, n, *[g.ptr for g in out])
+        r.sync()
+        for g in out:
+            untouched(g, tag + " 0 rays with maps")
+
+
+# ---- the disparity map -----------------------------------------------------------------------------------------------------------------------
+
+DISP_EDGES = [(0.0, 0.0), (1.0, 0.0), (-1.0, 0.0), (0.0, -0.0), (-0.0, 1.0), (-1.0, 2.0), (3.0, -0.5), (1e-12, 1.0), (1e-10, 1.0), (1.0000001e-10, 1.0),
+              (9.9999e-11, 1.0), (1e-40, 1.0), (1e-40, 1e-40), (1.0, 1e-40), (1e-45, 3e-39), (-1e-40, 1.0), (3e38, 1e-3), (np.inf, 1.0),
+              (-np.inf, 1.0), (np.inf, np.inf), (1.0, np.inf), (1.0, -np.inf), (np.inf, 0.0), (np.nan, 1.0), (1.0, np.nan), (np.nan, np.nan),
+              (np.nan, 0.0), (0.0, np.nan)]
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 1000])
+def test_disp_map(n, mult_dirs):
+    """adanerf_disp_map: bit for bit the fp32 function 1 / maximum(1e-10, depth / acc) with torch.max's (numpy.maximum's) NaN: an empty
+    ray (0 / 0) stays NaN, a negative or tiny quotient meets the floor, one block and a ragged second"""
+    rng = np.random.default_rng(5000 + n)
+    d = rng.uniform(0.1, 9.0, n).astype(np.float32)
+    a = rng.uniform(1e-3, 1.2, n).astype(np.float32)
+    e = np.array(DISP_EDGES, np.float32)
+    k = min(n, len(e))
+    first = 0 if n >= len(e) else (n * 7) % len(e)        # n = 1: one edge pair; the long arrays: all, at both ends of the blocks
+    d[:k], a[:k] = e[first:first + k, 0], e[first:first + k, 1]
+    if n > 2 * len(e):
+        d[-len(e):], a[-len(e):] = e[::-1, 0], e[::-1, 1]
+    with np.errstate(all="ignore"):
+        exp = (np.float32(1.0) / np.maximum(np.float32(1e-10), (d / a).astype(np.float32))).astype(np.float32)
+    with adanerf_amd.NeuralRenderer(adanerf_amd.Settings(mult_dirs["alpha"], 8, 8), precision="fp32") as r:
+        bufs = [r.to_device(d), r.to_device(a)]
+        out = Guarded(r, n * 4)
+        r.disp_map(*bufs, n, out.ptr)
+        r.sync()
+        got = out.body("disp_map %d" % n, np.float32)
+        assert np.array_equal(np.isnan(got), np.isnan(exp)), "NaN in other places: pairs %s" % np.flatnonzero(np.isnan(got) != np.isnan(exp))[:8].tolist()
+        ok = np.isnan(exp) | (got.view(np.uint32) == exp.view(np.uint32))
+        assert ok.all(), "pairs %s: %s / %s -> %s, not %s" % (np.flatnonzero(~ok)[:8].tolist(), d[~ok][:8], a[~ok][:8], got[~ok][:8], exp[~ok][:8])
+        if n >= len(e):
+            assert np.isnan(got[0]) and got[1] == 0.0 and got[2] == got[5] == np.float32(1.0) / np.float32(1e-10)      # 0/0, x/0, -x/0, negative
+        out = Guarded(r, 4)
+        r.disp_map(*bufs, 0, out.ptr)
+        r.sync()
+        untouched(out, "disp_map 0")
+        out = Guarded(r, n * 4)
+        for args in ((None, bufs[1], n, out.ptr), (bufs[0], None, n, out.ptr), (bufs[0], bufs[1], n, None), (bufs[0], bufs[1], -1, out.ptr)):
+            with pytest.raises(adanerf_amd.AdaNeRFError, match="error -1"):
+                r.disp_map(*args)
+        r.sync()
+        untouched(out, "disp_map refused")
 
 
 # ---- the inverse-CDF sampler -------------------------------------------------------------------------------------------------------------------

@@ -788,6 +788,33 @@ def test_header_is_plain_c_and_links_from_c(lib, tmp_path):
     assert sizes == "sizeof options=%d info=%d stats=%d" % (C.sizeof(R._Options), C.sizeof(R.Info), C.sizeof(R.Stats))
 
 
+def test_map_entry_points_are_declared_and_exported(lib, tmp_path):
+    """adanerf_composite_aux, adanerf_composite_classic_aux, adanerf_disp_map: tests/aux_abi_check.c compiled as C99 against the header,
+    linked with the library; a NULL context is refused and nothing is written; no struct changed; the Python host has the wrappers."""
+    import inspect
+    import shutil
+    import subprocess
+    gcc = shutil.which("gcc")
+    assert gcc, "gcc is needed to check the header from C"
+    from adanerf_amd.build import LIBDIR
+    exe = str(tmp_path / "aux_abi_check")
+    subprocess.run([gcc, "-std=c99", "-Wall", "-Werror", "-pedantic", os.path.join(ROOT, "tests", "aux_abi_check.c"), "-L", LIBDIR,
+                    "-ladanerf_hip", "-Wl,-rpath," + LIBDIR, "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout + out.stderr
+    lines = out.stdout.strip().splitlines()
+    assert lines[0] == "aux(NULL) rc=-1 -1 -1 maps=-7 -7 -7 abi=4"
+    assert lines[1] == "sizes %d %d %d" % (C.sizeof(R._Options), C.sizeof(R.Info), C.sizeof(R.Stats))
+    for name in ("adanerf_composite_aux", "adanerf_composite_classic_aux", "adanerf_disp_map"):
+        assert name in R.EXPORTS and hasattr(lib, name)
+    par = lambda f: list(inspect.signature(f).parameters)[1:]
+    assert par(R.NeuralRenderer.composite_aux) == ["raw", "sample_w", "ray_offsets", "ray_counts", "sample_key", "n_rays", "rgb_out", "rgba8_out", "depth_out", "acc_out"]
+    assert par(R.NeuralRenderer.composite_classic_aux) == ["raw", "sample_z", "rays", "n_rays", "n", "rgb_out", "rgba8_out", "depth_out", "acc_out"]
+    assert par(R.NeuralRenderer.disp_map) == ["depth", "acc", "n", "disp_out"]
+    assert par(R.NeuralRenderer.composite) == ["raw", "sample_w", "ray_offsets", "ray_counts", "n_rays", "rgb_out", "rgba8_out"]
+    assert par(R.NeuralRenderer.composite_classic) == ["raw", "sample_z", "rays", "n_rays", "n", "rgb_out", "rgba8_out"]
+
+
 def test_balanced_strip_rows():
     from adanerf_amd import sharding as S
     assert S.balanced_strip_rows(800, 1) == 8 and S.balanced_strip_rows(800, 2) == 8 and S.balanced_strip_rows(800, 4) == 8
