@@ -19,6 +19,7 @@ namespace adanerf {
 using tune::kSelRaysPerBlock;
 static_assert(kSelRaysPerBlock == 32 || kSelRaysPerBlock == 64, "segment must fit one wave");
 constexpr int kSelSegShift = kSelRaysPerBlock == 64 ? 6 : 5;
+constexpr float kFltMax = __FLT_MAX__;          // the largest finite float
 
 // Selection rule (src/nerf_raymarch_common.py:699-757 as a set rule):
 // keep the n_max largest values (ties: lower bin first) that are >= thr; if none is >= thr keep the
@@ -48,6 +49,22 @@ __device__ __forceinline__ void select_ray(float v0, float v1, int lane, int n_m
       uint64_t g0 = e0, g1 = e1;                 // {v >= hi}
       int ch = __popcll(e0) + __popcll(e1);
       uint64_t t0 = b0, t1 = b1;                 // {v >= lo}
+      if (m == INFINITY && ch < n_max) {
+        // fewer than n_max values are +inf: an infinite hi has no midpoint (the loop would stop at once and hand the finite
+        // candidates, which are not equal, to the tie rule), so bisect below the largest finite float instead
+        const uint64_t f0 = __ballot(v0 >= kFltMax), f1 = __ballot(v1 >= kFltMax);
+        const int cf = __popcll(f0) + __popcll(f1);
+        if (cf <= n_max) {
+          hi = kFltMax;
+          g0 = f0;
+          g1 = f1;
+          ch = cf;
+        } else {                                 // the cut falls among values equal to kFltMax: {v >= lo} \ {v >= hi} is that tie
+          lo = kFltMax;
+          t0 = f0;
+          t1 = f1;
+        }
+      }
       while (ch < n_max) {
         const float mid = lo + (hi - lo) * 0.5f;
         if (!(mid > lo) || !(mid < hi)) break;   // lo and hi are adjacent floats

@@ -408,7 +408,12 @@ int adanerf_sample_mlp(adanerf_ctx* ctx, int32_t first_ray, int32_t n_rays,
  *   d_ray_offsets  [n_rays] int32  exclusive prefix sum of counts (ray-major)
  *   d_ray_counts   [n_rays] int32  1..n_max
  *   d_sample_key   [>= n_rays*n_max] uint32  (local_ray << 7) | bin, ray-major, bins ascending
- *   d_sample_w     [>= n_rays*n_max] fp32    oracle value of the kept bin
+ *   d_sample_w     [>= n_rays*n_max] fp32    oracle value of the kept bin: the value the sampler ranked, i.e. AFTER the sigmoid
+ *                                            (losses[0] = BCEWithLogitsLoss) or the softmax over the bins (CrossEntropyLoss[Weighted])
+ *                                            of the context's model; the raw value of d_oracle under every other loss, and always
+ *                                            in the dense mode (thr == 0 ranks nothing).  Under the two transforming losses it never
+ *                                            reaches compositing: only NeRFWeightMultiplicationLoss multiplies by it (mult_mode is 0
+ *                                            otherwise).  The softmax's last bits depend on the selection kernel.
  *   d_total        [1] int32       S
  * thr == 0 selects the dense mode (all 128 bins; n_max must be 128). */
 int adanerf_compact(adanerf_ctx* ctx, const float* d_oracle, int32_t n_rays, int32_t n_max, float thr,

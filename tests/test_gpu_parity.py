@@ -523,7 +523,9 @@ def test_fused_selection_equals_separate_launches(cases, name, w, h, bs, samplin
     With ADANERF_FLAG_KEEP_ORACLE the oracle buffer is written and the same lane-pair code runs as its own launch;
     with ADANERF_FLAG_WAVE_SELECT the wave-per-ray kernel selects.  All three must agree bit for bit on every
     intermediate (counts, offsets, keys, kept oracle values) and on the image; the kept oracle buffer must be what
-    adanerf_sample_mlp returns."""
+    adanerf_sample_mlp returns.  "Bit for bit" is the contract of samplers WITHOUT a transform, which all of these cases are; what
+    the three forms owe each other under a sigmoid or a softmax (the two kernels sum the softmax in different orders) is stated and
+    tested in test_gpu_selection_transforms.py (test_fused_pair_and_wave_frames, test_pair_against_wave)."""
     z, meta, sc, wts, d = cases[name]
     res = []
     for kw in (dict(), dict(keep_oracle=True), dict(wave_select=True)):
