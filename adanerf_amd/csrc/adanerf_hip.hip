@@ -124,6 +124,7 @@ struct adanerf_ctx {
   FlipParams flip_params{};
   bool flip_lds_raised = false;      // flip_kernel may use more than 64 KB of dynamic LDS
   DevBuf reproj_zbuf, reproj_holes;  // adanerf_reproject: [width*height] uint64 z-buffer, the hole count; grown on demand
+  float px_dx = 0.f, px_dy = 0.f;    // adanerf_set_pixel_offset: kept here, not in ms.rg (calibrate_guard and adanerf_set_frame_size derive from / rewrite that)
   hipEvent_t peer_event = nullptr;   // adanerf_gather_to: orders the destination stream behind the copy
   uint64_t peer_tried = 0;           // bit d: peer access to device d has been requested once
 };
@@ -262,6 +263,11 @@ bool generic_split_sampling(const adanerf_ctx* c) {
   return c->generic0 && c->sampling_mode != ADANERF_SAMPLING_FP32 && c->ms.ray_samples == 0 && c->net0_split.w.p != nullptr;
 }
 
+// The ray generator in force: ms.rg with the sub-pixel offset applied to the pitch of the moment (model_setup.hpp with_pixel_offset).  What
+// the render path and the ray-generating stage entry points hand to their kernels; adanerf_reproject, adanerf_foveate,
+// adanerf_assemble_strips and the guard calibration read ms.rg itself.
+RayGenParams rg_in_force(const adanerf_ctx* c) { return with_pixel_offset(c->ms.rg, c->px_dx, c->px_dy); }
+
 bool has_budget_map(const adanerf_ctx* c) { return c->budget_n != nullptr || c->budget_thr != nullptr; }
 
 // sel != nullptr: the adaptive selection runs in the kernel's epilogue (k_select_pair.hip.hpp) and d_oracle may be null
@@ -272,7 +278,7 @@ int launch_sample_mlp(adanerf_ctx* c, int first_ray, int n_rays, float* d_oracle
     a.sel = *sel;
     a.fused_select = 1;
   }
-  a.g = c->ms.rg;
+  a.g = rg_in_force(c);
   a.net = c->net0.params;
   a.net16 = c->net0_split.params;
   a.overflow_flag = reinterpret_cast<int32_t*>(c->overflow.p);
@@ -473,6 +479,8 @@ int calibrate_guard(adanerf_ctx* c, int n_poses, uint32_t seed, bool install, fl
   constexpr int CW = 64, CH = 64, CR = CW * CH;
   const RayGenParams saved = c->ms.rg;
   const int saved_mode = c->sampling_mode;
+  const float saved_dx = c->px_dx, saved_dy = c->px_dy;      // its own 64 x 64 rays through pixel centres: the band must not depend on a jitter
+  c->px_dx = c->px_dy = 0.f;
   RayGenParams g = saved;
   // same field of view on a 64 x 64 image (setup_model's arithmetic): x_dist = tan(fov / 2) focal, y_dist = x_dist h / w
   const double x_dist = -saved.start_x + saved.x_pp / 2, y_dist = -saved.start_y + saved.y_pp / 2;
@@ -491,6 +499,8 @@ int calibrate_guard(adanerf_ctx* c, int n_poses, uint32_t seed, bool install, fl
     (void)hipStreamSynchronize(c->stream);      // before a_buf, b_buf and acc leave scope
     c->ms.rg = saved;
     c->sampling_mode = saved_mode;
+    c->px_dx = saved_dx;
+    c->px_dy = saved_dy;
     return code;
   };
   if ((rc = dev_alloc(c, &a_buf, static_cast<size_t>(CR) * kBins * sizeof(float)))) return done(rc);
@@ -700,7 +710,7 @@ int launch_sample_pdf(adanerf_ctx* c, const float* d_oracle, int n_rays, int n, 
 
 int launch_camera_rays(adanerf_ctx* c, int first_ray, int n_rays, float* d_rays) {
   if (n_rays <= 0) return ADANERF_OK;
-  hipLaunchKernelGGL(camera_rays_kernel, dim3((n_rays + 255) / 256), dim3(256), 0, c->stream, c->ms.rg, first_ray, n_rays, d_rays);
+  hipLaunchKernelGGL(camera_rays_kernel, dim3((n_rays + 255) / 256), dim3(256), 0, c->stream, rg_in_force(c), first_ray, n_rays, d_rays);
   HIP_RETURN(c, hipGetLastError());
 }
 
@@ -1028,6 +1038,65 @@ int adanerf_set_frame_size(adanerf_ctx* c, int32_t width, int32_t height) {
   return ADANERF_OK;
 }
 
+int adanerf_set_pixel_offset(adanerf_ctx* c, float dx, float dy) {
+  if (!c) return ADANERF_EINVAL;
+  if (!(std::fabs(dx) <= 1.f) || !(std::fabs(dy) <= 1.f))      // also a NaN
+    return fail(c, ADANERF_EINVAL, "adanerf_set_pixel_offset: dx and dy must be finite and within -1..1 (pixels)");
+  c->px_dx = dx;
+  c->px_dy = dy;
+  return ADANERF_OK;
+}
+
+int adanerf_get_pixel_offset(const adanerf_ctx* c, float out[2]) {
+  if (!c || !out) return ADANERF_EINVAL;
+  out[0] = c->px_dx;
+  out[1] = c->px_dy;
+  return ADANERF_OK;
+}
+
+namespace {
+
+// byte ranges [a, a + na) and [b, b + nb) share a byte
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+
+}  // namespace
+
+int adanerf_accumulate(adanerf_ctx* c, const float* d_rgb, int32_t n_rays, float* d_sum, int32_t first) {
+  if (!c) return ADANERF_EINVAL;
+  if (!d_rgb || !d_sum) return fail(c, ADANERF_EINVAL, "adanerf_accumulate: NULL image");
+  if (n_rays < 0 || n_rays > 0x7fffffff / 3) return fail(c, ADANERF_EINVAL, "adanerf_accumulate: n_rays must be >= 0 and n_rays * 3 <= 2^31 - 1");
+  if ((reinterpret_cast<uintptr_t>(d_rgb) | reinterpret_cast<uintptr_t>(d_sum)) & 3) return fail(c, ADANERF_EINVAL, "adanerf_accumulate: images must be 4-byte aligned");
+  const size_t bytes = static_cast<size_t>(n_rays) * 3 * sizeof(float);
+  if (d_rgb != d_sum && ranges_overlap(d_rgb, bytes, d_sum, bytes)) return fail(c, ADANERF_EINVAL, "adanerf_accumulate: frame and sum overlap without being the same image");
+  BIND(c);
+  if (n_rays == 0) return ADANERF_OK;
+  const int n = n_rays * 3;
+  const int grid = std::min((n + 255) / 256, 65536);      // grid-stride beyond 2^24 values
+  hipLaunchKernelGGL(accumulate_kernel, dim3(grid), dim3(256), 0, c->stream, d_rgb, d_sum, n, first != 0 ? 1 : 0);
+  HIP_RETURN(c, hipGetLastError());
+}
+
+int adanerf_resolve_mean(adanerf_ctx* c, const float* d_sum, int32_t n_rays, int32_t frames, void* d_rgba8, float* d_rgb) {
+  if (!c) return ADANERF_EINVAL;
+  if (!d_sum || (!d_rgba8 && !d_rgb)) return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean: NULL sum, or both outputs NULL");
+  if (n_rays < 0 || n_rays > 0x7fffffff / 3) return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean: n_rays must be >= 0 and n_rays * 3 <= 2^31 - 1");
+  if (frames < 1 || frames > 65536) return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean: frames must be in 1..65536");
+  if ((reinterpret_cast<uintptr_t>(d_sum) | reinterpret_cast<uintptr_t>(d_rgba8) | reinterpret_cast<uintptr_t>(d_rgb)) & 3)
+    return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean: images must be 4-byte aligned");
+  const size_t bytes = static_cast<size_t>(n_rays) * 3 * sizeof(float), bytes8 = static_cast<size_t>(n_rays) * 4;
+  if ((d_rgb && d_rgb != d_sum && ranges_overlap(d_sum, bytes, d_rgb, bytes)) ||
+      (d_rgba8 && (ranges_overlap(d_sum, bytes, d_rgba8, bytes8) || (d_rgb && ranges_overlap(d_rgb, bytes, d_rgba8, bytes8)))))
+    return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean: images overlap (only d_rgb_f32_out may be d_sum itself)");
+  BIND(c);
+  if (n_rays == 0) return ADANERF_OK;
+  hipLaunchKernelGGL(resolve_mean_kernel, dim3((n_rays + 255) / 256), dim3(256), 0, c->stream, d_sum, n_rays, static_cast<float>(frames), d_rgb,
+                     static_cast<uchar4*>(d_rgba8));
+  HIP_RETURN(c, hipGetLastError());
+}
+
 int adanerf_present(adanerf_ctx* c, const void* d_src_rgba8, int32_t src_w, int32_t src_h, void* d_dst_rgba8, int32_t dst_w, int32_t dst_h,
                     int32_t flags) {
   if (!c) return ADANERF_EINVAL;
@@ -1035,14 +1104,23 @@ int adanerf_present(adanerf_ctx* c, const void* d_src_rgba8, int32_t src_w, int3
   if (src_w < 1 || src_h < 1 || dst_w < 1 || dst_h < 1 || src_w > kPresentMaxSide || src_h > kPresentMaxSide || dst_w > kPresentMaxSide ||
       dst_h > kPresentMaxSide)
     return fail(c, ADANERF_EINVAL, "adanerf_present: every side must be in 1.." + std::to_string(kPresentMaxSide));
-  constexpr int32_t kFilters = ADANERF_PRESENT_NEAREST | ADANERF_PRESENT_LINEAR;
-  if ((flags & ~(ADANERF_PRESENT_FLIP_Y | kFilters)) || (flags & kFilters) == kFilters)
-    return fail(c, ADANERF_EINVAL, "adanerf_present: flags must be ADANERF_PRESENT_FLIP_Y with at most one of _NEAREST / _LINEAR");
+  constexpr int32_t kFilters = ADANERF_PRESENT_NEAREST | ADANERF_PRESENT_LINEAR | ADANERF_PRESENT_AREA;
+  if ((flags & ~(ADANERF_PRESENT_FLIP_Y | kFilters)) || ((flags & kFilters) & ((flags & kFilters) - 1)))
+    return fail(c, ADANERF_EINVAL, "adanerf_present: flags must be ADANERF_PRESENT_FLIP_Y with at most one of _NEAREST / _LINEAR / _AREA");
+  const bool area = (flags & ADANERF_PRESENT_AREA) != 0;
+  if (area && (src_w > 8 * dst_w || src_h > 8 * dst_h))      // bounds the kernel's loop at 9 taps per axis
+    return fail(c, ADANERF_EINVAL, "adanerf_present: ADANERF_PRESENT_AREA reduces by at most 8 per axis (reduce in two steps)");
   const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src_rgba8), d0 = reinterpret_cast<uintptr_t>(d_dst_rgba8);
   const uintptr_t s1 = s0 + static_cast<size_t>(src_w) * src_h * 4, d1 = d0 + static_cast<size_t>(dst_w) * dst_h * 4;
   if ((s0 | d0) & 3) return fail(c, ADANERF_EINVAL, "adanerf_present: images must be 4-byte aligned (uchar4)");
   if (s0 < d1 && d0 < s1) return fail(c, ADANERF_EINVAL, "adanerf_present: source and destination overlap");
   BIND(c);
+  if (area) {
+    const uint64_t den_a = 2ull * static_cast<uint64_t>(src_w) * static_cast<uint64_t>(src_h);      // 2 S
+    hipLaunchKernelGGL(present_area_kernel, dim3((dst_w * dst_h + 255) / 256), dim3(256), 0, c->stream, static_cast<const uchar4*>(d_src_rgba8),
+                       static_cast<uchar4*>(d_dst_rgba8), src_w, src_h, dst_w, dst_h, (flags & ADANERF_PRESENT_FLIP_Y) ? 1 : 0, den_a, ~0ull / den_a);
+    HIP_RETURN(c, hipGetLastError());
+  }
   const bool linear = (flags & kFilters) ? (flags & ADANERF_PRESENT_LINEAR) != 0 : dst_w > src_w;      // the reference's rule
   const uint64_t den = 8ull * static_cast<uint64_t>(dst_w) * static_cast<uint64_t>(dst_h);               // 2 D E
   const int threads = (1 + (dst_w + 3) / 4) * dst_h;
@@ -1114,7 +1192,7 @@ int adanerf_ray_features(adanerf_ctx* c, int32_t first_ray, int32_t n_rays, floa
   dim3 grid((n_rays + 255) / 256), block(256);
   const float* rz = reinterpret_cast<const float*>(c->rsi_z.p);
   const float d1 = c->ms.cfg.depthRange[1];
-  hipLaunchKernelGGL(ray_features_kernel, grid, block, 0, c->stream, c->ms.rg, first_ray, n_rays, d_feat, d_rays, c->ms.ray_samples, rz, d1, c->ms.fp0, c->ms.fd0);
+  hipLaunchKernelGGL(ray_features_kernel, grid, block, 0, c->stream, rg_in_force(c), first_ray, n_rays, d_feat, d_rays, c->ms.ray_samples, rz, d1, c->ms.fp0, c->ms.fd0);
   HIP_RETURN(c, hipGetLastError());
 }
 

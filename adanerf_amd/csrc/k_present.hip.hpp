@@ -95,4 +95,43 @@ __global__ __launch_bounds__(256) void present_kernel(const uchar4* __restrict__
   }
 }
 
+// ADANERF_PRESENT_AREA: the exact area (box) filter for any pair of sizes, per axis in units of 1 / dst of a source pixel.  Destination
+// pixel x covers [x s, (x + 1) s), source pixel i covers [i d, (i + 1) d); the weight is the overlap, the contributing i run from
+// floor(x s / d) to floor(((x + 1) s - 1) / d) and their weights sum to s.  Per channel V = sum_j sum_i wy wx v <= 255 S, S = src_w src_h
+// <= 2^28, out = floor((2 V + S) / (2 S)): half up.  den = 2 S and magic as in present_channel (2 V + S < 2^38).  The host admits
+// src <= 8 dst per axis: at most 9 taps.  A thread per destination pixel, one 4-byte store each, consecutive threads consecutive pixels.
+__global__ __launch_bounds__(256) void present_area_kernel(const uchar4* __restrict__ src, uchar4* __restrict__ dst, int src_w, int src_h,
+                                                           int dst_w, int dst_h, int flip, uint64_t den, uint64_t magic) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;      // dst_w * dst_h <= 2^28
+  const int y = t / dst_w, x = t - y * dst_w;
+  if (y >= dst_h) return;
+  const int xa = x * src_w, xb = xa + src_w, ya = y * src_h, yb = ya + src_h;      // < 2^28 + 2^14
+  const int i0 = xa / dst_w, i1 = (xb - 1) / dst_w, j0 = ya / dst_h, j1 = (yb - 1) / dst_h;
+  uint64_t v[4] = {0, 0, 0, 0};
+  for (int j = j0; j <= j1; ++j) {
+    const uint32_t wy = static_cast<uint32_t>(min((j + 1) * dst_h, yb) - max(j * dst_h, ya));
+    const uchar4* row = src + static_cast<size_t>(j) * src_w;
+    uint32_t r[4] = {0, 0, 0, 0};      // sum_i wx v <= 255 src_w < 2^22
+    for (int i = i0; i <= i1; ++i) {
+      const uint32_t wx = static_cast<uint32_t>(min((i + 1) * dst_w, xb) - max(i * dst_w, xa));
+      const uchar4 p = row[i];
+      r[0] += wx * p.x;
+      r[1] += wx * p.y;
+      r[2] += wx * p.z;
+      r[3] += wx * p.w;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] += static_cast<uint64_t>(wy) * r[k];
+  }
+  unsigned char o[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const uint64_t num = 2 * v[k] + (den >> 1);
+    uint32_t q = static_cast<uint32_t>(__umul64hi(num, magic));
+    if (num - q * den >= den) ++q;
+    o[k] = static_cast<unsigned char>(q);
+  }
+  dst[static_cast<size_t>(flip ? dst_h - 1 - y : y) * dst_w + x] = make_uchar4(o[0], o[1], o[2], o[3]);
+}
+
 }  // namespace adanerf

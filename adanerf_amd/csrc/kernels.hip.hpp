@@ -6,8 +6,9 @@
 //   A5+A6     shade_mlp16_kernel / shade_mlp32_kernel   fused PE + 8x256 shading MLP (bf16/f16/f32 MFMA)
 //   A7        composite_kernel       sigmoid + alpha * oracle weight, front-to-back
 //   N1        flip_kernel / flip_mean_kernel   FLIP error map and mean of an image pair (the evaluator's second metric)
-//   N3        present_kernel         the frame at the window's size (the viewer's blit: linear / nearest, y flip)
+//   N3        present_kernel / present_area_kernel   the frame at the window's size (the viewer's blit: linear / nearest, y flip; exact area filter)
 //   N4        reproject_clear_kernel / reproject_splat_kernel / reproject_resolve_kernel   a rendered frame warped to another pose by its depth
+//   N5        accumulate_kernel / resolve_mean_kernel   sum and mean of several sub-pixel frames (supersampling in time)
 // plus explicit-feature debug kernels (ray_features_kernel, shade_features_kernel) that materialise
 // what the reference launchers wrote to memory, for parity tests only.
 // The code lives in one header per stage; this file includes them all.
@@ -25,3 +26,4 @@
 #include "k_present.hip.hpp"
 #include "k_budget.hip.hpp"
 #include "k_reproject.hip.hpp"
+#include "k_accumulate.hip.hpp"

@@ -283,6 +283,20 @@ int frame_geometry(ModelSetup* ms, const adanerf_options* opt, int w, int h, std
   return ADANERF_OK;
 }
 
+RayGenParams with_pixel_offset(const RayGenParams& g, float dx, float dy) {
+  RayGenParams out = g;
+  // the product goes through a volatile: two rounded operations on every compiler setting, never one fused multiply-add
+  if (dx != 0.f) {
+    volatile double m = g.x_pp * static_cast<double>(dx);
+    out.start_x = g.start_x + m;
+  }
+  if (dy != 0.f) {
+    volatile double m = g.y_pp * static_cast<double>(dy);
+    out.start_y = g.start_y + m;
+  }
+  return out;
+}
+
 void depth_table(const ModelSetup& ms, bool dense, float* ztab128) {
   const Config& cf = ms.cfg;
   const float znear = cf.zNear.empty() ? 0.001f : cf.zNear.back();
@@ -389,6 +403,14 @@ int adanerf_host_parse_model(const char* model_dir, const adanerf_options* opt, 
   int rc = setup_model(model_dir, opt, &ms, &err);
   if (rc) return fail(rc, err);
   *info = ms.info;
+  return ADANERF_OK;
+}
+
+int adanerf_host_subpixel_grid(int32_t s, int32_t k, float* dx, float* dy) {
+  if (s < 1 || s > 8 || k < 0 || k >= s * s || !dx || !dy) return fail(ADANERF_EINVAL, "adanerf_host_subpixel_grid: s must be in 1..8, k in 0..s*s-1, outputs non-NULL");
+  const int i = k % s, j = k / s;
+  *dx = static_cast<float>((2.0 * i + 1.0 - s) / (2.0 * s));
+  *dy = static_cast<float>((2.0 * j + 1.0 - s) / (2.0 * s));
   return ADANERF_OK;
 }
 

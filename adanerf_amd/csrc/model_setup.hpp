@@ -77,6 +77,10 @@ int select_samples(ModelSetup* ms, int32_t num_samples, float threshold, std::st
 // camera and the view cell in rg stay.  batch_rays comes from opt->batch_rays, the value the caller asked for, never from the clamped
 // info.batch_rays.  On failure *ms is unchanged.  Needs ms->cfg.
 int frame_geometry(ModelSetup* ms, const adanerf_options* opt, int w, int h, std::string* err);
+// The ray generator with a sub-pixel offset in force (adanerf_set_pixel_offset): start_x + x_pp * (double)dx, start_y + y_pp * (double)dy,
+// each a rounded float64 multiply followed by a rounded float64 add (never fused); a component equal to 0 leaves that start value's bits
+// untouched.  The kernels' gen_ray keeps computing start + pp * col.
+RayGenParams with_pixel_offset(const RayGenParams& g, float dx, float dy);
 // world depth of each of the 128 bins: the sampler's cell centres, or (dense) the dense mode's uniform t-values
 void depth_table(const ModelSetup& ms, bool dense, float* ztab128);
 

@@ -6,7 +6,7 @@ reference's second default metric (``metrics = ["flip", "psnr"]`` :613-615): the
 
     python -m adanerf_amd.evaluate <model_dir> <dataset_dir> [--set test] [--out DIR] [--video out.y4m] [--precision bf16]
                                    [--metrics psnr flip] [--sweep-thresholds T ...] [--sweep-samples N ...] [--sweep-scales S ...]
-                                   [--reproject-stride K]
+                                   [--reproject-stride K] [--supersample S] [--present-filter nearest|linear|area]
 
 ``--sweep-thresholds`` / ``--sweep-samples`` render the set once per (N, threshold) of their cross product on ONE context
 (``NeuralRenderer.set_selection``: an AdaNeRF network is trained once and rendered at any sample budget) -- the two axes of a quality
@@ -18,6 +18,11 @@ dataset's ``w x h`` on the GPU (``adanerf_present``, the viewer's blit) and scor
 ``--reproject-stride K`` renders the poses with ``i % K == 0`` and warps the others from the nearest rendered pose before them
 (``adanerf_reproject``, holes filled from their neighbours): what a host that renders every K-th frame shows in between, scored against
 the same ground truth.
+
+``--supersample S`` makes every image the mean of S x S renders at the sub-pixel offsets of ``adanerf_host_subpixel_grid``, accumulated
+and resolved on the GPU (``NeuralRenderer.render_supersampled``) and scored from the fp32 mean: anti-aliasing in time, against the
+dataset's anti-aliased ground truth.  ``--present-filter area`` makes the ``--sweep-scales`` presentation an exact area filter
+(``ADANERF_PRESENT_AREA``): the only sensible choice for scales above 1, where the default rule decimates.
 
 Dataset layout (src/datasets.py:146-213, 361-365, 480-542): ``dataset_info.json`` (``resolution``,
 ``camera_angle_x``, ``view_cell_center``, ``view_cell_size`` ...), ``transforms_<set>.json`` with
@@ -35,7 +40,7 @@ from typing import List, Optional
 import numpy as np
 
 from .png import read_png, write_png
-from .renderer import NeuralRenderer, Settings, parse_fovea
+from .renderer import PRESENT_FILTERS, SUPERSAMPLE_MAX, NeuralRenderer, Settings, parse_fovea
 
 
 def load_dataset(dataset_dir: str, set_name: str = "test"):
@@ -95,7 +100,7 @@ def scaled_size(w: int, h: int, scale: float):
 def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: Optional[str] = None,
              precision: str = "bf16", batch_size: int = -1, max_frames: int = 0, quiet: bool = False,
              video: Optional[str] = None, fps: int = 30, metrics=("psnr",), fovea=None, sweep_thresholds=None, sweep_samples=None, reproject_stride=None,
-             sweep_scales=None):
+             supersample=None, present_filter=None, sweep_scales=None):
     """metrics: "psnr" (always reported where a ground-truth image exists) and / or "flip": each record gains ``flip``, the summary
     ``mean_flip``, and with out_dir the error map is written as an 8-bit greyscale ``%05d_flip.png``.
 
@@ -115,6 +120,13 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     ``mean_psnr_rendered``, ``mean_psnr_warped``, ``mean_hole_fraction`` and, with "flip", ``mean_flip_rendered`` / ``mean_flip_warped``;
     mean_samples_per_ray / mean_ms are those of the rendered frames.  At the dataset's resolution only (not with sweep_scales).
 
+    supersample (S in 1..8 or None): every image is the mean of S x S renders at the offsets of the regular sub-pixel grid
+    (NeuralRenderer.render_supersampled), scored from the fp32 mean; ms is the sum over the S x S renders, samples_per_ray is per rendered
+    frame; records and summary carry ``supersample``.  Not together with reproject_stride (the mean has no depth map to warp by).
+
+    present_filter (None, "nearest", "linear" or "area"): the filter of the sweep_scales presentation (NeuralRenderer.present); None is the
+    viewer's rule, which decimates a frame rendered above the dataset's size -- "area" averages it.
+
     fovea (``R:N:T[,R:N:T...],N:T`` or what renderer.parse_fovea makes of it, or None): every frame is rendered with per-ray budgets around a
     gaze at the centre of the rendered frame (radii in its pixels).  Records and summary keep their shape: PSNR / FLIP / samples per ray are
     those of the foveated frames -- the quality-against-cost table of a foveation setting."""
@@ -130,6 +142,13 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
         raise ValueError("reproject_stride must be >= 1, got %s" % (reproject_stride,))
     if stride and sweep_scales:
         raise ValueError("reproject_stride warps at the dataset's resolution: not together with sweep_scales")
+    ss = int(supersample) if supersample is not None else 0
+    if supersample is not None and not 1 <= ss <= SUPERSAMPLE_MAX:
+        raise ValueError("supersample must be in 1..%d, got %s" % (SUPERSAMPLE_MAX, supersample))
+    if ss and stride:
+        raise ValueError("supersample averages jittered frames, which have no single depth map to warp by: not together with reproject_stride")
+    if present_filter not in PRESENT_FILTERS:
+        raise ValueError("present_filter must be None, 'nearest', 'linear' or 'area', got %r" % (present_filter,))
     want_flip = "flip" in metrics
     meta, frames = load_dataset(dataset_dir, set_name)
     if max_frames > 0:
@@ -163,13 +182,15 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                     rec = dict(extra, frame=i, image=fr["image"], warped=True, hole_fraction=holes / float(w * h))
                 else:
                     r.set_camera(fr["pose"], fr["rot"])
-                    rgb, rgba, st = r.render_numpy()
+                    rgb, rgba, st = r.render_supersampled(ss) if ss else r.render_numpy()
                     if scale is not None:      # the frame as a w x h window shows it, filtered on the device
-                        rgba = r.present(w, h).reshape(-1, 4)
+                        rgba = r.present(w, h, filter=present_filter).reshape(-1, 4)
                         rgb = rgba[:, :3].astype(np.float32) / 255.0
                     rec = dict(extra, frame=i, image=fr["image"], samples_per_ray=st.total_samples / float(rw * rh), ms=st.ms_total)
                     if stride:
                         rec.update(warped=False)
+                    if ss:
+                        rec.update(supersample=ss)
                 if os.path.exists(fr["image"]):
                     gt = read_png(fr["image"])
                     if gt.shape[0] != h or gt.shape[1] != w:
@@ -202,15 +223,15 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                     r.set_frame_size(*scaled_size(w, h, sc))
                     key["scale"] = float(sc)
                 recs = render_set(os.path.join(out_dir, sweep_dir_name(**key)) if out_dir else None, key, sc)
-                sweep.append(dict(key, **{k: v for k, v in summarise(recs, want_flip).items() if k != "frames"}))
+                sweep.append(dict(key, **{k: v for k, v in summarise(recs, want_flip).items() if k != "frames"}, **(dict(supersample=ss) if ss else {})))
                 results.extend(recs)
         else:
             results = render_set(out_dir, {})
         if vid:
             vid.close()
     if sweep:
-        return dict(frames=len(frames), sweep=sweep), results
-    return summarise(results, want_flip), results
+        return dict(frames=len(frames), sweep=sweep, **(dict(supersample=ss) if ss else {})), results
+    return dict(summarise(results, want_flip), **(dict(supersample=ss) if ss else {})), results
 
 
 def summarise(results: List[dict], want_flip: bool) -> dict:
@@ -256,6 +277,12 @@ def build_parser():
     ap.add_argument("--reproject-stride", type=int, default=None, metavar="K",
                     help="render the poses with i %% K == 0 and warp the others from the nearest rendered pose before them (adanerf_reproject); "
                          "the summary gains mean_psnr_rendered / mean_psnr_warped / mean_hole_fraction (and mean_flip_* with --metrics flip)")
+    ap.add_argument("--supersample", type=int, default=None, choices=range(1, SUPERSAMPLE_MAX + 1), metavar="S",
+                    help="every image is the mean of S x S renders (S in 1..8) at the offsets of the regular sub-pixel grid, accumulated on the GPU "
+                         "and scored from the fp32 mean; records and summary gain `supersample`; not together with --reproject-stride")
+    ap.add_argument("--present-filter", default=None, choices=["nearest", "linear", "area"],
+                    help="filter of the --sweep-scales presentation (default: the viewer's rule, linear when enlarging, else nearest); area is "
+                         "the exact area filter and the only sensible choice for scales above 1, where nearest throws the extra rays away")
     ap.add_argument("--fovea", type=parse_fovea, default=None, metavar="R:N:T[,R:N:T...],N:T",
                     help="per-ray sample budgets around a gaze at the image centre: rings (radius px : N : threshold), then the entry outside "
                          "them; PSNR / FLIP / samples per ray are then those of the foveated frames")
@@ -263,10 +290,13 @@ def build_parser():
 
 
 def main(argv=None):
-    a = build_parser().parse_args(argv)
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    if a.supersample is not None and a.reproject_stride is not None:
+        ap.error("--supersample cannot be combined with --reproject-stride")
     summary, _ = evaluate(a.model_dir, a.dataset_dir, a.set, a.out, a.precision, a.batch_size, a.max_frames, video=a.video, fps=a.fps,
                           metrics=tuple(a.metrics), sweep_thresholds=a.sweep_thresholds, sweep_samples=a.sweep_samples, sweep_scales=a.sweep_scales,
-                          fovea=a.fovea, reproject_stride=a.reproject_stride)
+                          fovea=a.fovea, reproject_stride=a.reproject_stride, supersample=a.supersample, present_filter=a.present_filter)
     print(json.dumps(summary))
 
 

@@ -23,7 +23,7 @@ NeuralRenderer::~NeuralRenderer() {
   if (ctx) {
     if (d_gathered) adanerf_free(ctx, d_gathered);
     if (d_frame) adanerf_free(ctx, d_frame);
-    for (void* p : {d_depth, d_acc, d_warp})
+    for (void* p : {d_depth, d_acc, d_warp, d_rgb, d_sum})
       if (p) adanerf_free(ctx, p);
     if (d_window) adanerf_free(ctx, d_window);
     adanerf_destroy(ctx);
@@ -151,6 +151,12 @@ bool NeuralRenderer::init() {
   adanerf_get_info(ctx, &info_);
   world_ = world;
   strip_rows_ = strip_rows;
+  if (settings.supersample > 1 && (world > 1 || settings.render_oracle || settings.reproject > 1)) {
+    err = world > 1 ? "--supersample accumulates whole frames of one context; use it with --gpus 1"
+                    : (settings.render_oracle ? "--supersample averages rendered frames; not with --oracle"
+                                              : "--supersample: the mean of jittered frames has no depth map to warp by; not with --reproject");
+    return false;
+  }
   if (settings.reproject > 1 && (world > 1 || info_.use_ndc)) {
     err = world > 1 ? "--reproject warps whole frames of one context; use it with --gpus 1" : "--reproject: the depth of a useNDC model is NDC depth";
     return false;
@@ -179,6 +185,13 @@ bool NeuralRenderer::allocFrameBuffers() {
     return false;
   }
   d_shown = d_frame;
+  if (settings.supersample > 1) {
+    for (void** p : {&d_rgb, &d_sum}) {
+      if (*p && adanerf_free(ctx, *p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+      *p = nullptr;
+      if (adanerf_malloc(ctx, static_cast<size_t>(info_.width) * info_.height * 3 * sizeof(float), p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+    }
+  }
   if (settings.reproject > 1) {      // the aux outputs belong to the frame size: the library drops them when rays_local changes
     const size_t n = static_cast<size_t>(info_.width) * info_.height;
     have_source = false;
@@ -347,8 +360,8 @@ bool NeuralRenderer::render() {
     }
     return writeImageToFile();
   }
-  if (adanerf_render(ctx, d_frame, nullptr, &st) != ADANERF_OK) {
-    err = adanerf_last_error(ctx);
+  if (settings.supersample > 1 ? !renderSupersampled(&st) : adanerf_render(ctx, d_frame, nullptr, &st) != ADANERF_OK) {
+    if (settings.supersample <= 1) err = adanerf_last_error(ctx);
     return false;
   }
   if (st.guard_widened > guard_widened_seen) {      // the guarded selection's monitor saw its band violated and widened it (adanerf_hip.h)
@@ -379,6 +392,40 @@ bool NeuralRenderer::render() {
   return writeImageToFile();
 }
 
+// --supersample S: S x S renders of this frame's camera at the offsets of the regular sub-pixel grid, summed on the device; d_frame gets
+// the mean under the viewer's output contract.  The offset goes back to (0, 0).
+bool NeuralRenderer::renderSupersampled(adanerf_stats* st) {
+  const int S = settings.supersample, renders = S * S, n = info_.width * info_.height;
+  bool ok = true;
+  for (int k = 0; ok && k < renders; ++k) {
+    float dx = 0.f, dy = 0.f;
+    adanerf_stats sk;
+    std::memset(&sk, 0, sizeof(sk));
+    ok = adanerf_host_subpixel_grid(S, k, &dx, &dy) == ADANERF_OK && adanerf_set_pixel_offset(ctx, dx, dy) == ADANERF_OK &&
+         adanerf_render(ctx, nullptr, static_cast<float*>(d_rgb), &sk) == ADANERF_OK &&
+         adanerf_accumulate(ctx, static_cast<const float*>(d_rgb), n, static_cast<float*>(d_sum), k == 0) == ADANERF_OK;
+    const int64_t samples = st->total_samples + sk.total_samples;
+    const float ms[5] = {st->ms_total + sk.ms_total, st->ms_sample_mlp + sk.ms_sample_mlp, st->ms_compact + sk.ms_compact, st->ms_shade_mlp + sk.ms_shade_mlp,
+                         st->ms_composite + sk.ms_composite};
+    *st = sk;      // the counters "since create" of the last render
+    st->total_samples = samples;
+    st->ms_total = ms[0];
+    st->ms_sample_mlp = ms[1];
+    st->ms_compact = ms[2];
+    st->ms_shade_mlp = ms[3];
+    st->ms_composite = ms[4];
+  }
+  if (!ok) err = adanerf_last_error(ctx);      // before the offset goes back: that call succeeds and would not touch the message anyway
+  const bool back = adanerf_set_pixel_offset(ctx, 0.f, 0.f) == ADANERF_OK;
+  if (!ok) return false;
+  st->total_samples /= renders;      // per rendered frame, as the log's "avg samples ppx" counts
+  if (!back || adanerf_resolve_mean(ctx, static_cast<const float*>(d_sum), n, renders, d_frame, nullptr) != ADANERF_OK || adanerf_sync(ctx) != ADANERF_OK) {
+    err = adanerf_last_error(ctx);
+    return false;
+  }
+  return true;
+}
+
 // --reproject K: the last rendered frame at this frame's camera (adanerf_reproject, holes filled from their neighbours, the rest black)
 bool NeuralRenderer::warp(const float rot[9]) {
   int32_t holes = 0;
@@ -407,6 +454,7 @@ void NeuralRenderer::logInterval() {
             << " (total: " << s_num_total_samples / rendered << ")"
             << ", N: " << info_.num_samples << ", thr: " << info_.threshold << ", size: " << info_.width << "x" << info_.height
             << ", frames: " << sample_count << ", frame ms: " << s_total / rendered;
+  if (settings.supersample > 1) std::cout << ", renders per frame: " << settings.supersample * settings.supersample;
   if (settings.reproject > 1) std::cout << ", holes: " << s_holes / static_cast<double>(std::max(s_warped, 1)) << " (" << s_warped << " warped frames)";
   std::cout << std::endl;
   s_inference1 = s_inference2 = s_fc2 = s_rm = s_total = 0;
@@ -422,7 +470,10 @@ bool NeuralRenderer::writeImageToFile() {
   if (settings.write_images && !writeBmp("out.bmp", shown, static_cast<int>(settings.width), static_cast<int>(settings.height))) return false;
   if (!settings.write_window) return true;
   const int ww = static_cast<int>(settings.window_width), wh = static_cast<int>(settings.window_height);
-  if (adanerf_present(ctx, shown, static_cast<int>(settings.width), static_cast<int>(settings.height), d_window, ww, wh, 0) != ADANERF_OK) {
+  const int filter = settings.present_filter == "area" ? ADANERF_PRESENT_AREA
+                                                       : (settings.present_filter == "linear" ? ADANERF_PRESENT_LINEAR
+                                                                                              : (settings.present_filter == "nearest" ? ADANERF_PRESENT_NEAREST : 0));
+  if (adanerf_present(ctx, shown, static_cast<int>(settings.width), static_cast<int>(settings.height), d_window, ww, wh, filter) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;
   }

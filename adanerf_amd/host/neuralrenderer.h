@@ -80,6 +80,10 @@ class NeuralRenderer {
   void logInterval();                // the per-100-frame line of the single-context path
   long long s_holes = 0;             // holes of the warped frames / rendered and warped frames of the running interval
   int s_rendered = 0, s_warped = 0;
+  // --supersample S > 1: the fp32 frame of one sub-pixel render and the running sum of a shown frame's S x S renders, float [h*w*3] each
+  void* d_rgb = nullptr;
+  void* d_sum = nullptr;
+  bool renderSupersampled(adanerf_stats* st);   // S x S renders at the grid's offsets, accumulated and resolved into d_frame; *st: times summed, samples per render
   void* d_window = nullptr;          // --write-window: uchar4 [window_height*window_width], the frame as adanerf_present shows it
   int world_ = 1, strip_rows_ = 8;   // share layout chosen at init; a live context keeps its strip height
   bool allocFrameBuffers();          // d_frame, d_gathered, d_payload for the size in info_ (again after a size change)

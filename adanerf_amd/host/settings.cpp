@@ -21,6 +21,10 @@ const char* Settings::usage() {
          "                                                              gaze <X> <Y>: the --fovea gaze point, in pixels)\n"
          "               [--reproject K]      of every K frames render the first and warp it to the camera of the next K - 1 (depth\n"
          "                                    reprojection, holes filled from their neighbours); -w / --write-window write what was shown\n"
+         "               [--supersample S]    every shown frame is S x S renders (S in 1..8) at the offsets of a regular sub-pixel grid, summed and\n"
+         "                                    averaged on the device (anti-aliasing in time); -w / --write-window write the resolved image\n"
+         "               [--present-filter nearest|linear|area]     filter of the -ws window image; default: linear if the window is wider than\n"
+         "                                    the frame, else nearest (the viewer's blit); area: exact area filter, for a frame rendered larger\n"
          "               [--gpus N] [--same-device] [--sub-shares P]\n";
 }
 
@@ -145,6 +149,22 @@ bool Settings::init(int argc, char** argv, std::string* err) {
         return false;
       }
       reproject = static_cast<int>(k);
+    } else if (a == "--supersample") {
+      if (!need(i, 1)) return false;
+      char* end = nullptr;
+      const long k = std::strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end != 0 || k < 1 || k > 8) {
+        *err = "--supersample S: S must be an integer in 1..8";
+        return false;
+      }
+      supersample = static_cast<int>(k);
+    } else if (a == "--present-filter") {
+      if (!need(i, 1)) return false;
+      present_filter = argv[++i];
+      if (present_filter != "nearest" && present_filter != "linear" && present_filter != "area") {
+        *err = "--present-filter must be nearest, linear or area";
+        return false;
+      }
     } else if (a == "--oracle") {
       render_oracle = true;
     } else if (a == "--script") {

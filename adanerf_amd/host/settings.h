@@ -39,6 +39,9 @@ class Settings {
   static bool parseFovea(const std::string& spec, std::vector<int>* radius, std::vector<int>* n, std::vector<float>* thr, std::string* err);
   int reproject = 1;            // --reproject K: of every K frames the first is rendered, the next K - 1 are that frame warped to their own camera
                                 // (adanerf_reproject, fill on); 1: every frame is rendered
+  int supersample = 1;          // --supersample S (1..8): every shown frame is S x S renders at the offsets of adanerf_host_subpixel_grid, accumulated and
+                                // resolved on the device (adanerf_set_pixel_offset / adanerf_accumulate / adanerf_resolve_mean); 1: one render per frame
+  std::string present_filter;   // --present-filter nearest|linear|area: filter of the -ws window image (adanerf_present); empty: the viewer's rule
   bool render_oracle = false;   // --oracle: the viewer's 'O' key (inputhandler.cpp:76), sampling-network debug view
 
   // returns false and fills err on a malformed command line

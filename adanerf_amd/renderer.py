@@ -24,8 +24,9 @@ _PREC = {"bf16": PREC_BF16, "fp16": PREC_FP16, "f16": PREC_FP16, "fp32": PREC_FP
 BUF_RAYS, BUF_ORACLE, BUF_RAY_OFFSETS, BUF_RAY_COUNTS, BUF_SAMPLE_KEY, BUF_SAMPLE_W, BUF_RAW, BUF_TOTAL, BUF_SAMPLE_Z, BUF_RAW_COARSE = range(10)
 SAMPLER_ADAPTIVE, SAMPLER_PDF, SAMPLER_COARSE_FINE = 0, 1, 2
 FLAG_KEEP_ORACLE, FLAG_WAVE_SELECT, FLAG_NO_GUARD_CACHE, FLAG_GUARD_AUDIT_FILL = 1, 2, 4, 8
-PRESENT_FLIP_Y, PRESENT_NEAREST, PRESENT_LINEAR = 1, 2, 4      # adanerf_present flags
-PRESENT_FILTERS = {None: 0, "nearest": PRESENT_NEAREST, "linear": PRESENT_LINEAR}
+PRESENT_FLIP_Y, PRESENT_NEAREST, PRESENT_LINEAR, PRESENT_AREA = 1, 2, 4, 8      # adanerf_present flags
+PRESENT_FILTERS = {None: 0, "nearest": PRESENT_NEAREST, "linear": PRESENT_LINEAR, "area": PRESENT_AREA}
+SUPERSAMPLE_MAX = 8                                            # adanerf_host_subpixel_grid: s in 1..8
 REPROJECT_FILL = 1                                             # adanerf_reproject flag
 ABI_VERSION = 4
 GUARD_FROM = {0: "none", 1: "options", 2: "record", 3: "calibration", 4: "monitor"}
@@ -74,7 +75,8 @@ EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_las
            "adanerf_compact", "adanerf_compact_guarded", "adanerf_calibrate_guard", "adanerf_guard_calibration_file", "adanerf_shade_features", "adanerf_shade_mlp", "adanerf_shade_mlp_z", "adanerf_sample_pdf", "adanerf_sample_uniform", "adanerf_shade_mlp_coarse", "adanerf_sample_from_coarse",
            "adanerf_composite", "adanerf_composite_classic", "adanerf_composite_aux", "adanerf_composite_classic_aux", "adanerf_disp_map", "adanerf_copy_result_sampling_network", "adanerf_flip",
            "adanerf_render_oracle", "adanerf_gather_to", "adanerf_probe_mfma", "adanerf_malloc",
-           "adanerf_free", "adanerf_memcpy_h2d", "adanerf_memcpy_d2h", "adanerf_get_buffer"]
+           "adanerf_free", "adanerf_memcpy_h2d", "adanerf_memcpy_d2h", "adanerf_get_buffer",
+           "adanerf_set_pixel_offset", "adanerf_get_pixel_offset", "adanerf_accumulate", "adanerf_resolve_mean", "adanerf_host_subpixel_grid"]
 
 _lib = None
 
@@ -101,6 +103,11 @@ def load_library(path: Optional[str] = None):
     lib.adanerf_foveate.argtypes = [vp, C.c_float, C.c_float, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_float), vp, vp]
     lib.adanerf_compact_budget.argtypes = [vp, vp, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp, vp]
     lib.adanerf_present.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32]
+    lib.adanerf_set_pixel_offset.argtypes = [vp, C.c_float, C.c_float]
+    lib.adanerf_get_pixel_offset.argtypes = [vp, C.POINTER(C.c_float)]
+    lib.adanerf_accumulate.argtypes = [vp, vp, i32, vp, i32]
+    lib.adanerf_resolve_mean.argtypes = [vp, vp, i32, i32, vp, vp]
+    lib.adanerf_host_subpixel_grid.argtypes = [i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     fp = C.POINTER(C.c_float)
     lib.adanerf_reproject.argtypes = [vp, vp, vp, vp, fp, fp, fp, fp, C.c_float, C.c_uint32, i32, vp, vp, vp, C.POINTER(i32)]
     lib.adanerf_render.argtypes = [vp, vp, vp, C.POINTER(Stats)]
@@ -236,6 +243,21 @@ def _ptr(x):
 
 
 FOVEA_MAX_RINGS = 8
+
+
+def subpixel_grid(s: int):
+    """The regular s x s sub-pixel pattern (adanerf_host_subpixel_grid): [(dx, dy)] * s*s in pixels, row by row, each a float that fp32
+    holds exactly; s in 1..8, s = 1 gives [(0, 0)].  No device needed.  ValueError on anything else."""
+    if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 1 <= s <= SUPERSAMPLE_MAX:
+        raise ValueError("supersample: S must be an integer in 1..%d, got %r" % (SUPERSAMPLE_MAX, s))
+    lib = load_library()
+    out = []
+    for k in range(int(s) * int(s)):
+        dx, dy = C.c_float(0), C.c_float(0)
+        if lib.adanerf_host_subpixel_grid(int(s), k, C.byref(dx), C.byref(dy)) != 0:
+            raise AdaNeRFError("adanerf_host_subpixel_grid(%d, %d) failed" % (s, k))
+        out.append((float(dx.value), float(dy.value)))
+    return out
 
 
 def parse_fovea(spec: str):
@@ -486,6 +508,69 @@ class NeuralRenderer:
         self._check(self.foveate_device(gaze_xy, rings, n_map, thr_map))
         self._check(self.lib.adanerf_set_budget_map(self.handle, n_map.ptr, thr_map.ptr))
 
+    # -- anti-aliasing: sub-pixel offsets, accumulation ------------------------------------------------
+    def set_pixel_offset(self, dx: float = 0.0, dy: float = 0.0):
+        """The rays of the frames rendered from now on pass through (x + 0.5 + dx, y + 0.5 + dy) of their pixels (adanerf_set_pixel_offset):
+        |dx|, |dy| <= 1, (0, 0) is the pixel centre.  Survives set_frame_size."""
+        self._check(self.lib.adanerf_set_pixel_offset(self.handle, float(dx), float(dy)))
+
+    @property
+    def pixel_offset(self):
+        """(dx, dy) in force"""
+        out = (C.c_float * 2)()
+        self._check(self.lib.adanerf_get_pixel_offset(self.handle, out))
+        return float(out[0]), float(out[1])
+
+    subpixel_grid = staticmethod(subpixel_grid)
+
+    def accumulate_device(self, rgb, n_rays: int, sum_out, first: bool):
+        """sum_out = rgb (first) or sum_out + rgb over device [n_rays,3] fp32 images, on the context's stream (adanerf_accumulate)"""
+        self._check(self.lib.adanerf_accumulate(self.handle, _ptr(rgb), int(n_rays), _ptr(sum_out), 1 if first else 0))
+
+    def resolve_mean_device(self, sum_in, n_rays: int, frames: int, rgba8_out=None, rgb_out=None):
+        """sum_in / frames into rgb_out ([n_rays,3] fp32, may be sum_in) and / or rgba8_out ([n_rays] uchar4, the viewer's output contract),
+        on the context's stream (adanerf_resolve_mean)"""
+        self._check(self.lib.adanerf_resolve_mean(self.handle, _ptr(sum_in), int(n_rays), int(frames), _ptr(rgba8_out), _ptr(rgb_out)))
+
+    def render_supersampled(self, s: int):
+        """One anti-aliased frame: s*s renders at the offsets of subpixel_grid(s), accumulated and resolved on the device.  Returns
+        (rgb_mean [R,3] fp32, rgba8 [R,4] uint8, Stats): the stage times are summed over the s*s renders, the sample counts are per rendered
+        frame.  The device copies stay in ``_o_rgb`` / ``_o_rgba`` as after render_numpy (present() shows the resolved frame); the offset
+        that was in force is restored."""
+        grid = subpixel_grid(s)
+        n = self.info.rays_local
+        if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
+            self._o_rgb = self.empty((n, 3), np.float32)
+            self._o_rgba = self.empty((n, 4), np.uint8)
+        if not hasattr(self, "_ss_sum") or self._ss_sum.shape[0] != n:
+            if hasattr(self, "_ss_sum"):
+                self._ss_sum.free()
+                self._own.remove(self._ss_sum)
+            self._ss_sum = self.empty((n, 3), np.float32)
+        was = self.pixel_offset
+        total = Stats()
+        try:
+            for k, (dx, dy) in enumerate(grid):
+                self.set_pixel_offset(dx, dy)
+                st = self.render(None, self._o_rgb, stats=True)
+                self.accumulate_device(self._o_rgb, n, self._ss_sum, first=k == 0)
+                for name in ("ms_total", "ms_sample_mlp", "ms_compact", "ms_shade_mlp", "ms_composite", "total_samples", "batches", "shade_launches",
+                             "sample_launches", "rays_refined"):
+                    setattr(total, name, getattr(total, name) + getattr(st, name))
+                for name in ("rays", "sampling_overflow", "guard_max_seen", "guard_violations", "guard_widened", "guard_pair_seen", "guard_audited",
+                             "guard_audit_mismatch"):
+                    setattr(total, name, getattr(st, name))
+        finally:
+            self.set_pixel_offset(*was)
+        total.total_samples //= len(grid)
+        total.rays_refined //= len(grid)
+        self.resolve_mean_device(self._ss_sum, n, len(grid), self._o_rgba, self._o_rgb)
+        whole = n == self.info.width * self.info.height
+        self._last_frame = (self._o_rgba, self.info.width, self.info.height) if whole else None
+        self._rp_frame = None      # the mean of several jittered frames has no single depth map to warp by
+        self.last_stats = total
+        return self._o_rgb.numpy(), self._o_rgba.numpy(), total
+
     def render(self, rgba8_out=None, rgb_out=None, stats: bool = False) -> Optional[Stats]:
         """One frame into caller-owned device buffers ([rays_local] uchar4 / [rays_local,3] fp32).
         ``stats=True`` synchronises and returns the per-stage timing record."""
@@ -587,9 +672,11 @@ class NeuralRenderer:
                        filter: Optional[str] = None):
         """The viewer's blit from its render buffer to the window (interoprenderbuffer.cpp:87) on device images: row-major uchar4
         [src_h*src_w] -> [dst_h*dst_w], on the context's stream (adanerf_present).  filter None: the reference's rule (linear if the
-        destination is wider than the source, else nearest); "nearest" / "linear" force one.  flip_y: rows bottom-up (BMP order)."""
+        destination is wider than the source, else nearest); "nearest" / "linear" force one; "area" is the exact area filter
+        (ADANERF_PRESENT_AREA: a frame rendered larger than the window is averaged, not decimated; at most 8 to 1 per axis).
+        flip_y: rows bottom-up (BMP order)."""
         if filter not in PRESENT_FILTERS:
-            raise ValueError("present: filter must be None, 'nearest' or 'linear', got %r" % (filter,))
+            raise ValueError("present: filter must be None, 'nearest', 'linear' or 'area', got %r" % (filter,))
         self._check(self.lib.adanerf_present(self.handle, _ptr(src_rgba8), int(src_w), int(src_h), _ptr(dst_rgba8), int(dst_w), int(dst_h),
                                              (PRESENT_FLIP_Y if flip_y else 0) | PRESENT_FILTERS[filter]))
 

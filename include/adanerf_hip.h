@@ -13,7 +13,10 @@
  *   adanerf_set_selection                numRaymarchSamples / adaptiveSamplingThreshold: members of RayMarchFromPoses, handed to
  *                                        updateRayMarchFromPosesAdaptive on every call (src/featureset.cpp:80,153)
  *   adanerf_set_frame_size               Settings::width / height (src/settings.cpp:20-33), fixed for the life of the viewer's NeuralRenderer
- *   adanerf_present                      the blit from the render buffer to the window (src/interoprenderbuffer.cpp:87)
+ *   adanerf_set_pixel_offset             none: the ray table is fixed to pixel centres (src/util/raygeneration.py:10-26 of the reference's
+ *                                        PyTorch tree); with adanerf_accumulate / adanerf_resolve_mean this is supersampling in time
+ *   adanerf_present                      the blit from the render buffer to the window (src/interoprenderbuffer.cpp:87);
+ *                                        ADANERF_PRESENT_AREA replaces its nearest decimation by an exact area filter
  *   adanerf_reproject                    none: the viewer presents the frame it rendered (src/neuralrenderer.cpp:146-182 ->
  *                                        src/interoprenderbuffer.cpp:87); this stage sits in front of that step
  *   adanerf_render                       ImageGenerator::inference, 2-context adaptive branch
@@ -311,6 +314,27 @@ int adanerf_set_selection(adanerf_ctx* ctx, int32_t num_samples, float threshold
  *   their source and pose count in adanerf_info stay; the audit's phase and fill cycle start over (frames do not depend on either). */
 int adanerf_set_frame_size(adanerf_ctx* ctx, int32_t width, int32_t height);
 
+/* Sub-pixel ray offsets: the ray of pixel (x, y) passes through image point (x + 0.5 + dx, y + 0.5 + dy) -- positive dx towards higher
+ * columns, positive dy towards higher rows -- where the ray table of src/util/raygeneration.py:10-26 fixes it to the pixel centre.  A host
+ * that renders several frames at the offsets of adanerf_host_subpixel_grid and averages them (adanerf_accumulate, adanerf_resolve_mean)
+ * gets an anti-aliased still: what an evaluator wants against anti-aliased ground truth, a viewer while the camera rests.
+ *   dx, dy: finite, |dx| <= 1 and |dy| <= 1; anything else, a NaN included, returns ADANERF_EINVAL with nothing changed.  (0, 0) is the
+ *   state after adanerf_create: every frame is then byte for byte what it is without this entry point.
+ *   Definition, exact: the kernels keep computing vx = start_x + x_pp * col, vy = start_y + y_pp * row (float64).  With an offset in force
+ *   the ray generator handed to a launch carries start_x' = start_x + x_pp * (double)dx and start_y' = start_y + y_pp * (double)dy, each two
+ *   rounded float64 operations (multiply, then add; never fused); a component equal to 0 leaves that start value's bits untouched.
+ *   Ordering is that of adanerf_set_camera: renders issued afterwards see the offset, frames already enqueued keep theirs (the ray
+ *   generator's constants reach the kernels by value).  The offset is in pixels and survives adanerf_set_frame_size: it is applied to the
+ *   new pixel pitch.
+ *   Honoured by adanerf_render, adanerf_render_oracle, adanerf_ray_features, adanerf_sample_mlp and adanerf_sample_uniform.  Ignored,
+ *   deliberately, by adanerf_calibrate_guard (its own 64 x 64 rays: the band must not depend on a jitter), adanerf_reproject (it splats
+ *   through pixel centres), adanerf_foveate and adanerf_assemble_strips (both index whole pixels).
+ *   Sharded contexts, useNDC models, the PDF and coarse/fine samplers, guarded sampling and budget maps need nothing special: the offset
+ *   moves the ray inside its pixel, and the maps of adanerf_set_budget_map / adanerf_set_aux_outputs stay indexed by pixel. */
+int adanerf_set_pixel_offset(adanerf_ctx* ctx, float dx, float dy);
+/* out[0] = dx, out[1] = dy of the offset in force. */
+int adanerf_get_pixel_offset(const adanerf_ctx* ctx, float out[2]);
+
 /* Renders this context's rays.  d_rgba8_out: [rays_local] uchar4 (A=255), row-major over the shard's
  * rows -- for shard_world==1 that is the whole image, pixel (x,y) at y*w+x.  d_rgb_f32_out: optional
  * [rays_local,3] fp32 unclamped colour (parity output).  Either may be NULL.  stats != NULL makes
@@ -574,7 +598,8 @@ int adanerf_flip(adanerf_ctx* ctx, const float* d_test_rgb, const float* d_ref_r
 enum {
   ADANERF_PRESENT_FLIP_Y = 1,  /* rows are written bottom-up: the reference's destination rectangle (GL's origin) and the BMP row order */
   ADANERF_PRESENT_NEAREST = 2, /* force the nearest filter */
-  ADANERF_PRESENT_LINEAR = 4   /* force the linear filter; together with _NEAREST: ADANERF_EINVAL */
+  ADANERF_PRESENT_LINEAR = 4,  /* force the linear filter; together with _NEAREST: ADANERF_EINVAL */
+  ADANERF_PRESENT_AREA = 8     /* the exact area (box) filter, below; together with _NEAREST or _LINEAR: ADANERF_EINVAL */
 };
 
 /* The frame at the window's size: the headless counterpart of the viewer's blit from its render buffer (-s W H) to the window (-ws W H),
@@ -589,9 +614,33 @@ enum {
  * edge, their weights D - f and f (samples at pixel centres: equal sizes give the identity); y alike with E = 2 dst_h.  Per channel,
  * alpha included, v = the sum of the four weighted taps and out = floor((2 v + D E) / (2 D E)).  Nearest takes pixel
  * min(floor((2 x + 1) src_w / D), src_w - 1).  A NULL pointer, a side outside 1..16384, both filter flags, an unknown flag, a pointer
- * that is not 4-byte aligned or overlapping ranges return ADANERF_EINVAL. */
+ * that is not 4-byte aligned or overlapping ranges return ADANERF_EINVAL.
+ *   ADANERF_PRESENT_AREA: supersampling in space.  The blit of src/interoprenderbuffer.cpp:87 decimates a frame rendered larger than the
+ *   window (nearest); this filter averages it instead, exactly, for any pair of sizes.  Per axis, in units of 1 / dst_w of a source pixel:
+ *   destination pixel x covers [x src_w, (x + 1) src_w), source pixel i covers [i dst_w, (i + 1) dst_w), the weight is the overlap
+ *   wx(x, i) = max(0, min((i + 1) dst_w, (x + 1) src_w) - max(i dst_w, x src_w)); the contributing i run from floor(x src_w / dst_w) to
+ *   floor(((x + 1) src_w - 1) / dst_w) and their weights sum to src_w; wy alike.  Per channel, alpha included, V = sum_j sum_i wy wx v,
+ *   S = src_w src_h and out = floor((2 V + S) / (2 S)): rounded half up, in 64-bit integers.  Equal sizes give the identity, a constant
+ *   image stays constant, an exact 2 x reduction is the half-up rounded mean of each 2 x 2 block; enlarging is legal (the definition covers
+ *   it).  The filter needs src_w <= 8 dst_w and src_h <= 8 dst_h (at most 9 taps per axis), else ADANERF_EINVAL: reduce in two steps.
+ *   _FLIP_Y combines with it as with the other filters.  Without the flag nothing changes: the default for dst_w <= src_w stays nearest. */
 int adanerf_present(adanerf_ctx* ctx, const void* d_src_rgba8, int32_t src_w, int32_t src_h, void* d_dst_rgba8, int32_t dst_w,
                     int32_t dst_h, int32_t flags);
+
+/* Supersampling in time: the running sum of the fp32 frames rendered at several sub-pixel offsets (adanerf_set_pixel_offset), and its
+ * mean.  The viewer has no counterpart (one ray through each pixel centre, src/util/raygeneration.py:10-26).  Both run on the context's
+ * stream without a host synchronisation and are independent of the context's frame size (as adanerf_present is); n_rays == 0 does nothing.
+ *   adanerf_accumulate:   d_rgb_f32 [n_rays,3] is the d_rgb_f32_out of an adanerf_render, d_sum [n_rays,3] caller-owned.  first != 0:
+ *                         sum = rgb; otherwise sum = sum + rgb, one rounded fp32 addition per value (a NaN propagates).
+ *   adanerf_resolve_mean: m = sum / (float)frames, one IEEE fp32 division per value, frames in 1..65536.  d_rgb_f32_out [n_rays,3] or NULL
+ *                         receives m and may be d_sum itself; d_rgba8_out [n_rays] uchar4 or NULL receives the viewer's output contract as
+ *                         the compositing step writes it, (unsigned char)(fminf(fmaxf(m, 0), 1) * 255.0f) and A = 255 (a NaN becomes 0):
+ *                         with frames == 1 the d_rgb_f32_out of a render resolves to that render's d_rgba8_out byte for byte.
+ * ADANERF_EINVAL, with nothing written: a NULL d_rgb_f32 / d_sum, both outputs NULL; n_rays < 0 or n_rays * 3 beyond 2^31 - 1; frames
+ * outside 1..65536; a pointer that is not 4-byte aligned; images that overlap without being identical (d_rgb_f32 and d_sum, d_sum and
+ * d_rgb_f32_out), d_rgba8_out overlapping either fp32 image. */
+int adanerf_accumulate(adanerf_ctx* ctx, const float* d_rgb_f32, int32_t n_rays, float* d_sum, int32_t first);
+int adanerf_resolve_mean(adanerf_ctx* ctx, const float* d_sum, int32_t n_rays, int32_t frames, void* d_rgba8_out, float* d_rgb_f32_out);
 
 /* adanerf_reproject flags */
 enum { ADANERF_REPROJECT_FILL = 1 }; /* a destination pixel no source pixel lands in takes the farthest of its 8 neighbours' source pixels */
@@ -696,6 +745,12 @@ int adanerf_host_pack_weights(const char* model_dir, int32_t net, int32_t precis
 
 /* 128-entry world-depth table the shading stage indexes by bin (and dense t-values) for model_dir. */
 int adanerf_host_depth_table(const char* model_dir, const adanerf_options* opt, float* ztab128);
+
+
+/* The regular s x s sub-pixel pattern both hosts and the evaluator feed to adanerf_set_pixel_offset: for k in 0..s*s-1, i = k % s,
+ * j = k / s, *dx = (2 i + 1 - s) / (2 s), *dy alike from j, computed in double and cast to float.  s in 1..8, k in 0..s*s-1, non-NULL
+ * outputs; anything else returns ADANERF_EINVAL.  s == 1 gives (0, 0); the offsets of a grid sum to 0 on either axis. */
+int adanerf_host_subpixel_grid(int32_t s, int32_t k, float* dx, float* dy);
 
 #ifdef __cplusplus
 }
