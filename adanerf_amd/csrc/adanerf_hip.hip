@@ -291,11 +291,11 @@ int launch_sample_mlp(adanerf_ctx* c, int first_ray, int n_rays, float* d_oracle
     if (generic_split_sampling(c)) {
       // split-precision engine (fp32-class accuracy at 3 / 16 of the fp32-MFMA cycle count), weight tiles staged through LDS
       const int W0 = c->topo0.width;
-      if (tune::kGenericStaged && a.net16.n_bias > dispatch<64, 128, 256>(W0, [](auto w) { return uint32_t(gen_bias_cap<w()>()); }, 0u))
+      if (a.net16.n_bias > dispatch<64, 128, 256>(W0, [](auto w) { return uint32_t(gen_bias_cap<w()>()); }, 0u))
         return fail(c, ADANERF_EUNSUPPORTED, "sampling network: bias table exceeds the kernel's LDS capacity");      // cannot happen for depth <= 8
       return hip_rc(c, dispatch<kEnc10_4, kEnc2_2, kEncMax>(c->enc0, [&](auto e) {
         return dispatch<64, 128, 256>(W0, [&](auto w) {
-          hipLaunchKernelGGL((sample_mlp16x3_gen_kernel<enc_fp(e()), enc_fd(e()), w(), tune::kGenericStaged>), grid, block, 0, c->stream, a, c->gen0);
+          hipLaunchKernelGGL((sample_mlp16x3_gen_kernel<enc_fp(e()), enc_fd(e()), w()>), grid, block, 0, c->stream, a, c->gen0);
           return hipGetLastError();
         }, hipErrorInvalidValue);
       }, hipErrorInvalidValue), "hipGetLastError()");
@@ -641,8 +641,6 @@ int apply_frame_size(adanerf_ctx* c, int was_rays) {
   return ADANERF_OK;
 }
 
-constexpr int kShadeWaves = 8;   // one 8-wave workgroup per CU (two independent 4-wave workgroups measured 4.2-5.7 ms vs 3.8)
-
 int launch_shade_mlp(adanerf_ctx* c, const float* d_rays, const uint32_t* d_key, const int32_t* d_total, int max_samples, int prec,
                      float* d_raw, const float* d_z = nullptr, bool coarse = false) {
   if (max_samples <= 0) return ADANERF_OK;
@@ -664,20 +662,18 @@ int launch_shade_mlp(adanerf_ctx* c, const float* d_rays, const uint32_t* d_key,
   const int enc = coarse ? enc_layout(c->ms.fp0, c->ms.fd0, false) : c->enc1;      // generic nets only: kEnc10_4, or the catch-all 16-band layout
   auto for_elem = [&](auto&& f) { return prec == ADANERF_PREC_BF16 ? f(Bf16{}) : f(Fp16{}); };
   if (generic && prec != ADANERF_PREC_FP32) {
-    // Any topology / encoding layout on the 16-bit MFMA pipe (k_generic16.hip.hpp).  Staged: one copy of every weight tile per workgroup
-    // through LDS, gen_blocks 32-sample blocks per wave; else fragments straight from L2.  Persistent grid = the workgroups the chosen
+    // Any topology / encoding layout on the 16-bit MFMA pipe (k_generic16.hip.hpp): one copy of every weight tile per workgroup
+    // through LDS, gen_blocks 32-sample blocks per wave.  Persistent grid = the workgroups the chosen
     // instantiation really keeps resident (registers and LDS differ per width / layout).
-    if (tune::kGenericStaged && a.net.n_bias > dispatch<64, 128, 256, 512>(topo.width, [](auto w) { return uint32_t(gen_bias_cap<w()>()); }, 0u))
+    if (a.net.n_bias > dispatch<64, 128, 256, 512>(topo.width, [](auto w) { return uint32_t(gen_bias_cap<w()>()); }, 0u))
       return fail(c, ADANERF_EUNSUPPORTED, "shading network: bias table exceeds the kernel's LDS capacity");      // cannot happen for depth <= 8 (pack.hpp kMaxDepth)
     if ((rc = hip_rc(c, for_elem([&](auto et) {
       return dispatch<kEnc10_4, kEncMax>(enc, [&](auto e) {
         return dispatch<64, 128, 256, 512>(topo.width, [&](auto w) {
           using ET = decltype(et);
-          constexpr int FP = enc_fp(e()), FD = enc_fd(e()), W = w(), NB = tune::kGenericStaged ? gen_blocks<W, FP>() : 1;
+          constexpr int FP = enc_fp(e()), FD = enc_fd(e()), W = w(), NB = gen_blocks<W, FP>();
           const int tiles = (max_samples + 128 * NB - 1) / (128 * NB);
-          if constexpr (tune::kGenericStaged)      // the other form is not instantiated
-            return launch_persistent(c->grids, shade_mlp16_gen_staged_kernel<ET, FP, FD, W, NB, gen_occupancy<W, FP>()>, tiles, 256, c->stream, a, gen);
-          else return launch_persistent(c->grids, shade_mlp16_gen_kernel<ET, FP, FD, W>, tiles, 256, c->stream, a, gen);
+          return launch_persistent(c->grids, shade_mlp16_gen_staged_kernel<ET, FP, FD, W, NB, gen_occupancy<W, FP>()>, tiles, 256, c->stream, a, gen);
         }, hipErrorInvalidValue);
       }, hipErrorInvalidValue);
     }), kOccupancyQuery))) return rc;
@@ -687,12 +683,10 @@ int launch_shade_mlp(adanerf_ctx* c, const float* d_rays, const uint32_t* d_key,
   } else if (prec == ADANERF_PREC_FP32) {
     HIP_TRY(c, launch_shade_mlp_f32(c->grids, a, (max_samples + 127) / 128, c->stream));
   } else {
-    const int tile = kShadeWaves * 32;
-    const int tiles = (max_samples + tile - 1) / tile;
+    const int tiles = (max_samples + 255) / 256;
     if ((rc = hip_rc(c, for_elem([&](auto et) {
       using ET = decltype(et);
-      if (tune::kShadeBlocks != 2) return launch_persistent(c->grids, shade_mlp16_kernel<ET, 10, 4, kShadeWaves>, tiles, kShadeWaves * 64, c->stream, a);
-      // two sample blocks per wave, 4 waves x 64 samples (same 256-sample tile), one workgroup per CU
+      // two sample blocks per wave, 4 waves x 64 samples = 256-sample tiles, one workgroup per CU
       hipLaunchKernelGGL((shade_mlp16x2_kernel<ET, 10, 4>), dim3(std::min(tiles, c->ms.info.compute_units)), dim3(256), 0, c->stream, a);
       return hipSuccess;
     }), kOccupancyQuery))) return rc;

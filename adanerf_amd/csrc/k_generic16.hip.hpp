@@ -2,9 +2,8 @@
 // 64 / 128 / 256, shading also 512, skips at any layers or none, src/models.py:18-82, 199-277) and any encoding layout on the 16-bit MFMA pipe.
 // The specialised 8 x 256 kernels stage one fragment stream through an LDS ring whose chunk positions are compile-time
 // constants of that topology.  Here the layer table is a run-time argument: a run-time loop over the hidden layers with the layer's
-// tiles and k-steps unrolled, and the weights staged per output tile through two LDS buffers shared by the workgroup (TileStage below;
-// shipped).  The first form -- every wave fetching its fragments straight from global memory (L2 hits), layer_16_direct /
-// layer_16x3_direct -- is kept as the experiment baseline (tuning.hpp kGenericStaged, profiles/r03_generic_staged.md).
+// tiles and k-steps unrolled, and the weights staged per output tile through two LDS buffers shared by the workgroup (TileStage below).
+// (The first form, every wave fetching its fragments straight from global memory, was the baseline of profiles/r03_generic_staged.md.)
 // Device code only (gfx950, wave64); part of kernels.hip.hpp (main translation unit: accumulators in architectural VGPRs).
 #pragma once
 #include "k_generic_f32.hip.hpp"      // GenericTopo
@@ -12,83 +11,6 @@
 #include "k_sampling16.hip.hpp"   // split_pack, epilogue_pair_16x3
 
 namespace adanerf {
-
-// One 16-bit layer, fragments [m][s][lane][8 x 16 bit] from global memory, bias blocks [m][h][16] fp32 from global memory.
-// Input = two register segments of S1 / S2 k-steps (4 packed dwords each); KEEP_F32_TILE as layer_16.
-template <class ET, int S1, int S2, int MT, bool RELU, int KEEP_F32_TILE = -1>
-__device__ __forceinline__ void layer_16_direct(const u32x4* __restrict__ w, const float* __restrict__ bias, int lane, const uint32_t* in1,
-                                                const uint32_t* in2, uint32_t* out, f32x16* keep = nullptr) {
-  constexpr int KS = S1 + S2;
-  const int h = lane >> 5;
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    f32x16 acc;
-    const float4* bp = reinterpret_cast<const float4*>(bias + (m * 2 + h) * 16);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float4 b = bp[g];
-      acc[4 * g + 0] = b.x;
-      acc[4 * g + 1] = b.y;
-      acc[4 * g + 2] = b.z;
-      acc[4 * g + 3] = b.w;
-    }
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const u32x4 a = w[(m * KS + s) * 64 + lane];
-      const uint32_t* src = (s < S1) ? (in1 + 4 * s) : (in2 + 4 * (s - S1));
-      const u32x4 b = {src[0], src[1], src[2], src[3]};
-      acc = ET::mfma(a, b, acc);
-    }
-    if (KEEP_F32_TILE == m) {
-      *keep = acc;
-    } else {
-      const int gd = mfma_guard<ET, RELU>(acc);
-#pragma unroll
-      for (int g = 0; g < 4; ++g) epilogue_quad_16<ET, RELU>(acc, m, g, out, gd);
-    }
-  }
-}
-
-// A5 + A6 for any shading-net topology on the 16-bit engine.  Workgroup = 4 waves x 32 samples (two workgroups per CU).
-template <class ET, int FP, int FD, int W>
-__global__ __launch_bounds__(256, 2) void shade_mlp16_gen_kernel(ShadeArgs a, GenericTopo t) {
-  constexpr int QP = pe_slots(FP), QD = pe_slots(FD), MT = W / 32, KW = W / 16;      // KW: k-steps of a W-wide input
-  constexpr int TILE = 4 * 32;
-  const int lane = lane_id();
-  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
-  const int j = lane & 31, h = lane >> 5;
-  int total = a.total ? *a.total : a.max_samples;
-  if (total > a.max_samples) total = a.max_samples;
-  const u32x4* w = a.net.w;
-  const float* b = a.net.bias;
-  for (int tile = blockIdx.x; tile * TILE < total; tile += gridDim.x) {
-    const int s = tile * TILE + wave * 32 + j;
-    if (tile * TILE + wave * 32 >= total) continue;      // wave-uniform
-    asm volatile("" : "+v"(w), "+v"(b));                  // keep the fragment loads inside the loops (see shade_mlp32_kernel)
-    float x[3], dpe[3];
-    load_sample(a, s, total, x, dpe);
-    uint32_t pts[QP / 2], dirs[QD / 2], hA[W / 4], hB[W / 4 + 8];      // hB also receives the (MT + 1)-tile feature (+ alpha) layer's packed part
-    pe_pack<ET, FP>(x, h, pts);
-    pe_pack<ET, FD>(dpe, h, dirs);
-    layer_16_direct<ET, QP / 8, 0, MT, true>(w + a.net.w_off[0], b + a.net.b_off[0], lane, pts, pts, hA);
-#pragma unroll 1
-    for (int l = 1; l < t.depth; ++l) {
-      asm volatile("" : "+v"(w), "+v"(b));
-      if ((t.cat_mask >> l) & 1) layer_16_direct<ET, QP / 8, KW, MT, true>(w + a.net.w_off[l], b + a.net.b_off[l], lane, pts, hA, hB);      // cat([pts, h])
-      else layer_16_direct<ET, KW, 0, MT, true>(w + a.net.w_off[l], b + a.net.b_off[l], lane, hA, hA, hB);
-#pragma unroll
-      for (int i = 0; i < W / 4; ++i) hA[i] = hB[i];
-    }
-    const int lf = t.depth;
-    f32x16 alpha_tile;
-    layer_16_direct<ET, KW, 0, MT + 1, false, MT>(w + a.net.w_off[lf], b + a.net.b_off[lf], lane, hA, hA, hB, &alpha_tile);        // feature (+ alpha row)
-    layer_16_direct<ET, KW, QD / 8, MT / 2, true>(w + a.net.w_off[lf + 1], b + a.net.b_off[lf + 1], lane, hB, dirs, hA);          // cat([feature, dir])
-    f32x16 rgb_tile;
-    layer_16_direct<ET, KW / 2, 0, 1, false, 0>(w + a.net.w_off[lf + 2], b + a.net.b_off[lf + 2], lane, hA, hA, hB, &rgb_tile);
-    if (h == 0 && s < total)
-      store_raw(a, s, rgb_tile[0], rgb_tile[1], rgb_tile[2], alpha_tile[0]);
-  }
-}
 
 // ---- per-tile weight staging through LDS -------------------------------------------------------------------------------------------
 // Fetching every A fragment per wave costs 1 KiB through the vector-memory path per MFMA: four SIMDs x 1 KiB per 64 MFMA cycles is the
@@ -225,11 +147,11 @@ __device__ __forceinline__ void layer_16_staged(TileStage& st, float (&br)[16], 
   constexpr int KS = S1 + S2, D = KS < kStageAhead ? KS : kStageAhead;
   static_assert(KS * 1024 <= BUF_BYTES, "tile does not fit its LDS buffer");
   const int h = lane >> 5;
-  // Where do a tile's conversions (ReLU + pack, 16 x NB values) go?  tune::kGenericSpread<W>: spread, a quad at a time, over the k-steps of
+  // Where do a tile's conversions (ReLU + pack, 16 x NB values) go?  At width 256: spread, a quad at a time, over the k-steps of
   // the NEXT tile, between its MFMAs -- with one wave per SIMD (width 256) nothing else would issue while the pipe works, and nothing
   // else would keep the pipe working while they issue; costs a second accumulator set.  Otherwise right behind the tile's own
   // MFMAs (in one piece behind the next tile's barrier: measured in round 4, no effect, removed).  A layer's last tile always converts at once: the next layer reads its outputs.
-  constexpr bool SPREAD = tune::kGenericSpread != 0 && (tune::kGenericSpread >= 2 || O >= 64);      // O = W / 4 (+ 8): 1 = width 256 only
+  constexpr bool SPREAD = O >= 64;      // O = W / 4 (+ 8): from width 256 up (r04_variants_generic_spread.log)
   constexpr int QUADS = 4 * NB, QPS = (QUADS + KS - 1) / KS;      // quads of the previous tile converted per k-step
   f32x16 accs[SPREAD ? 2 : 1][NB];
   int guards[SPREAD ? 2 : 1][NB];      // mfma_guard of each finished accumulator (k_mlp16.hip.hpp): set behind a tile's last k-step
@@ -252,7 +174,7 @@ __device__ __forceinline__ void layer_16_staged(TileStage& st, float (&br)[16], 
     u32x4 fr[D];
 #pragma unroll
     for (int i = 0; i < D; ++i) fr[i] = lds_read128(rd + i * 1024);
-    if (LDSB && tune::kGenericBiasDirect && !(tune::kAblateGeneric & 2)) {
+    if (LDSB && !(tune::kAblateGeneric & 2)) {
       // the tile's own bias block straight into its accumulators (no copy a tile ahead, no 16 moves per block): the first MFMA
       // waits for these reads and its first fragment together
 #pragma unroll
@@ -270,9 +192,7 @@ __device__ __forceinline__ void layer_16_staged(TileStage& st, float (&br)[16], 
       if (tune::kAblateGeneric & 2) {      // timing ablation: no bias reads at all
 #pragma unroll
         for (int r = 0; r < 16; ++r) br[r] = 0.f;
-      } else if constexpr (LDSB) {
-        bias_request_lds(last ? next_bias : bias + (m + 1) * 128, h, br);
-      } else {      // table in global memory: bias / next_bias are byte offsets into it
+      } else if constexpr (!LDSB) {      // table in global memory: bias / next_bias are byte offsets into it
         bias_request(gbias + ((last ? next_bias : bias + (m + 1) * 128) >> 2), h, br);
       }
     }
@@ -442,46 +362,14 @@ __global__ __launch_bounds__(256, OCC) void shade_mlp16_gen_staged_kernel(ShadeA
 }
 
 // ---- sampling network of any topology on the split-precision engine ----------------------------------------------------------------
-// layer_16x3 (k_sampling16.hip.hpp) with the (hi, lo') fragment pairs fetched straight from global memory: per k-step
+// layer_16x3 (k_sampling16.hip.hpp) with the (hi, lo') fragment pairs staged per tile (2 KiB per k-step), order pinned as in
+// layer_16_staged: per k-step
 //   acc += Whi . xhi ;  cross += Whi . xlo' ;  cross += Wlo' . xhi         (v = acc + cross / 2048: 22-bit operands, fp32 accumulate)
 // Fragments [m][s][part][lane][8 x fp16] (pack.cpp, Elem::F16_SPLIT).  LAST: fp32 outputs instead of the next layer's (hi, lo') split.
-template <int KS, int MT, bool LAST>
-__device__ __forceinline__ void layer_16x3_direct(const u32x4* __restrict__ w, const float* __restrict__ bias, int lane, const uint32_t* in_hi,
-                                                  const uint32_t* in_lo, uint32_t* out_hi, uint32_t* out_lo, float* out_f32) {
-  const int h = lane >> 5;
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    f32x16 acc, cross;
-    const float4* bp = reinterpret_cast<const float4*>(bias + (m * 2 + h) * 16);
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float4 b = bp[g];
-      acc[4 * g + 0] = b.x;
-      acc[4 * g + 1] = b.y;
-      acc[4 * g + 2] = b.z;
-      acc[4 * g + 3] = b.w;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) cross[r] = 0.f;
-#pragma unroll
-    for (int s = 0; s < KS; ++s) {
-      const u32x4 whi = w[((m * KS + s) * 2 + 0) * 64 + lane], wlo = w[((m * KS + s) * 2 + 1) * 64 + lane];
-      const u32x4 bh = {in_hi[4 * s], in_hi[4 * s + 1], in_hi[4 * s + 2], in_hi[4 * s + 3]};
-      const u32x4 bl = {in_lo[4 * s], in_lo[4 * s + 1], in_lo[4 * s + 2], in_lo[4 * s + 3]};
-      acc = Fp16::mfma(whi, bh, acc);
-      cross = Fp16::mfma(whi, bl, cross);
-      cross = Fp16::mfma(wlo, bh, cross);
-    }
-#pragma unroll
-    for (int pi = 0; pi < 8; ++pi) epilogue_pair_16x3<LAST>(acc, cross, m, pi, out_hi, out_lo, out_f32);
-  }
-}
-
-// The same layer with the (hi, lo') pairs staged per tile (2 KiB per k-step), order pinned as in layer_16_staged.
 template <int BUF_BYTES, int KS, int MT, bool LAST>
 __device__ __forceinline__ void layer_16x3_staged(TileStage& st, float (&br)[16], uint32_t w_off, uint32_t bias, int lane,
                                                   const uint32_t* in_hi, const uint32_t* in_lo, uint32_t* out_hi, uint32_t* out_lo, float* out_f32,
-                                                  uint32_t next_off, int next_frags, uint32_t next_bias) {      // bias: LDS byte addresses
+                                                  uint32_t next_off, int next_frags) {      // bias: LDS byte address of the layer's blocks
   constexpr int D = KS < 2 ? KS : 2;      // pairs requested ahead
   static_assert(KS * 2048 <= BUF_BYTES, "tile does not fit its LDS buffer");
   const int h = lane >> 5;
@@ -502,7 +390,7 @@ __device__ __forceinline__ void layer_16x3_staged(TileStage& st, float (&br)[16]
       fh[i] = lds_read128(rd + (2 * i) * 1024);
       fl[i] = lds_read128(rd + (2 * i + 1) * 1024);
     }
-    if (tune::kGenericBiasDirect && !(tune::kAblateGeneric & 2)) {
+    if (!(tune::kAblateGeneric & 2)) {
       float b16[16];
       bias_request_lds(bias + m * 128, h, b16);
 #pragma unroll
@@ -510,17 +398,12 @@ __device__ __forceinline__ void layer_16x3_staged(TileStage& st, float (&br)[16]
         acc[r] = b16[r];
         cross[r] = 0.f;
       }
-    } else {
+    } else {      // timing ablation: no bias reads at all (the layer's first tile starts from the block the kernel requested)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         acc[r] = br[r];
         cross[r] = 0.f;
-      }
-      if (tune::kAblateGeneric & 2) {      // timing ablation: no bias reads at all
-#pragma unroll
-        for (int r = 0; r < 16; ++r) br[r] = 0.f;
-      } else {
-        bias_request_lds(last ? next_bias : bias + (m + 1) * 128, h, br);
+        br[r] = 0.f;
       }
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -544,94 +427,61 @@ __device__ __forceinline__ void layer_16x3_staged(TileStage& st, float (&br)[16]
 
 // A1 + A2 + A3 for any sampling-net topology without raySampleInput (depth 2..8, width 64 / 128 / 256) and any encoding layout.
 // One wave = 32 rays, 4 waves per workgroup; writes the raw outputs (selection by select_rows_kernel, as after the fp32 generic kernel).
-// STAGED: weight tiles through LDS, one copy per workgroup (tuning.hpp kGenericStaged); else every wave fetches its own from L2.
-template <int FP, int FD, int W, bool STAGED>
-__global__ __launch_bounds__(256, (STAGED && W <= 128 && FP <= 10) ? 2 : 1) void sample_mlp16x3_gen_kernel(SampleArgs a, GenericTopo t) {
+// Weight tiles go through LDS, one copy per workgroup, so every wave of the workgroup takes part in the copies and barriers.
+template <int FP, int FD, int W>
+__global__ __launch_bounds__(256, (W <= 128 && FP <= 10) ? 2 : 1) void sample_mlp16x3_gen_kernel(SampleArgs a, GenericTopo t) {
   constexpr int QD = pe_slots(FD), QP = pe_slots(FP), Q0 = QD + QP, MT = W / 32, KW = W / 16;
   constexpr int BUF = (Q0 / 8 > KW ? Q0 / 8 : KW) * 2048;
-  constexpr int BIAS_AT = (STAGED ? 2 * BUF : 0) + 4 * kPairLdsBytesPerWave;      // staged: the bias table behind the selection's staging block
-  __shared__ __attribute__((aligned(1024))) char stage_mem[BIAS_AT + (STAGED ? gen_bias_cap<W>() * 4 : 0)];
+  constexpr int BIAS_AT = 2 * BUF + 4 * kPairLdsBytesPerWave;      // the bias table behind the selection's staging block
+  __shared__ __attribute__((aligned(1024))) char stage_mem[BIAS_AT + gen_bias_cap<W>() * 4];
   const int lane = lane_id();
   const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
   const int j = lane & 31, h = lane >> 5;
   const int blk = blockIdx.x * 4 + wave;
-  if (!STAGED && blk * 32 >= a.n_rays) return;      // staged: every wave of the workgroup takes part in the copies and barriers
   const int local = blk * 32 + j;
   const bool valid = local < a.n_rays;
   const int ray = a.first_ray + (valid ? local : a.n_rays - 1);
-  int col, row;
-  ray_pixel(a.g, ray, &col, &row);
   float nds[3], p[3], u[3];
-  gen_ray(a.g, col, row, nds, p);
-  unit3(nds, u);
+  sample_ray(a.g, ray, nds, p, u);
   uint32_t aH[W / 4], aL[W / 4], bH[W / 4], bL[W / 4];
-  const u32x4* w = a.net16.w;
-  const float* const bias0 = a.net16.bias;
-  const float* b = bias0;
   float out[64];
-  if constexpr (STAGED) {
-    TileStage st;
-    ts_start(st, w, stage_mem, wave, lane);
-    ts_issue<BUF>(st, a.net16.w_off[0], 2 * (Q0 / 8), 0);
-    bias_table_fill<W>(reinterpret_cast<float*>(stage_mem + BIAS_AT), a.net16.bias, a.net16.n_bias);
-    const uint32_t bl = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(stage_mem)) + BIAS_AT;
-    auto bias_of = [&](int l) { return bl + a.net16.b_off[l] * 4u; };
-    float br[16];
-    bias_request_lds(bias_of(0), h, br);
-    {
-      float tt[Q0];
-      uint32_t iH[Q0 / 2], iL[Q0 / 2];
-      pe_eval<FD, true>(u, h, tt);            // [dir PE | pos PE]  (src/features.py:868-874)
-      pe_eval<FP, true>(p, h, tt + QD);
+  TileStage st;
+  ts_start(st, a.net16.w, stage_mem, wave, lane);
+  ts_issue<BUF>(st, a.net16.w_off[0], 2 * (Q0 / 8), 0);
+  bias_table_fill<W>(reinterpret_cast<float*>(stage_mem + BIAS_AT), a.net16.bias, a.net16.n_bias);
+  const uint32_t bl = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(stage_mem)) + BIAS_AT;
+  auto bias_of = [&](int l) { return bl + a.net16.b_off[l] * 4u; };
+  float br[16];      // read by the kAblateGeneric & 2 build only (layer_16x3_staged); without it two scalar loads of the prologue change places
+  bias_request_lds(bias_of(0), h, br);
+  {
+    float tt[Q0];
+    uint32_t iH[Q0 / 2], iL[Q0 / 2];
+    pe_eval<FD, true>(u, h, tt);            // [dir PE | pos PE]  (src/features.py:868-874)
+    pe_eval<FP, true>(p, h, tt + QD);
 #pragma unroll
-      for (int q = 0; q < Q0 / 2; ++q) split_pack(tt[2 * q], tt[2 * q + 1], &iH[q], &iL[q]);
-      layer_16x3_staged<BUF, Q0 / 8, MT, false>(st, br, a.net16.w_off[0], bias_of(0), lane, iH, iL, bH, bL, nullptr, a.net16.w_off[1], 2 * KW, bias_of(1));
-    }
-#pragma unroll 1
-    for (int l = 1; l + 1 < t.depth; ++l) {
-      layer_16x3_staged<BUF, KW, MT, false>(st, br, a.net16.w_off[l], bias_of(l), lane, bH, bL, aH, aL, nullptr, a.net16.w_off[l + 1], 2 * KW, bias_of(l + 1));
-#pragma unroll
-      for (int i = 0; i < W / 4; ++i) {
-        bH[i] = aH[i];
-        bL[i] = aL[i];
-      }
-    }
-    const int ll = t.depth - 1;
-    layer_16x3_staged<BUF, KW, 4, true>(st, br, a.net16.w_off[ll], bias_of(ll), lane, bH, bL, nullptr, nullptr, out, 0, 0, bias_of(ll));
-  } else {
-    {
-      float tt[Q0];
-      uint32_t iH[Q0 / 2], iL[Q0 / 2];
-      pe_eval<FD, true>(u, h, tt);            // [dir PE | pos PE]  (src/features.py:868-874)
-      pe_eval<FP, true>(p, h, tt + QD);
-#pragma unroll
-      for (int q = 0; q < Q0 / 2; ++q) split_pack(tt[2 * q], tt[2 * q + 1], &iH[q], &iL[q]);
-      layer_16x3_direct<Q0 / 8, MT, false>(w + a.net16.w_off[0], b + a.net16.b_off[0], lane, iH, iL, bH, bL, nullptr);
-    }
-#pragma unroll 1
-    for (int l = 1; l + 1 < t.depth; ++l) {
-      asm volatile("" : "+v"(w), "+v"(b));      // keep the fragment loads inside the loop (see shade_mlp32_kernel)
-      layer_16x3_direct<KW, MT, false>(w + a.net16.w_off[l], b + a.net16.b_off[l], lane, bH, bL, aH, aL, nullptr);
-#pragma unroll
-      for (int i = 0; i < W / 4; ++i) {
-        bH[i] = aH[i];
-        bL[i] = aL[i];
-      }
-    }
-    layer_16x3_direct<KW, 4, true>(w + a.net16.w_off[t.depth - 1], b + a.net16.b_off[t.depth - 1], lane, bH, bL, nullptr, nullptr, out);
+    for (int q = 0; q < Q0 / 2; ++q) split_pack(tt[2 * q], tt[2 * q + 1], &iH[q], &iL[q]);
+    layer_16x3_staged<BUF, Q0 / 8, MT, false>(st, br, a.net16.w_off[0], bias_of(0), lane, iH, iL, bH, bL, nullptr, a.net16.w_off[1], 2 * KW);
   }
+#pragma unroll 1
+  for (int l = 1; l + 1 < t.depth; ++l) {
+    layer_16x3_staged<BUF, KW, MT, false>(st, br, a.net16.w_off[l], bias_of(l), lane, bH, bL, aH, aL, nullptr, a.net16.w_off[l + 1], 2 * KW);
+#pragma unroll
+    for (int i = 0; i < W / 4; ++i) {
+      bH[i] = aH[i];
+      bL[i] = aL[i];
+    }
+  }
+  const int ll = t.depth - 1;
+  layer_16x3_staged<BUF, KW, 4, true>(st, br, a.net16.w_off[ll], bias_of(ll), lane, bH, bL, nullptr, nullptr, out, 0, 0);
   if (a.fused_select) {
     // A4 in the epilogue, as in sample_mlp16x3_kernel: the 128 raw outputs of ray j sit in lanes j and j + 32 (k_select_pair.hip.hpp)
-    const uint32_t sel_stage = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(stage_mem)) + (STAGED ? 2 * BUF : 0) + wave * kPairLdsBytesPerWave + lane * 16;
-    float z = 0.f;
-#pragma unroll
-    for (int i = 0; i < 64; ++i) z = __builtin_fmaf(out[i], 0.f, z);    // NaN iff some output is inf / NaN (fp16 range left)
-    const bool bad_ray = (z != z) | (pair_xchg(static_cast<uint32_t>(z != z)) != 0u);
+    const uint32_t sel_stage = pair_stage_addr(stage_mem + 2 * BUF, wave, lane);
+    const bool bad_ray = outputs_nonfinite(out);
     if (bad_ray && valid && h == 0 && a.overflow_flag) atomicAdd(a.overflow_flag, 1);
     pair_epilogue<false>(out, lane, local, valid, sel_stage, a.sel);      // never pass 2 of the guarded selection
   }
   if (valid) {
-    if (a.oracle_out) {
+    if (a.oracle_out) {      // store_oracle_row spelt out: through the helper this kernel gains or loses an instruction
       float* o = a.oracle_out + static_cast<size_t>(local) * kBins;
       bool bad = false;
 #pragma unroll
@@ -645,15 +495,9 @@ __global__ __launch_bounds__(256, (STAGED && W <= 128 && FP <= 10) ? 2 : 1) void
       const bool bad_ray = bad | (pair_xchg(static_cast<uint32_t>(bad)) != 0u);      // an activation left the fp16 range
       if (bad_ray && h == 0 && a.overflow_flag) atomicAdd(a.overflow_flag, 1);
     }
-    if (a.rays_out) {
-      float ro[3] = {p[0], p[1], p[2]}, rd[3] = {nds[0], nds[1], nds[2]};
-      if (a.g.use_ndc) ndc_ray(a.g, p, nds, ro, rd);
-      float4* r = reinterpret_cast<float4*>(a.rays_out + static_cast<size_t>(local) * 8);
-      if (h == 0) r[0] = make_float4(ro[0], ro[1], ro[2], 0.f);
-      else r[1] = make_float4(rd[0], rd[1], rd[2], 0.f);
-    }
+    if (a.rays_out) store_ray_record(a, local, h, p, nds);
   }
-  if constexpr (STAGED) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // no LDS-DMA may outlive the workgroup's LDS allocation (see above)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // no LDS-DMA may outlive the workgroup's LDS allocation (see above)
 }
 
 }  // namespace adanerf

@@ -87,11 +87,8 @@ __global__ __launch_bounds__(256) void sample_mlp_gen_kernel(SampleArgs a, Gener
   const int local = blk * 32 + j;
   const bool valid = local < a.n_rays;
   const int ray = a.first_ray + (valid ? local : a.n_rays - 1);
-  int col, row;
-  ray_pixel(a.g, ray, &col, &row);
   float nds[3], p[3], u[3];
-  gen_ray(a.g, col, row, nds, p);
-  unit3(nds, u);
+  sample_ray(a.g, ray, nds, p, u);
 
   float in0[Q0], bufA[QW], bufB[QW];
   pe_eval<FD, true>(u, h, in0);          // [dir PE | pos PE]  (src/features.py:868-874)
@@ -243,11 +240,8 @@ __global__ __launch_bounds__(256) void sample_mlp_gen_wide_kernel(SampleArgs a, 
   const int local = blk * 16 + j;
   const bool valid = local < a.n_rays;
   const int ray = a.first_ray + (valid ? local : a.n_rays - 1);
-  int col, row;
-  ray_pixel(a.g, ray, &col, &row);
   float nds[3], p[3], u[3];
-  gen_ray(a.g, col, row, nds, p);
-  unit3(nds, u);
+  sample_ray(a.g, ray, nds, p, u);
 
   float bufA[QW], bufB[QW];
   {

@@ -1,5 +1,5 @@
-// A5 + A6: 16-bit MFMA engine (LDS weight ring, layer_16), the fused PE + shading MLP kernels shade_mlp16_kernel /
-// shade_mlp32_kernel and the debug kernel shade_features_kernel.
+// A5 + A6: 16-bit MFMA engine (LDS weight ring; layer_16 for one 32-sample block per wave, layer_16x2 for two), the fused PE + shading
+// MLP kernels shade_mlp16x2_kernel / shade_mlp32_kernel and the debug kernel shade_features_kernel.
 // Device code only (gfx950, wave64); part of kernels.hip.hpp.
 #pragma once
 #include "k_common.hip.hpp"
@@ -67,7 +67,7 @@ struct Fp16 {
 // across the barrier (never vmcnt(0) in the loop).  Each wave keeps the current chunk's 8
 // fragments in registers and re-fills fragment i from the NEXT chunk right after the MFMA that
 // consumed it, so LDS latency hides behind the other 7 MFMAs.
-// Ring geometry, register ring depth, stagger / DMA grouping and the timing-ablation bits: tuning.hpp.
+// Ring geometry, register ring depth and the timing-ablation bits: tuning.hpp.
 using tune::kRegFrags;
 constexpr int kShadeFrags16 = 32 + 4 * 128 + 160 + 2 * 128 + 144 + 72 + 8;   // 1184 per pass (FP=10, FD=4)
 constexpr int kShadeBiasFloats = 8 * 256 + 288 + 128 + 32;                     // 2496
@@ -92,7 +92,7 @@ struct WStream {
   uint32_t rd_next;      // LDS byte address of (next chunk, this lane)
   uint32_t lds_base;     // LDS byte address of the ring
   uint32_t grp;          // 0: this wave synchronises at chunk position 0, 1: at position CF / 2 (see ws_sync)
-  uint32_t issuer;       // this wave issues LDS-DMA pieces (all waves, or one group only: tune::kDmaGroup)
+  uint32_t issuer;       // this wave issues LDS-DMA pieces (all waves, or one group only: sample_mlp16_kernel)
   uint32_t dma_lds;      // the chunk being copied: LDS byte address of this wave's first piece (M0 of its LPW copies) ...
   uint32_t dma_goff;     // ... and the stream byte offset of that piece (scalar offset of its LPW copies); set at the wave's synchronisation point
   bool stag;             // the workgroup runs its two wave groups half a chunk apart (compile-time constant per kernel)
@@ -153,14 +153,14 @@ __device__ __forceinline__ void ws_issue(WStream<CF, RS, LPW, NR>& st, uint32_t 
 // Synchronisation point k of the ring: own pieces of chunk k+1 have landed (<= (RS-3) LPW younger DMAs outstanding);
 // barrier => chunk k+1 is complete in LDS for every wave and every wave has consumed chunk k-1 (its MFMAs were issued
 // before the barrier, so its ds_reads returned) => refill the slot of chunk k-1 with chunk k+RS-1.
-// Waves of group 0 reach it at fragment position 0 of chunk k, waves of group 1 at position CF / 2 of chunk k (tune::kStagger):
+// Waves of group 0 reach it at fragment position 0 of chunk k, waves of group 1 at position CF / 2 of chunk k (a staggered workgroup):
 // the two waves that share a SIMD (wave i and wave i + 4 of an 8-wave workgroup) then run half an output tile apart, so
 // one of them is issuing MFMAs while the other is in its bias-read / epilogue / DMA-issue phase, instead of both hitting
 // those phases in the same cycles (a workgroup barrier per chunk otherwise keeps all eight waves in lockstep).  Both
 // groups see the same guarantees: a wave of group 1 is at most half a chunk ahead, i.e. still inside chunk k.
 // see ws_position
 __device__ __forceinline__ void ws_skip_pad() {
-  if (tune::kSkipPad >= 0) asm volatile("s_nop %0" ::"n"(tune::kSkipPad < 0 ? 0 : tune::kSkipPad) : "memory");
+  asm volatile("s_nop %0" ::"n"(tune::kSkipPad) : "memory");
 }
 
 template <int ABL, int CF, int RS, int LPW, int NR>
@@ -290,14 +290,9 @@ __device__ __forceinline__ void pe_pack(const float x[3], int h, uint32_t* out) 
 struct BiasRegs {
   f32x4 b0, b1, b2, b3;
 };
-// issue now, consume later: the reads stay in flight behind the MFMAs of the current tile
-__device__ __forceinline__ void lds_bias_issue(uint32_t byte_addr, BiasRegs& r) {
-  asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:16\n\tds_read_b128 %2, %4 offset:32\n\tds_read_b128 %3, %4 offset:48"
-               : "=&v"(r.b0), "=&v"(r.b1), "=&v"(r.b2), "=&v"(r.b3)
-               : "v"(byte_addr));
-}
-// The same request with the two LDS addresses every fragment re-fill of the wave is computed from passed through the statement ("+v"): a
-// re-fill issued behind it in program order cannot be scheduled in front of it, which is what a COUNTED wait for the block relies on
+// Issue now, consume later: the reads stay in flight behind the MFMAs of the current tile.  The two LDS addresses every fragment re-fill
+// of the wave is computed from are passed through the statement ("+v"): a re-fill issued behind it in program order cannot be scheduled
+// in front of it, which is what a COUNTED wait for the block relies on
 // (lds_bias_take<YOUNGER>: the re-fills of the tile are younger than the request).
 __device__ __forceinline__ void lds_bias_issue(uint32_t byte_addr, BiasRegs& r, uint32_t& rd0, uint32_t& rd1) {
   asm volatile("ds_read_b128 %0, %6\n\tds_read_b128 %1, %6 offset:16\n\tds_read_b128 %2, %6 offset:32\n\tds_read_b128 %3, %6 offset:48"
@@ -471,87 +466,6 @@ __device__ __forceinline__ void lds_stash_read(uint32_t byte_addr, uint32_t* v) 
   }
 }
 
-// A5+A6, 16-bit MFMA path.  Workgroup = WAVES waves x 32 samples; persistent over tiles; the weight
-// stream is cyclic so DMA prefetch runs across tile boundaries.  WAVES = 4 with two workgroups per CU
-// (two waves per SIMD from DIFFERENT workgroups): each workgroup has its own ring and barriers, so the
-// two waves sharing a SIMD are not in lockstep and one computes while the other waits at its barrier.
-template <class ET, int FP, int FD, int WAVES>
-__global__ __launch_bounds__(WAVES * 64, WAVES == 8 ? 2 : 2) void shade_mlp16_kernel(ShadeArgs a) {
-  static_assert(FP == 10 && FD == 4, "fragment positions below assume the 10-4 shading encoding");
-  static_assert(WAVES == 4 || WAVES == 8, "chunk = 8 fragments");
-  constexpr int QP = pe_slots(FP), QD = pe_slots(FD);
-  constexpr bool kOneGroupDma = tune::kDmaGroup >= 0 && WAVES == 8;
-  constexpr int TILE = WAVES * 32, CF = tune::kChunkFrags, RS = tune::kRingSlots, LPW = kOneGroupDma ? CF / 4 : CF / WAVES;
-  constexpr int kRingBytes = CF * RS * 1024;
-  static_assert(CF % WAVES == 0 && CF % kRegFrags == 0 && kShadeFrags16 % CF == 0 && CF % 8 == 0 && CF <= 32, "chunk geometry");
-  typedef WStream<CF, RS, LPW> WS;
-  constexpr int kStashBytes = WAVES * (QP / 8 + QD / 8) * 1024;      // PE slots computed once per tile and parked in LDS
-  __shared__ __attribute__((aligned(16))) char lds[kRingBytes + kShadeBiasFloats * 4 + kStashBytes];
-  const int lane = lane_id();
-  const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x) >> 6);
-  const int j = lane & 31, h = lane >> 5;
-  const uint32_t stash = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(lds)) + kRingBytes + kShadeBiasFloats * 4 +
-                         wave * (QP / 8 + QD / 8) * 1024 + lane * 16;
-  int total = a.total ? *a.total : a.max_samples;
-  if (total > a.max_samples) total = a.max_samples;
-  const int ntiles = (total + TILE - 1) / TILE;
-  if (static_cast<int>(blockIdx.x) >= ntiles) return;    // workgroup-uniform
-
-  {
-    float* lds_bias = reinterpret_cast<float*>(lds + kRingBytes);
-    for (int i = threadIdx.x; i < kShadeBiasFloats; i += blockDim.x) lds_bias[i] = a.net.bias[i];
-  }
-  __syncthreads();
-  WS st;
-  ws_start(st, a.net.w, kShadeFrags16 * 1024, lds, kOneGroupDma ? (wave & 3) : wave, lane,
-           (tune::kStagger && WAVES == 8) ? (wave >> 2) : -1, !kOneGroupDma || (wave >> 2) == tune::kDmaGroup);
-
-  // LDS byte address of the bias blocks of this lane-half
-  const uint32_t bias0 = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(lds)) + kRingBytes + h * 64;
-  const uint32_t* bo = a.net.b_off;
-  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int s = tile * TILE + wave * 32 + j;
-    uint32_t hA[64], hB[64];
-    {
-      float x[3], dpe[3];
-      load_sample(a, s, total, x, dpe);
-      uint32_t pts[QP / 2];
-      pe_pack<ET, FP>(x, h, pts);
-      uint32_t dirs[QD / 2];
-      pe_pack<ET, FD>(dpe, h, dirs);
-      lds_stash_write<QP / 8>(stash, pts);
-      lds_stash_write<QD / 8>(stash + (QP / 8) * 1024, dirs);
-      layer_16<ET, WS, QP / 8, 0, 8, true, 0>(st, bias0 + bo[0] * 4, lane, pts, pts, hA);
-    }
-#pragma unroll 1
-    for (int l = 1; l <= 3; l += 2) {
-      layer_16<ET, WS, 16, 0, 8, true, 0>(st, bias0 + bo[l] * 4, lane, hA, hA, hB);
-      layer_16<ET, WS, 16, 0, 8, true, 0>(st, bias0 + bo[l + 1] * 4, lane, hB, hB, hA);
-    }
-    {
-      // the skip connection takes the 32 position slots back from the LDS stash instead of holding 16 VGPRs across layers 1-4
-      uint32_t pts[QP / 2];
-      lds_stash_read<QP / 8>(stash, pts);
-      layer_16<ET, WS, QP / 8, 16, 8, true, 0>(st, bias0 + bo[5] * 4, lane, pts, hA, hB);   // cat([pts, h])
-    }
-    layer_16<ET, WS, 16, 0, 8, true, 0>(st, bias0 + bo[6] * 4, lane, hB, hB, hA);
-    layer_16<ET, WS, 16, 0, 8, true, 0>(st, bias0 + bo[7] * 4, lane, hA, hA, hB);
-    f32x16 alpha_tile;
-    layer_16<ET, WS, 16, 0, 9, false, 0, 8>(st, bias0 + bo[8] * 4, lane, hB, hB, hA, &alpha_tile);      // feature (+alpha row)
-    const float alpha = alpha_tile[0];
-    {
-      uint32_t dirs[QD / 2];
-      lds_stash_read<QD / 8>(stash + (QP / 8) * 1024, dirs);
-      layer_16<ET, WS, 16, QD / 8, 4, true, (32 + 4 * 128 + 160 + 2 * 128 + 144) % CF>(st, bias0 + bo[9] * 4, lane, hA, dirs, hB);             // cat([feature, dir])
-    }
-    f32x16 rgb_tile;
-    layer_16<ET, WS, 8, 0, 1, false, (32 + 4 * 128 + 160 + 2 * 128 + 144 + 72) % CF, 0>(st, bias0 + bo[10] * 4, lane, hB, hB, hA, &rgb_tile);
-    if (h == 0 && s < total)
-      store_raw(a, s, rgb_tile[0], rgb_tile[1], rgb_tile[2], alpha);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup's LDS allocation
-}
-
 // ---- two sample blocks per wave -------------------------------------------------------------------------------------------
 // layer_16 for TWO 32-sample column blocks held by one wave: every weight fragment read from LDS feeds two MFMAs (one per
 // block), so the LDS operand traffic, the DMA issue and the barriers per MFMA are half of layer_16's.  The price is the register
@@ -559,7 +473,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 8 ? 2 : 2) void shade_mlp16_ke
 // instruction stream hides latencies: the two accumulator chains alternate (no dependent back-to-back MFMAs), the bias block of
 // tile m + 1 is requested while tile m computes, and the epilogue of tile m - 1 (both blocks: 8 quads) is spread over the
 // first k-steps of tile m.  Both chains start from the bias registers as the C operand (no copies).
-// A finished tile pair (both blocks) whose conversion has not run yet: tune::kShadeCarry hands the LAST tile of a layer to the next layer, which
+// A finished tile pair (both blocks) whose conversion has not run yet: the LAST tile of a layer is handed to the next layer, which
 // converts it under the MFMAs of its own first tile (the outputs feed the last two k-steps of that tile's input segment) instead of at the
 // layer boundary with the matrix pipe idle.
 struct PendingTile2 {
@@ -578,13 +492,13 @@ __device__ __forceinline__ void layer_16x2(WS& st, uint32_t bias_addr, const uin
   constexpr int PER = (KS >= 8) ? 1 : (8 + KS - 1) / KS;      // epilogue quads of the previous tile per k-step
   constexpr bool kKeepAll = KEEP_F32_TILE == kKeepAllF32;     // every tile's raw accumulators go to keepA[m] / keepB[m] (the sampling net's 128 raw outputs)
   auto kept = [](int m) { return kKeepAll || KEEP_F32_TILE == m; };
-  constexpr bool kCarry = tune::kShadeCarry && !(ABL & 8);
+  constexpr bool kCarry = !(ABL & 8);
   constexpr bool kHasPend = kCarry && PEND_M >= 0;
   constexpr int PERP = 1;                                     // quads of a carried tile per k-step: all converted before the k-steps that read them
   static_assert(!kHasPend || KS >= 16, "a carried tile is consumed by the last two k-steps of a 16-k-step input segment, 6 k-steps behind its last conversion");
   static_assert(!CARRY_OUT || (KEEP_F32_TILE != MT - 1 && KEEP_F32_TILE != kKeepAllF32), "the kept tile is not converted");
   // LDS reads issued between a bias request and its use: the tile's KS fragment re-fills (none under ablation 2)
-  constexpr bool kCounted = tune::kBiasWaitCounted && tune::kSchedGroups && !(ABL & (2 | 4));
+  constexpr bool kCounted = !(ABL & (2 | 4));
   constexpr int kYounger = kCounted ? KS : 0;
   BiasRegs br;
   f32x16 pA, pB;
@@ -597,7 +511,7 @@ __device__ __forceinline__ void layer_16x2(WS& st, uint32_t bias_addr, const uin
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     f32x16 bias, accA, accB;
-    if (tune::kSchedGroups) __builtin_amdgcn_sched_barrier(0);      // one scheduling region per tile (the group solver's cost grows fast with the region)
+    __builtin_amdgcn_sched_barrier(0);      // one scheduling region per tile (the group solver's cost grows fast with the region)
     if (ABL & 4) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) bias[r] = 0.f;
@@ -619,7 +533,7 @@ __device__ __forceinline__ void layer_16x2(WS& st, uint32_t bias_addr, const uin
       // The previous tile's guards are taken in k-step E0: with a scheduling fence per k-step (below) a guard in k-step 0 sits right behind the tile's
       // first MFMA, one or two MFMAs after the accumulator's last write, and costs an `s_nop 6` per tile (hipcc counts an MFMA as ONE wait state of the 11 it
       // wants between the write and a VALU read); tune::kShadeGuardStep k-steps later the distance is there by itself.
-      constexpr int E0 = (tune::kShadeKstepFence && KS >= 8 + tune::kShadeGuardStep) ? tune::kShadeGuardStep : 0;
+      constexpr int E0 = KS >= 8 + tune::kShadeGuardStep ? tune::kShadeGuardStep : 0;
       if (m > 0 && !kept(m - 1) && !(ABL & 8) && s >= E0) {
         if (s == E0) {
           gA = mfma_guard<ET, RELU>(pA);
@@ -644,20 +558,18 @@ __device__ __forceinline__ void layer_16x2(WS& st, uint32_t bias_addr, const uin
           else if (q < 8) epilogue_quad_16<ET, PEND_RELU>(pB, PEND_M < 0 ? 0 : PEND_M, q - 4, pendB, gB);
         }
       }
-      if (tune::kSchedGroups) {
-        // pin the interleave the source describes: per k-step two MFMAs, the fragment re-fill, one epilogue quad (hipcc
-        // otherwise bunches a tile's re-fills and the previous tile's whole epilogue behind the first MFMAs of the tile)
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // MFMA
-        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);      // VALU
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // MFMA
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // DS read
-        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);      // VALU
-        // The clamped conversions are inline asm: no group mask matches them, so they float -- and hipcc sinks them to ONE wait state in front of the
-        // MFMA that reads their result (a VALU write the hazard recogniser cannot see needs 2: tests/test_host_cpu.py
-        // test_asm_conversions_are_two_wait_states_ahead_of_the_mfma_that_reads_them caught a carried tile's conversions there).  A scheduling barrier per
-        // k-step keeps every conversion in the k-step the source puts it in, k-steps away from its first reader.
-        if (tune::kShadeKstepFence) __builtin_amdgcn_sched_barrier(0);
-      }
+      // pin the interleave the source describes: per k-step two MFMAs, the fragment re-fill, one epilogue quad (hipcc
+      // otherwise bunches a tile's re-fills and the previous tile's whole epilogue behind the first MFMAs of the tile)
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // MFMA
+      __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);      // VALU
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // MFMA
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);      // DS read
+      __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);      // VALU
+      // The clamped conversions are inline asm: no group mask matches them, so they float -- and hipcc sinks them to ONE wait state in front of the
+      // MFMA that reads their result (a VALU write the hazard recogniser cannot see needs 2: tests/test_host_cpu.py
+      // test_asm_conversions_are_two_wait_states_ahead_of_the_mfma_that_reads_them caught a carried tile's conversions there).  A scheduling barrier per
+      // k-step keeps every conversion in the k-step the source puts it in, k-steps away from its first reader.
+      __builtin_amdgcn_sched_barrier(0);
     }
     if (kept(m)) {
       keepA[kKeepAll ? m : 0] = accA;
@@ -686,8 +598,8 @@ __device__ __forceinline__ void layer_16x2(WS& st, uint32_t bias_addr, const uin
   }
 }
 
-// A5+A6, 16-bit MFMA path, two sample blocks per wave (layer_16x2): workgroup = 4 waves (one per SIMD) x 64 samples = the same
-// 256-sample tile as shade_mlp16_kernel; same weight stream, ring and bias blocks.
+// A5+A6, 16-bit MFMA path, two sample blocks per wave (layer_16x2): workgroup = 4 waves (one per SIMD) x 64 samples = a 256-sample
+// tile, one workgroup per CU; persistent over tiles; the weight stream is cyclic so DMA prefetch runs across tile boundaries.
 template <class ET, int FP, int FD>
 __global__ __launch_bounds__(256) void shade_mlp16x2_kernel(ShadeArgs a) {
   static_assert(FP == 10 && FD == 4, "fragment positions below assume the 10-4 shading encoding");
@@ -719,7 +631,7 @@ __global__ __launch_bounds__(256) void shade_mlp16x2_kernel(ShadeArgs a) {
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int s0 = tile * TILE + wave * 64 + j, s1 = s0 + 32;
     uint32_t hA0[64], hB0[64], hA1[64], hB1[64];
-    PendingTile2 pend;      // a layer's last tile, converted under the next layer's first MFMAs (tune::kShadeCarry)
+    PendingTile2 pend;      // a layer's last tile, converted under the next layer's first MFMAs
     {
       float x[3], dpe[3];
       uint32_t pts0[QP / 2], pts1[QP / 2], dirs[QD / 2];

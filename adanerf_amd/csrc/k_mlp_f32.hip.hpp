@@ -1,5 +1,6 @@
-// fp32 MFMA MLP engine (v_mfma_f32_32x32x2_f32, activations fp32 in registers), the exact-fp32 sampling kernel
-// sample_mlp_kernel (A1+A2+A3) and the debug kernel ray_features_kernel.
+// fp32 MFMA MLP engine (v_mfma_f32_32x32x2_f32, activations fp32 in registers), the sampling kernels' arguments and shared ray I/O
+// (sample_ray, store_ray_record, store_oracle_row, outputs_nonfinite), the exact-fp32 sampling kernel sample_mlp_kernel (A1+A2+A3) and
+// the debug kernel ray_features_kernel.
 // Device code only (gfx950, wave64); part of kernels.hip.hpp.
 #pragma once
 #include "k_common.hip.hpp"
@@ -62,6 +63,57 @@ struct SampleArgs {
   const int32_t* n_list;
 };
 
+// ---- ray I/O of the sampling kernels (this file, k_generic_f32, k_sampling16, k_generic16) -----------------------------------------
+// Who uses which helper is decided on the assembly (tools/isa_diff.py, profiles/refactor_isa_identity.md): a kernel whose instruction
+// stream a helper would move keeps its own copy of that piece.  sample_ray: every sampling kernel and ray_features_kernel; the others:
+// 16-bit kernels only -- in the fp32 translation unit any change to the set of ray-record or oracle-row stores re-orders one division of
+// the NDC conversion in all three fp32 sampling kernels.
+// ray `ray` of the frame: direction nds (not normalised), sphere-exit point p, unit direction u
+__device__ __forceinline__ void sample_ray(const RayGenParams& g, int ray, float nds[3], float p[3], float u[3]) {
+  int col, row;
+  ray_pixel(g, ray, &col, &row);
+  gen_ray(g, col, row, nds, p);
+  unit3(nds, u);
+}
+
+// the ray's record in a.rays_out [n_rays,8] = (origin.xyz, 0, dir.xyz, 0), the NDC ray under use_ndc: a ray is held by two lanes (or
+// lane groups), `half` 0 writes the origin, the other the direction.  (The four 16-bit sampling kernels.)
+__device__ __forceinline__ void store_ray_record(const SampleArgs& a, int local, int half, const float p[3], const float nds[3]) {
+  float ro[3] = {p[0], p[1], p[2]}, rd[3] = {nds[0], nds[1], nds[2]};
+  if (a.g.use_ndc) ndc_ray(a.g, p, nds, ro, rd);
+  float4* r = reinterpret_cast<float4*>(a.rays_out + static_cast<size_t>(local) * 8);
+  if (half == 0) r[0] = make_float4(ro[0], ro[1], ro[2], 0.f);
+  else r[1] = make_float4(rd[0], rd[1], rd[2], 0.f);
+}
+
+// Lane half h's 64 of the ray's raw outputs to a.oracle_out [n_rays,128] (32-row form: value 16 m + 4 g + e of the half is bin
+// 32 m + 8 g + 4 h + e); at(i): value i.  An activation beyond the fp16 range (65504) shows up as inf / NaN here; a ray is owned by
+// lanes j and j + 32 (64 outputs each) and counted once in a.overflow_flag.  (sample_mlp16x3_kernel, sample_mlp16_kernel.)
+template <class At>
+__device__ __forceinline__ void store_oracle_row(const SampleArgs& a, int local, int h, At&& at) {
+  float* o = a.oracle_out + static_cast<size_t>(local) * kBins;
+  bool bad = false;
+#pragma unroll
+  for (int m = 0; m < 4; ++m)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const float4 v = make_float4(at(16 * m + 4 * g), at(16 * m + 4 * g + 1), at(16 * m + 4 * g + 2), at(16 * m + 4 * g + 3));
+      bad |= !(fabsf(v.x) < 3.0e38f) | !(fabsf(v.y) < 3.0e38f) | !(fabsf(v.z) < 3.0e38f) | !(fabsf(v.w) < 3.0e38f);
+      *reinterpret_cast<float4*>(o + 32 * m + 8 * g + 4 * h) = v;
+    }
+  const bool bad_ray = bad | (pair_xchg(static_cast<uint32_t>(bad)) != 0u);
+  if (bad_ray && h == 0 && a.overflow_flag) atomicAdd(a.overflow_flag, 1);
+}
+
+// in front of the fused selection: did the ray (this lane's 64 outputs or its partner's) leave the fp16 range?
+// (sample_mlp16_kernel, sample_mlp16x3_gen_kernel.)
+__device__ __forceinline__ bool outputs_nonfinite(const float (&out)[64]) {
+  float z = 0.f;
+#pragma unroll
+  for (int i = 0; i < 64; ++i) z = __builtin_fmaf(out[i], 0.f, z);    // NaN iff some output is inf / NaN
+  return (z != z) | (pair_xchg(static_cast<uint32_t>(z != z)) != 0u);
+}
+
 // A1+A2+A3.  One wave = one block of 32 rays; 4 waves per workgroup (one per SIMD, up to 512 VGPRs).
 template <int FP, int FD>
 __global__ __launch_bounds__(256) void sample_mlp_kernel(SampleArgs a) {
@@ -74,11 +126,8 @@ __global__ __launch_bounds__(256) void sample_mlp_kernel(SampleArgs a) {
   const bool valid = local < a.n_rays;
   const int ray = a.first_ray + (valid ? local : a.n_rays - 1);
 
-  int col, row;
-  ray_pixel(a.g, ray, &col, &row);
   float nds[3], p[3], u[3];
-  gen_ray(a.g, col, row, nds, p);
-  unit3(nds, u);
+  sample_ray(a.g, ray, nds, p, u);
 
   constexpr int QD = pe_slots(FD), QP = pe_slots(FP), Q0 = QD + QP;
   float bufA[128], bufB[128];
@@ -124,11 +173,8 @@ static __global__ __launch_bounds__(256) void ray_features_kernel(RayGenParams g
                                                            int ray_samples, const float* rsi_z, float rsi_d1, int FP, int FD) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_rays) return;
-  int col, row;
-  ray_pixel(g, first_ray + i, &col, &row);
   float nds[3], p[3], u[3];
-  gen_ray(g, col, row, nds, p);
-  unit3(nds, u);
+  sample_ray(g, first_ray + i, nds, p, u);
   if (feat) {
     const int ND = 3 + 6 * FD, NP = 3 + 6 * FP;
     float* f = feat + static_cast<size_t>(i) * (ND + NP + ray_samples * NP);

@@ -45,7 +45,7 @@ __device__ __forceinline__ void epilogue_pair_16x3(const f32x16& acc, const f32x
 }
 
 
-// A finished output tile whose epilogue (combine, ReLU, hi / lo' split) has not run yet.  tune::kSplitCarry: the LAST tile of a hidden layer
+// A finished output tile whose epilogue (combine, ReLU, hi / lo' split) has not run yet.  The LAST tile of a hidden layer
 // is handed to the next layer this way and converted under the MFMAs of that layer's first tile (its outputs feed k-steps 14 and 15 of the
 // next layer only), instead of 96 VALU instructions + the MFMA -> VALU wait states with the matrix pipe idle at every layer boundary.
 struct PendingTile3 {
@@ -60,9 +60,9 @@ __device__ __forceinline__ void layer_16x3(WS& st, uint32_t bias_addr, int lane,
   //  - the bias block of tile m+1 is requested right after tile m's accumulators are initialised,
   //  - the epilogue of tile m-1 is spread, one accumulator pair per k-step, over tile m's MFMAs.
   constexpr bool PIPE = !(tune::kAblateSample & 64);
-  constexpr bool CARRY = tune::kSplitCarry && PIPE && !(tune::kAblateSample & 8);
+  constexpr bool CARRY = PIPE && !(tune::kAblateSample & 8);
   static_assert(!HAS_PEND || KS == 16, "a pending tile writes inputs 56 .. 63: the k-steps 14 and 15 of a 256-wide layer");
-  constexpr bool kCounted = tune::kSplitBiasCounted && tune::kSchedGroupsSampling && !(tune::kAblateSample & 2);
+  constexpr bool kCounted = !(tune::kAblateSample & 2);
   BiasRegs br;
   f32x16 pacc, pcross;   // previous tile's accumulators (PIPE)
   if (HAS_PEND && CARRY) {
@@ -73,7 +73,7 @@ __device__ __forceinline__ void layer_16x3(WS& st, uint32_t bias_addr, int lane,
 #pragma unroll
   for (int m = 0; m < MT; ++m) {
     f32x16 acc, cross;
-    if (tune::kSchedGroupsSampling) __builtin_amdgcn_sched_barrier(0);      // one scheduling region per tile
+    __builtin_amdgcn_sched_barrier(0);      // one scheduling region per tile
     if (tune::kAblateSample & 4) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -111,18 +111,16 @@ __device__ __forceinline__ void layer_16x3(WS& st, uint32_t bias_addr, int lane,
           }
         }
       }
-      if (tune::kSchedGroupsSampling) {
-        // pin the k-step's interleave: three MFMAs, two fragment re-fills, the VALU of one epilogue pair spread between them
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, tune::kSgbValuSampling, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, tune::kSgbValuSampling, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x002, tune::kSgbValuSampling, 0);
-        if (tune::kSplitKstepFence) __builtin_amdgcn_sched_barrier(0);
-      }
+      // pin the k-step's interleave: three MFMAs, two fragment re-fills, the VALU of one epilogue pair spread between them
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x002, tune::kSgbValuSampling, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x002, tune::kSgbValuSampling, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(0x002, tune::kSgbValuSampling, 0);
+      __builtin_amdgcn_sched_barrier(0);
     }
     if ((tune::kAblateSample & 8) && !LAST) {
       asm volatile("" ::"v"(acc), "v"(cross));
@@ -134,7 +132,7 @@ __device__ __forceinline__ void layer_16x3(WS& st, uint32_t bias_addr, int lane,
       pacc = acc;
       pcross = cross;
     } else if (CARRY && !LAST) {
-      static_assert(LAST || !tune::kSplitCarry || MT == 8, "the carried tile is tile 7");
+      static_assert(LAST || MT == 8, "the carried tile is tile 7");
       pend.acc = acc;
       pend.cross = cross;
     } else {
@@ -166,8 +164,7 @@ __global__ __launch_bounds__(256) void sample_mlp16x3_kernel(SampleArgs a) {
   const int ntiles = (n_rays + TILE - 1) / TILE;
   if (static_cast<int>(blockIdx.x) >= ntiles) return;
   // staging block of the fused selection (pair_emit), wave-private
-  const uint32_t sel_stage = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(lds)) + kRingBytes + kBiasFloats * 4 +
-                             wave * kPairLdsBytesPerWave + lane * 16;
+  const uint32_t sel_stage = pair_stage_addr(lds + kRingBytes + kBiasFloats * 4, wave, lane);
 
   {
     float* lds_bias = reinterpret_cast<float*>(lds + kRingBytes);
@@ -186,11 +183,8 @@ __global__ __launch_bounds__(256) void sample_mlp16x3_kernel(SampleArgs a) {
     const int lidx = valid ? local : n_rays - 1;
     const int entry = a.ray_list ? a.ray_list[lidx] : 0;      // refinement pass: ray id (+ kRefineAuditBit), kept for the epilogue
     const int ray = a.first_ray + (a.ray_list ? (entry & kRefineRayMask) : lidx);
-    int col, row;
-    ray_pixel(a.g, ray, &col, &row);
     float nds[3], p[3], u[3];
-    gen_ray(a.g, col, row, nds, p);
-    unit3(nds, u);
+    sample_ray(a.g, ray, nds, p, u);
 
     uint32_t aH[64], aL[64], bH[64], bL[64];
     if (tune::kAblateSample & 256) {      // timing ablation (wrong results): no encoding, inputs = cheap functions of the ray
@@ -206,7 +200,7 @@ __global__ __launch_bounds__(256) void sample_mlp16x3_kernel(SampleArgs a) {
 #pragma unroll
       for (int q = 0; q < Q0 / 2; ++q) split_pack(t[2 * q], t[2 * q + 1], &aH[q], &aL[q]);
     }
-    PendingTile3 pend;      // a hidden layer's last tile, converted under the next layer's first MFMAs (tune::kSplitCarry)
+    PendingTile3 pend;      // a hidden layer's last tile, converted under the next layer's first MFMAs
     layer_16x3<WS, Q0 / 8, 8, false, 0, false>(st, bias0 + bo[0] * 4, lane, aH, aL, bH, bL, nullptr, pend);
 #pragma unroll 1
     for (int l = 1; l <= 5; l += 2) {
@@ -218,6 +212,7 @@ __global__ __launch_bounds__(256) void sample_mlp16x3_kernel(SampleArgs a) {
 
     if (a.fused_select) {
       // A4 in the epilogue: the 128 raw outputs of ray j sit in lanes j and j + 32 (k_select_pair.hip.hpp)
+      // (outputs_nonfinite spelt out: through the helper the last tile's epilogue comes out re-ordered, here and in sample_mlp16x2_kernel)
       float z = 0.f;
 #pragma unroll
       for (int i = 0; i < 64; ++i) z = __builtin_fmaf(out[i], 0.f, z);    // NaN iff some output is inf / NaN (fp16 range left)
@@ -231,29 +226,8 @@ __global__ __launch_bounds__(256) void sample_mlp16x3_kernel(SampleArgs a) {
       }
     }
     if (valid) {
-      if (a.oracle_out) {
-        float* o = a.oracle_out + static_cast<size_t>(local) * kBins;
-        bool bad = false;
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-          for (int g = 0; g < 4; ++g) {
-            float4 v = make_float4(out[16 * m + 4 * g], out[16 * m + 4 * g + 1], out[16 * m + 4 * g + 2], out[16 * m + 4 * g + 3]);
-            bad |= !(fabsf(v.x) < 3.0e38f) | !(fabsf(v.y) < 3.0e38f) | !(fabsf(v.z) < 3.0e38f) | !(fabsf(v.w) < 3.0e38f);
-            *reinterpret_cast<float4*>(o + 32 * m + 8 * g + 4 * h) = v;
-          }
-        // an activation beyond the fp16 range (65504) shows up as inf/NaN here; a ray is owned by lanes j and j + 32
-        // (64 outputs each), counted once
-        const bool bad_ray = bad | (pair_xchg(static_cast<uint32_t>(bad)) != 0u);
-        if (bad_ray && h == 0 && a.overflow_flag) atomicAdd(a.overflow_flag, 1);
-      }
-      if (a.rays_out) {
-        float ro[3] = {p[0], p[1], p[2]}, rd[3] = {nds[0], nds[1], nds[2]};
-        if (a.g.use_ndc) ndc_ray(a.g, p, nds, ro, rd);
-        float4* r = reinterpret_cast<float4*>(a.rays_out + static_cast<size_t>(local) * 8);
-        if (h == 0) r[0] = make_float4(ro[0], ro[1], ro[2], 0.f);
-        else r[1] = make_float4(rd[0], rd[1], rd[2], 0.f);
-      }
+      if (a.oracle_out) store_oracle_row(a, local, h, [&](int i) { return out[i]; });
+      if (a.rays_out) store_ray_record(a, local, h, p, nds);
     }
   }
   if (a.fused_select && a.ray_list) guard_flush(a.sel, gacc, lane);
@@ -279,8 +253,7 @@ constexpr int sample16_frags() { return ((pe_slots(FD) + pe_slots(FP)) / 8) * 8 
 template <int FP, int FD>
 __global__ __launch_bounds__(512, 2) void sample_mlp16_kernel(SampleArgs a) {
   constexpr int QD = pe_slots(FD), QP = pe_slots(FP), Q0 = QD + QP;
-  constexpr bool kOneGroupDma = tune::kDmaGroup >= 0;
-  constexpr int WAVES = 8, CF = 16, RS = 4, LPW = kOneGroupDma ? CF / 4 : CF / WAVES, TILE = WAVES * 32;   // 880 fragments = 55 chunks of 16
+  constexpr int WAVES = 8, CF = 16, RS = 4, LPW = CF / 4, TILE = WAVES * 32;   // 880 fragments = 55 chunks of 16; waves 0-3 copy the pieces
   constexpr int F0 = (Q0 / 8) * 8, FRAGS = sample16_frags<FP, FD>();
   static_assert(F0 % CF == 0 && FRAGS % CF == 0 && CF % WAVES == 0 && CF % kRegFrags == 0 && CF <= 32, "chunk geometry");
   typedef WStream<CF, RS, LPW> WS;
@@ -299,16 +272,14 @@ __global__ __launch_bounds__(512, 2) void sample_mlp16_kernel(SampleArgs a) {
   const bool has_partial = static_cast<int>(blockIdx.x) * k < rem;          // workgroup-uniform
   const int rounds = q + (has_partial ? 1 : 0);
   if (rounds == 0) return;
-  const uint32_t sel_stage = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(lds)) + kRingBytes + kBiasFloats * 4 +
-                             wave * kPairLdsBytesPerWave + lane * 16;
+  const uint32_t sel_stage = pair_stage_addr(lds + kRingBytes + kBiasFloats * 4, wave, lane);
   {
     float* lds_bias = reinterpret_cast<float*>(lds + kRingBytes);
     for (int i = threadIdx.x; i < kBiasFloats; i += blockDim.x) lds_bias[i] = a.net16.bias[i];
   }
   __syncthreads();
   WS st;
-  ws_start(st, a.net16.w, FRAGS * 1024, lds, kOneGroupDma ? (wave & 3) : wave, lane, tune::kStagger ? (wave >> 2) : -1,
-           !kOneGroupDma || (wave >> 2) == tune::kDmaGroup);
+  ws_start(st, a.net16.w, FRAGS * 1024, lds, wave & 3, lane, wave >> 2, (wave >> 2) == 0);      // staggered; group 0 issues the DMA
   const uint32_t bias0 = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(lds)) + kRingBytes + h * 64;
   const uint32_t* bo = a.net16.b_off;
 
@@ -325,18 +296,9 @@ __global__ __launch_bounds__(512, 2) void sample_mlp16_kernel(SampleArgs a) {
     const int local = wt * 32 + j;
     const bool valid = local < a.n_rays;
     const int ray = a.first_ray + (valid ? local : a.n_rays - 1);
-    int col, row;
-    ray_pixel(a.g, ray, &col, &row);
     float nds[3], p[3], u[3];
-    gen_ray(a.g, col, row, nds, p);
-    unit3(nds, u);
-    if (valid && a.rays_out) {
-      float ro[3] = {p[0], p[1], p[2]}, rd[3] = {nds[0], nds[1], nds[2]};
-      if (a.g.use_ndc) ndc_ray(a.g, p, nds, ro, rd);
-      float4* r = reinterpret_cast<float4*>(a.rays_out + static_cast<size_t>(local) * 8);
-      if (h == 0) r[0] = make_float4(ro[0], ro[1], ro[2], 0.f);
-      else r[1] = make_float4(rd[0], rd[1], rd[2], 0.f);
-    }
+    sample_ray(a.g, ray, nds, p, u);
+    if (valid && a.rays_out) store_ray_record(a, local, h, p, nds);
     uint32_t hA[64], hB[64];
     {
       float t[Q0];
@@ -344,8 +306,8 @@ __global__ __launch_bounds__(512, 2) void sample_mlp16_kernel(SampleArgs a) {
 #pragma unroll
         for (int q = 0; q < Q0; ++q) t[q] = (q & 1) ? u[q % 3] : p[q % 3];
       } else {
-        pe_eval<FD, !(tune::kAblateSample & 128) && !tune::kFastPeFp16Pass>(u, h, t);            // [dir PE | pos PE]  (src/features.py:868-874)
-        pe_eval<FP, !(tune::kAblateSample & 128) && !tune::kFastPeFp16Pass>(p, h, t + QD);
+        pe_eval<FD, false>(u, h, t);            // [dir PE | pos PE]  (src/features.py:868-874); one v_sin_f32 per slot (tuning.hpp)
+        pe_eval<FP, false>(p, h, t + QD);
       }
       uint32_t in0[Q0 / 2];
 #pragma unroll
@@ -361,31 +323,14 @@ __global__ __launch_bounds__(512, 2) void sample_mlp16_kernel(SampleArgs a) {
     layer_16<Fp16, WS, 16, 0, 4, false, F0 % CF, kKeepAllF32>(st, bias0 + bo[7] * 4, lane, hA, hA, hB, out);
     if (a.fused_select) {
       float x[64];
-      float z = 0.f;
 #pragma unroll
-      for (int i = 0; i < 64; ++i) {
-        x[i] = out[i >> 4][i & 15];
-        z = __builtin_fmaf(x[i], 0.f, z);
-      }
-      const bool bad_ray = (z != z) | (pair_xchg(static_cast<uint32_t>(z != z)) != 0u);
+      for (int i = 0; i < 64; ++i) x[i] = out[i >> 4][i & 15];
+      const bool bad_ray = outputs_nonfinite(x);
       // guard mode: a non-finite ray goes to the refinement pass, which does the counting
       if (bad_ray && valid && h == 0 && a.overflow_flag && !a.sel.guard_mask) atomicAdd(a.overflow_flag, 1);
       pair_epilogue<false>(x, lane, local, valid, sel_stage, a.sel, bad_ray);
     }
-    if (valid && a.oracle_out) {
-      float* o = a.oracle_out + static_cast<size_t>(local) * kBins;
-      bool bad = false;
-#pragma unroll
-      for (int m = 0; m < 4; ++m)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const float4 v = make_float4(out[m][4 * g], out[m][4 * g + 1], out[m][4 * g + 2], out[m][4 * g + 3]);
-          bad |= !(fabsf(v.x) < 3.0e38f) | !(fabsf(v.y) < 3.0e38f) | !(fabsf(v.z) < 3.0e38f) | !(fabsf(v.w) < 3.0e38f);
-          *reinterpret_cast<float4*>(o + 32 * m + 8 * g + 4 * h) = v;
-        }
-      const bool bad_ray = bad | (pair_xchg(static_cast<uint32_t>(bad)) != 0u);   // lanes j and j + 32 own one ray
-      if (bad_ray && h == 0 && a.overflow_flag) atomicAdd(a.overflow_flag, 1);    // an activation left the fp16 range
-    }
+    if (valid && a.oracle_out) store_oracle_row(a, local, h, [&](int i) { return out[i >> 4][i & 15]; });
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
@@ -412,8 +357,7 @@ __global__ __launch_bounds__(256) void sample_mlp16x2_kernel(SampleArgs a) {
   const int j = lane & 31, h = lane >> 5;
   const int ntiles = (a.n_rays + TILE - 1) / TILE;
   if (static_cast<int>(blockIdx.x) >= ntiles) return;
-  const uint32_t sel_stage = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(lds)) + kRingBytes + kBiasFloats * 4 +
-                             wave * kPairLdsBytesPerWave + lane * 16;
+  const uint32_t sel_stage = pair_stage_addr(lds + kRingBytes + kBiasFloats * 4, wave, lane);
   {
     float* lds_bias = reinterpret_cast<float*>(lds + kRingBytes);
     for (int i = threadIdx.x; i < kBiasFloats; i += blockDim.x) lds_bias[i] = a.net16.bias[i];
@@ -436,21 +380,12 @@ __global__ __launch_bounds__(256) void sample_mlp16x2_kernel(SampleArgs a) {
         local[b] = tile * TILE + wave * 64 + 32 * b + j;
         valid[b] = local[b] < a.n_rays;
         const int ray = a.first_ray + (valid[b] ? local[b] : a.n_rays - 1);
-        int col, row;
-        ray_pixel(a.g, ray, &col, &row);
         float nds[3], p[3], u[3];
-        gen_ray(a.g, col, row, nds, p);
-        unit3(nds, u);
-        if (valid[b] && a.rays_out) {
-          float ro[3] = {p[0], p[1], p[2]}, rd[3] = {nds[0], nds[1], nds[2]};
-          if (a.g.use_ndc) ndc_ray(a.g, p, nds, ro, rd);
-          float4* r = reinterpret_cast<float4*>(a.rays_out + static_cast<size_t>(local[b]) * 8);
-          if (h == 0) r[0] = make_float4(ro[0], ro[1], ro[2], 0.f);
-          else r[1] = make_float4(rd[0], rd[1], rd[2], 0.f);
-        }
+        sample_ray(a.g, ray, nds, p, u);
+        if (valid[b] && a.rays_out) store_ray_record(a, local[b], h, p, nds);
         float t[Q0];
-        pe_eval<FD, !tune::kFastPeFp16Pass>(u, h, t);            // [dir PE | pos PE]  (src/features.py:868-874), as sample_mlp16_kernel
-        pe_eval<FP, !tune::kFastPeFp16Pass>(p, h, t + QD);
+        pe_eval<FD, false>(u, h, t);            // [dir PE | pos PE]  (src/features.py:868-874), as sample_mlp16_kernel
+        pe_eval<FP, false>(p, h, t + QD);
 #pragma unroll
         for (int q = 0; q < Q0 / 2; ++q) in0[b][q] = Fp16::pack(t[2 * q], t[2 * q + 1]);
       }

@@ -64,6 +64,10 @@ inline float guard_pair_of(int transform, float eps, float eps_pair) {
 constexpr int kPairSegShift = 5;                 // a wave selects for 32 rays = one entry of seg_total
 constexpr int kPairMaxN = 16;                    // largest n_max this path handles (sorted lists live in registers)
 constexpr int kPairLdsBytesPerWave = 32 * 64 * 4;   // staging of 32 values per lane (two passes)
+// LDS byte address of this lane's slot in its wave's staging block; `blocks`: the workgroup's staging area (one block per wave)
+__device__ __forceinline__ uint32_t pair_stage_addr(const char* blocks, int wave, int lane) {
+  return static_cast<uint32_t>(reinterpret_cast<uintptr_t>(blocks)) + wave * kPairLdsBytesPerWave + lane * 16;
+}
 
 // The MFMA layout (layout.hpp): lane l = (j = l & 31, h = l >> 5) of a wave holds, for ray j, the 64 values
 // x[i], i = 16 m + r, of bins act_feature(i, h) = 32 m + 8 (r >> 2) + 4 h + (r & 3): within every group of 8 consecutive

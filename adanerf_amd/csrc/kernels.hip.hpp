@@ -3,7 +3,7 @@
 //   A1+A2+A3  sample_mlp_kernel      ray gen -> sphere exit -> oracle PE -> 8-layer sampling MLP (fp32 MFMA)
 //   A4        select_kernel / scan_blocks_kernel / expand_kernel   top-N + threshold, deterministic compaction
 //   A4b       trim_rows_kernel / trim_rows_wave_kernel / foveate_kernel   per-ray budgets: the selection trimmed to (n_r, thr_r), the maps of a gaze
-//   A5+A6     shade_mlp16_kernel / shade_mlp32_kernel   fused PE + 8x256 shading MLP (bf16/f16/f32 MFMA)
+//   A5+A6     shade_mlp16x2_kernel / shade_mlp32_kernel   fused PE + 8x256 shading MLP (bf16/f16/f32 MFMA)
 //   A7        composite_kernel       sigmoid + alpha * oracle weight, front-to-back
 //   N1        flip_kernel / flip_mean_kernel   FLIP error map and mean of an image pair (the evaluator's second metric)
 //   N3        present_kernel / present_area_kernel   the frame at the window's size (the viewer's blit: linear / nearest, y flip; exact area filter)

@@ -13,7 +13,7 @@ scenes and cameras are those of the golden case synthetic_fixed8, which test_ora
 
 Instantiations and the cases that reach them:
   launch_shade_mlp
-    shade_mlp16x2_kernel / shade_mlp16_kernel <Bf16|Fp16, 10, 4>       test_shading_engines[fixed_8x256] bf16, fp16; test_explicit_depths_inside_bins bf16
+    shade_mlp16x2_kernel <Bf16|Fp16, 10, 4>                            test_shading_engines[fixed_8x256] bf16, fp16; test_explicit_depths_inside_bins bf16
     shade_mlp32_kernel<10, 4>                                          test_shading_engines[fixed_8x256] fp32; test_explicit_depths_inside_bins fp32
     shade_mlp16_gen_staged_kernel <Bf16|Fp16, 10, 4, W> W = 64         [w40_d2_noskip], [w64_d3_skip1]
                                                         W = 128        [w96_d5_skips1_3], [w128_d6_skip2]; coarse net (test_coarse_net_...)
@@ -74,7 +74,7 @@ def compute_units(base_case, tmp_path_factory):
 
 def long_length(cu):
     """At least three laps of every persistent grid: no engine keeps more than 2 workgroups x 256 samples (rays) resident per CU --
-    launch_shade_mlp: fixed 16-bit kernels min(tiles, CUs) x 256 samples (kShadeBlocks == 2) or occupancy x 256 (8 waves x 32); staged
+    launch_shade_mlp: fixed 16-bit kernels min(tiles, CUs) x 256 samples (4 waves x two 32-sample blocks); staged
     16-bit kernels occupancy x 128 gen_blocks; fp32 kernels occupancy x 128 (64 in the wide form); launch_sample_mlp: the plain-fp16
     kernel occupancy x 256 rays, the split kernel occupancy x 128 rays."""
     return 3 * cu * 512 + 97

@@ -139,7 +139,7 @@ def test_device_code_has_no_crossbar_exchange_and_no_lds_dma_outliving_its_workg
         assert any(re.match(r"s_waitcnt\b.*vmcnt\(0\)", ln) for ln in tail), "%s: LDS-DMA in flight at s_endpgm" % name
         checked.append(name)
     # the kernels this is about: both 8 x 256 engines, the fp16 sampling pass, the run-time-shaped 16-bit kernels
-    for frag in ("shade_mlp16x2_kernel", "shade_mlp16_kernel", "sample_mlp16x3_kernel", "sample_mlp16_kernel", "shade_mlp16_gen_staged_kernel",
+    for frag in ("shade_mlp16x2_kernel", "sample_mlp16x3_kernel", "sample_mlp16_kernel", "shade_mlp16_gen_staged_kernel",
                  "sample_mlp16x3_gen_kernel"):
         assert any(frag in n for n in checked), frag
 
