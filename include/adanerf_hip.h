@@ -453,7 +453,14 @@ int adanerf_compact(adanerf_ctx* ctx, const float* d_oracle, int32_t n_rays, int
  * were looked at again.  d_monitor (may be NULL) [5] uint32, ADDED to / maximised into (the caller zeroes it): [0] float bits of
  * the largest |approx - exact| over the re-evaluated rows, [1] rows that exceeded a bound, [2] float bits of the largest
  * (kept - candidate) difference error, [3] audited rows whose approximate selection differs from the exact one, [4] audited rows.
- * n_max <= 16, thr > 0. */
+ * n_max <= 16, thr > 0.
+ * Under the context's sampler transform: eps always bounds the RAW values, |approx - exact| <= eps per entry of d_oracle_*; the rule runs
+ * on the transformed values with the band e = eps (no transform), eps / 4 (sigmoid), 1.01 (exp(2 eps) - 1) x the approximate row's largest
+ * probability (softmax), and the pair bound 2 e -- eps_pair is honoured without a transform only.  If the raw bound holds, counts, offsets,
+ * total and keys are those of adanerf_compact(d_oracle_exact, ...) bit for bit under every transform; d_sample_w holds the transformed
+ * exact values on the re-selected rays and the transformed approximate ones (within e of them) elsewhere; a row with a NaN or an infinity
+ * is always re-selected.  The monitor reports in RAW units under every transform: [0] and the bound of [1] are raw differences against
+ * eps; under a transform no pair bound is in use and [2] stays 0. */
 int adanerf_compact_guarded(adanerf_ctx* ctx, const float* d_oracle_approx, const float* d_oracle_exact, int32_t n_rays,
                             int32_t n_max, float thr, float eps, float eps_pair, int32_t audit_period, int32_t audit_phase,
                             int32_t audit_fill_cap, int32_t audit_cycle, int32_t* d_ray_offsets, int32_t* d_ray_counts, uint32_t* d_sample_key, float* d_sample_w,
