@@ -1173,6 +1173,65 @@ int adanerf_reproject(adanerf_ctx* c, const void* d_src_rgba8, const float* d_sr
   return ADANERF_OK;
 }
 
+int adanerf_temporal_resolve(adanerf_ctx* c, const float* d_cur_rgb, const float* d_cur_depth_map, const float* d_cur_acc_map, const float cur_pos[3],
+                             const float cur_rot_c2w[9], const float* d_hist_rgb, const float* d_hist_depth, const uint8_t* d_hist_count,
+                             const float prev_pos[3], const float prev_rot_c2w[9], float alpha, float depth_tol, float acc_min, int32_t flags,
+                             float* d_out_rgb, float* d_out_depth, uint8_t* d_out_count, void* d_out_rgba8, uint8_t* d_out_mask,
+                             int32_t* rejected_out) {
+  if (!c) return ADANERF_EINVAL;
+  if (!d_cur_rgb || !d_cur_depth_map || !d_cur_acc_map || !d_out_rgb) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: NULL image");
+  if (!cur_pos || !cur_rot_c2w || (d_hist_rgb && (!prev_pos || !prev_rot_c2w))) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: NULL pose");
+  for (int k = 0; k < 9; ++k) {
+    if (!std::isfinite(cur_rot_c2w[k]) || (k < 3 && !std::isfinite(cur_pos[k])))
+      return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: a pose entry is not finite");
+    if (d_hist_rgb && (!std::isfinite(prev_rot_c2w[k]) || (k < 3 && !std::isfinite(prev_pos[k]))))      // without a history the previous pose is not read
+      return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: a pose entry is not finite");
+  }
+  if (!(alpha > 0.f && alpha <= 1.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: alpha must lie in (0, 1]");      // also a NaN
+  if (!(depth_tol >= 0.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: depth_tol must be >= 0");
+  if (!(acc_min >= 0.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: acc_min must be >= 0");
+  if (flags & ~ADANERF_TEMPORAL_CLAMP) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: flags must be 0 or ADANERF_TEMPORAL_CLAMP");
+  const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  if ((at(d_cur_rgb) | at(d_cur_depth_map) | at(d_cur_acc_map) | at(d_hist_rgb) | at(d_hist_depth) | at(d_out_rgb) | at(d_out_depth) | at(d_out_rgba8)) & 3)
+    return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: fp32 and uchar4 images must be 4-byte aligned");
+  const int w = c->ms.info.width, h = c->ms.info.height, n = w * h;
+  const size_t b3 = static_cast<size_t>(n) * 3 * sizeof(float), b1 = static_cast<size_t>(n) * sizeof(float);
+  if ((d_hist_rgb && ranges_overlap(d_out_rgb, b3, d_hist_rgb, b3)) || ranges_overlap(d_out_rgb, b3, d_cur_rgb, b3) ||
+      (d_out_depth && d_hist_depth && ranges_overlap(d_out_depth, b1, d_hist_depth, b1)) ||
+      (d_out_count && d_hist_count && ranges_overlap(d_out_count, static_cast<size_t>(n), d_hist_count, static_cast<size_t>(n))))
+    return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: an output overlaps the image it is gathered from (the history is ping-ponged, not updated in place)");
+  if (c->ms.info.use_ndc) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_temporal_resolve: the depth_map of a useNDC model is NDC depth, not a distance along the ray");
+  if (c->ms.rg.world != 1) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_temporal_resolve: whole frames only (shard_world must be 1)");
+  BIND(c);
+  if (!c->reproj_holes.p) {      // the counter adanerf_reproject keeps its hole count in: both run on the context's stream, one after the other
+    if (int rc = dev_alloc(c, &c->reproj_holes, 64)) return rc;
+  }
+  TemporalParams p{};
+  p.g = c->ms.rg;      // pixel centres: the offset of adanerf_set_pixel_offset is not applied
+  std::memcpy(p.g.pos, cur_pos, 3 * sizeof(float));
+  std::memcpy(p.g.rot, cur_rot_c2w, 9 * sizeof(float));
+  if (d_hist_rgb) {
+    std::memcpy(p.prev_pos, prev_pos, 3 * sizeof(float));
+    std::memcpy(p.prev_rot, prev_rot_c2w, 9 * sizeof(float));
+  }
+  p.alpha = alpha;
+  p.depth_tol = depth_tol;
+  p.acc_min = acc_min;
+  p.origin_is_camera = c->ms.coarse_fine ? 1 : 0;
+  p.clamp = (flags & ADANERF_TEMPORAL_CLAMP) ? 1 : 0;
+  int32_t* rejected = reinterpret_cast<int32_t*>(c->reproj_holes.p);
+  HIP_TRY(c, hipMemsetAsync(rejected, 0, sizeof(int32_t), c->stream));
+  const dim3 grid((w + kTemporalTileW - 1) / kTemporalTileW, (h + kTemporalTileH - 1) / kTemporalTileH), block(256);
+  hipLaunchKernelGGL(temporal_resolve_kernel, grid, block, 0, c->stream, p, d_cur_rgb, d_cur_depth_map, d_cur_acc_map, d_hist_rgb, d_hist_depth, d_hist_count, d_out_rgb,
+                     d_out_depth, d_out_count, static_cast<uchar4*>(d_out_rgba8), d_out_mask, rejected);
+  HIP_TRY(c, hipGetLastError());
+  if (rejected_out) {
+    HIP_TRY(c, hipMemcpyAsync(rejected_out, rejected, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return ADANERF_OK;
+}
+
 int adanerf_sync(adanerf_ctx* c) {
   BIND(c);
   HIP_RETURN(c, hipStreamSynchronize(c->stream));

@@ -9,6 +9,7 @@
 //   N3        present_kernel / present_area_kernel   the frame at the window's size (the viewer's blit: linear / nearest, y flip; exact area filter)
 //   N4        reproject_clear_kernel / reproject_splat_kernel / reproject_resolve_kernel   a rendered frame warped to another pose by its depth
 //   N5        accumulate_kernel / resolve_mean_kernel   sum and mean of several sub-pixel frames (supersampling in time)
+//   N6        temporal_resolve_kernel   a history image carried to the pose of the moment, clamped and blended with the new frame (temporal anti-aliasing)
 // plus explicit-feature debug kernels (ray_features_kernel, shade_features_kernel) that materialise
 // what the reference launchers wrote to memory, for parity tests only.
 // The code lives in one header per stage; this file includes them all.
@@ -27,3 +28,4 @@
 #include "k_budget.hip.hpp"
 #include "k_reproject.hip.hpp"
 #include "k_accumulate.hip.hpp"
+#include "k_temporal.hip.hpp"

@@ -100,7 +100,7 @@ def scaled_size(w: int, h: int, scale: float):
 def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: Optional[str] = None,
              precision: str = "bf16", batch_size: int = -1, max_frames: int = 0, quiet: bool = False,
              video: Optional[str] = None, fps: int = 30, metrics=("psnr",), fovea=None, sweep_thresholds=None, sweep_samples=None, reproject_stride=None,
-             supersample=None, present_filter=None, sweep_scales=None):
+             supersample=None, present_filter=None, temporal=None, temporal_still=None, sweep_scales=None):
     """metrics: "psnr" (always reported where a ground-truth image exists) and / or "flip": each record gains ``flip``, the summary
     ``mean_flip``, and with out_dir the error map is written as an 8-bit greyscale ``%05d_flip.png``.
 
@@ -127,6 +127,16 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     present_filter (None, "nearest", "linear" or "area"): the filter of the sweep_scales presentation (NeuralRenderer.present); None is the
     viewer's rule, which decimates a frame rendered above the dataset's size -- "area" averages it.
 
+    temporal (ALPHA in (0, 1] or None): temporal anti-aliasing beside the plain frames.  The set is walked in order as ONE sequence: after
+    a pose's plain render the same pose is rendered once more at the next offset of the 2 x 2 sub-pixel cycle and resolved against the
+    history of the poses before it (NeuralRenderer.render_temporal, clamp on, the default depth tolerance), and that fp32 frame is scored
+    too.  Records gain ``psnr_temporal`` / ``mse_temporal``, ``rejected_fraction`` (pixels whose history was dropped, of w h; 1 on the
+    first pose) and, with "flip", ``flip_temporal``; the summary ``mean_psnr_temporal``, ``mean_rejected_fraction`` and
+    ``mean_flip_temporal``; out_dir gets ``%05d_temporal.png``.  The plain keys are those of a run without the option.
+    temporal_still (K >= 1 or None): per pose instead, the frame after K resolves at rest from an empty history (what a viewer shows K
+    frames after the camera stopped there); ALPHA is ``temporal`` or, without it, 0.1; the summary carries ``temporal_still``.
+    Neither goes with reproject_stride, supersample or sweep_scales.
+
     fovea (``R:N:T[,R:N:T...],N:T`` or what renderer.parse_fovea makes of it, or None): every frame is rendered with per-ray budgets around a
     gaze at the centre of the rendered frame (radii in its pixels).  Records and summary keep their shape: PSNR / FLIP / samples per ray are
     those of the foveated frames -- the quality-against-cost table of a foveation setting."""
@@ -147,6 +157,15 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
         raise ValueError("supersample must be in 1..%d, got %s" % (SUPERSAMPLE_MAX, supersample))
     if ss and stride:
         raise ValueError("supersample averages jittered frames, which have no single depth map to warp by: not together with reproject_stride")
+    still = int(temporal_still) if temporal_still is not None else 0
+    if temporal_still is not None and still < 1:
+        raise ValueError("temporal_still must be >= 1, got %s" % (temporal_still,))
+    ta = (0.1 if temporal is None else float(temporal)) if (temporal is not None or still) else 0.0
+    if temporal is not None and not 0.0 < ta <= 1.0:
+        raise ValueError("temporal must lie in (0, 1], got %s" % (temporal,))
+    if ta and (stride or ss or sweep_scales):
+        raise ValueError("temporal / temporal_still resolve one jittered render per frame at the dataset's resolution: not together with "
+                         "reproject_stride, supersample or sweep_scales")
     if present_filter not in PRESENT_FILTERS:
         raise ValueError("present_filter must be None, 'nearest', 'linear' or 'area', got %r" % (present_filter,))
     want_flip = "flip" in metrics
@@ -162,9 +181,11 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
         vid = Y4mWriter(video, w, h, fps) if video else None
         d_ref = r.empty((w * h, 3), np.float32) if want_flip else None
         d_map = r.empty((w * h,), np.float32) if want_flip and out_dir else None
-        d_pres = r.empty((w * h, 3), np.float32) if want_flip and (sweep_scales or stride) else None
+        d_pres = r.empty((w * h, 3), np.float32) if want_flip and (sweep_scales or stride or ta) else None
         if stride:
             r.enable_reprojection()
+        if ta:
+            r.enable_temporal(alpha=ta, grid=2)
 
         def render_set(out_dir, extra, scale=None):
             """one pass over the set at the selection (and, with a scale, the frame size) in force -> its records"""
@@ -174,7 +195,10 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                 os.makedirs(out_dir, exist_ok=True)
             if fovea:      # again for every setting: a frame size that changes the ray count drops the maps
                 r.foveate((0.5 * rw, 0.5 * rh), fovea)
+            if ta:
+                r.reset_temporal()      # a pass over the set is one sequence
             for i, fr in enumerate(frames):
+                ref = None
                 warped = bool(stride) and i % stride != 0
                 if warped:      # the last rendered frame at this pose: what a host that renders every K-th frame shows here
                     rgba, _, holes = r.reproject(fr["pose"], fr["rot"])
@@ -204,6 +228,19 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                         if d_map is not None:
                             fm = np.nan_to_num(d_map.numpy().reshape(h, w), nan=1.0)      # the map lies in [0, 1]
                             write_png(os.path.join(out_dir, "%05d_flip.png" % i), np.clip(np.rint(fm * 255.0), 0, 255).astype(np.uint8))
+                if ta:      # the same pose once more, jittered, resolved against the history (or K times from an empty one)
+                    if still:
+                        r.reset_temporal()
+                    for _ in range(still or 1):
+                        t_rgb, t_rgba, _, t_rejected, _ = r.render_temporal()
+                    rec.update(rejected_fraction=t_rejected / float(w * h))
+                    if ref is not None:
+                        t_mse = float(np.mean((t_rgb.astype(np.float64) - ref) ** 2))
+                        rec.update(mse_temporal=t_mse, psnr_temporal=psnr_from_mse(t_mse))
+                        if want_flip:
+                            rec.update(flip_temporal=r.flip_device(d_pres.upload(t_rgb), d_ref, w, h))
+                    if out_dir:
+                        write_png(os.path.join(out_dir, "%05d_temporal.png" % i), t_rgba[:, :3].reshape(h, w, 3))
                 if out_dir:
                     write_png(os.path.join(out_dir, "%05d.png" % i), rgba[:, :3].reshape(h, w, 3))
                 if vid:
@@ -230,8 +267,8 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
         if vid:
             vid.close()
     if sweep:
-        return dict(frames=len(frames), sweep=sweep, **(dict(supersample=ss) if ss else {})), results
-    return dict(summarise(results, want_flip), **(dict(supersample=ss) if ss else {})), results
+        return dict(frames=len(frames), sweep=sweep, **(dict(supersample=ss) if ss else {}), **(dict(temporal_still=still) if still else {})), results
+    return dict(summarise(results, want_flip), **(dict(supersample=ss) if ss else {}), **(dict(temporal_still=still) if still else {})), results
 
 
 def summarise(results: List[dict], want_flip: bool) -> dict:
@@ -251,6 +288,12 @@ def summarise(results: List[dict], want_flip: bool) -> dict:
                 summary["mean_flip_" + kind] = float(np.mean([x["flip"] for x in part])) if part else None
         holes = [x["hole_fraction"] for x in results if x.get("warped")]
         summary["mean_hole_fraction"] = float(np.mean(holes)) if holes else 0.0
+    if any("rejected_fraction" in x for x in results):      # temporal / temporal_still: the resolved frames beside the plain ones
+        part = [x for x in results if "psnr_temporal" in x]
+        summary["mean_psnr_temporal"] = float(np.mean([x["psnr_temporal"] for x in part])) if part else None
+        if want_flip:
+            summary["mean_flip_temporal"] = float(np.mean([x["flip_temporal"] for x in part])) if part else None
+        summary["mean_rejected_fraction"] = float(np.mean([x["rejected_fraction"] for x in results if "rejected_fraction" in x]))
     return summary
 
 
@@ -280,6 +323,12 @@ def build_parser():
     ap.add_argument("--supersample", type=int, default=None, choices=range(1, SUPERSAMPLE_MAX + 1), metavar="S",
                     help="every image is the mean of S x S renders (S in 1..8) at the offsets of the regular sub-pixel grid, accumulated on the GPU "
                          "and scored from the fp32 mean; records and summary gain `supersample`; not together with --reproject-stride")
+    ap.add_argument("--temporal", type=float, default=None, metavar="ALPHA",
+                    help="temporal anti-aliasing beside the plain frames: the set in order as one sequence, every pose rendered once more at the "
+                         "next sub-pixel offset and resolved against the history (adanerf_temporal_resolve, new-frame weight ALPHA in (0, 1]); the "
+                         "summary gains mean_psnr_temporal / mean_rejected_fraction (and mean_flip_temporal with --metrics flip)")
+    ap.add_argument("--temporal-still", type=int, default=None, metavar="K",
+                    help="per pose, score the frame after K resolves at rest from an empty history instead (ALPHA of --temporal, default 0.1)")
     ap.add_argument("--present-filter", default=None, choices=["nearest", "linear", "area"],
                     help="filter of the --sweep-scales presentation (default: the viewer's rule, linear when enlarging, else nearest); area is "
                          "the exact area filter and the only sensible choice for scales above 1, where nearest throws the extra rays away")
@@ -294,9 +343,12 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if a.supersample is not None and a.reproject_stride is not None:
         ap.error("--supersample cannot be combined with --reproject-stride")
+    if (a.temporal is not None or a.temporal_still is not None) and (a.supersample is not None or a.reproject_stride is not None or a.sweep_scales):
+        ap.error("--temporal / --temporal-still cannot be combined with --supersample, --reproject-stride or --sweep-scales")
     summary, _ = evaluate(a.model_dir, a.dataset_dir, a.set, a.out, a.precision, a.batch_size, a.max_frames, video=a.video, fps=a.fps,
                           metrics=tuple(a.metrics), sweep_thresholds=a.sweep_thresholds, sweep_samples=a.sweep_samples, sweep_scales=a.sweep_scales,
-                          fovea=a.fovea, reproject_stride=a.reproject_stride, supersample=a.supersample, present_filter=a.present_filter)
+                          fovea=a.fovea, reproject_stride=a.reproject_stride, supersample=a.supersample, present_filter=a.present_filter,
+                          temporal=a.temporal, temporal_still=a.temporal_still)
     print(json.dumps(summary))
 
 

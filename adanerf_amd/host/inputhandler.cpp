@@ -92,6 +92,8 @@ bool InputHandler::replay(const char* line) {
         if (end == val.c_str() || *end != 0 || !(x - x == 0.f)) return false;      // finite
       }
       renderer.setGaze(v[0], v[1]);
+    } else if (tok == "cut") {
+      renderer.cutHistory();
     } else if (tok == "size") {
       // two values, each read whole: "size 400 300"; the library validates the size when the frame is rendered
       long v[2];

@@ -23,7 +23,8 @@ class InputHandler {
   // (left button), "m x y" (mouse position), "n <int>" / "thr <float>" (sample budget N / selection threshold from this line's frame
   // on: NeuralRenderer::setSelection), "size <W> <H>" (frame size from this line's frame on, the window size stays:
   // NeuralRenderer::setFrameSize), "gaze <X> <Y>" (the --fovea gaze point in pixels from this line's frame on:
-  // NeuralRenderer::setGaze); returns false on a malformed line
+  // NeuralRenderer::setGaze), "cut" (--taa: this line's frame starts a new history: NeuralRenderer::cutHistory); returns false on a
+  // malformed line
   bool replay(const char* line);
 
  private:

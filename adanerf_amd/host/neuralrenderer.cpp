@@ -23,7 +23,7 @@ NeuralRenderer::~NeuralRenderer() {
   if (ctx) {
     if (d_gathered) adanerf_free(ctx, d_gathered);
     if (d_frame) adanerf_free(ctx, d_frame);
-    for (void* p : {d_depth, d_acc, d_warp, d_rgb, d_sum})
+    for (void* p : {d_depth, d_acc, d_warp, d_rgb, d_sum, d_hist[0][0], d_hist[0][1], d_hist[0][2], d_hist[1][0], d_hist[1][1], d_hist[1][2]})
       if (p) adanerf_free(ctx, p);
     if (d_window) adanerf_free(ctx, d_window);
     adanerf_destroy(ctx);
@@ -161,6 +161,11 @@ bool NeuralRenderer::init() {
     err = world > 1 ? "--reproject warps whole frames of one context; use it with --gpus 1" : "--reproject: the depth of a useNDC model is NDC depth";
     return false;
   }
+  if (settings.taa_alpha > 0.f && (world > 1 || settings.render_oracle || info_.use_ndc)) {
+    err = world > 1 ? "--taa resolves whole frames of one context; use it with --gpus 1"
+                    : (settings.render_oracle ? "--taa blends rendered frames; not with --oracle" : "--taa: the depth of a useNDC model is NDC depth");
+    return false;
+  }
   if (!allocFrameBuffers()) return false;
   if (settings.write_window &&
       adanerf_malloc(ctx, static_cast<size_t>(settings.window_width) * settings.window_height * 4, &d_window) != ADANERF_OK) {
@@ -185,6 +190,18 @@ bool NeuralRenderer::allocFrameBuffers() {
     return false;
   }
   d_shown = d_frame;
+  if (settings.taa_alpha > 0.f) {      // the aux outputs and the history belong to the frame size
+    const size_t n = static_cast<size_t>(info_.width) * info_.height;
+    taa_have = false;
+    void** bufs[] = {&d_rgb, &d_depth, &d_acc, &d_hist[0][0], &d_hist[0][1], &d_hist[0][2], &d_hist[1][0], &d_hist[1][1], &d_hist[1][2]};
+    const size_t bytes[] = {n * 12, n * 4, n * 4, n * 12, n * 4, n, n * 12, n * 4, n};
+    for (int k = 0; k < 9; ++k) {
+      if (*bufs[k] && adanerf_free(ctx, *bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+      *bufs[k] = nullptr;
+      if (adanerf_malloc(ctx, bytes[k], bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+    }
+    if (adanerf_set_aux_outputs(ctx, static_cast<float*>(d_depth), static_cast<float*>(d_acc)) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+  }
   if (settings.supersample > 1) {
     for (void** p : {&d_rgb, &d_sum}) {
       if (*p && adanerf_free(ctx, *p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
@@ -304,6 +321,7 @@ bool NeuralRenderer::render() {
     want_threshold = -1.f;
     adanerf_get_info(ctx, &info_);
     have_source = false;      // a new selection shows from this frame on: render it
+    taa_have = false;         // and --taa does not blend it with frames of the old one
   }
   if (!applyFovea()) return false;
   if (adanerf_set_camera(ctx, camera.getPosition(), rot) != ADANERF_OK) {
@@ -317,6 +335,7 @@ bool NeuralRenderer::render() {
     }
     sample_count++;
     have_source = false;      // the debug view has no depth to warp
+    taa_have = false;         // nor is it a frame --taa may blend with
     d_shown = d_frame;
     return writeImageToFile();
   }
@@ -360,7 +379,9 @@ bool NeuralRenderer::render() {
     }
     return writeImageToFile();
   }
-  if (settings.supersample > 1 ? !renderSupersampled(&st) : adanerf_render(ctx, d_frame, nullptr, &st) != ADANERF_OK) {
+  if (settings.taa_alpha > 0.f) {
+    if (!renderTemporal(&st, rot)) return false;
+  } else if (settings.supersample > 1 ? !renderSupersampled(&st) : adanerf_render(ctx, d_frame, nullptr, &st) != ADANERF_OK) {
     if (settings.supersample <= 1) err = adanerf_last_error(ctx);
     return false;
   }
@@ -426,6 +447,40 @@ bool NeuralRenderer::renderSupersampled(adanerf_stats* st) {
   return true;
 }
 
+// --taa: one render of this frame's camera at the next offset of the sub-pixel cycle, then adanerf_temporal_resolve against the history
+// (clamp on), which the result replaces; d_frame gets the resolved frame under the viewer's output contract.  The offset goes back to (0, 0).
+// The history's depth is tested only when the pose differs from the history's.
+bool NeuralRenderer::renderTemporal(adanerf_stats* st, const float rot[9]) {
+  const int S = settings.taa_grid;
+  float dx = 0.f, dy = 0.f;
+  const bool ok = adanerf_host_subpixel_grid(S, taa_k % (S * S), &dx, &dy) == ADANERF_OK && adanerf_set_pixel_offset(ctx, dx, dy) == ADANERF_OK &&
+                  adanerf_render(ctx, nullptr, static_cast<float*>(d_rgb), st) == ADANERF_OK;
+  if (!ok) err = adanerf_last_error(ctx);
+  const bool back = adanerf_set_pixel_offset(ctx, 0.f, 0.f) == ADANERF_OK;
+  if (!ok) return false;
+  taa_k = (taa_k + 1) % (S * S);
+  const int out = taa_have ? 1 - taa_side : 0;
+  void* const* hist = d_hist[taa_side];
+  // the camera has not moved since the history was written: nothing can have been uncovered, so no disocclusion test (as renderer.py)
+  const bool at_rest = taa_have && std::memcmp(prev_pos, camera.getPosition(), sizeof(prev_pos)) == 0 && std::memcmp(prev_rot, rot, sizeof(prev_rot)) == 0;
+  int32_t rejected = 0;
+  if (!back || adanerf_temporal_resolve(ctx, static_cast<const float*>(d_rgb), static_cast<const float*>(d_depth), static_cast<const float*>(d_acc),
+                                        camera.getPosition(), rot, taa_have ? static_cast<const float*>(hist[0]) : nullptr,
+                                        taa_have && !at_rest ? static_cast<const float*>(hist[1]) : nullptr, taa_have ? static_cast<const uint8_t*>(hist[2]) : nullptr,
+                                        prev_pos, prev_rot, settings.taa_alpha, settings.taa_tol, 0.5f, ADANERF_TEMPORAL_CLAMP,
+                                        static_cast<float*>(d_hist[out][0]), static_cast<float*>(d_hist[out][1]), static_cast<uint8_t*>(d_hist[out][2]),
+                                        d_frame, nullptr, &rejected) != ADANERF_OK) {
+    err = adanerf_last_error(ctx);
+    return false;
+  }
+  std::memcpy(prev_pos, camera.getPosition(), sizeof(prev_pos));
+  std::memcpy(prev_rot, rot, sizeof(prev_rot));
+  taa_side = out;
+  taa_have = true;
+  s_rejected += rejected;
+  return true;
+}
+
 // --reproject K: the last rendered frame at this frame's camera (adanerf_reproject, holes filled from their neighbours, the rest black)
 bool NeuralRenderer::warp(const float rot[9]) {
   int32_t holes = 0;
@@ -455,11 +510,13 @@ void NeuralRenderer::logInterval() {
             << ", N: " << info_.num_samples << ", thr: " << info_.threshold << ", size: " << info_.width << "x" << info_.height
             << ", frames: " << sample_count << ", frame ms: " << s_total / rendered;
   if (settings.supersample > 1) std::cout << ", renders per frame: " << settings.supersample * settings.supersample;
+  if (settings.taa_alpha > 0.f) std::cout << ", taa rejected: " << s_rejected / static_cast<double>(logging_interval) / settings.total_size;
   if (settings.reproject > 1) std::cout << ", holes: " << s_holes / static_cast<double>(std::max(s_warped, 1)) << " (" << s_warped << " warped frames)";
   std::cout << std::endl;
   s_inference1 = s_inference2 = s_fc2 = s_rm = s_total = 0;
   s_num_total_samples = 0;
   s_holes = 0;
+  s_rejected = 0;
   s_rendered = s_warped = 0;
 }
 

@@ -53,6 +53,8 @@ class NeuralRenderer {
     *y = gaze_y;
     return fovea_pending;
   }
+  // --taa: the next frame is shown as rendered and starts a new history (script token "cut"); without --taa nothing to drop
+  void cutHistory() { taa_have = false; }
   bool applyFrameSize();             // a pending setFrameSize, now: render() calls it; --dry-run calls it in render()'s place (host only)
   int batchesPerFrame() const;       // ceil(rays / batch_rays)
   bool writeImageToFile();           // out.bmp in the model directory (neuralrenderer.cpp:184-222); --write-window: out_window.bmp too
@@ -84,6 +86,14 @@ class NeuralRenderer {
   void* d_rgb = nullptr;
   void* d_sum = nullptr;
   bool renderSupersampled(adanerf_stats* st);   // S x S renders at the grid's offsets, accumulated and resolved into d_frame; *st: times summed, samples per render
+  // --taa: depth_map / acc_map (d_depth, d_acc) and the fp32 frame (d_rgb) of this frame's render; two history sets (rgb float [h*w*3], depth
+  // float [h*w], count uint8 [h*w]) that ping-pong, the pose of the one last written, the place in the offset cycle
+  void* d_hist[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+  bool taa_have = false;             // d_hist[taa_side] and prev_* describe a resolved frame of the size in force
+  int taa_side = 0, taa_k = 0;
+  float prev_pos[3] = {0, 0, 0}, prev_rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  long long s_rejected = 0;          // rejected pixels of the running interval's frames
+  bool renderTemporal(adanerf_stats* st, const float rot[9]);   // one render at the cycle's next offset, resolved against the history into d_frame
   void* d_window = nullptr;          // --write-window: uchar4 [window_height*window_width], the frame as adanerf_present shows it
   int world_ = 1, strip_rows_ = 8;   // share layout chosen at init; a live context keeps its strip height
   bool allocFrameBuffers();          // d_frame, d_gathered, d_payload for the size in info_ (again after a size change)

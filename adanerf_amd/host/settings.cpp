@@ -18,11 +18,16 @@ const char* Settings::usage() {
          "                                                              (+w -w ... b+ x y  b- x y  m x y; n <int> / thr <float>:\n"
          "                                                              sample budget N / threshold from that frame on;\n"
          "                                                              size <W> <H>: frame size from that frame on, the window stays;\n"
-         "                                                              gaze <X> <Y>: the --fovea gaze point, in pixels)\n"
+         "                                                              gaze <X> <Y>: the --fovea gaze point, in pixels;\n"
+         "                                                              cut: --taa starts a new history with that frame)\n"
          "               [--reproject K]      of every K frames render the first and warp it to the camera of the next K - 1 (depth\n"
          "                                    reprojection, holes filled from their neighbours); -w / --write-window write what was shown\n"
          "               [--supersample S]    every shown frame is S x S renders (S in 1..8) at the offsets of a regular sub-pixel grid, summed and\n"
          "                                    averaged on the device (anti-aliasing in time); -w / --write-window write the resolved image\n"
+         "               [--taa ALPHA[:TOL]]  temporal anti-aliasing: every frame is rendered at the next sub-pixel offset of a cycle and blended\n"
+         "                                    (weight ALPHA in (0, 1]) with a history carried to its camera by its depth; a history pixel whose depth\n"
+         "                                    is off by more than TOL (relative, default 0.02) is dropped; script token cut drops the history\n"
+         "               [--taa-grid S]       the cycle of --taa: the S x S regular sub-pixel grid, S in 1..8 (default 2)\n"
          "               [--present-filter nearest|linear|area]     filter of the -ws window image; default: linear if the window is wider than\n"
          "                                    the frame, else nearest (the viewer's blit); area: exact area filter, for a frame rendered larger\n"
          "               [--gpus N] [--same-device] [--sub-shares P]\n";
@@ -158,6 +163,28 @@ bool Settings::init(int argc, char** argv, std::string* err) {
         return false;
       }
       supersample = static_cast<int>(k);
+    } else if (a == "--taa") {
+      if (!need(i, 1)) return false;
+      const std::string spec = argv[++i];
+      const size_t colon = spec.find(':');
+      const std::string as = spec.substr(0, colon), ts = colon == std::string::npos ? "0.02" : spec.substr(colon + 1);
+      char *ea = nullptr, *et = nullptr;
+      const float al = std::strtof(as.c_str(), &ea), tl = std::strtof(ts.c_str(), &et);
+      if (as.empty() || *ea != 0 || ts.empty() || *et != 0 || !(al > 0.f && al <= 1.f) || !(tl >= 0.f && tl < INFINITY)) {
+        *err = "--taa ALPHA[:TOL]: ALPHA must lie in (0, 1], TOL must be a number >= 0";
+        return false;
+      }
+      taa_alpha = al;
+      taa_tol = tl;
+    } else if (a == "--taa-grid") {
+      if (!need(i, 1)) return false;
+      char* end = nullptr;
+      const long k = std::strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end != 0 || k < 1 || k > 8) {
+        *err = "--taa-grid S: S must be an integer in 1..8";
+        return false;
+      }
+      taa_grid = static_cast<int>(k);
     } else if (a == "--present-filter") {
       if (!need(i, 1)) return false;
       present_filter = argv[++i];
@@ -191,6 +218,11 @@ bool Settings::init(int argc, char** argv, std::string* err) {
   }
   if (ws_used && (window_width == 0 || window_height == 0)) {
     *err = "window size must be positive";
+    return false;
+  }
+  if (taa_alpha > 0.f && (reproject > 1 || supersample > 1)) {
+    *err = reproject > 1 ? "--taa renders and resolves every frame; not with --reproject"
+                         : "--taa spends one render per frame on a cycle of sub-pixel offsets; not with --supersample";
     return false;
   }
   total_size = width * height;

@@ -28,6 +28,7 @@ PRESENT_FLIP_Y, PRESENT_NEAREST, PRESENT_LINEAR, PRESENT_AREA = 1, 2, 4, 8      
 PRESENT_FILTERS = {None: 0, "nearest": PRESENT_NEAREST, "linear": PRESENT_LINEAR, "area": PRESENT_AREA}
 SUPERSAMPLE_MAX = 8                                            # adanerf_host_subpixel_grid: s in 1..8
 REPROJECT_FILL = 1                                             # adanerf_reproject flag
+TEMPORAL_CLAMP = 1                                             # adanerf_temporal_resolve flag
 ABI_VERSION = 4
 GUARD_FROM = {0: "none", 1: "options", 2: "record", 3: "calibration", 4: "monitor"}
 SAMPLING_MODES = {"split": 0, "fp16x3": 0, "fp32": 1, "fp16": 2, "guarded": 3}
@@ -76,7 +77,7 @@ EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_las
            "adanerf_composite", "adanerf_composite_classic", "adanerf_composite_aux", "adanerf_composite_classic_aux", "adanerf_disp_map", "adanerf_copy_result_sampling_network", "adanerf_flip",
            "adanerf_render_oracle", "adanerf_gather_to", "adanerf_probe_mfma", "adanerf_malloc",
            "adanerf_free", "adanerf_memcpy_h2d", "adanerf_memcpy_d2h", "adanerf_get_buffer",
-           "adanerf_set_pixel_offset", "adanerf_get_pixel_offset", "adanerf_accumulate", "adanerf_resolve_mean", "adanerf_host_subpixel_grid"]
+           "adanerf_set_pixel_offset", "adanerf_get_pixel_offset", "adanerf_accumulate", "adanerf_resolve_mean", "adanerf_host_subpixel_grid", "adanerf_temporal_resolve"]
 
 _lib = None
 
@@ -110,6 +111,8 @@ def load_library(path: Optional[str] = None):
     lib.adanerf_host_subpixel_grid.argtypes = [i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     fp = C.POINTER(C.c_float)
     lib.adanerf_reproject.argtypes = [vp, vp, vp, vp, fp, fp, fp, fp, C.c_float, C.c_uint32, i32, vp, vp, vp, C.POINTER(i32)]
+    lib.adanerf_temporal_resolve.argtypes = [vp, vp, vp, vp, fp, fp, vp, vp, vp, fp, fp, C.c_float, C.c_float, C.c_float, i32, vp, vp, vp, vp, vp,
+                                             C.POINTER(i32)]
     lib.adanerf_render.argtypes = [vp, vp, vp, C.POINTER(Stats)]
     lib.adanerf_assemble_strips.argtypes = [vp, vp, vp]
     lib.adanerf_set_aux_outputs.argtypes = [vp, vp, vp]
@@ -366,6 +369,8 @@ class NeuralRenderer:
         self._pose = None             # (pos [3], rot [9]) of the last set_camera
         self._rp_on = False           # enable_reprojection(): render_numpy keeps depth, acc and the pose of its frame
         self._rp_frame = None         # (device rgba8, depth, acc, pos, rot, rays) of the last render_numpy since then
+        self._ta = None               # enable_temporal(): alpha, depth_tol, clamp, the cycle of sub-pixel offsets and the place in it
+        self._ta_hist = None          # (index of the history's buffer set, pos, rot) of the last render_temporal since then
 
     # -- lifecycle -------------------------------------------------------------------------------
     def init(self) -> bool:
@@ -442,6 +447,7 @@ class NeuralRenderer:
         if hasattr(self, "_b_n") and self._b_n.shape[0] != self.info.rays_local:      # the library dropped the maps with the old rays_local
             self._drop_budget_buffers()
         self._rp_frame = None      # a frame of the old size cannot be warped with the new size's ray generator
+        self._ta_hist = None       # nor can a history of the old size be gathered from
         for name in ("_o_rgb", "_o_rgba"):
             if hasattr(self, name):
                 a = getattr(self, name)
@@ -666,6 +672,99 @@ class NeuralRenderer:
         rgba, depth, acc, pos, rot, _ = self._rp_frame
         holes = self.reproject_device(rgba, depth, acc, pos, rot, dst_pos, dst_rot, self._rp_rgba, None, self._rp_mask, acc_min=acc_min, fill=fill)
         return self._rp_rgba.numpy(), self._rp_mask.numpy(), holes
+
+    # -- temporal anti-aliasing: one jittered render per frame, resolved against a history ------------------
+    def temporal_resolve_device(self, cur_rgb, cur_depth, cur_acc, cur_pos, cur_rot, hist_rgb, hist_depth, hist_count, prev_pos, prev_rot,
+                                out_rgb, out_depth=None, out_count=None, out_rgba8=None, out_mask=None, alpha: float = 0.1,
+                                depth_tol: float = 0.02, acc_min: float = 0.5, clamp: bool = True, rejected: bool = True) -> Optional[int]:
+        """adanerf_temporal_resolve on device images of the context's frame size: the frame (fp32 rgb, depth_map, acc_map) rendered at
+        (cur_pos, cur_rot) blended with the history (rgb, depth, count: each may be None) the previous call wrote at (prev_pos, prev_rot)
+        into out_rgb and, if given, out_depth / out_count (the next call's history), out_rgba8 and out_mask (uint8: 1 the history was
+        used, 0 rejected).  Returns the number of rejected pixels (synchronous); with rejected=False nothing is read back and the outputs
+        are complete after sync()."""
+        f = [None if v is None else np.ascontiguousarray(v, dtype=np.float32).reshape(k) for v, k in ((cur_pos, 3), (cur_rot, 9), (prev_pos, 3), (prev_rot, 9))]
+        fp = [None if v is None else v.ctypes.data_as(C.POINTER(C.c_float)) for v in f]
+        n = C.c_int32(0)
+        self._check(self.lib.adanerf_temporal_resolve(self.handle, _ptr(cur_rgb), _ptr(cur_depth), _ptr(cur_acc), fp[0], fp[1], _ptr(hist_rgb),
+                                                      _ptr(hist_depth), _ptr(hist_count), fp[2], fp[3], float(alpha), float(depth_tol), float(acc_min),
+                                                      TEMPORAL_CLAMP if clamp else 0, _ptr(out_rgb), _ptr(out_depth), _ptr(out_count),
+                                                      _ptr(out_rgba8), _ptr(out_mask), C.byref(n) if rejected else None))
+        return int(n.value) if rejected else None
+
+    def _temporal_buffers(self):
+        """two history sets (rgb, depth, count) to ping-pong and the mask, made on first use and again after a frame size that changes
+        rays_local; the frame's depth_map / acc_map are the aux buffers reproject() uses too"""
+        n = self.info.rays_local
+        self._reproject_buffers()
+        if not hasattr(self, "_ta_sets") or self._ta_mask.shape[0] != n:
+            if hasattr(self, "_ta_sets"):
+                for a in [b for st in self._ta_sets for b in st] + [self._ta_mask]:
+                    a.free()
+                    self._own.remove(a)
+            self._ta_sets = [(self.empty((n, 3), np.float32), self.empty((n,), np.float32), self.empty((n,), np.uint8)) for _ in range(2)]
+            self._ta_mask = self.empty((n,), np.uint8)
+            self._ta_hist = None
+
+    def enable_temporal(self, alpha: float = 0.1, depth_tol: float = 0.02, clamp: bool = True, grid: int = 2):
+        """Temporal anti-aliasing from now on through render_temporal(): every frame is rendered at the next offset of the grid x grid
+        cycle of subpixel_grid and resolved against a history kept on the device (adanerf_temporal_resolve).  alpha in (0, 1]: the weight
+        of the new frame once the history is older than 1 / alpha frames (until then it is a running mean); depth_tol: relative depth
+        tolerance of the disocclusion test; clamp: the history is clamped to the new frame's 3 x 3 neighbourhood.  Whole frames of models
+        without useNDC only.  The depth_map / acc_map aux outputs become the renderer's own (as with enable_reprojection)."""
+        if self.info.use_ndc or self.info.rays_local != self.info.width * self.info.height:
+            raise AdaNeRFError("temporal anti-aliasing needs a whole frame of a model without useNDC")
+        if not 0.0 < float(alpha) <= 1.0:
+            raise ValueError("enable_temporal: alpha must lie in (0, 1], got %r" % (alpha,))
+        if not float(depth_tol) >= 0.0:
+            raise ValueError("enable_temporal: depth_tol must be >= 0, got %r" % (depth_tol,))
+        self._ta = dict(alpha=float(alpha), depth_tol=float(depth_tol), clamp=bool(clamp), offsets=subpixel_grid(grid), k=0)
+        self._ta_hist = None
+        self._temporal_buffers()
+
+    def reset_temporal(self):
+        """Drops the history (a cut): the next render_temporal returns its frame as rendered.  The offset cycle goes on."""
+        self._ta_hist = None
+
+    def render_temporal(self):
+        """One frame at the camera of the last set_camera, rendered at the next sub-pixel offset of the cycle and resolved against the
+        history, which it then replaces (two buffer sets ping-pong on the device).  Returns (rgb fp32 [R,3], rgba8 [R,4] uint8, mask [R]
+        uint8, rejected, Stats): mask 1 where the history was used; rejected counts the others (every pixel on the first frame and after
+        reset_temporal / set_frame_size).  While the pose is bit for bit the one of the call before, the history's depth is not tested
+        (nothing is uncovered while the camera rests) and nothing is rejected.  The offset that was in force is restored; present()
+        shows the resolved frame."""
+        if self._ta is None:
+            raise AdaNeRFError("render_temporal: call enable_temporal first")
+        if self._pose is None:
+            raise AdaNeRFError("render_temporal needs the pose of the frame: call set_camera first")
+        n = self.info.rays_local
+        self._temporal_buffers()
+        if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
+            self._o_rgb = self.empty((n, 3), np.float32)
+            self._o_rgba = self.empty((n, 4), np.uint8)
+        ta = self._ta
+        dx, dy = ta["offsets"][ta["k"] % len(ta["offsets"])]
+        ta["k"] += 1
+        was = self.pixel_offset
+        try:
+            self.set_pixel_offset(dx, dy)
+            st = self.render(None, self._o_rgb, stats=True)
+        finally:
+            self.set_pixel_offset(*was)
+        side = 0 if self._ta_hist is None else 1 - self._ta_hist[0]
+        out = self._ta_sets[side]
+        hist = (None, None, None) if self._ta_hist is None else self._ta_sets[self._ta_hist[0]]
+        prev = (None, None) if self._ta_hist is None else self._ta_hist[1:]
+        # The camera has not moved since the history was written: in a static scene nothing can have been uncovered, so there is no
+        # disocclusion test (d_hist_depth NULL).  The test would compare the depths of two jittered renders of one pose, and where a pixel
+        # spans several surfaces the jitter alone moves its depth past any tolerance: those pixels would restart their mean for nothing.
+        at_rest = self._ta_hist is not None and np.array_equal(prev[0], self._pose[0]) and np.array_equal(prev[1], self._pose[1])
+        rejected = self.temporal_resolve_device(self._o_rgb, self._rp_depth, self._rp_acc, self._pose[0], self._pose[1], hist[0], None if at_rest else hist[1], hist[2],
+                                                prev[0], prev[1], out[0], out[1], out[2], self._o_rgba, self._ta_mask, alpha=ta["alpha"],
+                                                depth_tol=ta["depth_tol"], clamp=ta["clamp"])
+        self._ta_hist = (side, self._pose[0], self._pose[1])
+        self._last_frame = (self._o_rgba, self.info.width, self.info.height)
+        self._rp_frame = None      # the aux maps now belong to a jittered frame whose colour was blended: nothing reproject() may warp
+        return out[0].numpy(), self._o_rgba.numpy(), self._ta_mask.numpy(), rejected, st
 
     # -- the frame at the window's size ---------------------------------------------------------------
     def present_device(self, src_rgba8, src_w: int, src_h: int, dst_rgba8, dst_w: int, dst_h: int, flip_y: bool = False,

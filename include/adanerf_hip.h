@@ -19,6 +19,8 @@
  *                                        ADANERF_PRESENT_AREA replaces its nearest decimation by an exact area filter
  *   adanerf_reproject                    none: the viewer presents the frame it rendered (src/neuralrenderer.cpp:146-182 ->
  *                                        src/interoprenderbuffer.cpp:87); this stage sits in front of that step
+ *   adanerf_temporal_resolve             none: the viewer shows each frame as rendered, without a history (src/neuralrenderer.cpp:146-182 ->
+ *                                        src/interoprenderbuffer.cpp:87); temporal anti-aliasing between the render and that step
  *   adanerf_render                       ImageGenerator::inference, 2-context adaptive branch
  *                                        (src/imagegenerator.cpp:282-394) as called from
  *                                        NeuralRenderer::render (src/neuralrenderer.cpp:146-182)
@@ -690,6 +692,63 @@ int adanerf_reproject(adanerf_ctx* ctx, const void* d_src_rgba8, const float* d_
                       const float src_pos[3], const float src_rot_c2w[9], const float dst_pos[3], const float dst_rot_c2w[9],
                       float acc_min, uint32_t hole_rgba8, int32_t flags, void* d_dst_rgba8, float* d_dst_depth, uint8_t* d_dst_mask,
                       int32_t* holes_out);
+
+/* adanerf_temporal_resolve flags */
+enum { ADANERF_TEMPORAL_CLAMP = 1 }; /* the history colour is clamped to the min / max of the current colour over the pixel's 3 x 3 neighbourhood */
+
+/* Temporal anti-aliasing: the stage a real-time host runs on every frame between adanerf_render and its present step.  A history image is
+ * carried to the pose of the moment by the new frame's own depth, tested for disocclusion, clamped to what the new frame can justify and
+ * blended with the new frame, which the host renders at the next sub-pixel offset of a small cycle (adanerf_set_pixel_offset,
+ * adanerf_host_subpixel_grid): one render per displayed frame converges to the supersampled still while the camera rests and stays
+ * anti-aliased while it moves.  The viewer has no counterpart: NeuralRenderer::render (src/neuralrenderer.cpp:146-182) hands each frame to
+ * the blit of src/interoprenderbuffer.cpp:87 as rendered.
+ *   d_cur_rgb [height*width,3] fp32, d_cur_depth_map / d_cur_acc_map [height*width] fp32: what one adanerf_render at cur_pos / cur_rot_c2w
+ *                           wrote (d_rgb_f32_out and the maps of adanerf_set_aux_outputs)
+ *   d_hist_rgb [height*width,3] fp32, d_hist_depth [height*width] fp32, d_hist_count [height*width] uint8: what the previous call wrote to
+ *                           d_out_rgb / d_out_depth / d_out_count, at prev_pos / prev_rot_c2w.  Caller-owned: a host ping-pongs two sets.
+ *                           d_hist_rgb NULL: no history (the first frame, a cut) -- every pixel is rejected and the previous pose is not
+ *                           read (it may be NULL).  d_hist_depth NULL: no disocclusion test.  d_hist_count NULL: constant alpha.
+ *   alpha                   weight of the new frame, in (0, 1]; depth_tol >= 0: relative depth tolerance of the disocclusion test;
+ *                           acc_min >= 0: as adanerf_reproject's; flags: 0 or ADANERF_TEMPORAL_CLAMP
+ *   d_out_rgb [height*width,3] fp32; d_out_depth, d_out_count, d_out_rgba8 ([height*width] uchar4), d_out_mask ([height*width] uint8):
+ *                           each may be NULL
+ *   rejected_out            host pointer or NULL: the number of pixels with mask 0; non-NULL makes the call synchronous (as holes_out of
+ *                           adanerf_reproject), with NULL the outputs are complete after adanerf_sync()
+ * All images have the context's CURRENT frame size and are indexed as adanerf_render's output is; fp32 and uchar4 images are 4-byte aligned.
+ * Definition, per destination pixel j = (x, y) (every operation a single rounded fp32 operation in this order; a gather: the same inputs
+ * give the same bits on every call):
+ *   1 surface   (nds, p) = this context's ray of the pixel at the current pose through the pixel CENTRE (the offset of
+ *               adanerf_set_pixel_offset is ignored, deliberately, as adanerf_reproject ignores it); o = p, or cur_pos
+ *               (ADANERF_SAMPLER_COARSE_FINE).  a = acc_map[j], t = depth_map[j] / a; near by adanerf_reproject's test (a >= acc_min, t
+ *               finite, t > 0; NaNs are far).
+ *   2 own depth near: P = o + nds t, q = P - cur_pos, zc_cur = -((R[2] q_0 + R[5] q_1) + R[8] q_2), R = cur_rot_c2w; far: +inf.  Written to
+ *               d_out_depth[j] whatever becomes of the history.
+ *   3 previous camera   adanerf_reproject's splat arithmetic with dst = prev: q = P - prev_pos (near) or nds (far), v_k, zc, u, vv as there;
+ *               rejected unless zc is finite and > 0, 0 <= u < width and 0 <= vv < height.  The nearest tap is floor(vv) * width + floor(u).
+ *   4 disocclusion (d_hist_depth given)   hd = d_hist_depth[nearest tap]; a near pixel is accepted iff hd is finite and
+ *               |zc - hd| <= depth_tol * zc, a far pixel iff hd == +inf.
+ *   5 history colour   fx = u - 0.5, x0 = floor(fx), wx = fx - x0, taps x0 and x0 + 1 clamped to 0 .. width - 1; y alike.  Per channel
+ *               top = c00 + wx (c01 - c00), bot = c10 + wx (c11 - c10), hst = top + wy (bot - top): a subtraction, a product, a sum each.
+ *   6 clamp (ADANERF_TEMPORAL_CLAMP)   per channel lo / hi = the minimum / maximum of d_cur_rgb over the pixels of j's 3 x 3 neighbourhood
+ *               that exist; a NaN is skipped (all NaN: lo = hi = NaN), -0 orders below +0.  hst = min(max(hst, lo), hi) by the same rules:
+ *               a NaN bound leaves hst as it is, a NaN hst takes the bound.
+ *   7 count     accepted: n' = min(d_hist_count[nearest tap] + 1, 255); rejected, or without d_hist_count: n' = 1.  d_out_count[j] = n'.
+ *               a_eff = fmaxf(alpha, 1.0f / (float)n') with d_hist_count, alpha without: a running mean until 1 / n' falls below alpha.
+ *   8 blend     accepted: out = hst + a_eff (cur - hst), mask 1; rejected: out = cur, the bits copied, mask 0.  d_out_rgba8 follows
+ *               adanerf_resolve_mean's byte contract.
+ * What it does not do: rejected pixels are not re-rendered (that needs a ray mask in the render path) and show the new frame's single
+ * jittered sample; the current frame is not un-jittered; no variance clipping; the scene is static.
+ * Runs on the context's stream in one launch; its only context-owned scratch is the 4-byte counter it shares with adanerf_reproject (made
+ * on first use, freed by adanerf_destroy); adanerf_render never allocates for it.
+ * ADANERF_EINVAL, with nothing written: a NULL current image, map, current pose or d_out_rgb; a NULL previous pose with a history; a pose
+ * entry that is read and not finite; alpha outside (0, 1] or NaN; depth_tol or acc_min negative or NaN; an unknown flag; a misaligned
+ * pointer; d_out_rgb overlapping d_hist_rgb or d_cur_rgb, d_out_depth overlapping d_hist_depth, d_out_count overlapping d_hist_count.
+ * ADANERF_EUNSUPPORTED, with nothing written: a useNDC model; a context with shard_world != 1. */
+int adanerf_temporal_resolve(adanerf_ctx* ctx, const float* d_cur_rgb, const float* d_cur_depth_map, const float* d_cur_acc_map,
+                             const float cur_pos[3], const float cur_rot_c2w[9], const float* d_hist_rgb, const float* d_hist_depth,
+                             const uint8_t* d_hist_count, const float prev_pos[3], const float prev_rot_c2w[9], float alpha, float depth_tol,
+                             float acc_min, int32_t flags, float* d_out_rgb, float* d_out_depth, uint8_t* d_out_count, void* d_out_rgba8,
+                             uint8_t* d_out_mask, int32_t* rejected_out);
 
 /* ---- measurement hook (bench.py's roofline) ---- */
 
