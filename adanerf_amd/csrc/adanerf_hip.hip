@@ -124,6 +124,7 @@ struct adanerf_ctx {
   FlipParams flip_params{};
   bool flip_lds_raised = false;      // flip_kernel may use more than 64 KB of dynamic LDS
   DevBuf reproj_zbuf, reproj_holes;  // adanerf_reproject: [width*height] uint64 z-buffer, the hole count; grown on demand
+  DevBuf upsample_zp;                // adanerf_temporal_upsample: [width*height] fp32 depths at the previous pose; grown on demand
   float px_dx = 0.f, px_dy = 0.f;    // adanerf_set_pixel_offset: kept here, not in ms.rg (calibrate_guard and adanerf_set_frame_size derive from / rewrite that)
   hipEvent_t peer_event = nullptr;   // adanerf_gather_to: orders the destination stream behind the copy
   uint64_t peer_tried = 0;           // bit d: peer access to device d has been requested once
@@ -1224,6 +1225,89 @@ int adanerf_temporal_resolve(adanerf_ctx* c, const float* d_cur_rgb, const float
   const dim3 grid((w + kTemporalTileW - 1) / kTemporalTileW, (h + kTemporalTileH - 1) / kTemporalTileH), block(256);
   hipLaunchKernelGGL(temporal_resolve_kernel, grid, block, 0, c->stream, p, d_cur_rgb, d_cur_depth_map, d_cur_acc_map, d_hist_rgb, d_hist_depth, d_hist_count, d_out_rgb,
                      d_out_depth, d_out_count, static_cast<uchar4*>(d_out_rgba8), d_out_mask, rejected);
+  HIP_TRY(c, hipGetLastError());
+  if (rejected_out) {
+    HIP_TRY(c, hipMemcpyAsync(rejected_out, rejected, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return ADANERF_OK;
+}
+
+int adanerf_temporal_upsample(adanerf_ctx* c, int32_t scale, const float* d_cur_rgb, const float* d_cur_depth_map, const float* d_cur_acc_map, float cur_dx,
+                              float cur_dy, const float cur_pos[3], const float cur_rot_c2w[9], const float* d_hist_rgb, const float* d_hist_depth,
+                              const uint8_t* d_hist_count, const float prev_pos[3], const float prev_rot_c2w[9], float alpha, float depth_tol,
+                              float acc_min, int32_t flags, float* d_out_rgb, float* d_out_depth, uint8_t* d_out_count, void* d_out_rgba8,
+                              uint8_t* d_out_mask, int32_t* rejected_out) {
+  if (!c) return ADANERF_EINVAL;
+  if (!d_cur_rgb || !d_cur_depth_map || !d_cur_acc_map || !d_out_rgb) return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: NULL image");
+  if (!cur_pos || !cur_rot_c2w || (d_hist_rgb && (!prev_pos || !prev_rot_c2w))) return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: NULL pose");
+  for (int k = 0; k < 9; ++k) {
+    if (!std::isfinite(cur_rot_c2w[k]) || (k < 3 && !std::isfinite(cur_pos[k])))
+      return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: a pose entry is not finite");
+    if (d_hist_rgb && (!std::isfinite(prev_rot_c2w[k]) || (k < 3 && !std::isfinite(prev_pos[k]))))      // without a history the previous pose is not read
+      return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: a pose entry is not finite");
+  }
+  if (scale < 1 || scale > kUpsampleMaxScale) return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: scale must lie in 1..4");
+  if (!(std::fabs(cur_dx) <= 1.f && std::fabs(cur_dy) <= 1.f))      // also a NaN
+    return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: the pixel offset must lie in [-1, 1] on both axes");
+  if (!(alpha > 0.f && alpha <= 1.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: alpha must lie in (0, 1]");      // also a NaN
+  if (!(depth_tol >= 0.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: depth_tol must be >= 0");
+  if (!(acc_min >= 0.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: acc_min must be >= 0");
+  if (flags & ~ADANERF_TEMPORAL_CLAMP) return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: flags must be 0 or ADANERF_TEMPORAL_CLAMP");
+  const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  if ((at(d_cur_rgb) | at(d_cur_depth_map) | at(d_cur_acc_map) | at(d_hist_rgb) | at(d_hist_depth) | at(d_out_rgb) | at(d_out_depth) | at(d_out_rgba8)) & 3)
+    return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: fp32 and uchar4 images must be 4-byte aligned");
+  const int w = c->ms.info.width, h = c->ms.info.height, n = w * h;
+  const int64_t N64 = static_cast<int64_t>(n) * scale * scale;
+  if (N64 >= (1ll << 25)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: the output's width*height must be < 2^25");
+  const int W = w * scale, H = h * scale;
+  const size_t N = static_cast<size_t>(N64), sf = sizeof(float);
+  if ((d_hist_rgb && ranges_overlap(d_out_rgb, N * 3 * sf, d_hist_rgb, N * 3 * sf)) || ranges_overlap(d_out_rgb, N * 3 * sf, d_cur_rgb, n * 3 * sf) ||
+      (d_out_depth && ((d_hist_depth && ranges_overlap(d_out_depth, N * sf, d_hist_depth, N * sf)) || ranges_overlap(d_out_depth, N * sf, d_cur_depth_map, n * sf) ||
+                       ranges_overlap(d_out_depth, N * sf, d_cur_acc_map, n * sf))) ||
+      (d_out_count && d_hist_count && ranges_overlap(d_out_count, N, d_hist_count, N)))
+    return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: an output overlaps the image it is gathered from (the history is ping-ponged, not updated in place)");
+  if (c->ms.info.use_ndc) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_temporal_upsample: the depth_map of a useNDC model is NDC depth, not a distance along the ray");
+  if (c->ms.rg.world != 1) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_temporal_upsample: whole frames only (shard_world must be 1)");
+  BIND(c);
+  if (!c->reproj_holes.p) {      // the counter shared with adanerf_reproject and adanerf_temporal_resolve: all run on the context's stream
+    if (int rc = dev_alloc(c, &c->reproj_holes, 64)) return rc;
+  }
+  const bool depth_test = d_hist_rgb && d_hist_depth;
+  if (depth_test && c->upsample_zp.bytes < static_cast<size_t>(n) * sf) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // a call in flight may still use the smaller buffer
+    if (int rc = dev_alloc(c, &c->upsample_zp, static_cast<size_t>(n) * sf)) return rc;
+  }
+  UpsampleParams p{};
+  p.g_lo = with_pixel_offset(c->ms.rg, cur_dx, cur_dy);      // the offset handed in, never the context's own
+  p.g_hi = c->ms.rg;
+  ray_geometry(c->ms.cfg.fov, W, H, c->ms.rg.strip_rows, 1, 0, &p.g_hi);      // what frame_geometry yields for (W, H); its focal as fp32 is read in the kernel
+  std::memcpy(p.g_lo.pos, cur_pos, 3 * sizeof(float));
+  std::memcpy(p.g_lo.rot, cur_rot_c2w, 9 * sizeof(float));
+  std::memcpy(p.g_hi.pos, cur_pos, 3 * sizeof(float));
+  std::memcpy(p.g_hi.rot, cur_rot_c2w, 9 * sizeof(float));
+  if (d_hist_rgb) {
+    std::memcpy(p.prev_pos, prev_pos, 3 * sizeof(float));
+    std::memcpy(p.prev_rot, prev_rot_c2w, 9 * sizeof(float));
+  }
+  p.alpha = alpha;
+  p.depth_tol = depth_tol;
+  p.acc_min = acc_min;
+  p.cur_dx = cur_dx;
+  p.cur_dy = cur_dy;
+  p.scale = scale;
+  p.origin_is_camera = c->ms.coarse_fine ? 1 : 0;
+  p.clamp = (flags & ADANERF_TEMPORAL_CLAMP) ? 1 : 0;
+  int32_t* rejected = reinterpret_cast<int32_t*>(c->reproj_holes.p);
+  float* zp = reinterpret_cast<float*>(c->upsample_zp.p);
+  HIP_TRY(c, hipMemsetAsync(rejected, 0, sizeof(int32_t), c->stream));
+  if (depth_test) {
+    hipLaunchKernelGGL(upsample_depth_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, p, d_cur_depth_map, d_cur_acc_map, zp);
+    HIP_TRY(c, hipGetLastError());
+  }
+  const dim3 grid((W + kTemporalTileW - 1) / kTemporalTileW, (H + kTemporalTileH - 1) / kTemporalTileH), block(256);
+  hipLaunchKernelGGL(upsample_resolve_kernel, grid, block, 0, c->stream, p, d_cur_rgb, d_cur_depth_map, d_cur_acc_map, zp, d_hist_rgb, d_hist_depth, d_hist_count,
+                     d_out_rgb, d_out_depth, d_out_count, static_cast<uchar4*>(d_out_rgba8), d_out_mask, rejected);
   HIP_TRY(c, hipGetLastError());
   if (rejected_out) {
     HIP_TRY(c, hipMemcpyAsync(rejected_out, rejected, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));

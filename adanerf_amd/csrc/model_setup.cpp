@@ -260,14 +260,17 @@ int frame_geometry(ModelSetup* ms, const adanerf_options* opt, int w, int h, std
   I.rays_local = R;
   I.rays_local_max = rows_of_rank(h, strip_rows, world, 0) * w;
   I.batch_rays = batch;
+  I.focal = ray_geometry(ms->cfg.fov, w, h, strip_rows, world, rank, &ms->rg);
+  return ADANERF_OK;
+}
+
+float ray_geometry(double fov, int w, int h, int strip_rows, int world, int rank, RayGenParams* rg) {
   // ray generation constants (A1: src/util/raygeneration.py:10-26, float64)
-  const double fov = ms->cfg.fov;
   const double focal = 0.5 * w / std::tan(0.5 * fov);   // src/datasets.py:182
-  I.focal = static_cast<float>(focal);
   const double x_dist = std::tan(fov / 2) * focal;
   const double y_dist = x_dist * (static_cast<double>(h) / w);
   const double x_pp = x_dist / (w / 2.0), y_pp = y_dist / (h / 2.0);
-  RayGenParams& g = ms->rg;
+  RayGenParams& g = *rg;
   g.start_x = -(x_dist - x_pp / 2);
   g.x_pp = x_pp;
   g.start_y = -(y_dist - y_pp / 2);
@@ -280,7 +283,7 @@ int frame_geometry(ModelSetup* ms, const adanerf_options* opt, int w, int h, std
   g.rank = rank;
   g.ndc_sw = static_cast<float>(-1.0 / (w / (2.0 * focal)));
   g.ndc_sh = static_cast<float>(-1.0 / (h / (2.0 * focal)));
-  return ADANERF_OK;
+  return static_cast<float>(focal);
 }
 
 RayGenParams with_pixel_offset(const RayGenParams& g, float dx, float dy) {

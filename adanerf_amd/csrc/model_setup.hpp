@@ -77,6 +77,10 @@ int select_samples(ModelSetup* ms, int32_t num_samples, float threshold, std::st
 // camera and the view cell in rg stay.  batch_rays comes from opt->batch_rays, the value the caller asked for, never from the clamped
 // info.batch_rays.  On failure *ms is unchanged.  Needs ms->cfg.
 int frame_geometry(ModelSetup* ms, const adanerf_options* opt, int w, int h, std::string* err);
+// The ray-generator half of frame_geometry, pure: the image half of *rg (pixel pitch, start, focal, size, strips, NDC scales) for a
+// w x h frame of a model with this field of view; the camera and the view cell in *rg stay.  Returns the focal length as fp32
+// (adanerf_info.focal).  adanerf_temporal_upsample builds the generator of its output size with it, from the same expressions.
+float ray_geometry(double fov, int w, int h, int strip_rows, int world, int rank, RayGenParams* rg);
 // The ray generator with a sub-pixel offset in force (adanerf_set_pixel_offset): start_x + x_pp * (double)dx, start_y + y_pp * (double)dy,
 // each a rounded float64 multiply followed by a rounded float64 add (never fused); a component equal to 0 leaves that start value's bits
 // untouched.  The kernels' gen_ray keeps computing start + pp * col.

@@ -100,7 +100,8 @@ def scaled_size(w: int, h: int, scale: float):
 def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: Optional[str] = None,
              precision: str = "bf16", batch_size: int = -1, max_frames: int = 0, quiet: bool = False,
              video: Optional[str] = None, fps: int = 30, metrics=("psnr",), fovea=None, sweep_thresholds=None, sweep_samples=None, reproject_stride=None,
-             supersample=None, present_filter=None, temporal=None, temporal_still=None, sweep_scales=None):
+             supersample=None, present_filter=None, temporal=None, temporal_still=None, temporal_upsample=None, temporal_upsample_frames=None,
+             sweep_scales=None):
     """metrics: "psnr" (always reported where a ground-truth image exists) and / or "flip": each record gains ``flip``, the summary
     ``mean_flip``, and with out_dir the error map is written as an 8-bit greyscale ``%05d_flip.png``.
 
@@ -137,6 +138,16 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     frames after the camera stopped there); ALPHA is ``temporal`` or, without it, 0.1; the summary carries ``temporal_still``.
     Neither goes with reproject_stride, supersample or sweep_scales.
 
+    temporal_upsample (S in 1..4 or None): temporal upsampling beside the plain frames.  The context renders at the dataset's size / S, which
+    must divide (ValueError otherwise).  Per pose the plain frame is the un-jittered small render shown at the dataset's size by
+    NeuralRenderer.present's linear filter (scored from that 8-bit image / 255); then, from an empty history and at rest, K =
+    temporal_upsample_frames (default S x S) frames are rendered at the offsets of the S x S cycle and resolved at the dataset's size
+    (NeuralRenderer.render_upsampled, clamp on, default alpha and tolerance), and the last fp32 frame is scored.  Records gain
+    ``psnr_upsampled`` / ``mse_upsampled``, ``rejected_fraction`` (of the last call, of w h), ``temporal_upsample`` and, with "flip",
+    ``flip_upsampled``; the summary ``mean_psnr_upsampled``, ``mean_rejected_fraction``, ``mean_flip_upsampled``, ``temporal_upsample``
+    and ``temporal_upsample_frames``; out_dir gets ``%05d_upsampled.png``.  samples_per_ray / ms are those of the small plain render.
+    Not with reproject_stride, supersample, sweep_scales, temporal or temporal_still.
+
     fovea (``R:N:T[,R:N:T...],N:T`` or what renderer.parse_fovea makes of it, or None): every frame is rendered with per-ray budgets around a
     gaze at the centre of the rendered frame (radii in its pixels).  Records and summary keep their shape: PSNR / FLIP / samples per ray are
     those of the foveated frames -- the quality-against-cost table of a foveation setting."""
@@ -166,6 +177,15 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     if ta and (stride or ss or sweep_scales):
         raise ValueError("temporal / temporal_still resolve one jittered render per frame at the dataset's resolution: not together with "
                          "reproject_stride, supersample or sweep_scales")
+    tu = int(temporal_upsample) if temporal_upsample is not None else 0
+    if temporal_upsample is not None and (tu != temporal_upsample or not 1 <= tu <= 4):
+        raise ValueError("temporal_upsample must be 1, 2, 3 or 4, got %s" % (temporal_upsample,))
+    if temporal_upsample_frames is not None and (not tu or int(temporal_upsample_frames) != temporal_upsample_frames or temporal_upsample_frames < 1):
+        raise ValueError("temporal_upsample_frames must be an integer >= 1 and goes with temporal_upsample, got %s" % (temporal_upsample_frames,))
+    tu_frames = int(temporal_upsample_frames) if temporal_upsample_frames is not None else tu * tu
+    if tu and (stride or ss or sweep_scales or ta):
+        raise ValueError("temporal_upsample renders at the dataset's size / S and resolves at the dataset's size: not together with "
+                         "reproject_stride, supersample, sweep_scales, temporal or temporal_still")
     if present_filter not in PRESENT_FILTERS:
         raise ValueError("present_filter must be None, 'nearest', 'linear' or 'area', got %r" % (present_filter,))
     want_flip = "flip" in metrics
@@ -173,23 +193,28 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     if max_frames > 0:
         frames = frames[:max_frames]
     w, h = meta["w"], meta["h"]
+    if tu and (w % tu or h % tu):
+        raise ValueError("temporal_upsample %d does not divide the dataset's %d x %d" % (tu, w, h))
     results: List[dict] = []
-    with NeuralRenderer(Settings(model_dir, w, h, batch_size=batch_size), precision=precision) as r:
+    with NeuralRenderer(Settings(model_dir, w // tu if tu else w, h // tu if tu else h, batch_size=batch_size), precision=precision) as r:
         if abs(r.info.fov - meta["fov"]) > 1e-4 and not quiet:
             print("warning: dataset camera_angle_x %.6f differs from the model's fov %.6f (the model's is used)" %
                   (meta["fov"], r.info.fov), file=sys.stderr)
         vid = Y4mWriter(video, w, h, fps) if video else None
         d_ref = r.empty((w * h, 3), np.float32) if want_flip else None
         d_map = r.empty((w * h,), np.float32) if want_flip and out_dir else None
-        d_pres = r.empty((w * h, 3), np.float32) if want_flip and (sweep_scales or stride or ta) else None
+        d_pres = r.empty((w * h, 3), np.float32) if want_flip and (sweep_scales or stride or ta or tu) else None
         if stride:
             r.enable_reprojection()
         if ta:
             r.enable_temporal(alpha=ta, grid=2)
+        if tu:
+            r.enable_temporal_upsample(scale=tu)
 
         def render_set(out_dir, extra, scale=None):
             """one pass over the set at the selection (and, with a scale, the frame size) in force -> its records"""
-            rw, rh = (w, h) if scale is None else (r.info.width, r.info.height)
+            rw, rh = (w, h) if scale is None and not tu else (r.info.width, r.info.height)
+            presented = scale is not None or bool(tu)
             recs: List[dict] = []
             if out_dir:
                 os.makedirs(out_dir, exist_ok=True)
@@ -207,8 +232,8 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                 else:
                     r.set_camera(fr["pose"], fr["rot"])
                     rgb, rgba, st = r.render_supersampled(ss) if ss else r.render_numpy()
-                    if scale is not None:      # the frame as a w x h window shows it, filtered on the device
-                        rgba = r.present(w, h, filter=present_filter).reshape(-1, 4)
+                    if presented:      # the frame as a w x h window shows it, filtered on the device
+                        rgba = r.present(w, h, filter="linear" if tu else present_filter).reshape(-1, 4)
                         rgb = rgba[:, :3].astype(np.float32) / 255.0
                     rec = dict(extra, frame=i, image=fr["image"], samples_per_ray=st.total_samples / float(rw * rh), ms=st.ms_total)
                     if stride:
@@ -223,7 +248,7 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                     mse = float(np.mean((rgb.astype(np.float64) - ref) ** 2))
                     rec.update(mse=mse, psnr=psnr_from_mse(mse))
                     if want_flip:       # the rendered frame is still on the device (render_numpy); argument order of src/evaluate.py:144
-                        d_test = r._o_rgb if scale is None and not warped else d_pres.upload(rgb)
+                        d_test = r._o_rgb if not presented and not warped else d_pres.upload(rgb)
                         rec.update(flip=r.flip_device(d_test, d_ref.upload(ref), w, h, error_map=d_map))
                         if d_map is not None:
                             fm = np.nan_to_num(d_map.numpy().reshape(h, w), nan=1.0)      # the map lies in [0, 1]
@@ -241,6 +266,18 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                             rec.update(flip_temporal=r.flip_device(d_pres.upload(t_rgb), d_ref, w, h))
                     if out_dir:
                         write_png(os.path.join(out_dir, "%05d_temporal.png" % i), t_rgba[:, :3].reshape(h, w, 3))
+                if tu:      # the same pose, at rest from an empty history: K jittered small renders resolved at the dataset's size
+                    r.reset_upsample()
+                    for _ in range(tu_frames):
+                        u_rgb, u_rgba, _, u_rejected, _ = r.render_upsampled()
+                    rec.update(temporal_upsample=tu, rejected_fraction=u_rejected / float(w * h))
+                    if ref is not None:
+                        u_mse = float(np.mean((u_rgb.astype(np.float64) - ref) ** 2))
+                        rec.update(mse_upsampled=u_mse, psnr_upsampled=psnr_from_mse(u_mse))
+                        if want_flip:
+                            rec.update(flip_upsampled=r.flip_device(d_pres.upload(u_rgb), d_ref, w, h))
+                    if out_dir:
+                        write_png(os.path.join(out_dir, "%05d_upsampled.png" % i), u_rgba[:, :3].reshape(h, w, 3))
                 if out_dir:
                     write_png(os.path.join(out_dir, "%05d.png" % i), rgba[:, :3].reshape(h, w, 3))
                 if vid:
@@ -268,7 +305,8 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
             vid.close()
     if sweep:
         return dict(frames=len(frames), sweep=sweep, **(dict(supersample=ss) if ss else {}), **(dict(temporal_still=still) if still else {})), results
-    return dict(summarise(results, want_flip), **(dict(supersample=ss) if ss else {}), **(dict(temporal_still=still) if still else {})), results
+    return dict(summarise(results, want_flip), **(dict(supersample=ss) if ss else {}), **(dict(temporal_still=still) if still else {}),
+                **(dict(temporal_upsample=tu, temporal_upsample_frames=tu_frames) if tu else {})), results
 
 
 def summarise(results: List[dict], want_flip: bool) -> dict:
@@ -288,7 +326,13 @@ def summarise(results: List[dict], want_flip: bool) -> dict:
                 summary["mean_flip_" + kind] = float(np.mean([x["flip"] for x in part])) if part else None
         holes = [x["hole_fraction"] for x in results if x.get("warped")]
         summary["mean_hole_fraction"] = float(np.mean(holes)) if holes else 0.0
-    if any("rejected_fraction" in x for x in results):      # temporal / temporal_still: the resolved frames beside the plain ones
+    if any("temporal_upsample" in x for x in results):      # temporal_upsample: the upsampled frames beside the enlarged small ones
+        part = [x for x in results if "psnr_upsampled" in x]
+        summary["mean_psnr_upsampled"] = float(np.mean([x["psnr_upsampled"] for x in part])) if part else None
+        if want_flip:
+            summary["mean_flip_upsampled"] = float(np.mean([x["flip_upsampled"] for x in part])) if part else None
+        summary["mean_rejected_fraction"] = float(np.mean([x["rejected_fraction"] for x in results if "rejected_fraction" in x]))
+    elif any("rejected_fraction" in x for x in results):      # temporal / temporal_still: the resolved frames beside the plain ones
         part = [x for x in results if "psnr_temporal" in x]
         summary["mean_psnr_temporal"] = float(np.mean([x["psnr_temporal"] for x in part])) if part else None
         if want_flip:
@@ -329,6 +373,12 @@ def build_parser():
                          "summary gains mean_psnr_temporal / mean_rejected_fraction (and mean_flip_temporal with --metrics flip)")
     ap.add_argument("--temporal-still", type=int, default=None, metavar="K",
                     help="per pose, score the frame after K resolves at rest from an empty history instead (ALPHA of --temporal, default 0.1)")
+    ap.add_argument("--temporal-upsample", type=int, default=None, choices=range(1, 5), metavar="S",
+                    help="temporal upsampling beside the plain frames: render at the dataset's size / S (which must divide), per pose resolve K "
+                         "jittered frames at rest at the dataset's size (adanerf_temporal_upsample) and score that frame; the plain frame is the "
+                         "un-jittered small render enlarged by the linear present filter; the summary gains mean_psnr_upsampled / "
+                         "mean_rejected_fraction (and mean_flip_upsampled with --metrics flip)")
+    ap.add_argument("--temporal-upsample-frames", type=int, default=None, metavar="K", help="frames resolved per pose (default S x S)")
     ap.add_argument("--present-filter", default=None, choices=["nearest", "linear", "area"],
                     help="filter of the --sweep-scales presentation (default: the viewer's rule, linear when enlarging, else nearest); area is "
                          "the exact area filter and the only sensible choice for scales above 1, where nearest throws the extra rays away")
@@ -345,10 +395,16 @@ def main(argv=None):
         ap.error("--supersample cannot be combined with --reproject-stride")
     if (a.temporal is not None or a.temporal_still is not None) and (a.supersample is not None or a.reproject_stride is not None or a.sweep_scales):
         ap.error("--temporal / --temporal-still cannot be combined with --supersample, --reproject-stride or --sweep-scales")
+    if a.temporal_upsample is not None and (a.temporal is not None or a.temporal_still is not None or a.supersample is not None or
+                                            a.reproject_stride is not None or a.sweep_scales):
+        ap.error("--temporal-upsample cannot be combined with --temporal, --temporal-still, --supersample, --reproject-stride or --sweep-scales")
+    if a.temporal_upsample_frames is not None and a.temporal_upsample is None:
+        ap.error("--temporal-upsample-frames goes with --temporal-upsample")
     summary, _ = evaluate(a.model_dir, a.dataset_dir, a.set, a.out, a.precision, a.batch_size, a.max_frames, video=a.video, fps=a.fps,
                           metrics=tuple(a.metrics), sweep_thresholds=a.sweep_thresholds, sweep_samples=a.sweep_samples, sweep_scales=a.sweep_scales,
                           fovea=a.fovea, reproject_stride=a.reproject_stride, supersample=a.supersample, present_filter=a.present_filter,
-                          temporal=a.temporal, temporal_still=a.temporal_still)
+                          temporal=a.temporal, temporal_still=a.temporal_still, temporal_upsample=a.temporal_upsample,
+                          temporal_upsample_frames=a.temporal_upsample_frames)
     print(json.dumps(summary))
 
 

@@ -23,7 +23,7 @@ NeuralRenderer::~NeuralRenderer() {
   if (ctx) {
     if (d_gathered) adanerf_free(ctx, d_gathered);
     if (d_frame) adanerf_free(ctx, d_frame);
-    for (void* p : {d_depth, d_acc, d_warp, d_rgb, d_sum, d_hist[0][0], d_hist[0][1], d_hist[0][2], d_hist[1][0], d_hist[1][1], d_hist[1][2]})
+    for (void* p : {d_depth, d_acc, d_warp, d_rgb, d_sum, d_hist[0][0], d_hist[0][1], d_hist[0][2], d_hist[1][0], d_hist[1][1], d_hist[1][2], d_up})
       if (p) adanerf_free(ctx, p);
     if (d_window) adanerf_free(ctx, d_window);
     adanerf_destroy(ctx);
@@ -166,6 +166,10 @@ bool NeuralRenderer::init() {
                     : (settings.render_oracle ? "--taa blends rendered frames; not with --oracle" : "--taa: the depth of a useNDC model is NDC depth");
     return false;
   }
+  if (settings.taau_scale > 0 && info_.use_ndc) {
+    err = "--taau: the depth of a useNDC model is NDC depth";
+    return false;
+  }
   if (!allocFrameBuffers()) return false;
   if (settings.write_window &&
       adanerf_malloc(ctx, static_cast<size_t>(settings.window_width) * settings.window_height * 4, &d_window) != ADANERF_OK) {
@@ -196,6 +200,18 @@ bool NeuralRenderer::allocFrameBuffers() {
     void** bufs[] = {&d_rgb, &d_depth, &d_acc, &d_hist[0][0], &d_hist[0][1], &d_hist[0][2], &d_hist[1][0], &d_hist[1][1], &d_hist[1][2]};
     const size_t bytes[] = {n * 12, n * 4, n * 4, n * 12, n * 4, n, n * 12, n * 4, n};
     for (int k = 0; k < 9; ++k) {
+      if (*bufs[k] && adanerf_free(ctx, *bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+      *bufs[k] = nullptr;
+      if (adanerf_malloc(ctx, bytes[k], bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+    }
+    if (adanerf_set_aux_outputs(ctx, static_cast<float*>(d_depth), static_cast<float*>(d_acc)) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+  }
+  if (settings.taau_scale > 0) {      // the render-size frame and aux outputs; the history and the shown frame at S w x S h
+    const size_t n = static_cast<size_t>(info_.width) * info_.height, N = n * settings.taau_scale * settings.taau_scale;
+    taa_have = false;
+    void** bufs[] = {&d_rgb, &d_depth, &d_acc, &d_hist[0][0], &d_hist[0][1], &d_hist[0][2], &d_hist[1][0], &d_hist[1][1], &d_hist[1][2], &d_up};
+    const size_t bytes[] = {n * 12, n * 4, n * 4, N * 12, N * 4, N, N * 12, N * 4, N, N * 4};
+    for (int k = 0; k < 10; ++k) {
       if (*bufs[k] && adanerf_free(ctx, *bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
       *bufs[k] = nullptr;
       if (adanerf_malloc(ctx, bytes[k], bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
@@ -379,7 +395,9 @@ bool NeuralRenderer::render() {
     }
     return writeImageToFile();
   }
-  if (settings.taa_alpha > 0.f) {
+  if (settings.taau_scale > 0) {
+    if (!renderUpsampled(&st, rot)) return false;
+  } else if (settings.taa_alpha > 0.f) {
     if (!renderTemporal(&st, rot)) return false;
   } else if (settings.supersample > 1 ? !renderSupersampled(&st) : adanerf_render(ctx, d_frame, nullptr, &st) != ADANERF_OK) {
     if (settings.supersample <= 1) err = adanerf_last_error(ctx);
@@ -408,7 +426,7 @@ bool NeuralRenderer::render() {
     have_source = true;
     since_render = 0;
   }
-  d_shown = d_frame;
+  d_shown = settings.taau_scale > 0 ? d_up : d_frame;
   logInterval();
   return writeImageToFile();
 }
@@ -481,6 +499,39 @@ bool NeuralRenderer::renderTemporal(adanerf_stats* st, const float rot[9]) {
   return true;
 }
 
+// --taau S: one render of this frame's camera at the next offset of the S x S cycle, then adanerf_temporal_upsample (clamp on) into the
+// history of S w x S h, which the result replaces; d_up gets the upsampled frame under the viewer's output contract.  The offset goes back
+// to (0, 0).  The history's depth is tested only when the pose differs from the history's.
+bool NeuralRenderer::renderUpsampled(adanerf_stats* st, const float rot[9]) {
+  const int S = settings.taau_scale;
+  float dx = 0.f, dy = 0.f;
+  const bool ok = adanerf_host_subpixel_grid(S, taa_k % (S * S), &dx, &dy) == ADANERF_OK && adanerf_set_pixel_offset(ctx, dx, dy) == ADANERF_OK &&
+                  adanerf_render(ctx, nullptr, static_cast<float*>(d_rgb), st) == ADANERF_OK;
+  if (!ok) err = adanerf_last_error(ctx);
+  const bool back = adanerf_set_pixel_offset(ctx, 0.f, 0.f) == ADANERF_OK;
+  if (!ok) return false;
+  taa_k = (taa_k + 1) % (S * S);
+  const int out = taa_have ? 1 - taa_side : 0;
+  void* const* hist = d_hist[taa_side];
+  const bool at_rest = taa_have && std::memcmp(prev_pos, camera.getPosition(), sizeof(prev_pos)) == 0 && std::memcmp(prev_rot, rot, sizeof(prev_rot)) == 0;
+  int32_t rejected = 0;
+  if (!back || adanerf_temporal_upsample(ctx, S, static_cast<const float*>(d_rgb), static_cast<const float*>(d_depth), static_cast<const float*>(d_acc), dx, dy,
+                                         camera.getPosition(), rot, taa_have ? static_cast<const float*>(hist[0]) : nullptr,
+                                         taa_have && !at_rest ? static_cast<const float*>(hist[1]) : nullptr,
+                                         taa_have ? static_cast<const uint8_t*>(hist[2]) : nullptr, prev_pos, prev_rot, settings.taau_alpha, settings.taau_tol,
+                                         0.5f, ADANERF_TEMPORAL_CLAMP, static_cast<float*>(d_hist[out][0]), static_cast<float*>(d_hist[out][1]),
+                                         static_cast<uint8_t*>(d_hist[out][2]), d_up, nullptr, &rejected) != ADANERF_OK) {
+    err = adanerf_last_error(ctx);
+    return false;
+  }
+  std::memcpy(prev_pos, camera.getPosition(), sizeof(prev_pos));
+  std::memcpy(prev_rot, rot, sizeof(prev_rot));
+  taa_side = out;
+  taa_have = true;
+  s_rejected += rejected;
+  return true;
+}
+
 // --reproject K: the last rendered frame at this frame's camera (adanerf_reproject, holes filled from their neighbours, the rest black)
 bool NeuralRenderer::warp(const float rot[9]) {
   int32_t holes = 0;
@@ -511,6 +562,8 @@ void NeuralRenderer::logInterval() {
             << ", frames: " << sample_count << ", frame ms: " << s_total / rendered;
   if (settings.supersample > 1) std::cout << ", renders per frame: " << settings.supersample * settings.supersample;
   if (settings.taa_alpha > 0.f) std::cout << ", taa rejected: " << s_rejected / static_cast<double>(logging_interval) / settings.total_size;
+  if (settings.taau_scale > 0)
+    std::cout << ", taau rejected: " << s_rejected / static_cast<double>(logging_interval) / settings.total_size / (settings.taau_scale * settings.taau_scale);
   if (settings.reproject > 1) std::cout << ", holes: " << s_holes / static_cast<double>(std::max(s_warped, 1)) << " (" << s_warped << " warped frames)";
   std::cout << std::endl;
   s_inference1 = s_inference2 = s_fc2 = s_rm = s_total = 0;
@@ -524,13 +577,15 @@ void NeuralRenderer::logInterval() {
 // -ws W H (interoprenderbuffer.cpp:87), presented on the device
 bool NeuralRenderer::writeImageToFile() {
   const void* shown = d_shown ? d_shown : d_frame;
-  if (settings.write_images && !writeBmp("out.bmp", shown, static_cast<int>(settings.width), static_cast<int>(settings.height))) return false;
+  const int up = shown == d_up && d_up ? settings.taau_scale : 1;      // --taau: the shown frame is S times the render size
+  const int sw = static_cast<int>(settings.width) * up, sh = static_cast<int>(settings.height) * up;
+  if (settings.write_images && !writeBmp("out.bmp", shown, sw, sh)) return false;
   if (!settings.write_window) return true;
   const int ww = static_cast<int>(settings.window_width), wh = static_cast<int>(settings.window_height);
   const int filter = settings.present_filter == "area" ? ADANERF_PRESENT_AREA
                                                        : (settings.present_filter == "linear" ? ADANERF_PRESENT_LINEAR
                                                                                               : (settings.present_filter == "nearest" ? ADANERF_PRESENT_NEAREST : 0));
-  if (adanerf_present(ctx, shown, static_cast<int>(settings.width), static_cast<int>(settings.height), d_window, ww, wh, filter) != ADANERF_OK) {
+  if (adanerf_present(ctx, shown, sw, sh, d_window, ww, wh, filter) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;
   }

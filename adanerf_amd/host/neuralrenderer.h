@@ -53,7 +53,7 @@ class NeuralRenderer {
     *y = gaze_y;
     return fovea_pending;
   }
-  // --taa: the next frame is shown as rendered and starts a new history (script token "cut"); without --taa nothing to drop
+  // --taa / --taau: the next frame is shown as rendered and starts a new history (script token "cut"); without them nothing to drop
   void cutHistory() { taa_have = false; }
   bool applyFrameSize();             // a pending setFrameSize, now: render() calls it; --dry-run calls it in render()'s place (host only)
   int batchesPerFrame() const;       // ceil(rays / batch_rays)
@@ -94,6 +94,10 @@ class NeuralRenderer {
   float prev_pos[3] = {0, 0, 0}, prev_rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   long long s_rejected = 0;          // rejected pixels of the running interval's frames
   bool renderTemporal(adanerf_stats* st, const float rot[9]);   // one render at the cycle's next offset, resolved against the history into d_frame
+  // --taau S: as --taa, with the two history sets and the shown frame d_up (uchar4) at S w x S h; the state above (taa_have, taa_side, taa_k,
+  // prev_*, s_rejected) is shared, the two being exclusive
+  void* d_up = nullptr;
+  bool renderUpsampled(adanerf_stats* st, const float rot[9]);   // one render at the cycle's next offset, resolved into the S w x S h history and d_up
   void* d_window = nullptr;          // --write-window: uchar4 [window_height*window_width], the frame as adanerf_present shows it
   int world_ = 1, strip_rows_ = 8;   // share layout chosen at init; a live context keeps its strip height
   bool allocFrameBuffers();          // d_frame, d_gathered, d_payload for the size in info_ (again after a size change)

@@ -19,7 +19,7 @@ const char* Settings::usage() {
          "                                                              sample budget N / threshold from that frame on;\n"
          "                                                              size <W> <H>: frame size from that frame on, the window stays;\n"
          "                                                              gaze <X> <Y>: the --fovea gaze point, in pixels;\n"
-         "                                                              cut: --taa starts a new history with that frame)\n"
+         "                                                              cut: --taa / --taau start a new history with that frame)\n"
          "               [--reproject K]      of every K frames render the first and warp it to the camera of the next K - 1 (depth\n"
          "                                    reprojection, holes filled from their neighbours); -w / --write-window write what was shown\n"
          "               [--supersample S]    every shown frame is S x S renders (S in 1..8) at the offsets of a regular sub-pixel grid, summed and\n"
@@ -28,6 +28,10 @@ const char* Settings::usage() {
          "                                    (weight ALPHA in (0, 1]) with a history carried to its camera by its depth; a history pixel whose depth\n"
          "                                    is off by more than TOL (relative, default 0.02) is dropped; script token cut drops the history\n"
          "               [--taa-grid S]       the cycle of --taa: the S x S regular sub-pixel grid, S in 1..8 (default 2)\n"
+         "               [--taau S[:ALPHA[:TOL]]]  temporal upsampling: -s W H stays the render size; every frame is rendered at the next offset of the\n"
+         "                                    S x S sub-pixel cycle (S in 1..4) and resolved into a history of S W x S H (weight ALPHA in (0, 1], default\n"
+         "                                    0.1; neighbourhood depth tolerance TOL, default 0.02); -w / --write-window write the S W x S H frame;\n"
+         "                                    script tokens cut and size drop the history\n"
          "               [--present-filter nearest|linear|area]     filter of the -ws window image; default: linear if the window is wider than\n"
          "                                    the frame, else nearest (the viewer's blit); area: exact area filter, for a frame rendered larger\n"
          "               [--gpus N] [--same-device] [--sub-shares P]\n";
@@ -185,6 +189,25 @@ bool Settings::init(int argc, char** argv, std::string* err) {
         return false;
       }
       taa_grid = static_cast<int>(k);
+    } else if (a == "--taau") {
+      if (!need(i, 1)) return false;
+      std::vector<std::string> f(1);
+      for (const char* ch = argv[++i]; *ch; ++ch) {
+        if (*ch == ':') f.emplace_back();
+        else f.back() += *ch;
+      }
+      char *es = nullptr, *ea = nullptr, *et = nullptr;
+      const long k = std::strtol(f[0].c_str(), &es, 10);
+      const float al = f.size() > 1 ? std::strtof(f[1].c_str(), &ea) : 0.1f, tl = f.size() > 2 ? std::strtof(f[2].c_str(), &et) : 0.02f;
+      bool ok = f.size() <= 3 && !f[0].empty() && *es == 0 && k >= 1 && k <= 4;
+      ok = ok && (f.size() < 2 || (!f[1].empty() && *ea == 0)) && (f.size() < 3 || (!f[2].empty() && *et == 0));
+      if (!ok || !(al > 0.f && al <= 1.f) || !(tl >= 0.f && tl < INFINITY)) {
+        *err = "--taau S[:ALPHA[:TOL]]: S must be an integer in 1..4, ALPHA must lie in (0, 1], TOL must be a number >= 0";
+        return false;
+      }
+      taau_scale = static_cast<int>(k);
+      taau_alpha = al;
+      taau_tol = tl;
     } else if (a == "--present-filter") {
       if (!need(i, 1)) return false;
       present_filter = argv[++i];
@@ -223,6 +246,14 @@ bool Settings::init(int argc, char** argv, std::string* err) {
   if (taa_alpha > 0.f && (reproject > 1 || supersample > 1)) {
     *err = reproject > 1 ? "--taa renders and resolves every frame; not with --reproject"
                          : "--taa spends one render per frame on a cycle of sub-pixel offsets; not with --supersample";
+    return false;
+  }
+  if (taau_scale > 0 && (taa_alpha > 0.f || reproject > 1 || supersample > 1 || gpus > 1 || render_oracle)) {
+    *err = taa_alpha > 0.f ? "--taau is a temporal resolve of its own; not with --taa"
+           : reproject > 1 ? "--taau renders and resolves every frame; not with --reproject"
+           : supersample > 1 ? "--taau spends one render per frame on a cycle of sub-pixel offsets; not with --supersample"
+           : gpus > 1 ? "--taau resolves whole frames of one context; use it with --gpus 1"
+                      : "--taau blends rendered frames; not with --oracle";
     return false;
   }
   total_size = width * height;

@@ -44,6 +44,9 @@ class Settings {
   float taa_alpha = 0.f;        // --taa ALPHA[:TOL]: temporal anti-aliasing (adanerf_temporal_resolve, clamp on): every frame is rendered at the next offset of
   float taa_tol = 0.02f;        // the --taa-grid cycle and blended with a history carried to its camera; ALPHA in (0, 1] the weight of the new frame, TOL >= 0
   int taa_grid = 2;             // the relative depth tolerance of the disocclusion test; --taa-grid S (1..8): the S x S cycle of adanerf_host_subpixel_grid.  0: off
+  int taau_scale = 0;           // --taau S[:ALPHA[:TOL]]: temporal upsampling (adanerf_temporal_upsample, clamp on): -s W H stays the render size, every frame is
+  float taau_alpha = 0.1f;      // rendered at the next offset of the S x S cycle and resolved into a history of S W x S H, which -w / --write-window write;
+  float taau_tol = 0.02f;       // S in 1..4, ALPHA in (0, 1] (default 0.1), TOL >= 0 the relative tolerance of the neighbourhood depth test (default 0.02).  0: off
   std::string present_filter;   // --present-filter nearest|linear|area: filter of the -ws window image (adanerf_present); empty: the viewer's rule
   bool render_oracle = false;   // --oracle: the viewer's 'O' key (inputhandler.cpp:76), sampling-network debug view
 

@@ -77,7 +77,8 @@ EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_las
            "adanerf_composite", "adanerf_composite_classic", "adanerf_composite_aux", "adanerf_composite_classic_aux", "adanerf_disp_map", "adanerf_copy_result_sampling_network", "adanerf_flip",
            "adanerf_render_oracle", "adanerf_gather_to", "adanerf_probe_mfma", "adanerf_malloc",
            "adanerf_free", "adanerf_memcpy_h2d", "adanerf_memcpy_d2h", "adanerf_get_buffer",
-           "adanerf_set_pixel_offset", "adanerf_get_pixel_offset", "adanerf_accumulate", "adanerf_resolve_mean", "adanerf_host_subpixel_grid", "adanerf_temporal_resolve"]
+           "adanerf_set_pixel_offset", "adanerf_get_pixel_offset", "adanerf_accumulate", "adanerf_resolve_mean", "adanerf_host_subpixel_grid", "adanerf_temporal_resolve",
+           "adanerf_temporal_upsample"]
 
 _lib = None
 
@@ -113,6 +114,8 @@ def load_library(path: Optional[str] = None):
     lib.adanerf_reproject.argtypes = [vp, vp, vp, vp, fp, fp, fp, fp, C.c_float, C.c_uint32, i32, vp, vp, vp, C.POINTER(i32)]
     lib.adanerf_temporal_resolve.argtypes = [vp, vp, vp, vp, fp, fp, vp, vp, vp, fp, fp, C.c_float, C.c_float, C.c_float, i32, vp, vp, vp, vp, vp,
                                              C.POINTER(i32)]
+    lib.adanerf_temporal_upsample.argtypes = [vp, i32, vp, vp, vp, C.c_float, C.c_float, fp, fp, vp, vp, vp, fp, fp, C.c_float, C.c_float, C.c_float, i32,
+                                              vp, vp, vp, vp, vp, C.POINTER(i32)]
     lib.adanerf_render.argtypes = [vp, vp, vp, C.POINTER(Stats)]
     lib.adanerf_assemble_strips.argtypes = [vp, vp, vp]
     lib.adanerf_set_aux_outputs.argtypes = [vp, vp, vp]
@@ -371,6 +374,8 @@ class NeuralRenderer:
         self._rp_frame = None         # (device rgba8, depth, acc, pos, rot, rays) of the last render_numpy since then
         self._ta = None               # enable_temporal(): alpha, depth_tol, clamp, the cycle of sub-pixel offsets and the place in it
         self._ta_hist = None          # (index of the history's buffer set, pos, rot) of the last render_temporal since then
+        self._tu = None               # enable_temporal_upsample(): scale, alpha, depth_tol, clamp, the offset cycle and the place in it
+        self._tu_hist = None          # (index of the history's buffer set, pos, rot) of the last render_upsampled since then
 
     # -- lifecycle -------------------------------------------------------------------------------
     def init(self) -> bool:
@@ -448,6 +453,7 @@ class NeuralRenderer:
             self._drop_budget_buffers()
         self._rp_frame = None      # a frame of the old size cannot be warped with the new size's ray generator
         self._ta_hist = None       # nor can a history of the old size be gathered from
+        self._tu_hist = None
         for name in ("_o_rgb", "_o_rgba"):
             if hasattr(self, name):
                 a = getattr(self, name)
@@ -765,6 +771,100 @@ class NeuralRenderer:
         self._last_frame = (self._o_rgba, self.info.width, self.info.height)
         self._rp_frame = None      # the aux maps now belong to a jittered frame whose colour was blended: nothing reproject() may warp
         return out[0].numpy(), self._o_rgba.numpy(), self._ta_mask.numpy(), rejected, st
+
+    # -- temporal upsampling: one jittered render at w x h per frame, resolved into a history of s w x s h ----
+    def temporal_upsample_device(self, scale: int, cur_rgb, cur_depth, cur_acc, cur_dx: float, cur_dy: float, cur_pos, cur_rot, hist_rgb, hist_depth,
+                                 hist_count, prev_pos, prev_rot, out_rgb, out_depth=None, out_count=None, out_rgba8=None, out_mask=None,
+                                 alpha: float = 0.1, depth_tol: float = 0.02, acc_min: float = 0.5, clamp: bool = True,
+                                 rejected: bool = True) -> Optional[int]:
+        """adanerf_temporal_upsample on device images: the frame (fp32 rgb, depth_map, acc_map) of the context's frame size w x h, rendered
+        at (cur_pos, cur_rot) with the pixel offset (cur_dx, cur_dy), resolved into images of scale w x scale h: the history (rgb, depth,
+        count: each may be None) the previous call wrote at (prev_pos, prev_rot), and out_rgb and, if given, out_depth / out_count (the
+        next call's history), out_rgba8 and out_mask (uint8: 1 the history was used, 2 a placeholder replaced, 0 rejected).  Returns the
+        number of rejected pixels (synchronous); with rejected=False nothing is read back and the outputs are complete after sync()."""
+        f = [None if v is None else np.ascontiguousarray(v, dtype=np.float32).reshape(k) for v, k in ((cur_pos, 3), (cur_rot, 9), (prev_pos, 3), (prev_rot, 9))]
+        fp = [None if v is None else v.ctypes.data_as(C.POINTER(C.c_float)) for v in f]
+        n = C.c_int32(0)
+        self._check(self.lib.adanerf_temporal_upsample(self.handle, int(scale), _ptr(cur_rgb), _ptr(cur_depth), _ptr(cur_acc), float(cur_dx), float(cur_dy),
+                                                       fp[0], fp[1], _ptr(hist_rgb), _ptr(hist_depth), _ptr(hist_count), fp[2], fp[3], float(alpha),
+                                                       float(depth_tol), float(acc_min), TEMPORAL_CLAMP if clamp else 0, _ptr(out_rgb), _ptr(out_depth),
+                                                       _ptr(out_count), _ptr(out_rgba8), _ptr(out_mask), C.byref(n) if rejected else None))
+        return int(n.value) if rejected else None
+
+    def _upsample_buffers(self):
+        """two history sets (rgb, depth, count) of the output size to ping-pong, its 8-bit image and mask, made on first use and again when
+        the output size changes; the frame's depth_map / acc_map are the aux buffers reproject() uses too"""
+        n = self.info.rays_local * self._tu["scale"] ** 2
+        self._reproject_buffers()
+        if not hasattr(self, "_tu_sets") or self._tu_mask.shape[0] != n:
+            if hasattr(self, "_tu_sets"):
+                for a in [b for st in self._tu_sets for b in st] + [self._tu_mask, self._tu_rgba]:
+                    if self._last_frame is not None and self._last_frame[0] is a:
+                        self._last_frame = None
+                    a.free()
+                    self._own.remove(a)
+            self._tu_sets = [(self.empty((n, 3), np.float32), self.empty((n,), np.float32), self.empty((n,), np.uint8)) for _ in range(2)]
+            self._tu_mask, self._tu_rgba = self.empty((n,), np.uint8), self.empty((n, 4), np.uint8)
+            self._tu_hist = None
+
+    def enable_temporal_upsample(self, scale: int = 2, alpha: float = 0.1, depth_tol: float = 0.02, clamp: bool = True):
+        """Temporal upsampling from now on through render_upsampled(): every frame is rendered at the context's frame size w x h, at the
+        next offset of the scale x scale cycle of subpixel_grid, and resolved into a history of scale w x scale h kept on the device
+        (adanerf_temporal_upsample).  alpha, depth_tol, clamp: as enable_temporal's (the depth test is the neighbourhood one).  Whole
+        frames of models without useNDC only.  The depth_map / acc_map aux outputs become the renderer's own."""
+        if self.info.use_ndc or self.info.rays_local != self.info.width * self.info.height:
+            raise AdaNeRFError("temporal upsampling needs a whole frame of a model without useNDC")
+        if int(scale) != scale or not 1 <= int(scale) <= 4:
+            raise ValueError("enable_temporal_upsample: scale must be 1, 2, 3 or 4, got %r" % (scale,))
+        if not 0.0 < float(alpha) <= 1.0:
+            raise ValueError("enable_temporal_upsample: alpha must lie in (0, 1], got %r" % (alpha,))
+        if not float(depth_tol) >= 0.0:
+            raise ValueError("enable_temporal_upsample: depth_tol must be >= 0, got %r" % (depth_tol,))
+        self._tu = dict(scale=int(scale), alpha=float(alpha), depth_tol=float(depth_tol), clamp=bool(clamp), offsets=subpixel_grid(int(scale)), k=0)
+        self._tu_hist = None
+        self._upsample_buffers()
+
+    def reset_upsample(self):
+        """Drops the history (a cut): the next render_upsampled shows every output pixel its nearest sample.  The offset cycle goes on."""
+        self._tu_hist = None
+
+    def render_upsampled(self):
+        """One frame at the camera of the last set_camera, rendered at w x h at the next sub-pixel offset of the cycle and resolved into
+        the history of W x H = scale w x scale h, which it then replaces (two buffer sets ping-pong on the device).  Returns (rgb fp32
+        [H*W,3], rgba8 [H*W,4] uint8, mask [H*W] uint8, rejected, Stats of the render): mask 1 where the history was used, 2 where it held
+        only a placeholder; rejected counts mask 0 (every pixel on the first frame and after reset_upsample / set_frame_size).  While the
+        pose is bit for bit the one of the call before, the history's depth is not tested (nothing is uncovered while the camera rests).
+        The offset that was in force is restored; present() shows the upsampled frame."""
+        if self._tu is None:
+            raise AdaNeRFError("render_upsampled: call enable_temporal_upsample first")
+        if self._pose is None:
+            raise AdaNeRFError("render_upsampled needs the pose of the frame: call set_camera first")
+        n = self.info.rays_local
+        self._upsample_buffers()
+        if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
+            self._o_rgb = self.empty((n, 3), np.float32)
+            self._o_rgba = self.empty((n, 4), np.uint8)
+        tu = self._tu
+        dx, dy = tu["offsets"][tu["k"] % len(tu["offsets"])]
+        tu["k"] += 1
+        was = self.pixel_offset
+        try:
+            self.set_pixel_offset(dx, dy)
+            st = self.render(None, self._o_rgb, stats=True)
+        finally:
+            self.set_pixel_offset(*was)
+        side = 0 if self._tu_hist is None else 1 - self._tu_hist[0]
+        out = self._tu_sets[side]
+        hist = (None, None, None) if self._tu_hist is None else self._tu_sets[self._tu_hist[0]]
+        prev = (None, None) if self._tu_hist is None else self._tu_hist[1:]
+        at_rest = self._tu_hist is not None and np.array_equal(prev[0], self._pose[0]) and np.array_equal(prev[1], self._pose[1])
+        rejected = self.temporal_upsample_device(tu["scale"], self._o_rgb, self._rp_depth, self._rp_acc, dx, dy, self._pose[0], self._pose[1], hist[0],
+                                                 None if at_rest else hist[1], hist[2], prev[0], prev[1], out[0], out[1], out[2], self._tu_rgba,
+                                                 self._tu_mask, alpha=tu["alpha"], depth_tol=tu["depth_tol"], clamp=tu["clamp"])
+        self._tu_hist = (side, self._pose[0], self._pose[1])
+        self._last_frame = (self._tu_rgba, self.info.width * tu["scale"], self.info.height * tu["scale"])
+        self._rp_frame = None      # the aux maps now belong to a jittered frame: nothing reproject() may warp
+        return out[0].numpy(), self._tu_rgba.numpy(), self._tu_mask.numpy(), rejected, st
 
     # -- the frame at the window's size ---------------------------------------------------------------
     def present_device(self, src_rgba8, src_w: int, src_h: int, dst_rgba8, dst_w: int, dst_h: int, flip_y: bool = False,

@@ -21,6 +21,8 @@
  *                                        src/interoprenderbuffer.cpp:87); this stage sits in front of that step
  *   adanerf_temporal_resolve             none: the viewer shows each frame as rendered, without a history (src/neuralrenderer.cpp:146-182 ->
  *                                        src/interoprenderbuffer.cpp:87); temporal anti-aliasing between the render and that step
+ *   adanerf_temporal_upsample            none: the viewer blits the frame it rendered (src/interoprenderbuffer.cpp:87), at whatever size it
+ *                                        was rendered; this stage rebuilds a frame of s x the render size over s^2 jittered renders
  *   adanerf_render                       ImageGenerator::inference, 2-context adaptive branch
  *                                        (src/imagegenerator.cpp:282-394) as called from
  *                                        NeuralRenderer::render (src/neuralrenderer.cpp:146-182)
@@ -749,6 +751,62 @@ int adanerf_temporal_resolve(adanerf_ctx* ctx, const float* d_cur_rgb, const flo
                              const uint8_t* d_hist_count, const float prev_pos[3], const float prev_rot_c2w[9], float alpha, float depth_tol,
                              float acc_min, int32_t flags, float* d_out_rgb, float* d_out_depth, uint8_t* d_out_count, void* d_out_rgba8,
                              uint8_t* d_out_mask, int32_t* rejected_out);
+
+/* Temporal upsampling: the frame is rendered at the context's frame size w x h with a sub-pixel offset and resolved into a history of
+ * W x H = s w x s h, s = scale in 1..4: s^2 times fewer rays per displayed frame, the full-resolution image rebuilt over the s^2 offsets
+ * of adanerf_host_subpixel_grid(s, .).  adanerf_temporal_resolve with two sizes and a neighbourhood depth test; that entry point is
+ * unchanged.  The viewer has no counterpart: it blits the frame it rendered (src/interoprenderbuffer.cpp:87).
+ *   d_cur_rgb [h*w,3], d_cur_depth_map / d_cur_acc_map [h*w] fp32: what one adanerf_render at cur_pos / cur_rot_c2w wrote with the pixel
+ *                           offset (cur_dx, cur_dy) in force; the offset is this call's argument and never read from the context
+ *   d_hist_rgb [H*W,3] fp32, d_hist_depth [H*W] fp32, d_hist_count [H*W] uint8: what the previous call wrote, at prev_pos / prev_rot_c2w.
+ *                           d_hist_rgb NULL: no history -- every pixel has mask 0 and the previous pose is not read.  d_hist_depth NULL:
+ *                           no disocclusion test.  d_hist_count NULL: constant alpha.
+ *   alpha, depth_tol, acc_min, flags, rejected_out: as adanerf_temporal_resolve's
+ *   d_out_rgb [H*W,3] fp32; d_out_depth [H*W] fp32, d_out_count [H*W] uint8, d_out_rgba8 [H*W] uchar4, d_out_mask [H*W] uint8: each may be NULL
+ * All images are row-major; fp32 and uchar4 images are 4-byte aligned.  G_lo is the context's ray generator with (cur_dx, cur_dy) applied
+ * exactly as adanerf_set_pixel_offset defines, at the current pose; G_hi is the generator a context of this model has at frame size W x H,
+ * at pixel centres and the current pose, focal_hi its focal length as fp32.  Definition (every operation a single rounded fp32 operation
+ * in this order; a gather: the same inputs give the same bits on every call):
+ * Pass A, per render pixel i = (x, y), only when d_hist_rgb and d_hist_depth are both given: (nds, p) = G_lo's ray of the pixel; o = p, or
+ *   cur_pos (ADANERF_SAMPLER_COARSE_FINE).  a = acc[i], t = depth[i] / a; near by adanerf_reproject's test.  near: P = o + nds t,
+ *   q = P - prev_pos, zp[i] = -((R[2] q_0 + R[5] q_1) + R[8] q_2), R = prev_rot_c2w.  Far, or a zp that is not finite: zp[i] = +inf.
+ * Pass B, per output pixel J = (X, Y):
+ *   1 sample    cx = ((float)X + 0.5f) / (float)s - cur_dx, ix = floor(cx) clamped to 0 .. w - 1; iy alike from cy; i = iy w + ix: the
+ *               render pixel whose jittered sample lies nearest the output pixel's centre.  ex = (((float)ix + 0.5f) + cur_dx) (float)s -
+ *               ((float)X + 0.5f), ey alike: the sample's distance from that centre in output pixels.  k = fmaxf(0, 1 - |ex|)
+ *               fmaxf(0, 1 - |ey|); inside = |ex| <= 0.5 and |ey| <= 0.5; cur = d_cur_rgb[i].
+ *   2 surface and own depth   (nds, p) = G_hi's ray of (X, Y); o as in pass A; a, t and near from render pixel i; P = o + nds t; zc_cur as
+ *               adanerf_temporal_resolve's step 2 (+inf if far), written to d_out_depth[J] whatever becomes of the history.
+ *   3 previous camera   adanerf_temporal_resolve's step 3 with W, H and focal_hi; tap = floor(vv) W + floor(u).
+ *   4 disocclusion (d_hist_depth given)   hd = d_hist_depth[tap].  Over the pixels of i's 3 x 3 render-size neighbourhood that exist: zmin /
+ *               zmax = the smallest / largest finite zp, any_far = some zp is +inf.  hd == +inf: accepted iff any_far.  hd finite: accepted
+ *               iff a finite zp exists and zmin - depth_tol zmin <= hd <= zmax + depth_tol zmax (a product, then a difference / sum).  Any
+ *               other hd: rejected.  The depths compared are those of one camera, so half a pixel of jitter between two renders of one
+ *               pose rejects nothing that a neighbour's surface explains.
+ *   5 history colour   four bilinear taps at W x H, as adanerf_temporal_resolve's step 5.
+ *   6 clamp (ADANERF_TEMPORAL_CLAMP)   lo / hi = minimum / maximum of d_cur_rgb over i's 3 x 3 render-size neighbourhood, by the order rules
+ *               of adanerf_temporal_resolve's step 6; hst = min(max(hst, lo), hi).
+ *   7 count     with d_hist_count: hc = d_hist_count[tap], live = accepted and hc >= 1; live: n' = min(hc + inside, 255), a_eff =
+ *               k fmaxf(alpha, 1.0f / (float)n'); not live: n' = inside.  Without: live = accepted, a_eff = k alpha, n' = live or inside.
+ *               d_out_count[J] = n'; 0 marks a pixel that so far holds only a neighbour's sample as a placeholder.
+ *   8 blend     live, k == 0: out = hst; live, k > 0: out = hst + a_eff (cur - hst); not live: out = cur, the bits copied.  mask 1: live; 2:
+ *               accepted with hc == 0 (a placeholder replaced); 0: rejected, counted in rejected_out.  d_out_rgba8 follows
+ *               adanerf_resolve_mean's byte contract.
+ * With the offsets of adanerf_host_subpixel_grid(s, .) every output pixel has inside true in exactly one frame of the s^2 cycle, with
+ * ex = ey = 0 to rounding: at rest from a cut, after s^2 calls every count is 1 and the image is the interleave of the s^2 renders.
+ * What it does not do: rejected pixels show the nearest sample and are not re-rendered (that needs a ray mask); no variance clipping;
+ * the scene is static; at s = 1 it is a temporal resolve with another depth test, not a replacement for adanerf_temporal_resolve.
+ * Two launches on the context's stream.  Context-owned scratch: zp ([h*w] fp32, grown on demand as adanerf_reproject's z-buffer is) and the
+ * counter shared with adanerf_reproject; both freed by adanerf_destroy; adanerf_render never allocates for them.
+ * ADANERF_EINVAL, with nothing written: everything adanerf_temporal_resolve refuses; scale outside 1..4; W H >= 2^25; cur_dx / cur_dy not
+ * finite or beyond +-1; d_out_rgb overlapping d_hist_rgb or d_cur_rgb, d_out_depth overlapping d_hist_depth, d_cur_depth_map or
+ * d_cur_acc_map, d_out_count overlapping d_hist_count.
+ * ADANERF_EUNSUPPORTED, with nothing written: a useNDC model; a context with shard_world != 1. */
+int adanerf_temporal_upsample(adanerf_ctx* ctx, int32_t scale, const float* d_cur_rgb, const float* d_cur_depth_map, const float* d_cur_acc_map,
+                              float cur_dx, float cur_dy, const float cur_pos[3], const float cur_rot_c2w[9], const float* d_hist_rgb,
+                              const float* d_hist_depth, const uint8_t* d_hist_count, const float prev_pos[3], const float prev_rot_c2w[9],
+                              float alpha, float depth_tol, float acc_min, int32_t flags, float* d_out_rgb, float* d_out_depth,
+                              uint8_t* d_out_count, void* d_out_rgba8, uint8_t* d_out_mask, int32_t* rejected_out);
 
 /* ---- measurement hook (bench.py's roofline) ---- */
 
