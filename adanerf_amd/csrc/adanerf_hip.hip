@@ -125,6 +125,10 @@ struct adanerf_ctx {
   bool flip_lds_raised = false;      // flip_kernel may use more than 64 KB of dynamic LDS
   DevBuf reproj_zbuf, reproj_holes;  // adanerf_reproject: [width*height] uint64 z-buffer, the hole count; grown on demand
   DevBuf upsample_zp;                // adanerf_temporal_upsample: [width*height] fp32 depths at the previous pose; grown on demand
+  // adanerf_render_masked: the mask as bit words, the ascending ray list and its count (for the frame), staged pixels of one listed batch
+  // (rgba8 [cap], rgb [cap,3], depth / acc / disp [3,cap]); grown on demand
+  DevBuf mask_bits, ray_list, ray_list_count, stage_rgba8, stage_rgb, stage_aux;
+  int stage_cap = 0;
   float px_dx = 0.f, px_dy = 0.f;    // adanerf_set_pixel_offset: kept here, not in ms.rg (calibrate_guard and adanerf_set_frame_size derive from / rewrite that)
   hipEvent_t peer_event = nullptr;   // adanerf_gather_to: orders the destination stream behind the copy
   uint64_t peer_tried = 0;           // bit d: peer access to device d has been requested once
@@ -271,9 +275,20 @@ RayGenParams rg_in_force(const adanerf_ctx* c) { return with_pixel_offset(c->ms.
 
 bool has_budget_map(const adanerf_ctx* c) { return c->budget_n != nullptr || c->budget_thr != nullptr; }
 
+// A batch whose rays are listed (adanerf_render_masked): ray i of the batch is ray first_ray + ids[i] of the frame, i < min(n_rays, *count).
+struct RayList {
+  const int32_t* ids;        // device, ascending ray ids
+  const int32_t* count;      // device, >= the n_rays of every launch over the list
+};
+
 // sel != nullptr: the adaptive selection runs in the kernel's epilogue (k_select_pair.hip.hpp) and d_oracle may be null
-int launch_sample_mlp(adanerf_ctx* c, int first_ray, int n_rays, float* d_oracle, float* d_rays, const SelectOut* sel = nullptr) {
+// list != nullptr: sample_mlp16x3_kernel alone generates the listed rays and writes rows, counts, segment totals and ray records at the list
+// position, as a dense batch (sel.refine_list stays null); a guarded context runs it as the split engine -- no first pass, no monitor
+int launch_sample_mlp(adanerf_ctx* c, int first_ray, int n_rays, float* d_oracle, float* d_rays, const SelectOut* sel = nullptr,
+                      const RayList* list = nullptr) {
   if (n_rays <= 0) return ADANERF_OK;
+  if (list && (c->generic0 || !sel || (c->sampling_mode != ADANERF_SAMPLING_SPLIT_FP16 && c->sampling_mode != ADANERF_SAMPLING_GUARDED)))
+    return fail(c, ADANERF_EUNSUPPORTED, "a ray list needs the 8 x 256 sampling network on the split-precision engine with the fused selection");
   SampleArgs a{};
   if (sel) {
     a.sel = *sel;
@@ -307,7 +322,11 @@ int launch_sample_mlp(adanerf_ctx* c, int first_ray, int n_rays, float* d_oracle
   // Guarded two-precision selection: plain fp16 for every ray, then the split engine on the rays the guard band flagged.
   // Only where the selection is fused; otherwise this mode is the split-precision engine.
   // Nor under a budget map: unrefined rays keep the fp16 engine's values in selw, and a trim by them would not be the exact selection.
-  const bool guarded = c->sampling_mode == ADANERF_SAMPLING_GUARDED && sel != nullptr && !has_budget_map(c);
+  const bool guarded = c->sampling_mode == ADANERF_SAMPLING_GUARDED && sel != nullptr && !has_budget_map(c) && !list;
+  if (list) {      // guard_mask, guard_rows, guard_seen and sel.refine_list stay null: guard_flush has nothing to write
+    a.ray_list = list->ids;
+    a.n_list = list->count;
+  }
   if (guarded) {
     // first guarded frame of a context created without a band: the model's record, or measure one
     if (int rc = c->guard_eps > 0.f ? 0 : ensure_guard_band(c)) return rc;
@@ -1674,17 +1693,12 @@ void poll_guard(adanerf_ctx* c) {
   }
 }
 
-}  // namespace
+// The three parts of a frame that adanerf_render and adanerf_render_masked share: the profiling record opened for n_batches batches
+// (begin_record), one batch through every stage (render_batch), the record closed and summed into the caller's stats (end_record).
 
-int adanerf_render(adanerf_ctx* c, void* d_rgba8, float* d_rgb, adanerf_stats* stats) {
-  BIND(c);
-  poll_guard(c);
-  const int R = c->ms.info.rays_local, B = c->ms.info.batch_rays, N = c->ms.info.num_samples;
-  const float thr = c->ms.info.threshold;
-  const int n_batches = R > 0 ? (R + B - 1) / B : 0;
-  const bool budget = has_budget_map(c);      // adaptive sampler, threshold > 0 (adanerf_set_budget_map / adanerf_set_selection see to it)
-  int rc = ensure_batch_buffers(c, std::min(B, std::max(R, 1)), N);
-  if (rc) return rc;
+// *record: the frame's batches record events and the image of `total`
+int begin_record(adanerf_ctx* c, adanerf_stats* stats, int n_batches, bool* record_out) {
+  int rc;
   if (stats && c->profiling && c->events_used) {   // a synchronous call starts a fresh record
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     reset_record(c);
@@ -1714,6 +1728,26 @@ int adanerf_render(adanerf_ctx* c, void* d_rgba8, float* d_rgb, adanerf_stats* s
       c->pinned_totals.push_back(p);
     }
   }
+  *record_out = record;
+  return ADANERF_OK;
+}
+
+// Where the pixels of a batch go: the batch's part of the caller's images (adanerf_render), or staging buffers (adanerf_render_masked).
+// depth / acc null with disp set: the disparity's two inputs go through the context's scratch.
+struct BatchOut {
+  float* rgb;
+  void* rgba8;
+  float* depth;
+  float* acc;
+  float* disp;
+};
+
+// Rays [first, first + n) of the context's rays -- or, with a list, the n rays list->ids[0 .. n) -- through every stage, on the context's stream.
+int render_batch(adanerf_ctx* c, int first, int n, const RayList* list, const BatchOut& out, bool record) {
+  const int B = c->ms.info.batch_rays, N = c->ms.info.num_samples;
+  const float thr = c->ms.info.threshold;
+  const bool budget = has_budget_map(c);      // adaptive sampler, threshold > 0 (adanerf_set_budget_map / adanerf_set_selection see to it)
+  int rc;
   float* rays = reinterpret_cast<float*>(c->rays.p);
   float* oracle = reinterpret_cast<float*>(c->oracle.p);
   int32_t* off = reinterpret_cast<int32_t*>(c->ray_offsets.p);
@@ -1723,69 +1757,103 @@ int adanerf_render(adanerf_ctx* c, void* d_rgba8, float* d_rgb, adanerf_stats* s
   float* sw = reinterpret_cast<float*>(c->sample_w.p);
   float* raw = reinterpret_cast<float*>(c->raw.p);
   int32_t* total = reinterpret_cast<int32_t*>(c->total.p);
+  hipEvent_t* ev = record ? &c->events[c->events_used] : nullptr;
+  if (ev) HIP_TRY(c, hipEventRecord(ev[0], c->stream));
+  const bool pdf = c->ms.info.sampler_mode == ADANERF_SAMPLER_PDF || cfm;      // explicit sample depths + classic compositing
+  if (cfm) {
+    // vanilla NeRF: camera rays, Nc uniform samples, coarse network ("sample_mlp" in the statistics: the first network)
+    uint32_t* keyc = reinterpret_cast<uint32_t*>(c->key_coarse.p);
+    float* rawc = reinterpret_cast<float*>(c->raw_coarse.p);
+    if ((rc = launch_camera_rays(c, first, n, rays))) return rc;
+    if ((rc = launch_sample_uniform(c, n, c->ms.n_coarse, off, cnt, keyc, total))) return rc;
+    if ((rc = launch_shade_mlp(c, rays, keyc, total, n * c->ms.n_coarse, c->ms.info.precision, rawc, nullptr, true))) return rc;
+    if (ev) HIP_TRY(c, hipEventRecord(ev[1], c->stream));
+    // weights -> pdf -> Nf more depths, merged with the Nc coarse ones ("compact")
+    if ((rc = launch_sample_fine(c, rawc, rays, n, off, cnt, key, reinterpret_cast<float*>(c->sample_z.p), total))) return rc;
+  }
+  // adaptive selection in the epilogue of the sampling kernel: the [R,128] oracle values never reach HBM
+  const bool fused = !pdf && thr > 0.f && use_pair_select(c, N) && c->sampling_mode != ADANERF_SAMPLING_FP32 && (!c->generic0 || generic_split_sampling(c)) &&
+                     !(c->opt.flags & ADANERF_FLAG_KEEP_ORACLE);
+  const SelectOut so = select_out(c, N, thr, cnt);
+  const BudgetMaps bm{c->budget_n, c->budget_thr, first};
+  if (!cfm && (rc = launch_sample_mlp(c, first, n, fused ? nullptr : oracle, rays, fused ? &so : nullptr, list))) return rc;
+  if (ev && !cfm) HIP_TRY(c, hipEventRecord(ev[1], c->stream));
+  float* sz = reinterpret_cast<float*>(c->sample_z.p);
+  if (cfm) rc = ADANERF_OK;
+  else if (pdf) rc = launch_sample_pdf(c, oracle, n, N, off, cnt, key, sw, sz, total);
+  else if (fused) {
+    rc = budget ? launch_trim(c, bm, n, N, thr, kPairSegShift, cnt) : ADANERF_OK;
+    if (!rc) rc = launch_expand(c, n, N, kPairSegShift, off, cnt, key, sw, total);
+  }
+  else if (thr == 0.f) {      // dense: implicit keys, the oracle buffer is the weight array (dense_offsets_kernel)
+    hipLaunchKernelGGL(dense_offsets_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, off, cnt, total);
+    HIP_TRY(c, hipGetLastError());
+  } else rc = launch_compact(c, oracle, n, N, thr, off, cnt, key, sw, total, budget ? &bm : nullptr);
+  if (rc) return rc;
+  const bool dense_implicit = !cfm && !pdf && !fused && thr == 0.f;
+  const uint32_t* key_s = dense_implicit ? nullptr : key;
+  const float* sw_s = dense_implicit ? oracle : sw;
+  if (ev) HIP_TRY(c, hipEventRecord(ev[2], c->stream));
+  const int64_t max_s = static_cast<int64_t>(n) * N;   // <= INT32_MAX: checked by setup_model
+  if ((rc = launch_shade_mlp(c, rays, key_s, total, static_cast<int>(max_s), c->ms.info.precision, raw, pdf ? sz : nullptr))) return rc;
+  if (ev) HIP_TRY(c, hipEventRecord(ev[3], c->stream));
+  float* depth_b = out.depth;
+  float* acc_b = out.acc;
+  if (out.disp && (!depth_b || !acc_b)) {      // disparity needs both maps of the batch
+    if ((rc = dev_alloc(c, &c->disp_scratch, static_cast<size_t>(B) * 2 * sizeof(float)))) return rc;
+    if (!depth_b) depth_b = reinterpret_cast<float*>(c->disp_scratch.p);
+    if (!acc_b) acc_b = reinterpret_cast<float*>(c->disp_scratch.p) + B;
+  }
+  if (pdf) rc = launch_composite_classic(c, raw, sz, rays, n, N, out.rgb, out.rgba8, depth_b, acc_b);
+  else rc = launch_composite(c, raw, sw_s, off, cnt, n, out.rgb, out.rgba8, key_s, depth_b, acc_b);
+  if (rc) return rc;
+  if (out.disp && n > 0) {
+    hipLaunchKernelGGL(disp_map_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, depth_b, acc_b, n, out.disp);
+    HIP_TRY(c, hipGetLastError());
+  }
+  if (ev) {
+    HIP_TRY(c, hipEventRecord(ev[4], c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->pinned_totals[c->events_used / 5], total, kTotalSlots * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    c->events_used += 5;
+  }
+  return ADANERF_OK;
+}
+
+// stats of the frame's n_batches batches (synchronous) when the caller asked for them; `rays`: what the frame rendered
+int end_record(adanerf_ctx* c, adanerf_stats* stats, int n_batches, bool record, int rays) {
+  if (record) c->prof_frames++;
+  if (stats) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    poll_guard(c);
+    if (int rc = sum_stats(c, stats)) return rc;
+    stats->rays = rays;
+    if (n_batches > 0 && record) {   // wall span of this frame, first launch -> last kernel end
+      const size_t e0 = c->events_used - static_cast<size_t>(n_batches) * 5;
+      HIP_TRY(c, hipEventElapsedTime(&stats->ms_total, c->events[e0], c->events[c->events_used - 1]));
+    }
+    reset_record(c);
+  }
+  return ADANERF_OK;
+}
+
+}  // namespace
+
+int adanerf_render(adanerf_ctx* c, void* d_rgba8, float* d_rgb, adanerf_stats* stats) {
+  BIND(c);
+  poll_guard(c);
+  const int R = c->ms.info.rays_local, B = c->ms.info.batch_rays, N = c->ms.info.num_samples;
+  const int n_batches = R > 0 ? (R + B - 1) / B : 0;
+  const bool budget = has_budget_map(c);
+  int rc = ensure_batch_buffers(c, std::min(B, std::max(R, 1)), N);
+  if (rc) return rc;
+  bool record = false;
+  if ((rc = begin_record(c, stats, n_batches, &record))) return rc;
+  int32_t* total = reinterpret_cast<int32_t*>(c->total.p);
   for (int b = 0; b < n_batches; ++b) {
     const int first = b * B, n = std::min(B, R - first);
-    hipEvent_t* ev = record ? &c->events[c->events_used] : nullptr;
-    if (ev) HIP_TRY(c, hipEventRecord(ev[0], c->stream));
-    const bool pdf = c->ms.info.sampler_mode == ADANERF_SAMPLER_PDF || cfm;      // explicit sample depths + classic compositing
-    if (cfm) {
-      // vanilla NeRF: camera rays, Nc uniform samples, coarse network ("sample_mlp" in the statistics: the first network)
-      uint32_t* keyc = reinterpret_cast<uint32_t*>(c->key_coarse.p);
-      float* rawc = reinterpret_cast<float*>(c->raw_coarse.p);
-      if ((rc = launch_camera_rays(c, first, n, rays))) return rc;
-      if ((rc = launch_sample_uniform(c, n, c->ms.n_coarse, off, cnt, keyc, total))) return rc;
-      if ((rc = launch_shade_mlp(c, rays, keyc, total, n * c->ms.n_coarse, c->ms.info.precision, rawc, nullptr, true))) return rc;
-      if (ev) HIP_TRY(c, hipEventRecord(ev[1], c->stream));
-      // weights -> pdf -> Nf more depths, merged with the Nc coarse ones ("compact")
-      if ((rc = launch_sample_fine(c, rawc, rays, n, off, cnt, key, reinterpret_cast<float*>(c->sample_z.p), total))) return rc;
-    }
-    // adaptive selection in the epilogue of the sampling kernel: the [R,128] oracle values never reach HBM
-    const bool fused = !pdf && thr > 0.f && use_pair_select(c, N) && c->sampling_mode != ADANERF_SAMPLING_FP32 && (!c->generic0 || generic_split_sampling(c)) &&
-                       !(c->opt.flags & ADANERF_FLAG_KEEP_ORACLE);
-    const SelectOut so = select_out(c, N, thr, cnt);
-    const BudgetMaps bm{c->budget_n, c->budget_thr, first};
-    if (!cfm && (rc = launch_sample_mlp(c, first, n, fused ? nullptr : oracle, rays, fused ? &so : nullptr))) return rc;
-    if (ev && !cfm) HIP_TRY(c, hipEventRecord(ev[1], c->stream));
-    float* sz = reinterpret_cast<float*>(c->sample_z.p);
-    if (cfm) rc = ADANERF_OK;
-    else if (pdf) rc = launch_sample_pdf(c, oracle, n, N, off, cnt, key, sw, sz, total);
-    else if (fused) {
-      rc = budget ? launch_trim(c, bm, n, N, thr, kPairSegShift, cnt) : ADANERF_OK;
-      if (!rc) rc = launch_expand(c, n, N, kPairSegShift, off, cnt, key, sw, total);
-    }
-    else if (thr == 0.f) {      // dense: implicit keys, the oracle buffer is the weight array (dense_offsets_kernel)
-      hipLaunchKernelGGL(dense_offsets_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, off, cnt, total);
-      HIP_TRY(c, hipGetLastError());
-    } else rc = launch_compact(c, oracle, n, N, thr, off, cnt, key, sw, total, budget ? &bm : nullptr);
-    if (rc) return rc;
-    const bool dense_implicit = !cfm && !pdf && !fused && thr == 0.f;
-    const uint32_t* key_s = dense_implicit ? nullptr : key;
-    const float* sw_s = dense_implicit ? oracle : sw;
-    if (ev) HIP_TRY(c, hipEventRecord(ev[2], c->stream));
-    const int64_t max_s = static_cast<int64_t>(n) * N;   // <= INT32_MAX: checked by setup_model
-    if ((rc = launch_shade_mlp(c, rays, key_s, total, static_cast<int>(max_s), c->ms.info.precision, raw, pdf ? sz : nullptr))) return rc;
-    if (ev) HIP_TRY(c, hipEventRecord(ev[3], c->stream));
-    float* rgb_b = d_rgb ? d_rgb + static_cast<size_t>(first) * 3 : nullptr;
-    void* rgba_b = d_rgba8 ? static_cast<char*>(d_rgba8) + static_cast<size_t>(first) * 4 : nullptr;
-    float* depth_b = c->aux_depth ? c->aux_depth + first : nullptr;
-    float* acc_b = c->aux_acc ? c->aux_acc + first : nullptr;
-    if (c->aux_disp && (!depth_b || !acc_b)) {      // disparity needs both maps of the batch
-      if ((rc = dev_alloc(c, &c->disp_scratch, static_cast<size_t>(B) * 2 * sizeof(float)))) return rc;
-      if (!depth_b) depth_b = reinterpret_cast<float*>(c->disp_scratch.p);
-      if (!acc_b) acc_b = reinterpret_cast<float*>(c->disp_scratch.p) + B;
-    }
-    if (pdf) rc = launch_composite_classic(c, raw, sz, rays, n, N, rgb_b, rgba_b, depth_b, acc_b);
-    else rc = launch_composite(c, raw, sw_s, off, cnt, n, rgb_b, rgba_b, key_s, depth_b, acc_b);
-    if (rc) return rc;
-    if (c->aux_disp && n > 0) {
-      hipLaunchKernelGGL(disp_map_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, depth_b, acc_b, n, c->aux_disp + first);
-      HIP_TRY(c, hipGetLastError());
-    }
-    if (ev) {
-      HIP_TRY(c, hipEventRecord(ev[4], c->stream));
-      HIP_TRY(c, hipMemcpyAsync(c->pinned_totals[c->events_used / 5], total, kTotalSlots * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-      c->events_used += 5;
-    }
+    const BatchOut out{d_rgb ? d_rgb + static_cast<size_t>(first) * 3 : nullptr, d_rgba8 ? static_cast<char*>(d_rgba8) + static_cast<size_t>(first) * 4 : nullptr,
+                       c->aux_depth ? c->aux_depth + first : nullptr, c->aux_acc ? c->aux_acc + first : nullptr, c->aux_disp ? c->aux_disp + first : nullptr};
+    if ((rc = render_batch(c, first, n, nullptr, out, record))) return rc;
   }
   // under a budget map the guarded mode renders as the split engine: no audit to move on, no monitor to read
   if (c->sampling_mode == ADANERF_SAMPLING_GUARDED && c->guard_mask.p && n_batches > 0 && !budget) ++c->guard_frame;      // the audit moves on
@@ -1799,19 +1867,104 @@ int adanerf_render(adanerf_ctx* c, void* d_rgba8, float* d_rgb, adanerf_stats* s
     HIP_TRY(c, hipEventRecord(c->guard_ev, c->stream));
     c->guard_ev_pending = true;
   }
-  if (record) c->prof_frames++;
-  if (stats) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    poll_guard(c);
-    if ((rc = sum_stats(c, stats))) return rc;
-    stats->rays = R;
-    if (n_batches > 0 && record) {   // wall span of this frame, first launch -> last kernel end
-      const size_t e0 = c->events_used - static_cast<size_t>(n_batches) * 5;
-      HIP_TRY(c, hipEventElapsedTime(&stats->ms_total, c->events[e0], c->events[c->events_used - 1]));
-    }
-    reset_record(c);
+  return end_record(c, stats, n_batches, record, R);
+}
+
+namespace {
+
+// adanerf_render_masked's own buffers: bit words, list and count for a frame of R rays; staging for a listed batch of n rays
+int ensure_mask_buffers(adanerf_ctx* c, int R, int n) {
+  const size_t words = (static_cast<size_t>(R) + 31) / 32;
+  if (c->mask_bits.bytes < words * sizeof(uint32_t) || c->ray_list.bytes < static_cast<size_t>(R) * sizeof(int32_t) || !c->ray_list_count.p || n > c->stage_cap) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // a masked call in flight may still use the smaller ones
+    n = std::max(n, c->stage_cap);
+    const size_t S = static_cast<size_t>(n);
+    int rc;
+    if ((rc = dev_alloc(c, &c->mask_bits, std::max(words, size_t(4)) * sizeof(uint32_t)))) return rc;
+    if ((rc = dev_alloc(c, &c->ray_list, static_cast<size_t>(std::max(R, 1)) * sizeof(int32_t)))) return rc;
+    if ((rc = dev_alloc(c, &c->ray_list_count, 64))) return rc;
+    if ((rc = dev_alloc(c, &c->stage_rgba8, std::max(S, size_t(1)) * 4))) return rc;
+    if ((rc = dev_alloc(c, &c->stage_rgb, std::max(S, size_t(1)) * 3 * sizeof(float)))) return rc;
+    if ((rc = dev_alloc(c, &c->stage_aux, std::max(S, size_t(1)) * 3 * sizeof(float)))) return rc;
+    c->stage_cap = n;
   }
   return ADANERF_OK;
+}
+
+}  // namespace
+
+int adanerf_render_masked(adanerf_ctx* c, const uint8_t* d_mask, uint32_t values, void* d_rgba8, float* d_rgb, adanerf_stats* stats, int32_t* n_rendered) {
+  if (!c) return ADANERF_EINVAL;
+  if (!d_mask) return fail(c, ADANERF_EINVAL, "adanerf_render_masked: NULL mask");
+  if (!d_rgba8 && !d_rgb) return fail(c, ADANERF_EINVAL, "adanerf_render_masked: both colour outputs NULL");
+  if (values == 0) return fail(c, ADANERF_EINVAL, "adanerf_render_masked: values == 0 selects no mask byte");
+  const int R = c->ms.info.rays_local, B = c->ms.info.batch_rays, N = c->ms.info.num_samples;
+  const auto refuse = [&](const char* why) { return fail(c, ADANERF_EUNSUPPORTED, std::string("adanerf_render_masked: ") + why); };
+  if (c->ms.coarse_fine) return refuse("the coarse / fine sampler has no ray list");
+  if (c->ms.info.sampler_mode == ADANERF_SAMPLER_PDF) return refuse("the PDF sampler has no ray list");
+  if (c->generic0) return refuse("run-time-shaped sampling networks have no ray list (the 8 x 256 network only)");
+  if (c->sampling_mode != ADANERF_SAMPLING_SPLIT_FP16 && c->sampling_mode != ADANERF_SAMPLING_GUARDED)
+    return refuse("sampling modes fp16 and fp32 have no ray list (split_fp16 or guarded only)");
+  if (!(c->ms.info.threshold > 0.f)) return refuse("a dense context (threshold 0) has no fused selection");
+  if (!use_pair_select(c, N) || (c->opt.flags & ADANERF_FLAG_KEEP_ORACLE))
+    return refuse("the ray list needs the fused selection (N <= 16, neither ADANERF_FLAG_KEEP_ORACLE nor ADANERF_FLAG_WAVE_SELECT)");
+  if (has_budget_map(c)) return refuse("a budget map is installed: its maps are indexed by frame position (remove it first)");
+  if (c->ms.rg.world != 1) return refuse("whole frames only (shard_world must be 1)");
+  BIND(c);
+  if (n_rendered) *n_rendered = 0;
+  if (R <= 0) return ADANERF_OK;
+  int rc = ensure_mask_buffers(c, R, 0);
+  if (rc) return rc;
+  // mask -> bit words -> ascending list + count (refine_list_kernel without an audit: the set bits, in order), then M comes back once
+  const int n_words = (R + 31) / 32, n_halves = 2 * n_words;
+  int32_t* ids = reinterpret_cast<int32_t*>(c->ray_list.p);
+  int32_t* count = reinterpret_cast<int32_t*>(c->ray_list_count.p);
+  hipLaunchKernelGGL(mask_bits_kernel, dim3((n_halves + 255) / 256), dim3(256), 0, c->stream, d_mask, R, values,
+                     (reinterpret_cast<uintptr_t>(d_mask) & 15) == 0 ? 1 : 0, n_halves, reinterpret_cast<uint16_t*>(c->mask_bits.p));
+  HIP_TRY(c, hipGetLastError());
+  hipLaunchKernelGGL(refine_list_kernel, dim3((n_words + 255) / 256), dim3(256), 0, c->stream, reinterpret_cast<const uint32_t*>(c->mask_bits.p), n_words, R, 0, 0, 0,
+                     0, ids, count);
+  HIP_TRY(c, hipGetLastError());
+  int32_t M = 0;
+  HIP_TRY(c, hipMemcpyAsync(&M, count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (M < 0 || M > R) return fail(c, ADANERF_EDEVICE, "adanerf_render_masked: the list count is outside 0..rays_local");
+  if (n_rendered) *n_rendered = M;
+  const int chunk = std::min(M, B), n_batches = M > 0 ? (M + B - 1) / B : 0;
+  if (M > 0) {
+    if ((rc = ensure_batch_buffers(c, chunk, N))) return rc;
+    if ((rc = ensure_mask_buffers(c, R, chunk))) return rc;
+    // a guarded context renders the list as the split engine: the count of re-evaluated rays goes to 0 in stream order (only a guarded
+    // frame writes it), as under a budget map; guard_frame, the band and the monitor's running values stay
+    if (c->sampling_mode == ADANERF_SAMPLING_GUARDED)
+      HIP_TRY(c, hipMemsetAsync(reinterpret_cast<int32_t*>(c->total.p) + kTotalRefined, 0, sizeof(int32_t), c->stream));
+  }
+  bool record = false;
+  if ((rc = begin_record(c, stats, n_batches, &record))) return rc;
+  const bool want_depth = c->aux_depth || c->aux_disp, want_acc = c->aux_acc || c->aux_disp;
+  float* aux = reinterpret_cast<float*>(c->stage_aux.p);
+  for (int b = 0; b < n_batches; ++b) {
+    const int at = b * B, n = std::min(B, M - at);
+    const RayList list{ids + at, count};      // *count = M >= n: the kernel's own bound is n
+    const BatchOut out{d_rgb ? reinterpret_cast<float*>(c->stage_rgb.p) : nullptr, d_rgba8 ? c->stage_rgba8.p : nullptr, want_depth ? aux : nullptr,
+                       want_acc ? aux + c->stage_cap : nullptr, c->aux_disp ? aux + 2 * static_cast<size_t>(c->stage_cap) : nullptr};
+    if ((rc = render_batch(c, 0, n, &list, out, record))) return rc;
+    MaskScatter s{};
+    s.list = list.ids;
+    s.rgba8 = static_cast<const uint32_t*>(out.rgba8);
+    s.rgb = out.rgb;
+    s.depth = out.depth;
+    s.acc = out.acc;
+    s.disp = out.disp;
+    s.o_rgba8 = static_cast<uint32_t*>(d_rgba8);
+    s.o_rgb = d_rgb;
+    s.o_depth = c->aux_depth;
+    s.o_acc = c->aux_acc;
+    s.o_disp = c->aux_disp;
+    hipLaunchKernelGGL(mask_scatter_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, s, n);
+    HIP_TRY(c, hipGetLastError());
+  }
+  return end_record(c, stats, n_batches, record, M);
 }
 
 int adanerf_set_aux_outputs(adanerf_ctx* c, float* d_depth_map, float* d_acc_map) {
@@ -2015,6 +2168,8 @@ int adanerf_get_buffer(adanerf_ctx* c, int32_t which, void** d_out, size_t* byte
     case ADANERF_BUF_TOTAL: b = &c->total; break;
     case ADANERF_BUF_SAMPLE_Z: b = &c->sample_z; break;
     case ADANERF_BUF_RAW_COARSE: b = &c->raw_coarse; break;
+    case ADANERF_BUF_RAY_LIST: b = &c->ray_list; break;
+    case ADANERF_BUF_RAY_LIST_COUNT: b = &c->ray_list_count; break;
     default: return fail(c, ADANERF_EINVAL, "unknown buffer id");
   }
   *d_out = b->p;

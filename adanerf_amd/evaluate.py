@@ -6,7 +6,7 @@ reference's second default metric (``metrics = ["flip", "psnr"]`` :613-615): the
 
     python -m adanerf_amd.evaluate <model_dir> <dataset_dir> [--set test] [--out DIR] [--video out.y4m] [--precision bf16]
                                    [--metrics psnr flip] [--sweep-thresholds T ...] [--sweep-samples N ...] [--sweep-scales S ...]
-                                   [--reproject-stride K] [--supersample S] [--present-filter nearest|linear|area]
+                                   [--reproject-stride K [--rerender holes|unsourced]] [--supersample S] [--present-filter nearest|linear|area]
 
 ``--sweep-thresholds`` / ``--sweep-samples`` render the set once per (N, threshold) of their cross product on ONE context
 (``NeuralRenderer.set_selection``: an AdaNeRF network is trained once and rendered at any sample budget) -- the two axes of a quality
@@ -17,7 +17,8 @@ dataset's ``w x h`` on the GPU (``adanerf_present``, the viewer's blit) and scor
 
 ``--reproject-stride K`` renders the poses with ``i % K == 0`` and warps the others from the nearest rendered pose before them
 (``adanerf_reproject``, holes filled from their neighbours): what a host that renders every K-th frame shows in between, scored against
-the same ground truth.
+the same ground truth.  ``--rerender holes|unsourced`` scores every warped frame once more with its holes (unsourced: the filled pixels too)
+rendered at its own pose (``adanerf_render_masked``).
 
 ``--supersample S`` makes every image the mean of S x S renders at the sub-pixel offsets of ``adanerf_host_subpixel_grid``, accumulated
 and resolved on the GPU (``NeuralRenderer.render_supersampled``) and scored from the fp32 mean: anti-aliasing in time, against the
@@ -40,7 +41,7 @@ from typing import List, Optional
 import numpy as np
 
 from .png import read_png, write_png
-from .renderer import PRESENT_FILTERS, SUPERSAMPLE_MAX, NeuralRenderer, Settings, parse_fovea
+from .renderer import PRESENT_FILTERS, RERENDER_VALUES, SUPERSAMPLE_MAX, NeuralRenderer, Settings, parse_fovea
 
 
 def load_dataset(dataset_dir: str, set_name: str = "test"):
@@ -101,7 +102,7 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
              precision: str = "bf16", batch_size: int = -1, max_frames: int = 0, quiet: bool = False,
              video: Optional[str] = None, fps: int = 30, metrics=("psnr",), fovea=None, sweep_thresholds=None, sweep_samples=None, reproject_stride=None,
              supersample=None, present_filter=None, temporal=None, temporal_still=None, temporal_upsample=None, temporal_upsample_frames=None,
-             sweep_scales=None):
+             rerender=None, sweep_scales=None):
     """metrics: "psnr" (always reported where a ground-truth image exists) and / or "flip": each record gains ``flip``, the summary
     ``mean_flip``, and with out_dir the error map is written as an 8-bit greyscale ``%05d_flip.png``.
 
@@ -120,6 +121,11 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     and, for a warped frame, ``hole_fraction`` (pixels nothing reached, of w h) in place of samples_per_ray / ms; the summary gains
     ``mean_psnr_rendered``, ``mean_psnr_warped``, ``mean_hole_fraction`` and, with "flip", ``mean_flip_rendered`` / ``mean_flip_warped``;
     mean_samples_per_ray / mean_ms are those of the rendered frames.  At the dataset's resolution only (not with sweep_scales).
+    rerender ("holes", "unsourced" or None; needs reproject_stride): every warped frame is scored a second time with its holes (unsourced: the
+    pixels filled from a neighbour too) rendered at its own pose (NeuralRenderer.reproject_rerender).  Warped records gain
+    ``psnr_rerendered`` / ``mse_rerendered`` and ``rerendered_fraction`` (pixels rendered, of w h), the summary
+    ``mean_psnr_warped_rerendered`` and ``mean_rerendered_fraction``; out_dir gets ``%05d_rerendered.png``.  Every other key is that of a run
+    without the option.
 
     supersample (S in 1..8 or None): every image is the mean of S x S renders at the offsets of the regular sub-pixel grid
     (NeuralRenderer.render_supersampled), scored from the fp32 mean; ms is the sum over the S x S renders, samples_per_ray is per rendered
@@ -161,6 +167,10 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     stride = int(reproject_stride) if reproject_stride is not None else 0
     if reproject_stride is not None and stride < 1:
         raise ValueError("reproject_stride must be >= 1, got %s" % (reproject_stride,))
+    if rerender not in RERENDER_VALUES:
+        raise ValueError("rerender must be None, 'holes' or 'unsourced', got %r" % (rerender,))
+    if rerender and not stride:
+        raise ValueError("rerender re-renders the holes of warped frames: it needs reproject_stride")
     if stride and sweep_scales:
         raise ValueError("reproject_stride warps at the dataset's resolution: not together with sweep_scales")
     ss = int(supersample) if supersample is not None else 0
@@ -229,6 +239,12 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                     rgba, _, holes = r.reproject(fr["pose"], fr["rot"])
                     rgb = rgba[:, :3].astype(np.float32) / 255.0
                     rec = dict(extra, frame=i, image=fr["image"], warped=True, hole_fraction=holes / float(w * h))
+                    if rerender:      # the same warp with its holes rendered at this pose
+                        rr_rgba, _, _, rerendered = r.reproject_rerender(fr["pose"], fr["rot"], rerender)
+                        rec.update(rerendered_fraction=rerendered / float(w * h))
+                        if out_dir:
+                            os.makedirs(out_dir, exist_ok=True)
+                            write_png(os.path.join(out_dir, "%05d_rerendered.png" % i), rr_rgba[:, :3].reshape(h, w, 3))
                 else:
                     r.set_camera(fr["pose"], fr["rot"])
                     rgb, rgba, st = r.render_supersampled(ss) if ss else r.render_numpy()
@@ -247,6 +263,9 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                     ref = gt[:, :, :3].astype(np.float32).reshape(-1, 3) / 255.0        # datasets.py:286-287
                     mse = float(np.mean((rgb.astype(np.float64) - ref) ** 2))
                     rec.update(mse=mse, psnr=psnr_from_mse(mse))
+                    if warped and rerender:
+                        rr_mse = float(np.mean(((rr_rgba[:, :3].astype(np.float32) / 255.0).astype(np.float64) - ref) ** 2))
+                        rec.update(mse_rerendered=rr_mse, psnr_rerendered=psnr_from_mse(rr_mse))
                     if want_flip:       # the rendered frame is still on the device (render_numpy); argument order of src/evaluate.py:144
                         d_test = r._o_rgb if not presented and not warped else d_pres.upload(rgb)
                         rec.update(flip=r.flip_device(d_test, d_ref.upload(ref), w, h, error_map=d_map))
@@ -326,6 +345,10 @@ def summarise(results: List[dict], want_flip: bool) -> dict:
                 summary["mean_flip_" + kind] = float(np.mean([x["flip"] for x in part])) if part else None
         holes = [x["hole_fraction"] for x in results if x.get("warped")]
         summary["mean_hole_fraction"] = float(np.mean(holes)) if holes else 0.0
+        if any("rerendered_fraction" in x for x in results):      # rerender: the warped frames once more, their holes rendered
+            part = [x["psnr_rerendered"] for x in results if "psnr_rerendered" in x]
+            summary["mean_psnr_warped_rerendered"] = float(np.mean(part)) if part else None
+            summary["mean_rerendered_fraction"] = float(np.mean([x["rerendered_fraction"] for x in results if "rerendered_fraction" in x]))
     if any("temporal_upsample" in x for x in results):      # temporal_upsample: the upsampled frames beside the enlarged small ones
         part = [x for x in results if "psnr_upsampled" in x]
         summary["mean_psnr_upsampled"] = float(np.mean([x["psnr_upsampled"] for x in part])) if part else None
@@ -364,6 +387,9 @@ def build_parser():
     ap.add_argument("--reproject-stride", type=int, default=None, metavar="K",
                     help="render the poses with i %% K == 0 and warp the others from the nearest rendered pose before them (adanerf_reproject); "
                          "the summary gains mean_psnr_rendered / mean_psnr_warped / mean_hole_fraction (and mean_flip_* with --metrics flip)")
+    ap.add_argument("--rerender", default=None, choices=["holes", "unsourced"],
+                    help="with --reproject-stride: score every warped frame once more with its holes (unsourced: the filled pixels too) rendered at "
+                         "its own pose (adanerf_render_masked); the summary gains mean_psnr_warped_rerendered / mean_rerendered_fraction")
     ap.add_argument("--supersample", type=int, default=None, choices=range(1, SUPERSAMPLE_MAX + 1), metavar="S",
                     help="every image is the mean of S x S renders (S in 1..8) at the offsets of the regular sub-pixel grid, accumulated on the GPU "
                          "and scored from the fp32 mean; records and summary gain `supersample`; not together with --reproject-stride")
@@ -391,6 +417,8 @@ def build_parser():
 def main(argv=None):
     ap = build_parser()
     a = ap.parse_args(argv)
+    if a.rerender is not None and a.reproject_stride is None:
+        ap.error("--rerender needs --reproject-stride")
     if a.supersample is not None and a.reproject_stride is not None:
         ap.error("--supersample cannot be combined with --reproject-stride")
     if (a.temporal is not None or a.temporal_still is not None) and (a.supersample is not None or a.reproject_stride is not None or a.sweep_scales):
@@ -402,7 +430,7 @@ def main(argv=None):
         ap.error("--temporal-upsample-frames goes with --temporal-upsample")
     summary, _ = evaluate(a.model_dir, a.dataset_dir, a.set, a.out, a.precision, a.batch_size, a.max_frames, video=a.video, fps=a.fps,
                           metrics=tuple(a.metrics), sweep_thresholds=a.sweep_thresholds, sweep_samples=a.sweep_samples, sweep_scales=a.sweep_scales,
-                          fovea=a.fovea, reproject_stride=a.reproject_stride, supersample=a.supersample, present_filter=a.present_filter,
+                          fovea=a.fovea, reproject_stride=a.reproject_stride, rerender=a.rerender, supersample=a.supersample, present_filter=a.present_filter,
                           temporal=a.temporal, temporal_still=a.temporal_still, temporal_upsample=a.temporal_upsample,
                           temporal_upsample_frames=a.temporal_upsample_frames)
     print(json.dumps(summary))

@@ -23,7 +23,7 @@ NeuralRenderer::~NeuralRenderer() {
   if (ctx) {
     if (d_gathered) adanerf_free(ctx, d_gathered);
     if (d_frame) adanerf_free(ctx, d_frame);
-    for (void* p : {d_depth, d_acc, d_warp, d_rgb, d_sum, d_hist[0][0], d_hist[0][1], d_hist[0][2], d_hist[1][0], d_hist[1][1], d_hist[1][2], d_up})
+    for (void* p : {d_depth, d_acc, d_warp, d_wmask, d_rgb, d_sum, d_hist[0][0], d_hist[0][1], d_hist[0][2], d_hist[1][0], d_hist[1][1], d_hist[1][2], d_up})
       if (p) adanerf_free(ctx, p);
     if (d_window) adanerf_free(ctx, d_window);
     adanerf_destroy(ctx);
@@ -228,7 +228,7 @@ bool NeuralRenderer::allocFrameBuffers() {
   if (settings.reproject > 1) {      // the aux outputs belong to the frame size: the library drops them when rays_local changes
     const size_t n = static_cast<size_t>(info_.width) * info_.height;
     have_source = false;
-    for (void** p : {&d_depth, &d_acc, &d_warp}) {
+    for (void** p : {&d_depth, &d_acc, &d_warp, &d_wmask}) {      // (the mask is a byte per pixel: a quarter of its allocation)
       if (*p && adanerf_free(ctx, *p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
       *p = nullptr;
       if (adanerf_malloc(ctx, n * 4, p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
@@ -536,9 +536,22 @@ bool NeuralRenderer::renderUpsampled(adanerf_stats* st, const float rot[9]) {
 bool NeuralRenderer::warp(const float rot[9]) {
   int32_t holes = 0;
   if (adanerf_reproject(ctx, d_frame, static_cast<const float*>(d_depth), static_cast<const float*>(d_acc), src_pos, src_rot, camera.getPosition(), rot,
-                        0.5f, 0xFF000000u, ADANERF_REPROJECT_FILL, d_warp, nullptr, nullptr, &holes) != ADANERF_OK) {
+                        0.5f, 0xFF000000u, ADANERF_REPROJECT_FILL, d_warp, nullptr, static_cast<uint8_t*>(d_wmask), &holes) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;
+  }
+  if (!settings.rerender.empty()) {
+    // --rerender: the holes (mask 0; unsourced: the filled pixels, mask 2, too) at this frame's camera, which render() has set.  The aux maps
+    // belong to the source frame and the next warp reads them: off for this call.
+    int32_t m = 0;
+    const bool ok = adanerf_set_aux_outputs(ctx, nullptr, nullptr) == ADANERF_OK &&
+                    adanerf_render_masked(ctx, static_cast<const uint8_t*>(d_wmask), settings.rerender == "holes" ? 1u : 5u, d_warp, nullptr, nullptr, &m) == ADANERF_OK;
+    if (!ok) err = adanerf_last_error(ctx);
+    const bool back = adanerf_set_aux_outputs(ctx, static_cast<float*>(d_depth), static_cast<float*>(d_acc)) == ADANERF_OK;
+    if (ok && !back) err = adanerf_last_error(ctx);
+    if (!ok || !back) return false;
+    s_rerendered += m;
+    if (settings.log_camera) std::printf("warped %d holes %d rerendered %d\n", sample_count, static_cast<int>(holes), static_cast<int>(m));
   }
   since_render++;
   sample_count++;
@@ -565,10 +578,12 @@ void NeuralRenderer::logInterval() {
   if (settings.taau_scale > 0)
     std::cout << ", taau rejected: " << s_rejected / static_cast<double>(logging_interval) / settings.total_size / (settings.taau_scale * settings.taau_scale);
   if (settings.reproject > 1) std::cout << ", holes: " << s_holes / static_cast<double>(std::max(s_warped, 1)) << " (" << s_warped << " warped frames)";
+  if (!settings.rerender.empty()) std::cout << ", rerendered: " << s_rerendered / static_cast<double>(std::max(s_warped, 1));
   std::cout << std::endl;
   s_inference1 = s_inference2 = s_fc2 = s_rm = s_total = 0;
   s_num_total_samples = 0;
   s_holes = 0;
+  s_rerendered = 0;
   s_rejected = 0;
   s_rendered = s_warped = 0;
 }

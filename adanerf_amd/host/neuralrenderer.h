@@ -74,12 +74,14 @@ class NeuralRenderer {
   void* d_depth = nullptr;
   void* d_acc = nullptr;
   void* d_warp = nullptr;            // uchar4 [h*w]
+  void* d_wmask = nullptr;           // --rerender: adanerf_reproject's mask of the warped frame, uint8 [h*w]
   const void* d_shown = nullptr;     // what the last frame presented: d_frame or d_warp (-w / --write-window write it)
   bool have_source = false;          // d_frame, d_depth, d_acc and src_* describe one rendered frame of the size and selection in force
   int since_render = 0;              // warped frames since it
   float src_pos[3] = {0, 0, 0}, src_rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   bool warp(const float rot[9]);     // this frame = the source frame at the camera of the moment
   void logInterval();                // the per-100-frame line of the single-context path
+  long long s_rerendered = 0;        // --rerender: pixels rendered into the warped frames of the running interval
   long long s_holes = 0;             // holes of the warped frames / rendered and warped frames of the running interval
   int s_rendered = 0, s_warped = 0;
   // --supersample S > 1: the fp32 frame of one sub-pixel render and the running sum of a shown frame's S x S renders, float [h*w*3] each

@@ -22,6 +22,8 @@ const char* Settings::usage() {
          "                                                              cut: --taa / --taau start a new history with that frame)\n"
          "               [--reproject K]      of every K frames render the first and warp it to the camera of the next K - 1 (depth\n"
          "                                    reprojection, holes filled from their neighbours); -w / --write-window write what was shown\n"
+         "               [--rerender holes|unsourced]     with --reproject K: render the warped frames' holes (unsourced: the pixels filled from a\n"
+         "                                    neighbour too) at their own camera instead of leaving the fill\n"
          "               [--supersample S]    every shown frame is S x S renders (S in 1..8) at the offsets of a regular sub-pixel grid, summed and\n"
          "                                    averaged on the device (anti-aliasing in time); -w / --write-window write the resolved image\n"
          "               [--taa ALPHA[:TOL]]  temporal anti-aliasing: every frame is rendered at the next sub-pixel offset of a cycle and blended\n"
@@ -158,6 +160,13 @@ bool Settings::init(int argc, char** argv, std::string* err) {
         return false;
       }
       reproject = static_cast<int>(k);
+    } else if (a == "--rerender") {
+      if (!need(i, 1)) return false;
+      rerender = argv[++i];
+      if (rerender != "holes" && rerender != "unsourced") {
+        *err = "--rerender must be holes or unsourced";
+        return false;
+      }
     } else if (a == "--supersample") {
       if (!need(i, 1)) return false;
       char* end = nullptr;
@@ -241,6 +250,10 @@ bool Settings::init(int argc, char** argv, std::string* err) {
   }
   if (ws_used && (window_width == 0 || window_height == 0)) {
     *err = "window size must be positive";
+    return false;
+  }
+  if (!rerender.empty() && reproject <= 1) {
+    *err = "--rerender re-renders the holes of warped frames; only with --reproject K, K > 1";
     return false;
   }
   if (taa_alpha > 0.f && (reproject > 1 || supersample > 1)) {

@@ -37,6 +37,8 @@ class Settings {
   std::vector<int> fovea_radius, fovea_n;
   std::vector<float> fovea_thr;
   static bool parseFovea(const std::string& spec, std::vector<int>* radius, std::vector<int>* n, std::vector<float>* thr, std::string* err);
+  std::string rerender;         // --rerender holes|unsourced (with --reproject K > 1): the warped frames' holes (or every pixel without a source pixel
+                                // of its own) are rendered at the frame's camera (adanerf_render_masked); empty: they stay filled from neighbours
   int reproject = 1;            // --reproject K: of every K frames the first is rendered, the next K - 1 are that frame warped to their own camera
                                 // (adanerf_reproject, fill on); 1: every frame is rendered
   int supersample = 1;          // --supersample S (1..8): every shown frame is S x S renders at the offsets of adanerf_host_subpixel_grid, accumulated and

@@ -22,13 +22,15 @@ PREC_BF16, PREC_FP16, PREC_FP32 = 0, 1, 2
 _PREC = {"bf16": PREC_BF16, "fp16": PREC_FP16, "f16": PREC_FP16, "fp32": PREC_FP32, "f32": PREC_FP32}
 
 BUF_RAYS, BUF_ORACLE, BUF_RAY_OFFSETS, BUF_RAY_COUNTS, BUF_SAMPLE_KEY, BUF_SAMPLE_W, BUF_RAW, BUF_TOTAL, BUF_SAMPLE_Z, BUF_RAW_COARSE = range(10)
+BUF_RAY_LIST, BUF_RAY_LIST_COUNT = 10, 11                      # adanerf_render_masked: the ascending ray ids of the last call, their number
 SAMPLER_ADAPTIVE, SAMPLER_PDF, SAMPLER_COARSE_FINE = 0, 1, 2
 FLAG_KEEP_ORACLE, FLAG_WAVE_SELECT, FLAG_NO_GUARD_CACHE, FLAG_GUARD_AUDIT_FILL = 1, 2, 4, 8
 PRESENT_FLIP_Y, PRESENT_NEAREST, PRESENT_LINEAR, PRESENT_AREA = 1, 2, 4, 8      # adanerf_present flags
 PRESENT_FILTERS = {None: 0, "nearest": PRESENT_NEAREST, "linear": PRESENT_LINEAR, "area": PRESENT_AREA}
 SUPERSAMPLE_MAX = 8                                            # adanerf_host_subpixel_grid: s in 1..8
 REPROJECT_FILL = 1                                             # adanerf_reproject flag
-TEMPORAL_CLAMP = 1                                             # adanerf_temporal_resolve flag
+RERENDER_VALUES = {None: 0, "holes": 1, "unsourced": 5}        # adanerf_render_masked `values` over adanerf_reproject's mask bytes (0 hole, 2 filled)
+TEMPORAL_CLAMP = 1                                          # adanerf_temporal_resolve flag
 ABI_VERSION = 4
 GUARD_FROM = {0: "none", 1: "options", 2: "record", 3: "calibration", 4: "monitor"}
 SAMPLING_MODES = {"split": 0, "fp16x3": 0, "fp32": 1, "fp16": 2, "guarded": 3}
@@ -78,7 +80,7 @@ EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_las
            "adanerf_render_oracle", "adanerf_gather_to", "adanerf_probe_mfma", "adanerf_malloc",
            "adanerf_free", "adanerf_memcpy_h2d", "adanerf_memcpy_d2h", "adanerf_get_buffer",
            "adanerf_set_pixel_offset", "adanerf_get_pixel_offset", "adanerf_accumulate", "adanerf_resolve_mean", "adanerf_host_subpixel_grid", "adanerf_temporal_resolve",
-           "adanerf_temporal_upsample"]
+           "adanerf_temporal_upsample", "adanerf_render_masked"]
 
 _lib = None
 
@@ -117,6 +119,7 @@ def load_library(path: Optional[str] = None):
     lib.adanerf_temporal_upsample.argtypes = [vp, i32, vp, vp, vp, C.c_float, C.c_float, fp, fp, vp, vp, vp, fp, fp, C.c_float, C.c_float, C.c_float, i32,
                                               vp, vp, vp, vp, vp, C.POINTER(i32)]
     lib.adanerf_render.argtypes = [vp, vp, vp, C.POINTER(Stats)]
+    lib.adanerf_render_masked.argtypes = [vp, vp, C.c_uint32, vp, vp, C.POINTER(Stats), C.POINTER(i32)]
     lib.adanerf_assemble_strips.argtypes = [vp, vp, vp]
     lib.adanerf_set_aux_outputs.argtypes = [vp, vp, vp]
     lib.adanerf_set_disp_output.argtypes = [vp, vp]
@@ -595,6 +598,16 @@ class NeuralRenderer:
             self.last_stats = st
         return st
 
+    def render_masked(self, mask, values: int = 1, rgba8=None, rgb=None):
+        """adanerf_render_masked: only the pixels p with mask[p] < 32 and bit mask[p] of ``values`` set are rendered, into the device
+        images ``rgba8`` ([rays_local] uchar4) / ``rgb`` ([rays_local,3] fp32) -- at least one -- and into the aux maps in force; every
+        other element keeps its bytes.  ``mask``: [rays_local] uint8 on the device (the masks of reproject / the temporal stages select
+        directly: values=1 their holes, values=5 everything without a source pixel).  Returns (M, Stats of the M rays)."""
+        st, m = Stats(), C.c_int32(0)
+        self._check(self.lib.adanerf_render_masked(self.handle, _ptr(mask), int(values) & 0xFFFFFFFF, _ptr(rgba8), _ptr(rgb), C.byref(st), C.byref(m)))
+        self.last_stats = st
+        return int(m.value), st
+
     def set_aux_outputs(self, depth_map=None, acc_map=None):
         """Subsequent renders also fill [rays_local] fp32 depth_map (sum w z) / acc_map (sum w); None switches them off."""
         self._check(self.lib.adanerf_set_aux_outputs(self.handle, _ptr(depth_map), _ptr(acc_map)))
@@ -678,6 +691,24 @@ class NeuralRenderer:
         rgba, depth, acc, pos, rot, _ = self._rp_frame
         holes = self.reproject_device(rgba, depth, acc, pos, rot, dst_pos, dst_rot, self._rp_rgba, None, self._rp_mask, acc_min=acc_min, fill=fill)
         return self._rp_rgba.numpy(), self._rp_mask.numpy(), holes
+
+    def reproject_rerender(self, dst_pos, dst_rot, rerender: str = "holes", fill: bool = True, acc_min: float = 0.5):
+        """reproject(), then the pixels the warp could not source rendered at the destination pose into the warped colour:
+        ``rerender="holes"`` the pixels nothing reached (mask 0), ``"unsourced"`` those filled from a neighbour as well (mask 0 and 2) --
+        render_masked with values 1 / 5 over the warp's own mask.  The camera moves to (dst_pos, dst_rot) and stays there; the frame kept
+        for warping (colour, depth_map, acc_map, its pose) is untouched: the aux maps belong to it and the next warp reads them, so they
+        are switched off for the masked call and the warped depth is not re-rendered.  Returns (rgba8, mask, holes, rerendered).
+        (A method of its own: reproject()'s signature is what its callers and tests know.)"""
+        if rerender not in ("holes", "unsourced"):
+            raise AdaNeRFError("reproject_rerender: rerender must be 'holes' or 'unsourced'")
+        _, mask, holes = self.reproject(dst_pos, dst_rot, fill=fill, acc_min=acc_min)
+        self.set_camera(dst_pos, dst_rot)
+        self.set_aux_outputs(None, None)
+        try:
+            rerendered, _ = self.render_masked(self._rp_mask, RERENDER_VALUES[rerender], rgba8=self._rp_rgba)
+        finally:
+            self.set_aux_outputs(self._rp_depth, self._rp_acc)
+        return self._rp_rgba.numpy(), mask, holes, rerendered
 
     # -- temporal anti-aliasing: one jittered render per frame, resolved against a history ------------------
     def temporal_resolve_device(self, cur_rgb, cur_depth, cur_acc, cur_pos, cur_rot, hist_rgb, hist_depth, hist_count, prev_pos, prev_rot,

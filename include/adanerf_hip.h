@@ -26,6 +26,8 @@
  *   adanerf_render                       ImageGenerator::inference, 2-context adaptive branch
  *                                        (src/imagegenerator.cpp:282-394) as called from
  *                                        NeuralRenderer::render (src/neuralrenderer.cpp:146-182)
+ *   adanerf_render_masked                none: ImageGenerator::inference always runs every ray of the frame; this renders the rays a mask
+ *                                        selects (the holes of adanerf_reproject, the rejected pixels of the temporal stages)
  *   adanerf_ray_features                 updateSpherePosDirBatchedUnrolledEnc
  *                                        (include/cuda/adanerf_cuda_kernels.cuh:41-45)
  *   adanerf_sample_mlp                   contexts[0]->executeV2 (src/imagegenerator.cpp:308-312)
@@ -344,6 +346,39 @@ int adanerf_get_pixel_offset(const adanerf_ctx* ctx, float out[2]);
  * [rays_local,3] fp32 unclamped colour (parity output).  Either may be NULL.  stats != NULL makes
  * the call synchronous and fills the per-stage timings. */
 int adanerf_render(adanerf_ctx* ctx, void* d_rgba8_out, float* d_rgb_f32_out, adanerf_stats* stats);
+
+/* Renders only the pixels a mask selects: what a host needs to re-render the disocclusion holes of adanerf_reproject, the rejected pixels
+ * of the temporal stages, or any region of interest, at a cost that follows the number of selected pixels.
+ *   d_mask       [rays_local] uint8, device memory, caller-owned, indexed as d_rgba8_out is; read, never written
+ *   values       pixel p is rendered iff mask[p] < 32 and bit mask[p] of `values` is set.  The mask bytes of adanerf_reproject (0 hole,
+ *                1 source, 2 filled) and of adanerf_temporal_resolve / _upsample select directly: values = 1 the holes (the rejected
+ *                pixels), values = 5 everything without a source pixel of its own.
+ *   d_rgba8_out / d_rgb_f32_out   as adanerf_render's; either may be NULL, not both
+ *   stats        NULL or the record of the M rendered rays (rays = M, total_samples = the sum of their counts); makes the call's tail
+ *                synchronous as adanerf_render's does
+ *   n_rendered   host pointer or NULL: M
+ * Contract: every rendered pixel carries, in the colour outputs and in the maps of adanerf_set_aux_outputs / adanerf_set_disp_output, the
+ * bytes adanerf_render would write there with the same context state (camera, selection, frame size, pixel offset -- all honoured);
+ * every other element of every output keeps the bytes it had.  It holds because every stage is position-invariant per ray, as batched
+ * and guarded frames already are byte for byte what unbatched and unguarded ones are.
+ * Mechanism: the mask becomes bit words and those an ascending list of ray ids with its count (two launches; deterministic: the same
+ * list on every call); M is read back once (4 bytes and one stream synchronisation, as adanerf_reproject's hole count -- the call is
+ * never fully asynchronous); the split-precision sampling kernel then generates the listed rays as a dense batch of M, selection,
+ * shading and compositing run unchanged on it into context-owned staging buffers, and one launch scatters the pixels.  M above
+ * adanerf_info.batch_rays is walked in chunks of batch_rays; M = 0 launches nothing after the list.  Ordering is that of
+ * adanerf_set_camera.  ADANERF_BUF_RAY_LIST / _RAY_LIST_COUNT hold the list afterwards; the batch buffers describe the last chunk.
+ * A context with ADANERF_SAMPLING_GUARDED renders this call as the split-precision engine (exact, what the guarded frame equals): no
+ * first pass and no audit; the band, the audit's phase and the monitor's counters are untouched and rays_refined of the call is 0, as
+ * under a budget map.
+ * ADANERF_EINVAL, with nothing written: a NULL mask; both colour outputs NULL; values == 0.
+ * ADANERF_EUNSUPPORTED, with nothing written and a message naming the reason -- refused, not done by this entry point: the sampling modes
+ * ADANERF_SAMPLING_FP16 and _FP32; run-time-shaped sampling networks (anything but 8 x 256 with a 10-4 / 2-2 encoding); a dense
+ * context (threshold 0), N above 16, ADANERF_FLAG_KEEP_ORACLE or ADANERF_FLAG_WAVE_SELECT (no fused selection); ADANERF_SAMPLER_PDF and
+ * _COARSE_FINE; an installed budget map (its maps are indexed by frame position and would have to be gathered); a shard of a frame
+ * (shard_world != 1).  Also not done: re-rendering inside the temporal hosts (extra samples where a full frame exists: a policy for a
+ * host to set), and launches sized on the device that would spare the 4-byte read-back. */
+int adanerf_render_masked(adanerf_ctx* ctx, const uint8_t* d_mask, uint32_t values, void* d_rgba8_out, float* d_rgb_f32_out,
+                          adanerf_stats* stats, int32_t* n_rendered);
 
 /* Secondary outputs of the compositing step (reference: adaptive_raw2outputs / nerf_raw2outputs return them next to the
  * colour, src/nerf_raymarch_common.py:137-139 and :60-62; the viewer has no counterpart): until reset with NULLs, every
@@ -684,7 +719,8 @@ enum { ADANERF_REPROJECT_FILL = 1 }; /* a destination pixel no source pixel land
  *   Without one and with ADANERF_REPROJECT_FILL: among the 8 neighbours' winners (never filled results) the LARGEST key -- the farthest
  *   surface, the usual choice behind a disocclusion -- gives colour and depth, mask 2.  Otherwise hole_rgba8, depth 0, mask 0.
  * What it does not do: a splat covers one pixel, so background can show through the cracks of a magnified foreground (a forward move);
- * view-dependent colour stays that of the source pose; re-rendering only the holes would need a ray mask in the render path.
+ * view-dependent colour stays that of the source pose.  The holes are re-rendered by adanerf_render_masked(d_dst_mask, 1, d_dst_rgba8, ..)
+ * with the camera at the destination pose (values 5: the filled pixels too).
  * Runs on the context's stream in three launches (clear, splat, resolve); the z-buffer and the hole count live in context-owned scratch,
  * grown on demand (the stream is synchronised only then), never shrunk, freed by adanerf_destroy; adanerf_render never allocates them.
  * ADANERF_EINVAL, with nothing written: a NULL source image, destination colour or pose; a pose entry that is not finite; acc_min NaN or
@@ -738,8 +774,9 @@ enum { ADANERF_TEMPORAL_CLAMP = 1 }; /* the history colour is clamped to the min
  *               a_eff = fmaxf(alpha, 1.0f / (float)n') with d_hist_count, alpha without: a running mean until 1 / n' falls below alpha.
  *   8 blend     accepted: out = hst + a_eff (cur - hst), mask 1; rejected: out = cur, the bits copied, mask 0.  d_out_rgba8 follows
  *               adanerf_resolve_mean's byte contract.
- * What it does not do: rejected pixels are not re-rendered (that needs a ray mask in the render path) and show the new frame's single
- * jittered sample; the current frame is not un-jittered; no variance clipping; the scene is static.
+ * What it does not do: rejected pixels show the new frame's single jittered sample -- more samples for them are a host's choice
+ * (adanerf_render_masked(d_out_mask, 1, ..) at further offsets; neither host does it); the current frame is not un-jittered; no variance
+ * clipping; the scene is static.
  * Runs on the context's stream in one launch; its only context-owned scratch is the 4-byte counter it shares with adanerf_reproject (made
  * on first use, freed by adanerf_destroy); adanerf_render never allocates for it.
  * ADANERF_EINVAL, with nothing written: a NULL current image, map, current pose or d_out_rgb; a NULL previous pose with a history; a pose
@@ -794,7 +831,8 @@ int adanerf_temporal_resolve(adanerf_ctx* ctx, const float* d_cur_rgb, const flo
  *               adanerf_resolve_mean's byte contract.
  * With the offsets of adanerf_host_subpixel_grid(s, .) every output pixel has inside true in exactly one frame of the s^2 cycle, with
  * ex = ey = 0 to rounding: at rest from a cut, after s^2 calls every count is 1 and the image is the interleave of the s^2 renders.
- * What it does not do: rejected pixels show the nearest sample and are not re-rendered (that needs a ray mask); no variance clipping;
+ * What it does not do: rejected pixels show the nearest sample (their mask selects them for adanerf_render_masked on a context of the
+ * output size; neither host does it); no variance clipping;
  * the scene is static; at s = 1 it is a temporal resolve with another depth test, not a replacement for adanerf_temporal_resolve.
  * Two launches on the context's stream.  Context-owned scratch: zp ([h*w] fp32, grown on demand as adanerf_reproject's z-buffer is) and the
  * counter shared with adanerf_reproject; both freed by adanerf_destroy; adanerf_render never allocates for them.
@@ -837,7 +875,9 @@ enum {
   ADANERF_BUF_RAW = 6,         /* [S,4] fp32 */
   ADANERF_BUF_TOTAL = 7,       /* [1] int32 */
   ADANERF_BUF_SAMPLE_Z = 8,    /* [S] fp32 (ADANERF_SAMPLER_PDF / _COARSE_FINE) */
-  ADANERF_BUF_RAW_COARSE = 9   /* [batch*Nc,4] fp32 (ADANERF_SAMPLER_COARSE_FINE) */
+  ADANERF_BUF_RAW_COARSE = 9,  /* [batch*Nc,4] fp32 (ADANERF_SAMPLER_COARSE_FINE) */
+  ADANERF_BUF_RAY_LIST = 10,   /* [M] int32: the ascending ray ids of the last adanerf_render_masked (NULL before the first) */
+  ADANERF_BUF_RAY_LIST_COUNT = 11 /* [1] int32: M of that call */
 };
 int adanerf_get_buffer(adanerf_ctx* ctx, int32_t which, void** d_out, size_t* bytes_out);
 
