@@ -117,6 +117,7 @@ struct adanerf_ctx {
   float* aux_disp = nullptr;         // adanerf_set_disp_output
   const uint8_t* budget_n = nullptr;  // adanerf_set_budget_map: caller-owned [rays_local] per-ray N / threshold, read by the trim kernels of every render
   const float* budget_thr = nullptr;
+  const float* depth_limit = nullptr; // adanerf_set_depth_limit: caller-owned [rays_local] camera-space depths, read by the depth trim of every render
   DevBuf disp_scratch;               // [2, batch] depth / accumulation of the batch when the caller asked for disparity only
   // adanerf_flip: filter tables of the last pixels-per-degree value, per-tile sums, the mean; grown on demand
   DevBuf flip_tab, flip_partial, flip_mean;
@@ -442,12 +443,33 @@ int launch_trim(adanerf_ctx* c, const BudgetMaps& bm, int n_rays, int n_max, flo
   HIP_RETURN(c, hipGetLastError());
 }
 
+// Per-ray depth limits: the selection of the batch (after the budget trim, if any) trimmed to the entries in front of the caller's surface
+// before launch_expand (k_depth_limit.hip.hpp).  zc is indexed by local ray: ray i of the batch is entry first + i, with a list first + list[i].
+struct DepthLimit {
+  const float* zc;
+  int first;
+  const int32_t* list;       // device ray ids of a listed batch, or null
+  const float* rays;         // [n,8] ray records of the batch
+  const float* ztab;         // [128] depth per bin
+  DepthPose pose;
+};
+
+DepthPose depth_pose(const float pos[3], const float rot[9]) { return DepthPose{{pos[0], pos[1], pos[2]}, rot[2], rot[5], rot[8]}; }
+
+int launch_depth_limit(adanerf_ctx* c, const DepthLimit& dl, int n_rays, int n_max, int seg_shift, int32_t* d_cnt) {
+  if (n_rays <= 0) return ADANERF_OK;
+  hipLaunchKernelGGL(depth_limit_kernel, dim3((n_rays + 255) / 256), dim3(256), 0, c->stream, d_cnt, reinterpret_cast<uint8_t*>(c->selbin.p),
+                     reinterpret_cast<float*>(c->selw.p), dl.rays, dl.zc, dl.list, dl.first, dl.pose, dl.ztab, n_rays, n_max, seg_shift,
+                     reinterpret_cast<int32_t*>(c->block_total.p));
+  HIP_RETURN(c, hipGetLastError());
+}
+
 // the pair selection keeps its sorted candidate lists in registers: n_max <= kPairMaxN; ADANERF_FLAG_WAVE_SELECT forces the
 // wave-per-ray select_kernel (any n_max)
 bool use_pair_select(const adanerf_ctx* c, int n_max) { return n_max <= kPairMaxN && !(c->opt.flags & ADANERF_FLAG_WAVE_SELECT); }
 
 int launch_compact(adanerf_ctx* c, const float* d_oracle, int n_rays, int n_max, float thr, int32_t* d_off, int32_t* d_cnt,
-                   uint32_t* d_key, float* d_w, int32_t* d_total, const BudgetMaps* bm = nullptr) {
+                   uint32_t* d_key, float* d_w, int32_t* d_total, const BudgetMaps* bm = nullptr, const DepthLimit* dl = nullptr) {
   if (n_rays <= 0) return ADANERF_OK;
   if (thr == 0.0f) {
     const size_t n = static_cast<size_t>(n_rays) * kBins;
@@ -460,6 +482,8 @@ int launch_compact(adanerf_ctx* c, const float* d_oracle, int n_rays, int n_max,
                        static_cast<const int32_t*>(nullptr));
     if (bm)
       if (int rc = launch_trim(c, *bm, n_rays, n_max, thr, kPairSegShift, d_cnt)) return rc;
+    if (dl)
+      if (int rc = launch_depth_limit(c, *dl, n_rays, n_max, kPairSegShift, d_cnt)) return rc;
     return launch_expand(c, n_rays, n_max, kPairSegShift, d_off, d_cnt, d_key, d_w, d_total);
   }
   const int nblk = (n_rays + kSelRaysPerBlock - 1) / kSelRaysPerBlock;
@@ -468,6 +492,8 @@ int launch_compact(adanerf_ctx* c, const float* d_oracle, int n_rays, int n_max,
                      reinterpret_cast<int32_t*>(c->block_total.p));
   if (bm)
     if (int rc = launch_trim(c, *bm, n_rays, n_max, thr, kSelSegShift, d_cnt)) return rc;
+  if (dl)
+    if (int rc = launch_depth_limit(c, *dl, n_rays, n_max, kSelSegShift, d_cnt)) return rc;
   return launch_expand(c, n_rays, n_max, kSelSegShift, d_off, d_cnt, d_key, d_w, d_total);
 }
 
@@ -656,6 +682,7 @@ int apply_frame_size(adanerf_ctx* c, int was_rays) {
     c->aux_depth = c->aux_acc = c->aux_disp = nullptr;
     c->budget_n = nullptr;      // the budget maps were sized for the old rays_local too
     c->budget_thr = nullptr;
+    c->depth_limit = nullptr;      // and so was the depth limit
   }
   c->guard_frame = 0;
   return ADANERF_OK;
@@ -1013,6 +1040,8 @@ int adanerf_set_selection(adanerf_ctx* c, int32_t num_samples, float threshold) 
     return fail(c, ADANERF_EUNSUPPORTED, "this model's sampler takes no threshold (adanerf_create ignores options.threshold for it): pass a negative one");
   if (threshold == 0.f && has_budget_map(c))
     return fail(c, ADANERF_EUNSUPPORTED, "threshold 0 (dense) keeps every bin: remove the budget map first (adanerf_set_budget_map with two NULLs)");
+  if (threshold == 0.f && c->depth_limit)
+    return fail(c, ADANERF_EUNSUPPORTED, "threshold 0 (dense) keeps every bin with implicit keys: remove the depth limit first (adanerf_set_depth_limit with NULL)");
   ModelSetup& ms = c->ms;
   const adanerf_info was = ms.info;
   const ModelSetup::PosBound was_bound = ms.pos_bound;
@@ -1776,6 +1805,9 @@ int render_batch(adanerf_ctx* c, int first, int n, const RayList* list, const Ba
                      !(c->opt.flags & ADANERF_FLAG_KEEP_ORACLE);
   const SelectOut so = select_out(c, N, thr, cnt);
   const BudgetMaps bm{c->budget_n, c->budget_thr, first};
+  // adaptive sampler, threshold > 0, no NDC (adanerf_set_depth_limit / adanerf_set_selection see to it); the pose in force reaches the kernel by value
+  const bool limited = c->depth_limit != nullptr;
+  const DepthLimit dl{c->depth_limit, first, list ? list->ids : nullptr, rays, c->ms.sp.ztab, depth_pose(c->ms.rg.pos, c->ms.rg.rot)};
   if (!cfm && (rc = launch_sample_mlp(c, first, n, fused ? nullptr : oracle, rays, fused ? &so : nullptr, list))) return rc;
   if (ev && !cfm) HIP_TRY(c, hipEventRecord(ev[1], c->stream));
   float* sz = reinterpret_cast<float*>(c->sample_z.p);
@@ -1783,12 +1815,13 @@ int render_batch(adanerf_ctx* c, int first, int n, const RayList* list, const Ba
   else if (pdf) rc = launch_sample_pdf(c, oracle, n, N, off, cnt, key, sw, sz, total);
   else if (fused) {
     rc = budget ? launch_trim(c, bm, n, N, thr, kPairSegShift, cnt) : ADANERF_OK;
+    if (!rc && limited) rc = launch_depth_limit(c, dl, n, N, kPairSegShift, cnt);
     if (!rc) rc = launch_expand(c, n, N, kPairSegShift, off, cnt, key, sw, total);
   }
   else if (thr == 0.f) {      // dense: implicit keys, the oracle buffer is the weight array (dense_offsets_kernel)
     hipLaunchKernelGGL(dense_offsets_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, off, cnt, total);
     HIP_TRY(c, hipGetLastError());
-  } else rc = launch_compact(c, oracle, n, N, thr, off, cnt, key, sw, total, budget ? &bm : nullptr);
+  } else rc = launch_compact(c, oracle, n, N, thr, off, cnt, key, sw, total, budget ? &bm : nullptr, limited ? &dl : nullptr);
   if (rc) return rc;
   const bool dense_implicit = !cfm && !pdf && !fused && thr == 0.f;
   const uint32_t* key_s = dense_implicit ? nullptr : key;
@@ -2041,6 +2074,58 @@ int adanerf_compact_budget(adanerf_ctx* c, const float* d_oracle, int32_t n_rays
   if (int rc = ensure_compact_scratch(c, n_rays, n_max)) return rc;
   const BudgetMaps bm{d_n_map, d_thr_map, 0};
   return launch_compact(c, d_oracle, n_rays, n_max, thr, d_off, d_cnt, d_key, d_w, d_total, &bm);
+}
+
+int adanerf_set_depth_limit(adanerf_ctx* c, const float* d_limit_zc) {
+  if (!c) return ADANERF_EINVAL;
+  if (d_limit_zc) {
+    if (c->ms.coarse_fine || c->ms.info.sampler_mode != ADANERF_SAMPLER_ADAPTIVE)
+      return fail(c, ADANERF_EUNSUPPORTED, "adanerf_set_depth_limit: a depth limit trims the adaptive selection: this model's sampler has none");
+    if (c->ms.info.use_ndc) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_set_depth_limit: the samples of a useNDC model live in NDC space, not along the camera's viewing axis");
+    if (c->ms.info.dense) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_set_depth_limit: threshold 0 (dense) keeps every bin with implicit keys: there is no selection to trim");
+    if (reinterpret_cast<uintptr_t>(d_limit_zc) & 3) return fail(c, ADANERF_EINVAL, "adanerf_set_depth_limit: the map must be 4-byte aligned");
+  }
+  c->depth_limit = d_limit_zc;
+  return ADANERF_OK;
+}
+
+int adanerf_compact_depth_limit(adanerf_ctx* c, const float* d_oracle, int32_t n_rays, int32_t n_max, float thr, const float* d_rays,
+                                const float* d_limit_zc, const float pos[3], const float rot[9], int32_t* d_off, int32_t* d_cnt, uint32_t* d_key,
+                                float* d_w, int32_t* d_total) {
+  BIND(c);
+  if (!d_oracle || !d_rays || !d_limit_zc || !pos || !rot || !d_off || !d_cnt || !d_key || !d_w || !d_total) return fail(c, ADANERF_EINVAL, "NULL buffer");
+  if (n_rays < 0 || n_max < 1 || n_max > kBins || !(thr > 0.f)) return fail(c, ADANERF_EINVAL, "n_rays/n_max/thr out of range (thr must be > 0: the dense mode selects nothing)");
+  if (static_cast<int64_t>(n_rays) >= (1ll << 25)) return fail(c, ADANERF_EINVAL, "n_rays must be < 2^25 per batch");
+  if (static_cast<int64_t>(n_rays) * n_max > 0x7fffffffll) return fail(c, ADANERF_EINVAL, "n_rays * n_max exceeds 2^31 - 1");
+  if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_limit_zc) & 3))
+    return fail(c, ADANERF_EINVAL, "d_rays must be 16-byte aligned, d_limit_zc 4-byte aligned");
+  if (!c->ms.sp.ztab) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_compact_depth_limit: this context has no depth table");
+  if (int rc = ensure_compact_scratch(c, n_rays, n_max)) return rc;
+  const DepthLimit dl{d_limit_zc, 0, nullptr, d_rays, c->ms.sp.ztab, depth_pose(pos, rot)};
+  return launch_compact(c, d_oracle, n_rays, n_max, thr, d_off, d_cnt, d_key, d_w, d_total, nullptr, &dl);
+}
+
+int adanerf_blend_behind(adanerf_ctx* c, const float* d_rgb, const float* d_acc, const float* d_behind_rgb, int32_t n, float* d_out_rgb, void* d_out_rgba8) {
+  if (!c) return ADANERF_EINVAL;
+  if (!d_rgb || !d_acc || !d_behind_rgb) return fail(c, ADANERF_EINVAL, "adanerf_blend_behind: NULL input image");
+  if (!d_out_rgb && !d_out_rgba8) return fail(c, ADANERF_EINVAL, "adanerf_blend_behind: both outputs NULL");
+  if (n < 0 || n > 0x7fffffff / 3) return fail(c, ADANERF_EINVAL, "adanerf_blend_behind: n must be >= 0 and n * 3 <= 2^31 - 1");
+  if ((reinterpret_cast<uintptr_t>(d_rgb) | reinterpret_cast<uintptr_t>(d_acc) | reinterpret_cast<uintptr_t>(d_behind_rgb) | reinterpret_cast<uintptr_t>(d_out_rgb) |
+       reinterpret_cast<uintptr_t>(d_out_rgba8)) & 3)
+    return fail(c, ADANERF_EINVAL, "adanerf_blend_behind: images must be 4-byte aligned");
+  const size_t bytes = static_cast<size_t>(n) * 3 * sizeof(float), bytes1 = static_cast<size_t>(n) * 4;
+  const void* const in[3] = {d_rgb, d_acc, d_behind_rgb};
+  const size_t in_bytes[3] = {bytes, bytes1, bytes};
+  for (int i = 0; i < 3; ++i) {
+    if (d_out_rgb && !(i == 0 && d_out_rgb == d_rgb) && ranges_overlap(in[i], in_bytes[i], d_out_rgb, bytes))
+      return fail(c, ADANERF_EINVAL, "adanerf_blend_behind: d_out_rgb overlaps an input (only d_rgb itself may be the output)");
+    if (d_out_rgba8 && ranges_overlap(in[i], in_bytes[i], d_out_rgba8, bytes1)) return fail(c, ADANERF_EINVAL, "adanerf_blend_behind: d_out_rgba8 overlaps an input");
+  }
+  if (d_out_rgb && d_out_rgba8 && ranges_overlap(d_out_rgb, bytes, d_out_rgba8, bytes1)) return fail(c, ADANERF_EINVAL, "adanerf_blend_behind: the two outputs overlap");
+  BIND(c);
+  if (n == 0) return ADANERF_OK;
+  hipLaunchKernelGGL(blend_behind_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_rgb, d_acc, d_behind_rgb, n, d_out_rgb, static_cast<uchar4*>(d_out_rgba8));
+  HIP_RETURN(c, hipGetLastError());
 }
 
 int adanerf_set_stream(adanerf_ctx* c, void* hip_stream) {

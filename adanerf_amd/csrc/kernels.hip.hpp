@@ -3,6 +3,7 @@
 //   A1+A2+A3  sample_mlp_kernel      ray gen -> sphere exit -> oracle PE -> 8-layer sampling MLP (fp32 MFMA)
 //   A4        select_kernel / scan_blocks_kernel / expand_kernel   top-N + threshold, deterministic compaction
 //   A4b       trim_rows_kernel / trim_rows_wave_kernel / foveate_kernel   per-ray budgets: the selection trimmed to (n_r, thr_r), the maps of a gaze
+//   A4c       depth_limit_kernel     per-ray depth limits: the selection trimmed to the samples in front of a rasterised surface
 //   A5+A6     shade_mlp16x2_kernel / shade_mlp32_kernel   fused PE + 8x256 shading MLP (bf16/f16/f32 MFMA)
 //   A7        composite_kernel       sigmoid + alpha * oracle weight, front-to-back
 //   N1        flip_kernel / flip_mean_kernel   FLIP error map and mean of an image pair (the evaluator's second metric)
@@ -12,6 +13,7 @@
 //   N6        temporal_resolve_kernel   a history image carried to the pose of the moment, clamped and blended with the new frame (temporal anti-aliasing)
 //   N7        upsample_depth_kernel / upsample_resolve_kernel   a frame rendered at w x h resolved into a history of s w x s h (temporal upsampling)
 //   N8        mask_bits_kernel / mask_scatter_kernel   a byte mask as bit words for refine_list_kernel; the pixels of a listed batch to their places (masked rendering)
+//   N9        blend_behind_kernel   the rasterised colour behind a depth-limited frame, through the transmittance that is left (hybrid rendering)
 // plus explicit-feature debug kernels (ray_features_kernel, shade_features_kernel) that materialise
 // what the reference launchers wrote to memory, for parity tests only.
 // The code lives in one header per stage; this file includes them all.
@@ -33,3 +35,5 @@
 #include "k_temporal.hip.hpp"
 #include "k_upsample.hip.hpp"
 #include "k_mask.hip.hpp"
+#include "k_depth_limit.hip.hpp"
+#include "k_blend.hip.hpp"

@@ -4,6 +4,7 @@
 #include <cstdio>
 #include <cstring>
 #include <exception>
+#include <limits>
 
 namespace adanerf {
 
@@ -414,6 +415,67 @@ int adanerf_host_subpixel_grid(int32_t s, int32_t k, float* dx, float* dy) {
   const int i = k % s, j = k / s;
   *dx = static_cast<float>((2.0 * i + 1.0 - s) / (2.0 * s));
   *dy = static_cast<float>((2.0 * j + 1.0 - s) / (2.0 * s));
+  return ADANERF_OK;
+}
+
+int adanerf_host_sphere_zc(int32_t width, int32_t height, float focal, const float pos[3], const float rot_c2w[9], const float center[3], float radius,
+                           float* zc_out) {
+  if (!pos || !rot_c2w || !center || !zc_out) return fail(ADANERF_EINVAL, "adanerf_host_sphere_zc: NULL argument");
+  if (width < 1 || width > 16384 || height < 1 || height > 16384) return fail(ADANERF_EINVAL, "adanerf_host_sphere_zc: width and height must be in 1..16384");
+  bool finite = std::isfinite(focal) && std::isfinite(radius);
+  for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(pos[i]) && std::isfinite(center[i]);
+  for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(rot_c2w[i]);
+  if (!finite) return fail(ADANERF_EINVAL, "adanerf_host_sphere_zc: every value must be finite");
+  if (!(radius > 0.f) || !(focal > 0.f)) return fail(ADANERF_EINVAL, "adanerf_host_sphere_zc: radius and focal must be > 0");
+  // every intermediate goes through a volatile: one rounded float64 operation per step on every compiler setting, never a fused
+  // multiply-add (with_pixel_offset); the order is the one the header states
+  volatile double e[3], c[3], m0, m1, m2, s;
+  for (int i = 0; i < 3; ++i) e[i] = static_cast<double>(center[i]) - static_cast<double>(pos[i]);
+  for (int k = 0; k < 3; ++k) {      // c = R^T e
+    m0 = static_cast<double>(rot_c2w[k]) * e[0];
+    m1 = static_cast<double>(rot_c2w[3 + k]) * e[1];
+    m2 = static_cast<double>(rot_c2w[6 + k]) * e[2];
+    s = m0 + m1;
+    c[k] = s + m2;
+  }
+  m0 = c[0] * c[0];
+  m1 = c[1] * c[1];
+  m2 = c[2] * c[2];
+  s = m0 + m1;
+  volatile double cc = s + m2;
+  volatile double rr = static_cast<double>(radius) * static_cast<double>(radius);
+  volatile double g = cc - rr;
+  const double f = static_cast<double>(focal), hw = 0.5 * width, hh = 0.5 * height;
+  const float inf = std::numeric_limits<float>::infinity();
+  for (int y = 0; y < height; ++y) {
+    volatile double ny = (y + 0.5) - hh;
+    volatile double py = ny / f;
+    const double vy = -py;
+    for (int x = 0; x < width; ++x) {
+      volatile double nx = (x + 0.5) - hw;
+      volatile double vx = nx / f;
+      m0 = vx * vx;
+      m1 = vy * vy;
+      s = m0 + m1;
+      volatile double a = s + 1.0;
+      m0 = vx * c[0];
+      m1 = vy * c[1];
+      s = m0 + m1;
+      volatile double b = s - c[2];
+      m0 = b * b;
+      m1 = a * g;
+      volatile double disc = m0 - m1;
+      float out = inf;
+      if (disc >= 0.0) {
+        volatile double q = std::sqrt(disc);
+        volatile double n0 = b - q, n1 = b + q;
+        volatile double t0 = n0 / a, t1 = n1 / a;
+        if (t0 > 0.0) out = static_cast<float>(t0);
+        else if (t1 > 0.0) out = static_cast<float>(t1);
+      }
+      zc_out[static_cast<size_t>(y) * width + x] = out;
+    }
+  }
   return ADANERF_OK;
 }
 

@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -23,7 +24,7 @@ NeuralRenderer::~NeuralRenderer() {
   if (ctx) {
     if (d_gathered) adanerf_free(ctx, d_gathered);
     if (d_frame) adanerf_free(ctx, d_frame);
-    for (void* p : {d_depth, d_acc, d_warp, d_wmask, d_rgb, d_sum, d_hist[0][0], d_hist[0][1], d_hist[0][2], d_hist[1][0], d_hist[1][1], d_hist[1][2], d_up})
+    for (void* p : {d_depth, d_acc, d_warp, d_wmask, d_rgb, d_sum, d_hist[0][0], d_hist[0][1], d_hist[0][2], d_hist[1][0], d_hist[1][1], d_hist[1][2], d_up, d_limit, d_behind})
       if (p) adanerf_free(ctx, p);
     if (d_window) adanerf_free(ctx, d_window);
     adanerf_destroy(ctx);
@@ -225,6 +226,18 @@ bool NeuralRenderer::allocFrameBuffers() {
       if (adanerf_malloc(ctx, static_cast<size_t>(info_.width) * info_.height * 3 * sizeof(float), p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
     }
   }
+  if (!settings.occluders.empty()) {      // the limit and the acc map belong to the frame size: the library drops them when rays_local changes
+    const size_t n = static_cast<size_t>(info_.width) * info_.height;
+    occ_have = false;
+    void** bufs[] = {&d_rgb, &d_acc, &d_limit, &d_behind};
+    const size_t bytes[] = {n * 12, n * 4, n * 4, n * 12};
+    for (int k = 0; k < 4; ++k) {
+      if (*bufs[k] && adanerf_free(ctx, *bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+      *bufs[k] = nullptr;
+      if (adanerf_malloc(ctx, bytes[k], bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+    }
+    if (adanerf_set_aux_outputs(ctx, nullptr, static_cast<float*>(d_acc)) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+  }
   if (settings.reproject > 1) {      // the aux outputs belong to the frame size: the library drops them when rays_local changes
     const size_t n = static_cast<size_t>(info_.width) * info_.height;
     have_source = false;
@@ -399,6 +412,8 @@ bool NeuralRenderer::render() {
     if (!renderUpsampled(&st, rot)) return false;
   } else if (settings.taa_alpha > 0.f) {
     if (!renderTemporal(&st, rot)) return false;
+  } else if (!settings.occluders.empty()) {
+    if (!renderHybrid(&st, rot)) return false;
   } else if (settings.supersample > 1 ? !renderSupersampled(&st) : adanerf_render(ctx, d_frame, nullptr, &st) != ADANERF_OK) {
     if (settings.supersample <= 1) err = adanerf_last_error(ctx);
     return false;
@@ -459,6 +474,46 @@ bool NeuralRenderer::renderSupersampled(adanerf_stats* st) {
   if (!ok) return false;
   st->total_samples /= renders;      // per rendered frame, as the log's "avg samples ppx" counts
   if (!back || adanerf_resolve_mean(ctx, static_cast<const float*>(d_sum), n, renders, d_frame, nullptr) != ADANERF_OK || adanerf_sync(ctx) != ADANERF_OK) {
+    err = adanerf_last_error(ctx);
+    return false;
+  }
+  return true;
+}
+
+// --occluder: the spheres' camera-space depth for every pixel (adanerf_host_sphere_zc, per-pixel minimum on the host; the nearest sphere's
+// flat colour behind it) filled again when the camera or the frame size has changed, one render under that limit, and the colour behind
+// let through with the transmittance left (adanerf_blend_behind) into d_frame.
+bool NeuralRenderer::renderHybrid(adanerf_stats* st, const float rot[9]) {
+  const int w = info_.width, h = info_.height;
+  const size_t n = static_cast<size_t>(w) * h;
+  if (!occ_have || std::memcmp(occ_pos, camera.getPosition(), sizeof(occ_pos)) != 0 || std::memcmp(occ_rot, rot, sizeof(occ_rot)) != 0) {
+    std::vector<float> limit(n, INFINITY), behind(n * 3, 0.f), one(n);
+    for (const Settings::Occluder& o : settings.occluders) {
+      if (adanerf_host_sphere_zc(w, h, info_.focal, camera.getPosition(), rot, o.center, o.radius, one.data()) != ADANERF_OK) {
+        err = adanerf_last_error(nullptr);
+        return false;
+      }
+      for (size_t i = 0; i < n; ++i)
+        if (one[i] < limit[i]) {      // the nearest sphere; the first given on a tie
+          limit[i] = one[i];
+          std::memcpy(&behind[3 * i], o.rgb, sizeof(o.rgb));
+        }
+    }
+    // the copies synchronise: no frame in flight still reads the buffers
+    if (adanerf_memcpy_h2d(ctx, d_limit, limit.data(), n * sizeof(float)) != ADANERF_OK ||
+        adanerf_memcpy_h2d(ctx, d_behind, behind.data(), n * 3 * sizeof(float)) != ADANERF_OK ||
+        adanerf_set_depth_limit(ctx, static_cast<const float*>(d_limit)) != ADANERF_OK) {
+      err = adanerf_last_error(ctx);
+      return false;
+    }
+    std::memcpy(occ_pos, camera.getPosition(), sizeof(occ_pos));
+    std::memcpy(occ_rot, rot, sizeof(occ_rot));
+    occ_have = true;
+  }
+  if (adanerf_render(ctx, nullptr, static_cast<float*>(d_rgb), st) != ADANERF_OK ||
+      adanerf_blend_behind(ctx, static_cast<const float*>(d_rgb), static_cast<const float*>(d_acc), static_cast<const float*>(d_behind), static_cast<int32_t>(n),
+                           nullptr, d_frame) != ADANERF_OK ||
+      adanerf_sync(ctx) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;
   }

@@ -100,6 +100,13 @@ class NeuralRenderer {
   // prev_*, s_rejected) is shared, the two being exclusive
   void* d_up = nullptr;
   bool renderUpsampled(adanerf_stats* st, const float rot[9]);   // one render at the cycle's next offset, resolved into the S w x S h history and d_up
+  // --occluder: the limit (float [h*w]) and the colour behind it (float [h*w*3]) of the spheres at the pose and size they were last filled
+  // for; the fp32 frame (d_rgb) and acc_map (d_acc) of this frame's render
+  void* d_limit = nullptr;
+  void* d_behind = nullptr;
+  bool occ_have = false;             // d_limit / d_behind hold the spheres as seen from occ_pos / occ_rot at the size in force
+  float occ_pos[3] = {0, 0, 0}, occ_rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  bool renderHybrid(adanerf_stats* st, const float rot[9]);   // the map refilled if the camera or the size moved, one render under it, blended into d_frame
   void* d_window = nullptr;          // --write-window: uchar4 [window_height*window_width], the frame as adanerf_present shows it
   int world_ = 1, strip_rows_ = 8;   // share layout chosen at init; a live context keeps its strip height
   bool allocFrameBuffers();          // d_frame, d_gathered, d_payload for the size in info_ (again after a size change)

@@ -14,6 +14,8 @@ const char* Settings::usage() {
          "               [--samples N] [--threshold T] [--oracle]\n"
          "               [--fovea R:N:T[,R:N:T...],N:T]     per-ray budgets: rings around the gaze (radius px : N : threshold), then the\n"
          "                                                  entry outside them; the gaze starts at the frame centre\n"
+         "               [--occluder cx,cy,cz,r[,R,G,B]]    hybrid rendering (repeatable): every ray stops at the nearest of these spheres and its\n"
+         "                                                  flat colour (0..1, default 0.5 grey) shows through what the volume in front leaves\n"
          "               [--script FILE] [--log-camera] [--dry-run]     input replay: one line of events per frame\n"
          "                                                              (+w -w ... b+ x y  b- x y  m x y; n <int> / thr <float>:\n"
          "                                                              sample budget N / threshold from that frame on;\n"
@@ -75,6 +77,33 @@ bool Settings::parseFovea(const std::string& spec, std::vector<int>* radius, std
     thr->push_back(t);
   }
   if (radius->size() > 8) return bad("at most 8 rings");
+  return true;
+}
+
+// cx,cy,cz,r[,R,G,B] -- every field read whole; what adanerf_host_sphere_zc would refuse is refused here, with the spec in the message
+bool Settings::parseOccluder(const std::string& spec, Occluder* out, std::string* err) {
+  auto bad = [&](const char* why) {
+    *err = "--occluder " + spec + ": " + why + " (expected cx,cy,cz,r[,R,G,B])";
+    return false;
+  };
+  std::vector<std::string> f(1);
+  for (char ch : spec) {
+    if (ch == ',') f.emplace_back();
+    else f.back() += ch;
+  }
+  if (f.size() != 4 && f.size() != 7) return bad("four or seven values");
+  float v[7] = {0.f, 0.f, 0.f, 0.f, 0.5f, 0.5f, 0.5f};
+  for (size_t k = 0; k < f.size(); ++k) {
+    char* end = nullptr;
+    v[k] = std::strtof(f[k].c_str(), &end);
+    if (end == f[k].c_str() || *end != 0 || !std::isfinite(v[k])) return bad("not a finite number");
+  }
+  if (!(v[3] > 0.f)) return bad("the radius must be > 0");
+  for (int k = 0; k < 3; ++k) {
+    out->center[k] = v[k];
+    out->rgb[k] = v[4 + k];
+  }
+  out->radius = v[3];
   return true;
 }
 
@@ -151,6 +180,11 @@ bool Settings::init(int argc, char** argv, std::string* err) {
     } else if (a == "--fovea") {
       if (!need(i, 1)) return false;
       if (!parseFovea(argv[++i], &fovea_radius, &fovea_n, &fovea_thr, err)) return false;
+    } else if (a == "--occluder") {
+      if (!need(i, 1)) return false;
+      Occluder o;
+      if (!parseOccluder(argv[++i], &o, err)) return false;
+      occluders.push_back(o);
     } else if (a == "--reproject") {
       if (!need(i, 1)) return false;
       char* end = nullptr;
@@ -267,6 +301,12 @@ bool Settings::init(int argc, char** argv, std::string* err) {
            : supersample > 1 ? "--taau spends one render per frame on a cycle of sub-pixel offsets; not with --supersample"
            : gpus > 1 ? "--taau resolves whole frames of one context; use it with --gpus 1"
                       : "--taau blends rendered frames; not with --oracle";
+    return false;
+  }
+  if (!occluders.empty() && (gpus > 1 || render_oracle || reproject > 1 || supersample > 1 || taa_alpha > 0.f || taau_scale > 0)) {
+    *err = gpus > 1 ? "--occluder blends whole frames of one context; use it with --gpus 1"
+           : render_oracle ? "--occluder limits rendered frames; not with --oracle"
+                           : "--occluder: the temporal and reprojection stages take no depth limit; not with --reproject, --supersample, --taa or --taau";
     return false;
   }
   total_size = width * height;

@@ -37,6 +37,14 @@ class Settings {
   std::vector<int> fovea_radius, fovea_n;
   std::vector<float> fovea_thr;
   static bool parseFovea(const std::string& spec, std::vector<int>* radius, std::vector<int>* n, std::vector<float>* thr, std::string* err);
+  // --occluder cx,cy,cz,r[,R,G,B] (repeatable): hybrid rendering against sphere occluders -- the frame is rendered under the depth limit of
+  // the spheres' camera-space depth (per-pixel minimum, adanerf_host_sphere_zc / adanerf_set_depth_limit) and the nearest sphere's flat colour
+  // (0..1 per channel, default 0.5 grey) is let through with the transmittance left (adanerf_blend_behind).  Empty: off
+  struct Occluder {
+    float center[3], radius, rgb[3];
+  };
+  std::vector<Occluder> occluders;
+  static bool parseOccluder(const std::string& spec, Occluder* out, std::string* err);
   std::string rerender;         // --rerender holes|unsourced (with --reproject K > 1): the warped frames' holes (or every pixel without a source pixel
                                 // of its own) are rendered at the frame's camera (adanerf_render_masked); empty: they stay filled from neighbours
   int reproject = 1;            // --reproject K: of every K frames the first is rendered, the next K - 1 are that frame warped to their own camera

@@ -80,7 +80,8 @@ EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_las
            "adanerf_render_oracle", "adanerf_gather_to", "adanerf_probe_mfma", "adanerf_malloc",
            "adanerf_free", "adanerf_memcpy_h2d", "adanerf_memcpy_d2h", "adanerf_get_buffer",
            "adanerf_set_pixel_offset", "adanerf_get_pixel_offset", "adanerf_accumulate", "adanerf_resolve_mean", "adanerf_host_subpixel_grid", "adanerf_temporal_resolve",
-           "adanerf_temporal_upsample", "adanerf_render_masked"]
+           "adanerf_temporal_upsample", "adanerf_render_masked",
+           "adanerf_set_depth_limit", "adanerf_compact_depth_limit", "adanerf_blend_behind", "adanerf_host_sphere_zc"]
 
 _lib = None
 
@@ -106,6 +107,10 @@ def load_library(path: Optional[str] = None):
     lib.adanerf_set_budget_map.argtypes = [vp, vp, vp]
     lib.adanerf_foveate.argtypes = [vp, C.c_float, C.c_float, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_float), vp, vp]
     lib.adanerf_compact_budget.argtypes = [vp, vp, i32, i32, C.c_float, vp, vp, vp, vp, vp, vp, vp]
+    lib.adanerf_set_depth_limit.argtypes = [vp, vp]
+    lib.adanerf_compact_depth_limit.argtypes = [vp, vp, i32, i32, C.c_float, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp, vp, vp, vp]
+    lib.adanerf_blend_behind.argtypes = [vp, vp, vp, vp, i32, vp, vp]
+    lib.adanerf_host_sphere_zc.argtypes = [i32, i32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float)]
     lib.adanerf_present.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32]
     lib.adanerf_set_pixel_offset.argtypes = [vp, C.c_float, C.c_float]
     lib.adanerf_get_pixel_offset.argtypes = [vp, C.POINTER(C.c_float)]
@@ -269,6 +274,24 @@ def subpixel_grid(s: int):
     return out
 
 
+def sphere_zc(width: int, height: int, focal: float, pos, rot_c2w, center, radius: float) -> np.ndarray:
+    """The camera-space depth of a sphere for every pixel of a width x height frame (adanerf_host_sphere_zc): [height*width] fp32, +inf
+    where the pixel's ray misses it -- an occluder for set_depth_limit / render_hybrid without a rasteriser.  ``focal``: Info.focal.  No
+    device needed.  ValueError on what the library refuses (a side outside 1..16384, a value that is not finite, radius <= 0)."""
+    lib = load_library()
+    fp = C.POINTER(C.c_float)
+    p = np.ascontiguousarray(pos, dtype=np.float32).reshape(3)
+    r = np.ascontiguousarray(rot_c2w, dtype=np.float32).reshape(9)
+    c = np.ascontiguousarray(center, dtype=np.float32).reshape(3)
+    ok = 1 <= int(width) <= 16384 and 1 <= int(height) <= 16384
+    out = np.empty(int(width) * int(height) if ok else 1, dtype=np.float32)
+    if lib.adanerf_host_sphere_zc(int(width), int(height), float(focal), p.ctypes.data_as(fp), r.ctypes.data_as(fp), c.ctypes.data_as(fp), float(radius),
+                                  out.ctypes.data_as(fp)) != 0:
+        raise ValueError("adanerf_host_sphere_zc(%r x %r, focal %r, radius %r) refused: sides in 1..16384, finite values, radius > 0" %
+                         (width, height, focal, radius))
+    return out
+
+
 def parse_fovea(spec: str):
     """``R:N:T[,R:N:T...],N:T`` -> [(R, N, T), ..., (N, T)]: concentric rings around the gaze (radius in whole pixels, strictly ascending,
     at most 8), each with the sample budget N (0..255, 0 = the context's) and the threshold T of the pixels inside it, then the entry of
@@ -379,6 +402,8 @@ class NeuralRenderer:
         self._ta_hist = None          # (index of the history's buffer set, pos, rot) of the last render_temporal since then
         self._tu = None               # enable_temporal_upsample(): scale, alpha, depth_tol, clamp, the offset cycle and the place in it
         self._tu_hist = None          # (index of the history's buffer set, pos, rot) of the last render_upsampled since then
+        self._dl_in_force = None      # what the last set_depth_limit installed; render_hybrid puts it back
+        self._aux_in_force = (None, None)   # (depth_map, acc_map) of the last set_aux_outputs, likewise
 
     # -- lifecycle -------------------------------------------------------------------------------
     def init(self) -> bool:
@@ -449,8 +474,11 @@ class NeuralRenderer:
         size stays; the renderer's own output buffers (render_numpy) are made again at the next frame; device buffers the caller made
         for the old size, the ones behind set_aux_outputs / set_disp_output included (the library drops those when rays_local
         changes), are the caller's to re-make.  Refreshes and returns ``self.info``."""
+        was_rays = self.info.rays_local
         self._check(self.lib.adanerf_set_frame_size(self.handle, 0 if width is None else int(width), 0 if height is None else int(height)))
         self.refresh_info()
+        if self.info.rays_local != was_rays:      # the library dropped the per-ray buffers of the old rays_local
+            self._dl_in_force, self._aux_in_force = None, (None, None)
         self.settings.width, self.settings.height = self.info.width, self.info.height
         if hasattr(self, "_b_n") and self._b_n.shape[0] != self.info.rays_local:      # the library dropped the maps with the old rays_local
             self._drop_budget_buffers()
@@ -522,6 +550,72 @@ class NeuralRenderer:
         n_map, thr_map = self.budget_buffers()
         self._check(self.foveate_device(gaze_xy, rings, n_map, thr_map))
         self._check(self.lib.adanerf_set_budget_map(self.handle, n_map.ptr, thr_map.ptr))
+
+    # -- hybrid rendering: depth limits, the rasterised colour behind --------------------------------------
+    def set_depth_limit(self, limit_zc=None):
+        """Every ray of the frames rendered from now on stops at its entry of ``limit_zc`` (adanerf_set_depth_limit): [rays_local] fp32
+        camera-space depths (the distance along the viewing axis; +inf or NaN: no limit for that ray).  A numpy array (uploaded into the
+        renderer's own buffer), a device buffer (a DeviceArray, a pointer) or None (off).  A frame size that changes rays_local removes it."""
+        if isinstance(limit_zc, np.ndarray):
+            n = self.info.rays_local
+            if limit_zc.size != n:
+                raise ValueError("set_depth_limit: %d entries for %d local rays" % (limit_zc.size, n))
+            if not hasattr(self, "_dl_buf") or self._dl_buf.shape[0] != n:
+                if hasattr(self, "_dl_buf"):
+                    self._dl_buf.free()
+                    self._own.remove(self._dl_buf)
+                self._dl_buf = self.empty((n,), np.float32)
+            self.sync()      # frames in flight still read the buffer
+            self._dl_buf.upload(limit_zc.reshape(-1).astype(np.float32, copy=False))
+            limit_zc = self._dl_buf
+        self._check(self.lib.adanerf_set_depth_limit(self.handle, _ptr(limit_zc)))
+        self._dl_in_force = limit_zc
+
+    def blend_behind(self, rgb, acc, behind_rgb, n: int, rgb_out=None, rgba8_out=None):
+        """rgb + clamp(1 - acc, 0, 1) * behind_rgb over device [n,3] / [n] fp32 images into rgb_out ([n,3] fp32, may be rgb) and / or
+        rgba8_out ([n] uchar4), on the context's stream (adanerf_blend_behind)"""
+        self._check(self.lib.adanerf_blend_behind(self.handle, _ptr(rgb), _ptr(acc), _ptr(behind_rgb), int(n), _ptr(rgb_out), _ptr(rgba8_out)))
+
+    sphere_zc = staticmethod(sphere_zc)
+
+    def render_hybrid(self, limit_zc: np.ndarray, behind_rgb: np.ndarray):
+        """One frame of the neural scene in front of rasterised geometry: ``limit_zc`` [rays_local] fp32 camera-space depths of the geometry
+        (+inf where there is none), ``behind_rgb`` [rays_local,3] fp32 its colour.  Installs the limit, renders with the acc map attached,
+        blends, and restores the limit and the aux outputs that were in force.  Returns (rgb [R,3] fp32, rgba8 [R,4] uint8, Stats of the
+        render); the device copies stay in ``_o_rgb`` / ``_o_rgba`` as after render_numpy."""
+        n = self.info.rays_local
+        behind = np.ascontiguousarray(behind_rgb, dtype=np.float32).reshape(-1)
+        if behind.size != 3 * n:
+            raise ValueError("render_hybrid: %d colour values for %d local rays" % (behind.size, n))
+        if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
+            self._o_rgb = self.empty((n, 3), np.float32)
+            self._o_rgba = self.empty((n, 4), np.uint8)
+        limit = np.ascontiguousarray(limit_zc, dtype=np.float32).reshape(-1)
+        if limit.size != n:
+            raise ValueError("render_hybrid: %d limits for %d local rays" % (limit.size, n))
+        if not hasattr(self, "_hy_acc") or self._hy_acc.shape[0] != n:
+            for name in ("_hy_acc", "_hy_behind", "_hy_limit"):
+                if hasattr(self, name):
+                    a = getattr(self, name)
+                    a.free()
+                    self._own.remove(a)
+            self._hy_acc, self._hy_behind, self._hy_limit = self.empty((n,), np.float32), self.empty((n, 3), np.float32), self.empty((n,), np.float32)
+        was_limit, was_aux = self._dl_in_force, self._aux_in_force
+        self.sync()      # frames in flight still read the buffers
+        self._hy_behind.upload(behind)
+        self._hy_limit.upload(limit)
+        try:
+            self.set_depth_limit(self._hy_limit)
+            self.set_aux_outputs(was_aux[0], self._hy_acc)
+            st = self.render(None, self._o_rgb, stats=True)
+            self.blend_behind(self._o_rgb, self._hy_acc, self._hy_behind, n, self._o_rgb, self._o_rgba)
+        finally:
+            self.set_depth_limit(was_limit)
+            self.set_aux_outputs(*was_aux)
+        whole = n == self.info.width * self.info.height
+        self._last_frame = (self._o_rgba, self.info.width, self.info.height) if whole else None
+        self._rp_frame = None      # the blended frame's depth is not the volume's alone
+        return self._o_rgb.numpy(), self._o_rgba.numpy(), st
 
     # -- anti-aliasing: sub-pixel offsets, accumulation ------------------------------------------------
     def set_pixel_offset(self, dx: float = 0.0, dy: float = 0.0):
@@ -611,6 +705,7 @@ class NeuralRenderer:
     def set_aux_outputs(self, depth_map=None, acc_map=None):
         """Subsequent renders also fill [rays_local] fp32 depth_map (sum w z) / acc_map (sum w); None switches them off."""
         self._check(self.lib.adanerf_set_aux_outputs(self.handle, _ptr(depth_map), _ptr(acc_map)))
+        self._aux_in_force = (depth_map, acc_map)      # render_hybrid puts them back
 
     def set_disp_output(self, disp_map=None):
         """Subsequent renders also fill [rays_local] fp32 disp_map = 1 / max(1e-10, depth_map / acc_map); None switches it off."""
@@ -1006,6 +1101,16 @@ class NeuralRenderer:
     def compact(self, oracle, n_rays: int, n_max: int, thr: float, ray_offsets, ray_counts, sample_key, sample_w, total):
         self._check(self.lib.adanerf_compact(self.handle, _ptr(oracle), n_rays, n_max, thr, _ptr(ray_offsets),
                                              _ptr(ray_counts), _ptr(sample_key), _ptr(sample_w), _ptr(total)))
+
+    def compact_depth_limit(self, oracle, n_rays: int, n_max: int, thr: float, rays, limit_zc, pos, rot_c2w, ray_offsets, ray_counts, sample_key,
+                            sample_w, total) -> int:
+        """adanerf_compact_depth_limit: the selection at (n_max, thr), the depth trim of ray r to limit_zc[r] under the pose (pos, rot_c2w)
+        with the ray records ``rays`` [n_rays,8], then the compaction.  Returns the library's code instead of raising: tests look at both."""
+        fp = C.POINTER(C.c_float)
+        p = np.ascontiguousarray(pos, dtype=np.float32).reshape(3)
+        r = np.ascontiguousarray(rot_c2w, dtype=np.float32).reshape(9)
+        return self.lib.adanerf_compact_depth_limit(self.handle, _ptr(oracle), n_rays, n_max, thr, _ptr(rays), _ptr(limit_zc), p.ctypes.data_as(fp),
+                                                    r.ctypes.data_as(fp), _ptr(ray_offsets), _ptr(ray_counts), _ptr(sample_key), _ptr(sample_w), _ptr(total))
 
     def compact_budget(self, oracle, n_rays: int, n_max: int, thr: float, n_map, thr_map, ray_offsets, ray_counts, sample_key, sample_w, total):
         self._check(self.lib.adanerf_compact_budget(self.handle, _ptr(oracle), n_rays, n_max, thr, _ptr(n_map), _ptr(thr_map), _ptr(ray_offsets),

@@ -313,8 +313,8 @@ int adanerf_set_selection(adanerf_ctx* ctx, int32_t num_samples, float threshold
  *   memory is allocated (new buffers first, then the old ones freed) only when the batch exceeds that, never released before
  *   adanerf_destroy, and the stream is synchronised only then; a shrink allocates nothing, a call that changes neither value touches
  *   nothing, and adanerf_render never allocates for it.
- *   The caller-owned per-ray buffers of adanerf_set_aux_outputs / adanerf_set_disp_output / adanerf_set_budget_map were sized for the old
- *   rays_local: a call that CHANGES rays_local resets all five to NULL (set them again for the new size); a call that does not change it
+ *   The caller-owned per-ray buffers of adanerf_set_aux_outputs / adanerf_set_disp_output / adanerf_set_budget_map /
+ *   adanerf_set_depth_limit were sized for the old rays_local: a call that CHANGES rays_local resets all six to NULL (set them again for the new size); a call that does not change it
  *   leaves them.
  *   ADANERF_SAMPLING_GUARDED: the band belongs to (model, N, threshold) and its calibration runs on its own 64 x 64 rays, so the bounds,
  *   their source and pose count in adanerf_info stay; the audit's phase and fill cycle start over (frames do not depend on either). */
@@ -428,6 +428,56 @@ int adanerf_set_budget_map(adanerf_ctx* ctx, const uint8_t* d_n_map, const float
 int adanerf_foveate(adanerf_ctx* ctx, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* n,
                     const float* thr, uint8_t* d_n_map, float* d_thr_map);
 
+/* Hybrid rendering: the neural scene next to rasterised geometry (controllers, hands, avatars, UI panels, a cockpit).  Every ray stops
+ * at the depth the rasteriser reports for its pixel; the samples in front of it are composited, the samples at or behind it are never
+ * shaded, and adanerf_blend_behind lets the rasterised colour through with the transmittance that is left.  Painting the geometry over
+ * a finished frame by comparing against depth_map / acc_map is wrong wherever the scene is semi-transparent in front of the geometry,
+ * and pays for every sample nobody sees.
+ *   d_limit_zc [rays_local] fp32, device memory, caller-owned, indexed as d_rgba8_out is; NULL turns the feature off.  The value is a
+ *   camera-space depth, the distance along the camera's viewing axis: the zc adanerf_reproject writes to d_dst_depth and
+ *   adanerf_temporal_resolve to d_out_depth, what adanerf_host_sphere_zc computes; a GL host linearises its depth buffer first
+ *   (INTEGRATION.md).
+ *   Ordering is that of adanerf_set_camera; the map is read by the renders issued afterwards at the time their kernels run, so a caller may
+ *   rewrite it on the context's stream between frames.  adanerf_set_frame_size resets it to NULL when it changes rays_local.
+ * Rule (every operation a single rounded fp32 operation in this order; the same inputs give the same bits): entry k of ray r's selected
+ * row has bin b; z = ztab[b], the context's depth table (adanerf_host_depth_table); (o, d) = the ray's record in ADANERF_BUF_RAYS (it comes
+ * out of the sampling kernel, so the pixel offset in force is honoured); P_i = o_i + d_i z (a product, then a sum); q_i = P_i - pos_i;
+ * zc = -((R[2] q_0 + R[5] q_1) + R[8] q_2), pos and R = rot_c2w the pose in force (step 2 of adanerf_temporal_resolve).  The entry is
+ * dropped iff zc >= L_r.  So: a NaN limit keeps the whole row and so does +inf (against finite zc); a NaN zc is kept; equality drops; no
+ * entry is kept "as a fallback", and a row may become empty.  Survivors stay in ascending bin order with their weights untouched.
+ * Mechanism: one small kernel (a thread per ray, rows rewritten in place, the segment totals recomputed by integer sums in a fixed order,
+ * no atomics) after the selection -- fused, pair or wave -- and the budget trim, if any, and before the compaction.  With both maps
+ * installed ray r carries the budget selection at (n_r, thr_r) with the entries at or behind the limit removed.  Without a limit nothing
+ * new is launched: every frame is byte for byte what it was.  Shading and compositing consume counts and offsets and do not change; every
+ * shading kernel bounds its tiles by the device total and both compositing kernels loop k < count, so an empty row is legal:
+ * d_ray_counts is 0..n_max under a limit, and an empty ray composites to rgb 0, RGBA8 (0, 0, 0, 255), depth_map 0, acc_map 0, disp_map NaN.
+ * After a render adanerf_stats.total_samples and ADANERF_BUF_RAY_COUNTS / _RAY_OFFSETS / _SAMPLE_KEY / _SAMPLE_W / _TOTAL describe the
+ * trimmed selection.  Measured at 800 x 800, N 8, threshold 0.2 (profiles/depth_limit_measured.md): the trim kernel 11.3 us, and a frame
+ * with a quarter / half of its pixels behind a sphere 0.83 / 0.66 of the unlimited frame's time.
+ *   ADANERF_SAMPLING_GUARDED needs no special case: the rule reads bins, never values, and guarded bins are exact; the band, the audit and
+ *   the monitor are untouched.  Shards: the map is indexed by local ray, as the budget maps are.  adanerf_render_masked works with a limit
+ *   installed (the listed ray i reads L[list[i]]): each rendered pixel gets the bytes adanerf_render would write.
+ * ADANERF_EUNSUPPORTED, with nothing changed: a dense context (threshold 0: keys are implicit there); ADANERF_SAMPLER_PDF and
+ * _COARSE_FINE; a useNDC model (its samples live in NDC space).  While a limit is installed adanerf_set_selection refuses threshold 0.
+ * ADANERF_EINVAL: a map that is not 4-byte aligned.
+ * What it does not do: NDC models; dense, PDF and coarse/fine contexts; selecting the top N among the visible bins only (the rule trims
+ * the selection the context made: a ray whose N best bins all lie behind the surface comes out empty); limits inside the temporal and
+ * reprojection stages (their depth is the volume's own); an evaluator mode. */
+int adanerf_set_depth_limit(adanerf_ctx* ctx, const float* d_limit_zc);
+
+/* The second half of hybrid rendering: per pixel t = 1 - acc (one fp32 subtraction); !(t > 0) gives t = 0 (a NaN too); t > 1 gives t = 1;
+ * t == 0: out = rgb, the bits copied (a NaN in the behind image cannot leak); otherwise out_c = rgb_c + t * behind_c, a product, then a
+ * sum, each rounded to fp32.
+ *   d_rgb [n,3] fp32 / d_acc [n] fp32: d_rgb_f32_out and the acc_map of a render under a depth limit; d_behind_rgb [n,3] fp32: the
+ *   rasterised colour (anything where the limit is +inf: acc decides what shows)
+ *   d_out_rgb [n,3] fp32 or NULL, may be d_rgb itself; d_out_rgba8 [n] uchar4 or NULL, adanerf_resolve_mean's byte contract
+ * One launch on the context's stream, no host synchronisation; independent of the context's frame size (as adanerf_accumulate is);
+ * n == 0 does nothing.  Measured: 5.4 us for 640 000 pixels with the RGBA8 output (profiles/depth_limit_measured.md).
+ * ADANERF_EINVAL, with nothing written: a NULL input; both outputs NULL; n < 0 or n * 3 beyond 2^31 - 1; a pointer that is not 4-byte
+ * aligned; an output overlapping an input (only d_out_rgb == d_rgb is legal) or the other output. */
+int adanerf_blend_behind(adanerf_ctx* ctx, const float* d_rgb, const float* d_acc, const float* d_behind_rgb, int32_t n, float* d_out_rgb,
+                         void* d_out_rgba8);
+
 /* De-interleaves the gathered shard payloads ([shard_world][rays_local_max] uchar4, rank-major)
  * into the full row-major image [h*w] uchar4. */
 int adanerf_assemble_strips(adanerf_ctx* ctx, const void* d_gathered, void* d_image_out);
@@ -511,6 +561,14 @@ int adanerf_compact_guarded(adanerf_ctx* ctx, const float* d_oracle_approx, cons
 int adanerf_compact_budget(adanerf_ctx* ctx, const float* d_oracle, int32_t n_rays, int32_t n_max, float thr, const uint8_t* d_n_map,
                            const float* d_thr_map, int32_t* d_ray_offsets, int32_t* d_ray_counts, uint32_t* d_sample_key,
                            float* d_sample_w, int32_t* d_total);
+
+/* adanerf_compact with a depth limit, for tests: the selection at (n_max, thr), then the trim of ray r to the entries with zc < d_limit_zc[r]
+ * (the rule of adanerf_set_depth_limit, with d_rays [n_rays,8] the ray records -- 16-byte aligned --, pos / rot_c2w the pose, and the
+ * context's depth table in force), then the compaction.  thr > 0.  Honours ADANERF_FLAG_WAVE_SELECT and n_max > 16 as adanerf_compact
+ * does.  Outputs as adanerf_compact, with d_ray_counts 0..n_max. */
+int adanerf_compact_depth_limit(adanerf_ctx* ctx, const float* d_oracle, int32_t n_rays, int32_t n_max, float thr, const float* d_rays,
+                                const float* d_limit_zc, const float pos[3], const float rot_c2w[9], int32_t* d_ray_offsets,
+                                int32_t* d_ray_counts, uint32_t* d_sample_key, float* d_sample_w, int32_t* d_total);
 
 /* Calibrates the band of ADANERF_SAMPLING_GUARDED for the loaded model: n_poses cameras drawn inside the view cell
  * (positions uniform in 90 % of it, any orientation; seeded), 64 x 64 rays covering the field of view each, through both the
@@ -869,7 +927,7 @@ enum {
   ADANERF_BUF_RAYS = 0,        /* [batch,8] fp32 */
   ADANERF_BUF_ORACLE = 1,      /* [batch,128] fp32 */
   ADANERF_BUF_RAY_OFFSETS = 2, /* [batch] int32 */
-  ADANERF_BUF_RAY_COUNTS = 3,  /* [batch] int32 */
+  ADANERF_BUF_RAY_COUNTS = 3,  /* [batch] int32; 0..N under adanerf_set_depth_limit */
   ADANERF_BUF_SAMPLE_KEY = 4,  /* [S] uint32; not written in dense mode (threshold 0): sample i is ray i >> 7, bin i & 127 */
   ADANERF_BUF_SAMPLE_W = 5,    /* [S] fp32; not written in dense mode: the kept values are ADANERF_BUF_ORACLE itself */
   ADANERF_BUF_RAW = 6,         /* [S,4] fp32 */
@@ -915,6 +973,20 @@ int adanerf_host_depth_table(const char* model_dir, const adanerf_options* opt, 
  * j = k / s, *dx = (2 i + 1 - s) / (2 s), *dy alike from j, computed in double and cast to float.  s in 1..8, k in 0..s*s-1, non-NULL
  * outputs; anything else returns ADANERF_EINVAL.  s == 1 gives (0, 0); the offsets of a grid sum to 0 on either axis. */
 int adanerf_host_subpixel_grid(int32_t s, int32_t k, float* dx, float* dy);
+
+/* An occluder without a rasteriser, for both hosts and the tests: the camera-space depth (the zc of adanerf_set_depth_limit) of a sphere
+ * for every pixel of a width x height frame with pixel pitch 1 and focal length `focal` (adanerf_info.focal), seen from pos / rot_c2w
+ * (conventions of adanerf_set_camera).  zc_out [height*width] fp32, row-major; a pixel whose ray misses the sphere gets +inf.
+ * Everything in float64, each step one rounded operation in this order, never fused; the cast to float comes last:
+ *   e_i = center_i - pos_i;  c_k = (R[k] e_0 + R[3+k] e_1) + R[6+k] e_2 (the centre in camera space, R^T e);
+ *   g = ((c_0 c_0 + c_1 c_1) + c_2 c_2) - radius radius
+ *   pixel (x, y): vx = ((x + 0.5) - 0.5 width) / focal, vy = -(((y + 0.5) - 0.5 height) / focal), vz = -1 -- the inverse of adanerf_reproject's
+ *   projection; a = (vx vx + vy vy) + 1;  b = (vx c_0 + vy c_1) - c_2;  disc = b b - a g
+ *   disc >= 0: s = sqrt(disc), t0 = (b - s) / a, t1 = (b + s) / a; zc = t0 if t0 > 0, else t1 if t1 > 0 -- the smallest root t > 0 of
+ *   |t v - c|^2 = radius^2, which is zc because vz = -1.  Otherwise (and with !(disc >= 0)) +inf.
+ * ADANERF_EINVAL: a NULL pointer; a side outside 1..16384; a value that is not finite; radius <= 0; focal <= 0. */
+int adanerf_host_sphere_zc(int32_t width, int32_t height, float focal, const float pos[3], const float rot_c2w[9], const float center[3],
+                           float radius, float* zc_out);
 
 #ifdef __cplusplus
 }
