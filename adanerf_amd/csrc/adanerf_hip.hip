@@ -2128,6 +2128,52 @@ int adanerf_blend_behind(adanerf_ctx* c, const float* d_rgb, const float* d_acc,
   HIP_RETURN(c, hipGetLastError());
 }
 
+int adanerf_foveate_density(adanerf_ctx* c, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* stride, uint8_t* d_mask) {
+  if (!c) return ADANERF_EINVAL;
+  if (!d_mask) return fail(c, ADANERF_EINVAL, "adanerf_foveate_density: NULL mask");
+  DensityRule f;
+  if (const char* why = density_rule_fill(gaze_x, gaze_y, n_rings, radius_px, stride, &f)) return fail(c, ADANERF_EINVAL, std::string("adanerf_foveate_density: ") + why);
+  if (c->ms.rg.world != 1) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_foveate_density: whole frames only (shard_world must be 1): the reconstruction reads a pixel's neighbours");
+  BIND(c);
+  const int w = c->ms.info.width, h = c->ms.info.height;
+  const int64_t groups = (static_cast<int64_t>(w) * h + 3) / 4;      // four pixels per thread
+  if (groups <= 0) return ADANERF_OK;
+  hipLaunchKernelGGL(density_mask_kernel, dim3(static_cast<unsigned>((groups + 255) / 256)), dim3(256), 0, c->stream, f, w, h,
+                     (reinterpret_cast<uintptr_t>(d_mask) & 3) == 0 ? 1 : 0, d_mask);
+  HIP_RETURN(c, hipGetLastError());
+}
+
+int adanerf_fill_density(adanerf_ctx* c, const uint8_t* d_mask, int32_t width, int32_t height, float* d_rgb, float* d_depth_map, float* d_acc_map, void* d_rgba8,
+                         int32_t* unfilled_out) {
+  if (!c) return ADANERF_EINVAL;
+  if (!d_mask || !d_rgb) return fail(c, ADANERF_EINVAL, "adanerf_fill_density: NULL mask or d_rgb");
+  if (width < 1 || height < 1 || width > kPresentMaxSide || height > kPresentMaxSide)
+    return fail(c, ADANERF_EINVAL, "adanerf_fill_density: every side must be in 1.." + std::to_string(kPresentMaxSide));
+  if ((reinterpret_cast<uintptr_t>(d_rgb) | reinterpret_cast<uintptr_t>(d_depth_map) | reinterpret_cast<uintptr_t>(d_acc_map) | reinterpret_cast<uintptr_t>(d_rgba8)) & 3)
+    return fail(c, ADANERF_EINVAL, "adanerf_fill_density: fp32 and uchar4 images must be 4-byte aligned");
+  const size_t n = static_cast<size_t>(width) * static_cast<size_t>(height);
+  const void* const img[5] = {d_mask, d_rgb, d_depth_map, d_acc_map, d_rgba8};
+  const size_t img_bytes[5] = {n, n * 3 * sizeof(float), n * sizeof(float), n * sizeof(float), n * 4};
+  for (int i = 0; i < 5; ++i)
+    for (int j = i + 1; j < 5; ++j)
+      if (img[i] && img[j] && ranges_overlap(img[i], img_bytes[i], img[j], img_bytes[j]))
+        return fail(c, ADANERF_EINVAL, "adanerf_fill_density: the images overlap one another or the mask");
+  BIND(c);
+  if (!c->reproj_holes.p) {      // the counter shared with adanerf_reproject and the temporal stages: all run on the context's stream
+    if (int rc = dev_alloc(c, &c->reproj_holes, 64)) return rc;
+  }
+  int32_t* unfilled = reinterpret_cast<int32_t*>(c->reproj_holes.p);
+  HIP_TRY(c, hipMemsetAsync(unfilled, 0, sizeof(int32_t), c->stream));
+  const DensityFill d{d_mask, d_rgb, d_depth_map, d_acc_map, static_cast<uchar4*>(d_rgba8), unfilled};
+  hipLaunchKernelGGL(density_fill_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, c->stream, d, width, height);
+  HIP_TRY(c, hipGetLastError());
+  if (unfilled_out) {
+    HIP_TRY(c, hipMemcpyAsync(unfilled_out, unfilled, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return ADANERF_OK;
+}
+
 int adanerf_set_stream(adanerf_ctx* c, void* hip_stream) {
   BIND(c);
   HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -14,6 +14,7 @@
 //   N7        upsample_depth_kernel / upsample_resolve_kernel   a frame rendered at w x h resolved into a history of s w x s h (temporal upsampling)
 //   N8        mask_bits_kernel / mask_scatter_kernel   a byte mask as bit words for refine_list_kernel; the pixels of a listed batch to their places (masked rendering)
 //   N9        blend_behind_kernel   the rasterised colour behind a depth-limited frame, through the transmittance that is left (hybrid rendering)
+//   N10       density_mask_kernel / density_fill_kernel   the render mask of a gaze and rings of strides; the pixels between the rendered ones, bilinear (foveated ray density)
 // plus explicit-feature debug kernels (ray_features_kernel, shade_features_kernel) that materialise
 // what the reference launchers wrote to memory, for parity tests only.
 // The code lives in one header per stage; this file includes them all.
@@ -37,3 +38,4 @@
 #include "k_mask.hip.hpp"
 #include "k_depth_limit.hip.hpp"
 #include "k_blend.hip.hpp"
+#include "k_density.hip.hpp"

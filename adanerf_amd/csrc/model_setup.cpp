@@ -1,5 +1,6 @@
 // See model_setup.hpp.  Also the three entry points of the C ABI that never touch a device.
 #include "model_setup.hpp"
+#include "density_rule.hpp"
 
 #include <cstdio>
 #include <cstring>
@@ -476,6 +477,17 @@ int adanerf_host_sphere_zc(int32_t width, int32_t height, float focal, const flo
       zc_out[static_cast<size_t>(y) * width + x] = out;
     }
   }
+  return ADANERF_OK;
+}
+
+int adanerf_host_density_mask(int32_t width, int32_t height, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* stride,
+                              uint8_t* mask_out) {
+  if (!mask_out) return fail(ADANERF_EINVAL, "adanerf_host_density_mask: NULL mask");
+  if (width < 1 || width > 16384 || height < 1 || height > 16384) return fail(ADANERF_EINVAL, "adanerf_host_density_mask: width and height must be in 1..16384");
+  DensityRule f;
+  if (const char* why = density_rule_fill(gaze_x, gaze_y, n_rings, radius_px, stride, &f)) return fail(ADANERF_EINVAL, std::string("adanerf_host_density_mask: ") + why);
+  for (int y = 0; y < height; ++y)
+    for (int x = 0; x < width; ++x) mask_out[static_cast<size_t>(y) * width + x] = density_mask_byte(f, x, y, width, height);
   return ADANERF_OK;
 }
 

@@ -7,6 +7,7 @@ reference's second default metric (``metrics = ["flip", "psnr"]`` :613-615): the
     python -m adanerf_amd.evaluate <model_dir> <dataset_dir> [--set test] [--out DIR] [--video out.y4m] [--precision bf16]
                                    [--metrics psnr flip] [--sweep-thresholds T ...] [--sweep-samples N ...] [--sweep-scales S ...]
                                    [--reproject-stride K [--rerender holes|unsourced]] [--supersample S] [--present-filter nearest|linear|area]
+                                   [--fovea-density R:S[,R:S...],S]
 
 ``--sweep-thresholds`` / ``--sweep-samples`` render the set once per (N, threshold) of their cross product on ONE context
 (``NeuralRenderer.set_selection``: an AdaNeRF network is trained once and rendered at any sample budget) -- the two axes of a quality
@@ -25,6 +26,10 @@ and resolved on the GPU (``NeuralRenderer.render_supersampled``) and scored from
 dataset's anti-aliased ground truth.  ``--present-filter area`` makes the ``--sweep-scales`` presentation an exact area filter
 (``ADANERF_PRESENT_AREA``): the only sensible choice for scales above 1, where the default rule decimates.
 
+``--fovea-density SPEC`` scores, beside every full frame, the same pose rendered at a foveated ray density around a gaze at the frame
+centre (``NeuralRenderer.render_foveated``: the lattice of ``adanerf_foveate_density`` rendered, the pixels in between rebuilt by
+``adanerf_fill_density``), on the same context.
+
 Dataset layout (src/datasets.py:146-213, 361-365, 480-542): ``dataset_info.json`` (``resolution``,
 ``camera_angle_x``, ``view_cell_center``, ``view_cell_size`` ...), ``transforms_<set>.json`` with
 ``frames[i].file_path`` ("./test/00000") and ``frames[i].transform_matrix`` (4x4 camera-to-world; pose =
@@ -41,7 +46,7 @@ from typing import List, Optional
 import numpy as np
 
 from .png import read_png, write_png
-from .renderer import PRESENT_FILTERS, RERENDER_VALUES, SUPERSAMPLE_MAX, NeuralRenderer, Settings, parse_fovea
+from .renderer import PRESENT_FILTERS, RERENDER_VALUES, SUPERSAMPLE_MAX, NeuralRenderer, Settings, parse_fovea, parse_fovea_density
 
 
 def load_dataset(dataset_dir: str, set_name: str = "test"):
@@ -102,7 +107,7 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
              precision: str = "bf16", batch_size: int = -1, max_frames: int = 0, quiet: bool = False,
              video: Optional[str] = None, fps: int = 30, metrics=("psnr",), fovea=None, sweep_thresholds=None, sweep_samples=None, reproject_stride=None,
              supersample=None, present_filter=None, temporal=None, temporal_still=None, temporal_upsample=None, temporal_upsample_frames=None,
-             rerender=None, sweep_scales=None):
+             rerender=None, fovea_density=None, sweep_scales=None):
     """metrics: "psnr" (always reported where a ground-truth image exists) and / or "flip": each record gains ``flip``, the summary
     ``mean_flip``, and with out_dir the error map is written as an 8-bit greyscale ``%05d_flip.png``.
 
@@ -156,9 +161,20 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
 
     fovea (``R:N:T[,R:N:T...],N:T`` or what renderer.parse_fovea makes of it, or None): every frame is rendered with per-ray budgets around a
     gaze at the centre of the rendered frame (radii in its pixels).  Records and summary keep their shape: PSNR / FLIP / samples per ray are
-    those of the foveated frames -- the quality-against-cost table of a foveation setting."""
+    those of the foveated frames -- the quality-against-cost table of a foveation setting.
+
+    fovea_density (``R:S[,R:S...],S`` or what renderer.parse_fovea_density makes of it, or None): foveated ray density beside the full
+    frames.  After a pose's full render the same pose is rendered at the density of a gaze at the frame centre and reconstructed
+    (NeuralRenderer.render_foveated), and that fp32 frame is scored too.  Records gain ``psnr_foveated`` / ``mse_foveated``,
+    ``rendered_fraction`` (rays rendered, of w h), ``ms_foveated`` (the masked render's own time; the fill is not in it) and, with "flip",
+    ``flip_foveated``; the summary ``mean_psnr_foveated``, ``mean_rendered_fraction``, ``mean_ms_foveated`` and ``mean_flip_foveated``;
+    out_dir gets ``%05d_foveated.png``.  The plain keys are those of a run without the option.  Not with fovea (the masked render refuses
+    budget maps), reproject_stride, supersample, sweep_scales, temporal, temporal_still or temporal_upsample."""
     if isinstance(fovea, str):
         fovea = parse_fovea(fovea)
+    if fovea_density is not None:
+        fovea_density = parse_fovea_density(fovea_density) if isinstance(fovea_density, str) else parse_fovea_density(
+            ",".join(":".join(str(int(v)) for v in ring) for ring in fovea_density))
     unknown = sorted(set(metrics) - {"psnr", "flip"})
     if unknown:
         raise ValueError("unknown metrics %s (known: psnr, flip)" % unknown)
@@ -196,6 +212,9 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     if tu and (stride or ss or sweep_scales or ta):
         raise ValueError("temporal_upsample renders at the dataset's size / S and resolves at the dataset's size: not together with "
                          "reproject_stride, supersample, sweep_scales, temporal or temporal_still")
+    if fovea_density and (fovea or stride or ss or sweep_scales or ta or tu):
+        raise ValueError("fovea_density renders a lattice of whole frames at the dataset's resolution without budget maps: not together with "
+                         "fovea, reproject_stride, supersample, sweep_scales, temporal, temporal_still or temporal_upsample")
     if present_filter not in PRESENT_FILTERS:
         raise ValueError("present_filter must be None, 'nearest', 'linear' or 'area', got %r" % (present_filter,))
     want_flip = "flip" in metrics
@@ -213,7 +232,7 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
         vid = Y4mWriter(video, w, h, fps) if video else None
         d_ref = r.empty((w * h, 3), np.float32) if want_flip else None
         d_map = r.empty((w * h,), np.float32) if want_flip and out_dir else None
-        d_pres = r.empty((w * h, 3), np.float32) if want_flip and (sweep_scales or stride or ta or tu) else None
+        d_pres = r.empty((w * h, 3), np.float32) if want_flip and (sweep_scales or stride or ta or tu) else None      # (the foveated frame is scored in place)
         if stride:
             r.enable_reprojection()
         if ta:
@@ -232,6 +251,8 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                 r.foveate((0.5 * rw, 0.5 * rh), fovea)
             if ta:
                 r.reset_temporal()      # a pass over the set is one sequence
+            if fovea_density:      # again for every setting: the mask belongs to the frame size
+                r.foveate_density((0.5 * rw, 0.5 * rh), fovea_density)
             for i, fr in enumerate(frames):
                 ref = None
                 warped = bool(stride) and i % stride != 0
@@ -297,6 +318,16 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                             rec.update(flip_upsampled=r.flip_device(d_pres.upload(u_rgb), d_ref, w, h))
                     if out_dir:
                         write_png(os.path.join(out_dir, "%05d_upsampled.png" % i), u_rgba[:, :3].reshape(h, w, 3))
+                if fovea_density:      # the same pose at the gaze's ray density, reconstructed; after the full frame's scores: it reuses its images
+                    f_rgb, f_rgba, f_rendered, f_st = r.render_foveated()
+                    rec.update(rendered_fraction=f_rendered / float(w * h), ms_foveated=f_st.ms_total)
+                    if ref is not None:
+                        f_mse = float(np.mean((f_rgb.astype(np.float64) - ref) ** 2))
+                        rec.update(mse_foveated=f_mse, psnr_foveated=psnr_from_mse(f_mse))
+                        if want_flip:
+                            rec.update(flip_foveated=r.flip_device(r._o_rgb, d_ref, w, h))
+                    if out_dir:
+                        write_png(os.path.join(out_dir, "%05d_foveated.png" % i), f_rgba[:, :3].reshape(h, w, 3))
                 if out_dir:
                     write_png(os.path.join(out_dir, "%05d.png" % i), rgba[:, :3].reshape(h, w, 3))
                 if vid:
@@ -361,6 +392,13 @@ def summarise(results: List[dict], want_flip: bool) -> dict:
         if want_flip:
             summary["mean_flip_temporal"] = float(np.mean([x["flip_temporal"] for x in part])) if part else None
         summary["mean_rejected_fraction"] = float(np.mean([x["rejected_fraction"] for x in results if "rejected_fraction" in x]))
+    if any("rendered_fraction" in x for x in results):      # fovea_density: the reconstructed frames beside the full ones
+        part = [x for x in results if "psnr_foveated" in x]
+        summary["mean_psnr_foveated"] = float(np.mean([x["psnr_foveated"] for x in part])) if part else None
+        if want_flip:
+            summary["mean_flip_foveated"] = float(np.mean([x["flip_foveated"] for x in part])) if part else None
+        summary["mean_rendered_fraction"] = float(np.mean([x["rendered_fraction"] for x in results if "rendered_fraction" in x]))
+        summary["mean_ms_foveated"] = float(np.mean([x["ms_foveated"] for x in results if "ms_foveated" in x]))
     return summary
 
 
@@ -411,6 +449,11 @@ def build_parser():
     ap.add_argument("--fovea", type=parse_fovea, default=None, metavar="R:N:T[,R:N:T...],N:T",
                     help="per-ray sample budgets around a gaze at the image centre: rings (radius px : N : threshold), then the entry outside "
                          "them; PSNR / FLIP / samples per ray are then those of the foveated frames")
+    ap.add_argument("--fovea-density", default=None, metavar="R:S[,R:S...],S",
+                    help="foveated ray density beside the full frames, gaze at the frame centre: rings (radius px : stride 1|2|4|8), then the "
+                         "stride outside them; every pose is rendered once more on that lattice and reconstructed (adanerf_foveate_density / "
+                         "adanerf_render_masked / adanerf_fill_density); the summary gains mean_psnr_foveated / mean_rendered_fraction / "
+                         "mean_ms_foveated (and mean_flip_foveated with --metrics flip)")
     return ap
 
 
@@ -426,13 +469,21 @@ def main(argv=None):
     if a.temporal_upsample is not None and (a.temporal is not None or a.temporal_still is not None or a.supersample is not None or
                                             a.reproject_stride is not None or a.sweep_scales):
         ap.error("--temporal-upsample cannot be combined with --temporal, --temporal-still, --supersample, --reproject-stride or --sweep-scales")
+    if a.fovea_density is not None:
+        try:
+            parse_fovea_density(a.fovea_density)
+        except ValueError as e:
+            ap.error(str(e))
+        if (a.fovea is not None or a.reproject_stride is not None or a.supersample is not None or a.sweep_scales or a.temporal is not None or
+                a.temporal_still is not None or a.temporal_upsample is not None):
+            ap.error("--fovea-density cannot be combined with --fovea, --reproject-stride, --supersample, --sweep-scales or the --temporal options")
     if a.temporal_upsample_frames is not None and a.temporal_upsample is None:
         ap.error("--temporal-upsample-frames goes with --temporal-upsample")
     summary, _ = evaluate(a.model_dir, a.dataset_dir, a.set, a.out, a.precision, a.batch_size, a.max_frames, video=a.video, fps=a.fps,
                           metrics=tuple(a.metrics), sweep_thresholds=a.sweep_thresholds, sweep_samples=a.sweep_samples, sweep_scales=a.sweep_scales,
                           fovea=a.fovea, reproject_stride=a.reproject_stride, rerender=a.rerender, supersample=a.supersample, present_filter=a.present_filter,
                           temporal=a.temporal, temporal_still=a.temporal_still, temporal_upsample=a.temporal_upsample,
-                          temporal_upsample_frames=a.temporal_upsample_frames)
+                          temporal_upsample_frames=a.temporal_upsample_frames, fovea_density=a.fovea_density)
     print(json.dumps(summary))
 
 

@@ -24,7 +24,7 @@ NeuralRenderer::~NeuralRenderer() {
   if (ctx) {
     if (d_gathered) adanerf_free(ctx, d_gathered);
     if (d_frame) adanerf_free(ctx, d_frame);
-    for (void* p : {d_depth, d_acc, d_warp, d_wmask, d_rgb, d_sum, d_hist[0][0], d_hist[0][1], d_hist[0][2], d_hist[1][0], d_hist[1][1], d_hist[1][2], d_up, d_limit, d_behind})
+    for (void* p : {d_depth, d_acc, d_warp, d_wmask, d_rgb, d_sum, d_hist[0][0], d_hist[0][1], d_hist[0][2], d_hist[1][0], d_hist[1][1], d_hist[1][2], d_up, d_limit, d_behind, d_dmask})
       if (p) adanerf_free(ctx, p);
     if (d_window) adanerf_free(ctx, d_window);
     adanerf_destroy(ctx);
@@ -219,6 +219,17 @@ bool NeuralRenderer::allocFrameBuffers() {
     }
     if (adanerf_set_aux_outputs(ctx, static_cast<float*>(d_depth), static_cast<float*>(d_acc)) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
   }
+  if (!settings.density_stride.empty()) {      // the mask and the fp32 frame belong to the frame size
+    const size_t n = static_cast<size_t>(info_.width) * info_.height;
+    fovea_pending = true;
+    void** bufs[] = {&d_rgb, &d_dmask};
+    const size_t bytes[] = {n * 12, n};
+    for (int k = 0; k < 2; ++k) {
+      if (*bufs[k] && adanerf_free(ctx, *bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+      *bufs[k] = nullptr;
+      if (adanerf_malloc(ctx, bytes[k], bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+    }
+  }
   if (settings.supersample > 1) {
     for (void** p : {&d_rgb, &d_sum}) {
       if (*p && adanerf_free(ctx, *p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
@@ -333,6 +344,36 @@ bool NeuralRenderer::applyFovea() {
   return true;
 }
 
+// --fovea-density: the mask of the gaze and the size in force, filled on the device; again after a "gaze" token and after a "size" token
+// (allocFrameBuffers makes the buffer for the new size).  Until a "gaze" token the gaze is the centre of the frame in force.
+bool NeuralRenderer::applyFoveaDensity() {
+  if (settings.density_stride.empty() || !fovea_pending || !ctx) return true;
+  fovea_pending = false;
+  if (!gaze_set) {
+    gaze_x = 0.5f * static_cast<float>(info_.width);
+    gaze_y = 0.5f * static_cast<float>(info_.height);
+  }
+  if (adanerf_foveate_density(ctx, gaze_x, gaze_y, static_cast<int32_t>(settings.density_radius.size()), settings.density_radius.data(),
+                              settings.density_stride.data(), static_cast<uint8_t*>(d_dmask)) != ADANERF_OK)
+    return err = adanerf_last_error(ctx), false;
+  return true;
+}
+
+// --fovea-density: the lattice of the mask rendered into d_frame / d_rgb (adanerf_render_masked), the pixels in between rebuilt from it in
+// both (adanerf_fill_density).  *st describes the rendered rays.
+bool NeuralRenderer::renderFoveated(adanerf_stats* st) {
+  int32_t m = 0;
+  if (adanerf_render_masked(ctx, static_cast<const uint8_t*>(d_dmask), 1u, d_frame, static_cast<float*>(d_rgb), st, &m) != ADANERF_OK ||
+      adanerf_fill_density(ctx, static_cast<const uint8_t*>(d_dmask), info_.width, info_.height, static_cast<float*>(d_rgb), nullptr, nullptr, d_frame, nullptr) != ADANERF_OK ||
+      adanerf_sync(ctx) != ADANERF_OK) {
+    err = adanerf_last_error(ctx);
+    return false;
+  }
+  s_density_rendered += m;
+  if (settings.log_camera) std::printf("foveated %d rendered %d of %u\n", sample_count, static_cast<int>(m), settings.total_size);
+  return true;
+}
+
 bool NeuralRenderer::render() {
   float rot[9];
   camera.getRotMatrix(rot);
@@ -353,6 +394,7 @@ bool NeuralRenderer::render() {
     taa_have = false;         // and --taa does not blend it with frames of the old one
   }
   if (!applyFovea()) return false;
+  if (!applyFoveaDensity()) return false;
   if (adanerf_set_camera(ctx, camera.getPosition(), rot) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;
@@ -414,6 +456,8 @@ bool NeuralRenderer::render() {
     if (!renderTemporal(&st, rot)) return false;
   } else if (!settings.occluders.empty()) {
     if (!renderHybrid(&st, rot)) return false;
+  } else if (!settings.density_stride.empty()) {
+    if (!renderFoveated(&st)) return false;
   } else if (settings.supersample > 1 ? !renderSupersampled(&st) : adanerf_render(ctx, d_frame, nullptr, &st) != ADANERF_OK) {
     if (settings.supersample <= 1) err = adanerf_last_error(ctx);
     return false;
@@ -633,12 +677,14 @@ void NeuralRenderer::logInterval() {
   if (settings.taau_scale > 0)
     std::cout << ", taau rejected: " << s_rejected / static_cast<double>(logging_interval) / settings.total_size / (settings.taau_scale * settings.taau_scale);
   if (settings.reproject > 1) std::cout << ", holes: " << s_holes / static_cast<double>(std::max(s_warped, 1)) << " (" << s_warped << " warped frames)";
+  if (!settings.density_stride.empty()) std::cout << ", rendered fraction: " << s_density_rendered / static_cast<double>(logging_interval) / settings.total_size;
   if (!settings.rerender.empty()) std::cout << ", rerendered: " << s_rerendered / static_cast<double>(std::max(s_warped, 1));
   std::cout << std::endl;
   s_inference1 = s_inference2 = s_fc2 = s_rm = s_total = 0;
   s_num_total_samples = 0;
   s_holes = 0;
   s_rerendered = 0;
+  s_density_rendered = 0;
   s_rejected = 0;
   s_rendered = s_warped = 0;
 }

@@ -41,7 +41,7 @@ class NeuralRenderer {
     *h = want_height;
     return size_pending;
   }
-  // --fovea: the gaze point from the next frame on (script token "gaze X Y", pixels); every context's maps are filled again in render()
+  // --fovea / --fovea-density: the gaze point from the next frame on (script token "gaze X Y", pixels); the maps / the mask are filled again in render()
   void setGaze(float x, float y) {
     gaze_x = x;
     gaze_y = y;
@@ -107,6 +107,12 @@ class NeuralRenderer {
   bool occ_have = false;             // d_limit / d_behind hold the spheres as seen from occ_pos / occ_rot at the size in force
   float occ_pos[3] = {0, 0, 0}, occ_rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   bool renderHybrid(adanerf_stats* st, const float rot[9]);   // the map refilled if the camera or the size moved, one render under it, blended into d_frame
+  // --fovea-density: the mask of the gaze and the size in force (uint8 [h*w]; 0 = rendered, else the pixel's stride); the fp32 frame (d_rgb)
+  // the lattice is rendered into and the pixels in between are rebuilt in, together with d_frame
+  void* d_dmask = nullptr;
+  long long s_density_rendered = 0;  // rays rendered in the running interval's frames
+  bool applyFoveaDensity();          // the mask filled again: at start, after "gaze", after "size" (fovea_pending, shared with --fovea: the two are exclusive)
+  bool renderFoveated(adanerf_stats* st);   // adanerf_render_masked over the lattice, adanerf_fill_density for the rest, into d_frame
   void* d_window = nullptr;          // --write-window: uchar4 [window_height*window_width], the frame as adanerf_present shows it
   int world_ = 1, strip_rows_ = 8;   // share layout chosen at init; a live context keeps its strip height
   bool allocFrameBuffers();          // d_frame, d_gathered, d_payload for the size in info_ (again after a size change)

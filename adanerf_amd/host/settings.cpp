@@ -14,13 +14,15 @@ const char* Settings::usage() {
          "               [--samples N] [--threshold T] [--oracle]\n"
          "               [--fovea R:N:T[,R:N:T...],N:T]     per-ray budgets: rings around the gaze (radius px : N : threshold), then the\n"
          "                                                  entry outside them; the gaze starts at the frame centre\n"
+         "               [--fovea-density R:S[,R:S...],S]   foveated ray density: rings around the gaze (radius px : stride 1|2|4|8), then the\n"
+         "                                                  stride outside them; every S-th pixel per axis is rendered, the rest rebuilt\n"
          "               [--occluder cx,cy,cz,r[,R,G,B]]    hybrid rendering (repeatable): every ray stops at the nearest of these spheres and its\n"
          "                                                  flat colour (0..1, default 0.5 grey) shows through what the volume in front leaves\n"
          "               [--script FILE] [--log-camera] [--dry-run]     input replay: one line of events per frame\n"
          "                                                              (+w -w ... b+ x y  b- x y  m x y; n <int> / thr <float>:\n"
          "                                                              sample budget N / threshold from that frame on;\n"
          "                                                              size <W> <H>: frame size from that frame on, the window stays;\n"
-         "                                                              gaze <X> <Y>: the --fovea gaze point, in pixels;\n"
+         "                                                              gaze <X> <Y>: the --fovea / --fovea-density gaze, px;\n"
          "                                                              cut: --taa / --taau start a new history with that frame)\n"
          "               [--reproject K]      of every K frames render the first and warp it to the camera of the next K - 1 (depth\n"
          "                                    reprojection, holes filled from their neighbours); -w / --write-window write what was shown\n"
@@ -75,6 +77,42 @@ bool Settings::parseFovea(const std::string& spec, std::vector<int>* radius, std
     const float t = std::strtof(f.back().c_str(), &end);
     if (end == f.back().c_str() || *end != 0 || t != t) return bad("a threshold is not a number");
     thr->push_back(t);
+  }
+  if (radius->size() > 8) return bad("at most 8 rings");
+  return true;
+}
+
+// R:S[,R:S...],S -- every field read whole; what adanerf_foveate_density would refuse is refused here, with the spec in the message
+bool Settings::parseFoveaDensity(const std::string& spec, std::vector<int>* radius, std::vector<int>* stride, std::string* err) {
+  auto bad = [&](const char* why) {
+    *err = "--fovea-density " + spec + ": " + why + " (expected R:S[,R:S...],S)";
+    return false;
+  };
+  radius->clear();
+  stride->clear();
+  std::vector<std::string> parts(1);
+  for (char ch : spec) {
+    if (ch == ',') parts.emplace_back();
+    else parts.back() += ch;
+  }
+  for (size_t k = 0; k < parts.size(); ++k) {
+    std::vector<std::string> f(1);
+    for (char ch : parts[k]) {
+      if (ch == ':') f.emplace_back();
+      else f.back() += ch;
+    }
+    const bool last = k + 1 == parts.size();
+    if (f.size() != (last ? 1u : 2u)) return bad(last ? "the last entry must be S" : "a ring must be R:S");
+    for (size_t j = 0; j < f.size(); ++j) {
+      char* end = nullptr;
+      const long v = std::strtol(f[j].c_str(), &end, 10);
+      if (end == f[j].c_str() || *end != 0) return bad("not an integer");
+      const bool is_radius = !last && j == 0;
+      if (is_radius && (v < 0 || v > 0x7fffffffl || (!radius->empty() && v <= radius->back()))) return bad("radii must be >= 0 and strictly ascending");
+      if (!is_radius && v != 1 && v != 2 && v != 4 && v != 8) return bad("a stride must be 1, 2, 4 or 8");
+      if (!is_radius && !stride->empty() && v < stride->back()) return bad("strides must not decrease outward");
+      (is_radius ? radius : stride)->push_back(static_cast<int>(v));
+    }
   }
   if (radius->size() > 8) return bad("at most 8 rings");
   return true;
@@ -180,6 +218,9 @@ bool Settings::init(int argc, char** argv, std::string* err) {
     } else if (a == "--fovea") {
       if (!need(i, 1)) return false;
       if (!parseFovea(argv[++i], &fovea_radius, &fovea_n, &fovea_thr, err)) return false;
+    } else if (a == "--fovea-density") {
+      if (!need(i, 1)) return false;
+      if (!parseFoveaDensity(argv[++i], &density_radius, &density_stride, err)) return false;
     } else if (a == "--occluder") {
       if (!need(i, 1)) return false;
       Occluder o;
@@ -308,6 +349,19 @@ bool Settings::init(int argc, char** argv, std::string* err) {
            : render_oracle ? "--occluder limits rendered frames; not with --oracle"
                            : "--occluder: the temporal and reprojection stages take no depth limit; not with --reproject, --supersample, --taa or --taau";
     return false;
+  }
+  if (!density_stride.empty()) {      // adanerf_render_masked's own limits, and the stages that take whole rendered frames
+    const char* why = !fovea_n.empty() ? "a budget map is indexed by frame position and the masked render refuses it; not with --fovea"
+                      : (gpus > 1 || sub_shares > 1) ? "the reconstruction reads a pixel's neighbours in whole frames of one context; use it with --gpus 1 and --sub-shares 1"
+                      : (sampling == "fp16" || sampling == "fp32") ? "the masked render needs the split or guarded sampling mode; not with --sampling fp16 or fp32"
+                      : render_oracle ? "it reconstructs rendered frames; not with --oracle"
+                      : (reproject > 1 || supersample > 1 || taa_alpha > 0.f || taau_scale > 0 || !occluders.empty())
+                          ? "the lattice is not coupled to the other stages; not with --reproject, --supersample, --taa, --taau or --occluder"
+                          : nullptr;
+    if (why) {
+      *err = std::string("--fovea-density: ") + why;
+      return false;
+    }
   }
   total_size = width * height;
   if (sampling.empty()) sampling = "split";      // exact by construction; guarded / fp16 are opt-in (the default rule)

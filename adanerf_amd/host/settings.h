@@ -37,6 +37,12 @@ class Settings {
   std::vector<int> fovea_radius, fovea_n;
   std::vector<float> fovea_thr;
   static bool parseFovea(const std::string& spec, std::vector<int>* radius, std::vector<int>* n, std::vector<float>* thr, std::string* err);
+  // --fovea-density R:S[,R:S...],S: foveated ray density around the same gaze point (adanerf_foveate_density / adanerf_render_masked /
+  // adanerf_fill_density): up to 8 rings, radius in whole pixels strictly ascending, each with the stride S (1, 2, 4 or 8: every S-th pixel per
+  // axis is rendered, the rest rebuilt from them) of the pixels inside it, never decreasing outward; the last entry is the stride outside every
+  // ring.  Empty density_stride: off
+  std::vector<int> density_radius, density_stride;
+  static bool parseFoveaDensity(const std::string& spec, std::vector<int>* radius, std::vector<int>* stride, std::string* err);
   // --occluder cx,cy,cz,r[,R,G,B] (repeatable): hybrid rendering against sphere occluders -- the frame is rendered under the depth limit of
   // the spheres' camera-space depth (per-pixel minimum, adanerf_host_sphere_zc / adanerf_set_depth_limit) and the nearest sphere's flat colour
   // (0..1 per channel, default 0.5 grey) is let through with the transmittance left (adanerf_blend_behind).  Empty: off

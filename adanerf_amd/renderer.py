@@ -81,7 +81,8 @@ EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_las
            "adanerf_free", "adanerf_memcpy_h2d", "adanerf_memcpy_d2h", "adanerf_get_buffer",
            "adanerf_set_pixel_offset", "adanerf_get_pixel_offset", "adanerf_accumulate", "adanerf_resolve_mean", "adanerf_host_subpixel_grid", "adanerf_temporal_resolve",
            "adanerf_temporal_upsample", "adanerf_render_masked",
-           "adanerf_set_depth_limit", "adanerf_compact_depth_limit", "adanerf_blend_behind", "adanerf_host_sphere_zc"]
+           "adanerf_set_depth_limit", "adanerf_compact_depth_limit", "adanerf_blend_behind", "adanerf_host_sphere_zc",
+           "adanerf_foveate_density", "adanerf_fill_density", "adanerf_host_density_mask"]
 
 _lib = None
 
@@ -111,6 +112,9 @@ def load_library(path: Optional[str] = None):
     lib.adanerf_compact_depth_limit.argtypes = [vp, vp, i32, i32, C.c_float, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp, vp, vp, vp]
     lib.adanerf_blend_behind.argtypes = [vp, vp, vp, vp, i32, vp, vp]
     lib.adanerf_host_sphere_zc.argtypes = [i32, i32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float)]
+    lib.adanerf_foveate_density.argtypes = [vp, C.c_float, C.c_float, i32, C.POINTER(i32), C.POINTER(i32), vp]
+    lib.adanerf_fill_density.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(i32)]
+    lib.adanerf_host_density_mask.argtypes = [i32, i32, C.c_float, C.c_float, i32, C.POINTER(i32), C.POINTER(i32), vp]
     lib.adanerf_present.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32]
     lib.adanerf_set_pixel_offset.argtypes = [vp, C.c_float, C.c_float]
     lib.adanerf_get_pixel_offset.argtypes = [vp, C.POINTER(C.c_float)]
@@ -322,6 +326,60 @@ def parse_fovea(spec: str):
     return out
 
 
+DENSITY_STRIDES = (1, 2, 4, 8)
+
+
+def parse_fovea_density(spec: str):
+    """``R:S[,R:S...],S`` -> [(R, S), ..., (S,)]: concentric rings around the gaze (radius in whole pixels, strictly ascending, at most 8),
+    each with the stride S (1, 2, 4 or 8: every S-th pixel per axis is rendered) of the pixels inside it, then the stride of the pixels
+    outside every ring; strides never decrease outward.  The form adanerf_foveate_density / NeuralRenderer.foveate_density take.
+    ValueError on anything else."""
+    parts = [p.strip() for p in str(spec).split(",")]
+    if not parts or any(not p for p in parts):
+        raise ValueError("fovea density %r: expected R:S[,R:S...],S" % (spec,))
+    out = []
+    for k, p in enumerate(parts):
+        f = p.split(":")
+        last = k == len(parts) - 1
+        if len(f) != (1 if last else 2):
+            raise ValueError("fovea density %r: %r must be %s" % (spec, p, "S (the outside stride comes last)" if last else "R:S"))
+        try:
+            ints = [int(v) for v in f]
+        except ValueError:
+            raise ValueError("fovea density %r: %r is not %s" % (spec, p, "S" if last else "R:S")) from None
+        if ints[-1] not in DENSITY_STRIDES:
+            raise ValueError("fovea density %r: a stride must be 1, 2, 4 or 8" % (spec,))
+        if out and ints[-1] < out[-1][-1]:
+            raise ValueError("fovea density %r: strides must not decrease outward" % (spec,))
+        if not last and (ints[0] < 0 or ints[0] >= 1 << 31 or (out and ints[0] <= out[-1][0])):
+            raise ValueError("fovea density %r: radii must be >= 0 and strictly ascending" % (spec,))
+        out.append(tuple(ints))
+    if len(out) - 1 > FOVEA_MAX_RINGS:
+        raise ValueError("fovea density %r: at most %d rings" % (spec, FOVEA_MAX_RINGS))
+    return out
+
+
+def _density_arrays(rings):
+    rings = [tuple(r) for r in rings]
+    nr = len(rings) - 1
+    radius = (C.c_int32 * max(nr, 1))(*[int(r[0]) for r in rings[:-1]])
+    stride = (C.c_int32 * (nr + 1))(*[int(r[-1]) for r in rings])
+    return nr, radius, stride
+
+
+def density_mask(width: int, height: int, gaze_xy, rings) -> np.ndarray:
+    """The mask of adanerf_foveate_density on the host (adanerf_host_density_mask): [height*width] uint8, 0 = rendered, else the pixel's
+    stride.  ``rings`` as parse_fovea_density returns them, or its string.  No device needed.  ValueError on what the library refuses."""
+    if isinstance(rings, str):
+        rings = parse_fovea_density(rings)
+    nr, radius, stride = _density_arrays(rings)
+    ok = 1 <= int(width) <= 16384 and 1 <= int(height) <= 16384
+    out = np.empty(int(width) * int(height) if ok else 1, dtype=np.uint8)
+    if load_library().adanerf_host_density_mask(int(width), int(height), float(gaze_xy[0]), float(gaze_xy[1]), nr, radius, stride, out.ctypes.data) != 0:
+        raise ValueError("adanerf_host_density_mask(%r x %r, gaze %r, %r) refused" % (width, height, tuple(gaze_xy), rings))
+    return out
+
+
 def choose_sampling(settings, pos=None, rot_c2w=None, precision="bf16", frames: int = 6, warmup: int = 2, margin: float = DEFAULT_RULE_MARGIN, **kw):
     """The default rule per workload: renders `frames` frames of this model / frame size / threshold in the split mode (exact by construction) and in
     the guarded mode (same frames while its measured band holds) and returns ("guarded" | "split", record): guarded only if it is >= margin faster
@@ -404,6 +462,7 @@ class NeuralRenderer:
         self._tu_hist = None          # (index of the history's buffer set, pos, rot) of the last render_upsampled since then
         self._dl_in_force = None      # what the last set_depth_limit installed; render_hybrid puts it back
         self._aux_in_force = (None, None)   # (depth_map, acc_map) of the last set_aux_outputs, likewise
+        self._fd = None               # foveate_density(): (gaze, rings, width, height) the device mask _fd_mask was filled for
 
     # -- lifecycle -------------------------------------------------------------------------------
     def init(self) -> bool:
@@ -485,6 +544,7 @@ class NeuralRenderer:
         self._rp_frame = None      # a frame of the old size cannot be warped with the new size's ray generator
         self._ta_hist = None       # nor can a history of the old size be gathered from
         self._tu_hist = None
+        self._fd = None            # the density mask is per frame size: foveate_density() fills it again
         for name in ("_o_rgb", "_o_rgba"):
             if hasattr(self, name):
                 a = getattr(self, name)
@@ -550,6 +610,58 @@ class NeuralRenderer:
         n_map, thr_map = self.budget_buffers()
         self._check(self.foveate_device(gaze_xy, rings, n_map, thr_map))
         self._check(self.lib.adanerf_set_budget_map(self.handle, n_map.ptr, thr_map.ptr))
+
+    # -- foveated ray density: a mask of strides around the gaze, the pixels in between rebuilt ------------
+    def foveate_density_device(self, gaze_xy, rings, mask) -> int:
+        """adanerf_foveate_density into a device buffer ([height*width] uint8): rings as parse_fovea_density returns them, [(R, S), ...,
+        (S,)].  Returns the library's code (0, or an error with nothing written) instead of raising: tests look at both."""
+        nr, radius, stride = _density_arrays(rings)
+        return self.lib.adanerf_foveate_density(self.handle, float(gaze_xy[0]), float(gaze_xy[1]), nr, radius, stride, _ptr(mask))
+
+    def fill_density_device(self, mask, width: int, height: int, rgb, depth_map=None, acc_map=None, rgba8=None, count: bool = True):
+        """adanerf_fill_density over device images, in place: every pixel whose mask byte is 2, 4 or 8 becomes the bilinear blend of the
+        rendered corners of its cell.  Returns (code, unfilled); ``count=False`` passes no counter (asynchronous, unfilled is None)."""
+        u = C.c_int32(-1)
+        rc = self.lib.adanerf_fill_density(self.handle, _ptr(mask), int(width), int(height), _ptr(rgb), _ptr(depth_map), _ptr(acc_map), _ptr(rgba8),
+                                           C.byref(u) if count else None)
+        return rc, (int(u.value) if count else None)
+
+    density_mask = staticmethod(density_mask)
+
+    def foveate_density(self, gaze_xy, rings):
+        """Foveated ray density from now on for render_foveated(): fills the renderer's own device mask from the gaze point (pixels) and
+        the rings ([(R, S), ..., (S,)] or the string parse_fovea_density takes).  Call again when the gaze moves; a frame-size change
+        drops the mask, so call again after set_frame_size too."""
+        if isinstance(rings, str):
+            rings = parse_fovea_density(rings)
+        n = self.info.width * self.info.height
+        if not hasattr(self, "_fd_mask") or self._fd_mask.shape[0] != n:
+            if hasattr(self, "_fd_mask"):
+                self.sync()      # a frame in flight still reads the mask
+                self._fd_mask.free()
+                self._own.remove(self._fd_mask)
+            self._fd_mask = self.empty((n,), np.uint8)
+        self._fd = None
+        self._check(self.foveate_density_device(gaze_xy, rings, self._fd_mask))
+        self._fd = ((float(gaze_xy[0]), float(gaze_xy[1])), [tuple(r) for r in rings], self.info.width, self.info.height)
+
+    def render_foveated(self):
+        """One frame at the density foveate_density() set: adanerf_render_masked over the mask's lattice into the renderer's own images,
+        then adanerf_fill_density for the pixels in between -- colour, RGBA8 and the aux maps in force.  Returns (rgb [R,3] fp32, rgba8
+        [R,4] uint8, rendered, Stats of the rendered rays); the device copies stay in ``_o_rgb`` / ``_o_rgba`` as after render_numpy."""
+        w, h = self.info.width, self.info.height
+        if self._fd is None or self._fd[2:] != (w, h):
+            raise AdaNeRFError("render_foveated: no density mask for %d x %d (call foveate_density first, and again after set_frame_size)" % (w, h))
+        n = self.info.rays_local
+        if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
+            self._o_rgb = self.empty((n, 3), np.float32)
+            self._o_rgba = self.empty((n, 4), np.uint8)
+        rendered, st = self.render_masked(self._fd_mask, 1, self._o_rgba, self._o_rgb)
+        rc, _ = self.fill_density_device(self._fd_mask, w, h, self._o_rgb, self._aux_in_force[0], self._aux_in_force[1], self._o_rgba, count=False)
+        self._check(rc)
+        self._last_frame = (self._o_rgba, w, h)
+        self._rp_frame = None      # the depth between the rendered pixels is interpolated, not the volume's own
+        return self._o_rgb.numpy(), self._o_rgba.numpy(), rendered, st
 
     # -- hybrid rendering: depth limits, the rasterised colour behind --------------------------------------
     def set_depth_limit(self, limit_zc=None):

@@ -478,6 +478,61 @@ int adanerf_set_depth_limit(adanerf_ctx* ctx, const float* d_limit_zc);
 int adanerf_blend_behind(adanerf_ctx* ctx, const float* d_rgb, const float* d_acc, const float* d_behind_rgb, int32_t n, float* d_out_rgb,
                          void* d_out_rgba8);
 
+/* Foveated ray density: the second half of foveation.  adanerf_foveate lowers the samples per ray away from the gaze; this lowers the
+ * rays.  The mask below is dense at the gaze and thins to every 2nd, 4th or 8th pixel per axis outside it, adanerf_render_masked(d_mask, 1,
+ * ..) renders exactly its lattice, and adanerf_fill_density rebuilds the pixels in between.
+ *   radius_px[n_rings]  adanerf_foveate's rules: whole pixels, strictly ascending, n_rings in 0..8
+ *   stride[n_rings + 1] each 1, 2, 4 or 8, never decreasing from one entry to the next; the last entry applies outside every ring
+ *   d_mask              [height*width] uint8, device memory, at the context's current frame size, indexed as d_rgba8_out is
+ * One launch on the context's stream, no host synchronisation.  Definition, in integers only:
+ *   ring      adanerf_foveate's rule unchanged: gx2 = lrintf(2 gaze_x), gy2 alike, clamped as there; q = (2 x + 1 - gx2)^2 + (2 y + 1 - gy2)^2;
+ *             ring k contains the pixel iff q <= 4 radius_px[k]^2; s(x, y) = stride[k] of the first ring that contains it, else stride[n_rings]
+ *   rendered  pixel (x, y) iff some level L of 1, 2, 4, 8 passes all of: L divides x; L divides y; s(nx, ny) <= L, where (nx, ny) is the
+ *             pixel of the box [max(x - L + 1, 0), min(x + L - 1, w - 1)] x [max(y - L + 1, 0), min(y + L - 1, h - 1)] whose centre lies
+ *             nearest the gaze: per axis the integer c of the interval that minimises |2 c + 1 - gx2|, the lower c on a tie.  Strides never
+ *             decrease outward, so that pixel carries the smallest stride of the box.
+ *   byte      0 for a rendered pixel; every other pixel gets its own stride s(x, y), which is 2, 4 or 8
+ * A pixel on the lattice of its own ring passes at L = s (the box contains it); beyond that every lattice point of stride L is rendered as
+ * soon as any pixel within L - 1 of it per axis belongs to a ring of stride L or finer, also a point that sits in a coarser ring.  That
+ * closes the pattern at ring borders: every corner adanerf_fill_density reads is a rendered pixel, for any gaze, radii and frame size.
+ * At 800 x 800 with radii 120 / 300 and strides 1 / 2 / 4 the mask renders 127 399 of 640 000 pixels (19.9 %).
+ * ADANERF_EINVAL, with nothing written: a NULL mask or array; a gaze that is not finite; n_rings outside 0..8; radii negative or not
+ * strictly ascending; a stride outside {1, 2, 4, 8} or a decreasing one.
+ * ADANERF_EUNSUPPORTED, with nothing written: shard_world != 1 (the reconstruction needs a pixel's neighbours; adanerf_render_masked
+ * refuses shards too). */
+int adanerf_foveate_density(adanerf_ctx* ctx, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* stride,
+                            uint8_t* d_mask);
+
+/* The reconstruction: one launch on the context's stream, a gather, in place.
+ *   d_mask [height*width] uint8; d_rgb [height*width,3] fp32, required; d_depth_map / d_acc_map [height*width] fp32 and d_rgba8
+ *   [height*width] uchar4, each may be NULL.  width and height are arguments, independent of the context's frame size (as
+ *   adanerf_present's are).
+ * Per pixel (x, y) with mask byte s:
+ *   s not in {2, 4, 8}: nothing of the pixel is touched, in any image (0 is a rendered pixel; any other value is free for a caller's marks)
+ *   otherwise the corners are x0 = x & ~(s - 1); x1 = x0 + s, but x1 = x0 if x == x0 or x0 + s >= width; y alike; the used corners are the
+ *   distinct ones among (x0 | x1, y0 | y1).  A used corner whose mask byte is not 0: the pixel is left untouched and counted in
+ *   *unfilled_out -- 0 with a mask of adanerf_foveate_density; with any other mask the result is still deterministic, because a thread
+ *   reads only pixels of byte 0 and no thread writes those.
+ *   fx = (float)(x - x0) / (float)s, fy alike (both exact); per channel top = c00 + fx (c01 - c00), bot = c10 + fx (c11 - c10),
+ *   out = top + fy (bot - top), c01 the corner at (x1, y0), c10 at (x0, y1): each step a subtraction, a product and a sum, each rounded
+ *   to fp32 and never fused.  On an axis where the two taps are the same pixel that step is skipped and the value's bits are copied (an
+ *   infinity does not turn into a NaN that way).
+ *   d_depth_map and d_acc_map get the same interpolation (both are sums over the samples and so linear in the weights); d_rgba8 of a
+ *   filled pixel is adanerf_resolve_mean's byte contract applied to `out`.
+ * unfilled_out: the 4-byte counter shared with adanerf_reproject; with a non-NULL pointer the call is synchronous, with NULL the images
+ * are complete after adanerf_sync().  Measured at 800 x 800 with radii 120 / 300 and strides 1 / 2 / 4
+ * (profiles/foveated_density_measured.md): the mask kernel 7 us, the fill kernel 12.5 us with the RGBA8 image, the whole frame -- masked
+ * render and fill -- 1.12 ms where adanerf_render takes 4.91 ms.
+ * ADANERF_EINVAL, with nothing written: a NULL mask or d_rgb; a side outside 1..16384; an fp32 or uchar4 pointer that is not 4-byte
+ * aligned; images that overlap one another or the mask.
+ * What it does not do: combine with budget maps (the hosts refuse the pair: a ray's budget would have to be reconstructed too); rotate the
+ * lattice from frame to frame or couple it to the temporal stages (adanerf_temporal_resolve sees a reconstructed frame as any other); an
+ * edge-aware or depth-aware filter (the blend is bilinear across depth edges); anything specific to useNDC models (their depth_map is
+ * interpolated as a number like any other); sizing launches on the device (the ray count of the masked render is read back once per frame,
+ * as adanerf_render_masked does). */
+int adanerf_fill_density(adanerf_ctx* ctx, const uint8_t* d_mask, int32_t width, int32_t height, float* d_rgb, float* d_depth_map,
+                         float* d_acc_map, void* d_rgba8, int32_t* unfilled_out);
+
 /* De-interleaves the gathered shard payloads ([shard_world][rays_local_max] uchar4, rank-major)
  * into the full row-major image [h*w] uchar4. */
 int adanerf_assemble_strips(adanerf_ctx* ctx, const void* d_gathered, void* d_image_out);
@@ -987,6 +1042,12 @@ int adanerf_host_subpixel_grid(int32_t s, int32_t k, float* dx, float* dy);
  * ADANERF_EINVAL: a NULL pointer; a side outside 1..16384; a value that is not finite; radius <= 0; focal <= 0. */
 int adanerf_host_sphere_zc(int32_t width, int32_t height, float focal, const float pos[3], const float rot_c2w[9], const float center[3],
                            float radius, float* zc_out);
+
+/* The mask of adanerf_foveate_density computed on the host, for a width x height frame: the same rule compiled from the same text, byte
+ * for byte what the device writes.  mask_out [height*width] uint8, row-major.
+ * ADANERF_EINVAL, with nothing written: everything adanerf_foveate_density refuses; a side outside 1..16384. */
+int adanerf_host_density_mask(int32_t width, int32_t height, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px,
+                              const int32_t* stride, uint8_t* mask_out);
 
 #ifdef __cplusplus
 }
