@@ -1140,6 +1140,46 @@ int adanerf_resolve_mean(adanerf_ctx* c, const float* d_sum, int32_t n_rays, int
   HIP_RETURN(c, hipGetLastError());
 }
 
+int adanerf_accumulate_masked(adanerf_ctx* c, const float* d_rgb, const uint8_t* d_mask, uint32_t values, int32_t n_rays, float* d_sum, int32_t first) {
+  if (!c) return ADANERF_EINVAL;
+  if (!d_rgb || !d_sum) return fail(c, ADANERF_EINVAL, "adanerf_accumulate_masked: NULL image");
+  if (!d_mask || values == 0) return fail(c, ADANERF_EINVAL, "adanerf_accumulate_masked: NULL mask, or values == 0 selects no mask byte");
+  if (n_rays < 0 || n_rays > 0x7fffffff / 3) return fail(c, ADANERF_EINVAL, "adanerf_accumulate_masked: n_rays must be >= 0 and n_rays * 3 <= 2^31 - 1");
+  if ((reinterpret_cast<uintptr_t>(d_rgb) | reinterpret_cast<uintptr_t>(d_sum)) & 3) return fail(c, ADANERF_EINVAL, "adanerf_accumulate_masked: images must be 4-byte aligned");
+  const size_t bytes = static_cast<size_t>(n_rays) * 3 * sizeof(float);
+  if (d_rgb != d_sum && ranges_overlap(d_rgb, bytes, d_sum, bytes))
+    return fail(c, ADANERF_EINVAL, "adanerf_accumulate_masked: frame and sum overlap without being the same image");
+  if (ranges_overlap(d_mask, static_cast<size_t>(n_rays), d_sum, bytes)) return fail(c, ADANERF_EINVAL, "adanerf_accumulate_masked: the mask overlaps the sum");
+  BIND(c);
+  if (n_rays == 0) return ADANERF_OK;
+  const int n = n_rays * 3;
+  const int grid = std::min((n + 255) / 256, 65536);      // grid-stride beyond 2^24 values
+  hipLaunchKernelGGL(accumulate_masked_kernel, dim3(grid), dim3(256), 0, c->stream, d_rgb, d_mask, values, d_sum, n, first != 0 ? 1 : 0);
+  HIP_RETURN(c, hipGetLastError());
+}
+
+int adanerf_resolve_mean_masked(adanerf_ctx* c, const float* d_sum, const uint8_t* d_mask, uint32_t values, int32_t n_rays, int32_t frames, void* d_rgba8,
+                                float* d_rgb) {
+  if (!c) return ADANERF_EINVAL;
+  if (!d_sum || (!d_rgba8 && !d_rgb)) return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean_masked: NULL sum, or both outputs NULL");
+  if (!d_mask || values == 0) return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean_masked: NULL mask, or values == 0 selects no mask byte");
+  if (n_rays < 0 || n_rays > 0x7fffffff / 3) return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean_masked: n_rays must be >= 0 and n_rays * 3 <= 2^31 - 1");
+  if (frames < 1 || frames > 65536) return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean_masked: frames must be in 1..65536");
+  if ((reinterpret_cast<uintptr_t>(d_sum) | reinterpret_cast<uintptr_t>(d_rgba8) | reinterpret_cast<uintptr_t>(d_rgb)) & 3)
+    return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean_masked: images must be 4-byte aligned");
+  const size_t bytes = static_cast<size_t>(n_rays) * 3 * sizeof(float), bytes8 = static_cast<size_t>(n_rays) * 4;
+  if ((d_rgb && d_rgb != d_sum && ranges_overlap(d_sum, bytes, d_rgb, bytes)) ||
+      (d_rgba8 && (ranges_overlap(d_sum, bytes, d_rgba8, bytes8) || (d_rgb && ranges_overlap(d_rgb, bytes, d_rgba8, bytes8)))))
+    return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean_masked: images overlap (only d_rgb_f32_out may be d_sum itself)");
+  if ((d_rgb && ranges_overlap(d_mask, static_cast<size_t>(n_rays), d_rgb, bytes)) || (d_rgba8 && ranges_overlap(d_mask, static_cast<size_t>(n_rays), d_rgba8, bytes8)))
+    return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean_masked: the mask overlaps an output");
+  BIND(c);
+  if (n_rays == 0) return ADANERF_OK;
+  hipLaunchKernelGGL(resolve_mean_masked_kernel, dim3((n_rays + 255) / 256), dim3(256), 0, c->stream, d_sum, d_mask, values, n_rays, static_cast<float>(frames),
+                     d_rgb, static_cast<uchar4*>(d_rgba8));
+  HIP_RETURN(c, hipGetLastError());
+}
+
 int adanerf_present(adanerf_ctx* c, const void* d_src_rgba8, int32_t src_w, int32_t src_h, void* d_dst_rgba8, int32_t dst_w, int32_t dst_h,
                     int32_t flags) {
   if (!c) return ADANERF_EINVAL;
@@ -2169,6 +2209,29 @@ int adanerf_fill_density(adanerf_ctx* c, const uint8_t* d_mask, int32_t width, i
   HIP_TRY(c, hipGetLastError());
   if (unfilled_out) {
     HIP_TRY(c, hipMemcpyAsync(unfilled_out, unfilled, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return ADANERF_OK;
+}
+
+int adanerf_contrast_mask(adanerf_ctx* c, const float* d_rgb, int32_t width, int32_t height, float threshold, uint8_t* d_mask, int32_t* n_flagged) {
+  if (!c) return ADANERF_EINVAL;
+  if (!d_rgb || !d_mask) return fail(c, ADANERF_EINVAL, "adanerf_contrast_mask: NULL image or mask");
+  if (const char* why = contrast_rule_check(width, height, threshold)) return fail(c, ADANERF_EINVAL, std::string("adanerf_contrast_mask: ") + why);
+  if (reinterpret_cast<uintptr_t>(d_rgb) & 3) return fail(c, ADANERF_EINVAL, "adanerf_contrast_mask: d_rgb must be 4-byte aligned");
+  const size_t n = static_cast<size_t>(width) * static_cast<size_t>(height);
+  if (ranges_overlap(d_rgb, n * 3 * sizeof(float), d_mask, n)) return fail(c, ADANERF_EINVAL, "adanerf_contrast_mask: the mask overlaps the image");
+  BIND(c);
+  if (!c->reproj_holes.p) {      // the counter shared with adanerf_reproject, the temporal stages and adanerf_fill_density: all run on the context's stream
+    if (int rc = dev_alloc(c, &c->reproj_holes, 64)) return rc;
+  }
+  int32_t* flagged = reinterpret_cast<int32_t*>(c->reproj_holes.p);
+  if (n_flagged) HIP_TRY(c, hipMemsetAsync(flagged, 0, sizeof(int32_t), c->stream));
+  const dim3 grid(static_cast<unsigned>((width + kContrastTileW - 1) / kContrastTileW), static_cast<unsigned>((height + kContrastTileH - 1) / kContrastTileH));
+  hipLaunchKernelGGL(contrast_mask_kernel, grid, dim3(256), 0, c->stream, d_rgb, width, height, threshold, d_mask, n_flagged ? flagged : nullptr);
+  HIP_TRY(c, hipGetLastError());
+  if (n_flagged) {
+    HIP_TRY(c, hipMemcpyAsync(n_flagged, flagged, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   return ADANERF_OK;

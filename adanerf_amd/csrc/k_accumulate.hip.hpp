@@ -6,6 +6,7 @@
 // Bandwidth-bound and tiny beside a frame's two networks: grid-stride over the values, a thread per pixel in the resolve.  No LDS.
 #pragma once
 #include "k_common.hip.hpp"
+#include "k_mask.hip.hpp"
 
 namespace adanerf {
 
@@ -33,6 +34,33 @@ __global__ __launch_bounds__(256) void accumulate_kernel(const float* rgb, float
 __global__ __launch_bounds__(256) void resolve_mean_kernel(const float* sum, int n_rays, float frames, float* rgb_out, uchar4* __restrict__ rgba8_out) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n_rays) return;
+  const size_t o = 3 * static_cast<size_t>(r);
+  const float m0 = __fdiv_rn(sum[o], frames), m1 = __fdiv_rn(sum[o + 1], frames), m2 = __fdiv_rn(sum[o + 2], frames);
+  if (rgb_out) {
+    rgb_out[o] = m0;
+    rgb_out[o + 1] = m1;
+    rgb_out[o + 2] = m2;
+  }
+  if (rgba8_out) rgba8_out[r] = rgba8_of(m0, m1, m2);
+}
+
+// N11 (adaptive supersampling): accumulate_kernel for the pixels the mask selects (mask_selects, k_mask.hip.hpp: the test of
+// adanerf_render_masked).  Value i belongs to pixel i / 3; nothing of any other pixel is read or written.  A thread per value as there, so
+// the loads and stores of a wave stay contiguous where the mask selects a run of pixels.
+__global__ __launch_bounds__(256) void accumulate_masked_kernel(const float* rgb, const uint8_t* __restrict__ mask, uint32_t values, float* sum, int n, int first) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
+    if (!mask_selects(mask[static_cast<uint32_t>(i) / 3u], values)) continue;
+    const float v = rgb[i];
+    sum[i] = first ? v : __fadd_rn(sum[i], v);
+  }
+}
+
+// resolve_mean_kernel for the pixels the mask selects; every element of every other pixel keeps its bytes in both outputs
+__global__ __launch_bounds__(256) void resolve_mean_masked_kernel(const float* sum, const uint8_t* __restrict__ mask, uint32_t values, int n_rays, float frames,
+                                                                  float* rgb_out, uchar4* __restrict__ rgba8_out) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_rays || !mask_selects(mask[r], values)) return;
   const size_t o = 3 * static_cast<size_t>(r);
   const float m0 = __fdiv_rn(sum[o], frames), m1 = __fdiv_rn(sum[o + 1], frames), m2 = __fdiv_rn(sum[o + 2], frames);
   if (rgb_out) {

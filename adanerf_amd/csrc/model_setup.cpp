@@ -1,5 +1,6 @@
 // See model_setup.hpp.  Also the three entry points of the C ABI that never touch a device.
 #include "model_setup.hpp"
+#include "contrast_rule.hpp"
 #include "density_rule.hpp"
 
 #include <cstdio>
@@ -488,6 +489,27 @@ int adanerf_host_density_mask(int32_t width, int32_t height, float gaze_x, float
   if (const char* why = density_rule_fill(gaze_x, gaze_y, n_rings, radius_px, stride, &f)) return fail(ADANERF_EINVAL, std::string("adanerf_host_density_mask: ") + why);
   for (int y = 0; y < height; ++y)
     for (int x = 0; x < width; ++x) mask_out[static_cast<size_t>(y) * width + x] = density_mask_byte(f, x, y, width, height);
+  return ADANERF_OK;
+}
+
+int adanerf_host_contrast_mask(const float* rgb, int32_t width, int32_t height, float threshold, uint8_t* mask, int32_t* n_flagged) {
+  if (!rgb || !mask) return fail(ADANERF_EINVAL, "adanerf_host_contrast_mask: NULL image or mask");
+  if (const char* why = contrast_rule_check(width, height, threshold)) return fail(ADANERF_EINVAL, std::string("adanerf_host_contrast_mask: ") + why);
+  if (reinterpret_cast<uintptr_t>(rgb) & 3) return fail(ADANERF_EINVAL, "adanerf_host_contrast_mask: rgb must be 4-byte aligned");
+  const size_t n = static_cast<size_t>(width) * static_cast<size_t>(height);
+  const uintptr_t a0 = reinterpret_cast<uintptr_t>(rgb), b0 = reinterpret_cast<uintptr_t>(mask);
+  if (a0 < b0 + n && b0 < a0 + n * 3 * sizeof(float)) return fail(ADANERF_EINVAL, "adanerf_host_contrast_mask: the mask overlaps the image");
+  const auto plane = [&](int ch) {
+    return [=](int x, int y) { return contrast_display(rgb[(static_cast<size_t>(y) * width + x) * 3 + ch]); };
+  };
+  int32_t count = 0;
+  for (int y = 0; y < height; ++y)
+    for (int x = 0; x < width; ++x) {
+      const uint8_t m = contrast_mask_byte(x, y, width, height, threshold, plane(0), plane(1), plane(2));
+      mask[static_cast<size_t>(y) * width + x] = m;
+      count += m == 0;
+    }
+  if (n_flagged) *n_flagged = count;
   return ADANERF_OK;
 }
 

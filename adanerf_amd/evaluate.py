@@ -7,7 +7,7 @@ reference's second default metric (``metrics = ["flip", "psnr"]`` :613-615): the
     python -m adanerf_amd.evaluate <model_dir> <dataset_dir> [--set test] [--out DIR] [--video out.y4m] [--precision bf16]
                                    [--metrics psnr flip] [--sweep-thresholds T ...] [--sweep-samples N ...] [--sweep-scales S ...]
                                    [--reproject-stride K [--rerender holes|unsourced]] [--supersample S] [--present-filter nearest|linear|area]
-                                   [--fovea-density R:S[,R:S...],S]
+                                   [--fovea-density R:S[,R:S...],S] [--supersample-contrast T]
 
 ``--sweep-thresholds`` / ``--sweep-samples`` render the set once per (N, threshold) of their cross product on ONE context
 (``NeuralRenderer.set_selection``: an AdaNeRF network is trained once and rendered at any sample budget) -- the two axes of a quality
@@ -25,6 +25,10 @@ rendered at its own pose (``adanerf_render_masked``).
 and resolved on the GPU (``NeuralRenderer.render_supersampled``) and scored from the fp32 mean: anti-aliasing in time, against the
 dataset's anti-aliased ground truth.  ``--present-filter area`` makes the ``--sweep-scales`` presentation an exact area filter
 (``ADANERF_PRESENT_AREA``): the only sensible choice for scales above 1, where the default rule decimates.
+
+``--supersample-contrast T`` (with ``--supersample S``, S >= 2) spends the S x S renders only where the frame has edges
+(``NeuralRenderer.render_supersampled_adaptive``: one render at the pixel centres, ``adanerf_contrast_mask`` on it, the sub-pixel renders of
+the flagged pixels alone through ``adanerf_render_masked``); the summary gains ``mean_refined_fraction``.
 
 ``--fovea-density SPEC`` scores, beside every full frame, the same pose rendered at a foveated ray density around a gaze at the frame
 centre (``NeuralRenderer.render_foveated``: the lattice of ``adanerf_foveate_density`` rendered, the pixels in between rebuilt by
@@ -107,7 +111,7 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
              precision: str = "bf16", batch_size: int = -1, max_frames: int = 0, quiet: bool = False,
              video: Optional[str] = None, fps: int = 30, metrics=("psnr",), fovea=None, sweep_thresholds=None, sweep_samples=None, reproject_stride=None,
              supersample=None, present_filter=None, temporal=None, temporal_still=None, temporal_upsample=None, temporal_upsample_frames=None,
-             rerender=None, fovea_density=None, sweep_scales=None):
+             rerender=None, fovea_density=None, supersample_contrast=None, sweep_scales=None):
     """metrics: "psnr" (always reported where a ground-truth image exists) and / or "flip": each record gains ``flip``, the summary
     ``mean_flip``, and with out_dir the error map is written as an 8-bit greyscale ``%05d_flip.png``.
 
@@ -135,6 +139,11 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     supersample (S in 1..8 or None): every image is the mean of S x S renders at the offsets of the regular sub-pixel grid
     (NeuralRenderer.render_supersampled), scored from the fp32 mean; ms is the sum over the S x S renders, samples_per_ray is per rendered
     frame; records and summary carry ``supersample``.  Not together with reproject_stride (the mean has no depth map to warp by).
+
+    supersample_contrast (T in [0, 1] or None; needs supersample >= 2): adaptive supersampling -- every image is one render at the pixel
+    centres whose edge pixels (a neighbour differs by more than T in some channel's display value) are replaced by the mean of their S x S
+    sub-pixel renders (NeuralRenderer.render_supersampled_adaptive).  ms is the sum over all passes, samples_per_ray is the centre
+    frame's; records gain ``refined_fraction`` (pixels refined, of w h), the summary ``mean_refined_fraction``.
 
     present_filter (None, "nearest", "linear" or "area"): the filter of the sweep_scales presentation (NeuralRenderer.present); None is the
     viewer's rule, which decimates a frame rendered above the dataset's size -- "area" averages it.
@@ -192,6 +201,13 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     ss = int(supersample) if supersample is not None else 0
     if supersample is not None and not 1 <= ss <= SUPERSAMPLE_MAX:
         raise ValueError("supersample must be in 1..%d, got %s" % (SUPERSAMPLE_MAX, supersample))
+    contrast = None
+    if supersample_contrast is not None:
+        contrast = float(supersample_contrast)
+        if not (np.isfinite(contrast) and 0.0 <= contrast <= 1.0):
+            raise ValueError("supersample_contrast must lie in [0, 1], got %s" % (supersample_contrast,))
+        if ss < 2:
+            raise ValueError("supersample_contrast refines the edges of a supersampled frame: it needs supersample >= 2")
     if ss and stride:
         raise ValueError("supersample averages jittered frames, which have no single depth map to warp by: not together with reproject_stride")
     still = int(temporal_still) if temporal_still is not None else 0
@@ -268,7 +284,10 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                             write_png(os.path.join(out_dir, "%05d_rerendered.png" % i), rr_rgba[:, :3].reshape(h, w, 3))
                 else:
                     r.set_camera(fr["pose"], fr["rot"])
-                    rgb, rgba, st = r.render_supersampled(ss) if ss else r.render_numpy()
+                    if contrast is not None:
+                        rgb, rgba, _, refined, st = r.render_supersampled_adaptive(ss, contrast)
+                    else:
+                        rgb, rgba, st = r.render_supersampled(ss) if ss else r.render_numpy()
                     if presented:      # the frame as a w x h window shows it, filtered on the device
                         rgba = r.present(w, h, filter="linear" if tu else present_filter).reshape(-1, 4)
                         rgb = rgba[:, :3].astype(np.float32) / 255.0
@@ -277,6 +296,8 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                         rec.update(warped=False)
                     if ss:
                         rec.update(supersample=ss)
+                    if contrast is not None:
+                        rec.update(refined_fraction=refined / float(rw * rh))
                 if os.path.exists(fr["image"]):
                     gt = read_png(fr["image"])
                     if gt.shape[0] != h or gt.shape[1] != w:
@@ -399,6 +420,8 @@ def summarise(results: List[dict], want_flip: bool) -> dict:
             summary["mean_flip_foveated"] = float(np.mean([x["flip_foveated"] for x in part])) if part else None
         summary["mean_rendered_fraction"] = float(np.mean([x["rendered_fraction"] for x in results if "rendered_fraction" in x]))
         summary["mean_ms_foveated"] = float(np.mean([x["ms_foveated"] for x in results if "ms_foveated" in x]))
+    if any("refined_fraction" in x for x in results):      # supersample_contrast: the share of the pixels that got the S x S renders
+        summary["mean_refined_fraction"] = float(np.mean([x["refined_fraction"] for x in results if "refined_fraction" in x]))
     return summary
 
 
@@ -454,6 +477,10 @@ def build_parser():
                          "stride outside them; every pose is rendered once more on that lattice and reconstructed (adanerf_foveate_density / "
                          "adanerf_render_masked / adanerf_fill_density); the summary gains mean_psnr_foveated / mean_rendered_fraction / "
                          "mean_ms_foveated (and mean_flip_foveated with --metrics flip)")
+    ap.add_argument("--supersample-contrast", type=float, default=None, metavar="T",
+                    help="with --supersample S >= 2: adaptive supersampling -- one render at the pixel centres, the S x S renders only for the "
+                         "pixels a neighbour of which differs by more than T (0..1) in some channel (adanerf_contrast_mask / "
+                         "adanerf_render_masked); the summary gains mean_refined_fraction")
     return ap
 
 
@@ -477,13 +504,19 @@ def main(argv=None):
         if (a.fovea is not None or a.reproject_stride is not None or a.supersample is not None or a.sweep_scales or a.temporal is not None or
                 a.temporal_still is not None or a.temporal_upsample is not None):
             ap.error("--fovea-density cannot be combined with --fovea, --reproject-stride, --supersample, --sweep-scales or the --temporal options")
+    if a.supersample_contrast is not None:
+        if a.supersample is None or a.supersample < 2:
+            ap.error("--supersample-contrast requires --supersample S with S >= 2")
+        if not (np.isfinite(a.supersample_contrast) and 0.0 <= a.supersample_contrast <= 1.0):
+            ap.error("--supersample-contrast T: T must lie in [0, 1]")
     if a.temporal_upsample_frames is not None and a.temporal_upsample is None:
         ap.error("--temporal-upsample-frames goes with --temporal-upsample")
     summary, _ = evaluate(a.model_dir, a.dataset_dir, a.set, a.out, a.precision, a.batch_size, a.max_frames, video=a.video, fps=a.fps,
                           metrics=tuple(a.metrics), sweep_thresholds=a.sweep_thresholds, sweep_samples=a.sweep_samples, sweep_scales=a.sweep_scales,
                           fovea=a.fovea, reproject_stride=a.reproject_stride, rerender=a.rerender, supersample=a.supersample, present_filter=a.present_filter,
                           temporal=a.temporal, temporal_still=a.temporal_still, temporal_upsample=a.temporal_upsample,
-                          temporal_upsample_frames=a.temporal_upsample_frames, fovea_density=a.fovea_density)
+                          temporal_upsample_frames=a.temporal_upsample_frames, fovea_density=a.fovea_density,
+                          supersample_contrast=a.supersample_contrast)
     print(json.dumps(summary))
 
 

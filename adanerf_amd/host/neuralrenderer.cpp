@@ -24,7 +24,7 @@ NeuralRenderer::~NeuralRenderer() {
   if (ctx) {
     if (d_gathered) adanerf_free(ctx, d_gathered);
     if (d_frame) adanerf_free(ctx, d_frame);
-    for (void* p : {d_depth, d_acc, d_warp, d_wmask, d_rgb, d_sum, d_hist[0][0], d_hist[0][1], d_hist[0][2], d_hist[1][0], d_hist[1][1], d_hist[1][2], d_up, d_limit, d_behind, d_dmask})
+    for (void* p : {d_depth, d_acc, d_warp, d_wmask, d_rgb, d_sum, d_hist[0][0], d_hist[0][1], d_hist[0][2], d_hist[1][0], d_hist[1][1], d_hist[1][2], d_up, d_limit, d_behind, d_dmask, d_stage, d_cmask})
       if (p) adanerf_free(ctx, p);
     if (d_window) adanerf_free(ctx, d_window);
     adanerf_destroy(ctx);
@@ -235,6 +235,16 @@ bool NeuralRenderer::allocFrameBuffers() {
       if (*p && adanerf_free(ctx, *p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
       *p = nullptr;
       if (adanerf_malloc(ctx, static_cast<size_t>(info_.width) * info_.height * 3 * sizeof(float), p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+    }
+    if (settings.supersample_contrast >= 0.f) {      // the staging image and the mask belong to the frame size too
+      const size_t n = static_cast<size_t>(info_.width) * info_.height;
+      void** bufs[] = {&d_stage, &d_cmask};
+      const size_t bytes[] = {n * 12, n};
+      for (int k = 0; k < 2; ++k) {
+        if (*bufs[k] && adanerf_free(ctx, *bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+        *bufs[k] = nullptr;
+        if (adanerf_malloc(ctx, bytes[k], bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+      }
     }
   }
   if (!settings.occluders.empty()) {      // the limit and the acc map belong to the frame size: the library drops them when rays_local changes
@@ -493,6 +503,7 @@ bool NeuralRenderer::render() {
 // --supersample S: S x S renders of this frame's camera at the offsets of the regular sub-pixel grid, summed on the device; d_frame gets
 // the mean under the viewer's output contract.  The offset goes back to (0, 0).
 bool NeuralRenderer::renderSupersampled(adanerf_stats* st) {
+  if (settings.supersample_contrast >= 0.f) return renderSupersampledAdaptive(st);
   const int S = settings.supersample, renders = S * S, n = info_.width * info_.height;
   bool ok = true;
   for (int k = 0; ok && k < renders; ++k) {
@@ -521,6 +532,44 @@ bool NeuralRenderer::renderSupersampled(adanerf_stats* st) {
     err = adanerf_last_error(ctx);
     return false;
   }
+  return true;
+}
+
+// --supersample S --supersample-contrast T: the centre frame (offset (0, 0)) into d_frame / d_rgb, its contrast mask, and -- if any pixel is
+// flagged -- the S x S renders of the grid for the flagged pixels alone, summed and averaged over the centre frame.  A flagged pixel carries
+// the bytes of --supersample S, every other the bytes of a plain render.  No aux or disparity map is installed on this path (--supersample
+// refuses every option that installs one), so there is none to switch off for the masked passes.  *st: the centre frame's record, the
+// stage times summed over all passes.  The offset goes back to (0, 0).
+bool NeuralRenderer::renderSupersampledAdaptive(adanerf_stats* st) {
+  const int S = settings.supersample, renders = S * S, w = info_.width, h = info_.height, n = w * h;
+  const uint8_t* mask = static_cast<const uint8_t*>(d_cmask);
+  float *rgb = static_cast<float*>(d_rgb), *stage = static_cast<float*>(d_stage), *sum = static_cast<float*>(d_sum);
+  int32_t flagged = 0;
+  bool ok = adanerf_set_pixel_offset(ctx, 0.f, 0.f) == ADANERF_OK && adanerf_render(ctx, d_frame, rgb, st) == ADANERF_OK &&
+            adanerf_contrast_mask(ctx, rgb, w, h, settings.supersample_contrast, static_cast<uint8_t*>(d_cmask), &flagged) == ADANERF_OK;
+  for (int k = 0; ok && flagged > 0 && k < renders; ++k) {
+    float dx = 0.f, dy = 0.f;
+    int32_t m = 0;
+    adanerf_stats sk;
+    std::memset(&sk, 0, sizeof(sk));
+    ok = adanerf_host_subpixel_grid(S, k, &dx, &dy) == ADANERF_OK && adanerf_set_pixel_offset(ctx, dx, dy) == ADANERF_OK &&
+         adanerf_render_masked(ctx, mask, 1u, nullptr, stage, &sk, &m) == ADANERF_OK &&
+         adanerf_accumulate_masked(ctx, stage, mask, 1u, n, sum, k == 0) == ADANERF_OK;
+    st->ms_total += sk.ms_total;
+    st->ms_sample_mlp += sk.ms_sample_mlp;
+    st->ms_compact += sk.ms_compact;
+    st->ms_shade_mlp += sk.ms_shade_mlp;
+    st->ms_composite += sk.ms_composite;
+  }
+  if (!ok) err = adanerf_last_error(ctx);      // before the offset goes back: that call succeeds and would not touch the message anyway
+  const bool back = adanerf_set_pixel_offset(ctx, 0.f, 0.f) == ADANERF_OK;
+  if (!ok) return false;
+  if (!back || (flagged > 0 && adanerf_resolve_mean_masked(ctx, sum, mask, 1u, n, renders, d_frame, rgb) != ADANERF_OK) || adanerf_sync(ctx) != ADANERF_OK) {
+    err = adanerf_last_error(ctx);
+    return false;
+  }
+  s_refined += flagged;
+  if (settings.log_camera) std::printf("adaptive supersample %d refined %d of %u\n", sample_count, static_cast<int>(flagged), settings.total_size);
   return true;
 }
 
@@ -673,6 +722,7 @@ void NeuralRenderer::logInterval() {
             << ", N: " << info_.num_samples << ", thr: " << info_.threshold << ", size: " << info_.width << "x" << info_.height
             << ", frames: " << sample_count << ", frame ms: " << s_total / rendered;
   if (settings.supersample > 1) std::cout << ", renders per frame: " << settings.supersample * settings.supersample;
+  if (settings.supersample_contrast >= 0.f) std::cout << ", refined fraction: " << s_refined / static_cast<double>(logging_interval) / settings.total_size;
   if (settings.taa_alpha > 0.f) std::cout << ", taa rejected: " << s_rejected / static_cast<double>(logging_interval) / settings.total_size;
   if (settings.taau_scale > 0)
     std::cout << ", taau rejected: " << s_rejected / static_cast<double>(logging_interval) / settings.total_size / (settings.taau_scale * settings.taau_scale);
@@ -685,6 +735,7 @@ void NeuralRenderer::logInterval() {
   s_holes = 0;
   s_rerendered = 0;
   s_density_rendered = 0;
+  s_refined = 0;
   s_rejected = 0;
   s_rendered = s_warped = 0;
 }

@@ -88,6 +88,12 @@ class NeuralRenderer {
   void* d_rgb = nullptr;
   void* d_sum = nullptr;
   bool renderSupersampled(adanerf_stats* st);   // S x S renders at the grid's offsets, accumulated and resolved into d_frame; *st: times summed, samples per render
+  // --supersample-contrast T: d_rgb holds the centre frame's fp32 colour, d_stage (float [h*w*3]) one masked sub-pixel render, d_cmask (uint8
+  // [h*w]) the contrast mask of the centre frame (0 = refined)
+  void* d_stage = nullptr;
+  void* d_cmask = nullptr;
+  long long s_refined = 0;           // pixels refined in the running interval's frames
+  bool renderSupersampledAdaptive(adanerf_stats* st);   // the centre frame into d_frame / d_rgb, then the S x S masked renders of its flagged pixels over it
   // --taa: depth_map / acc_map (d_depth, d_acc) and the fp32 frame (d_rgb) of this frame's render; two history sets (rgb float [h*w*3], depth
   // float [h*w], count uint8 [h*w]) that ping-pong, the pose of the one last written, the place in the offset cycle
   void* d_hist[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};

@@ -30,6 +30,8 @@ const char* Settings::usage() {
          "                                    neighbour too) at their own camera instead of leaving the fill\n"
          "               [--supersample S]    every shown frame is S x S renders (S in 1..8) at the offsets of a regular sub-pixel grid, summed and\n"
          "                                    averaged on the device (anti-aliasing in time); -w / --write-window write the resolved image\n"
+         "               [--supersample-contrast T]   with --supersample S >= 2: one render at the pixel centres, then the S x S renders only for\n"
+         "                                    the pixels a neighbour of which differs by more than T (0..1) in some channel (adaptive supersampling)\n"
          "               [--taa ALPHA[:TOL]]  temporal anti-aliasing: every frame is rendered at the next sub-pixel offset of a cycle and blended\n"
          "                                    (weight ALPHA in (0, 1]) with a history carried to its camera by its depth; a history pixel whose depth\n"
          "                                    is off by more than TOL (relative, default 0.02) is dropped; script token cut drops the history\n"
@@ -251,6 +253,15 @@ bool Settings::init(int argc, char** argv, std::string* err) {
         return false;
       }
       supersample = static_cast<int>(k);
+    } else if (a == "--supersample-contrast") {
+      if (!need(i, 1)) return false;
+      char* end = nullptr;
+      const float t = std::strtof(argv[++i], &end);
+      if (end == argv[i] || *end != 0 || !(t >= 0.f && t <= 1.f)) {
+        *err = "--supersample-contrast T: T must be a number in [0, 1]";
+        return false;
+      }
+      supersample_contrast = t;
     } else if (a == "--taa") {
       if (!need(i, 1)) return false;
       const std::string spec = argv[++i];
@@ -329,6 +340,10 @@ bool Settings::init(int argc, char** argv, std::string* err) {
   }
   if (!rerender.empty() && reproject <= 1) {
     *err = "--rerender re-renders the holes of warped frames; only with --reproject K, K > 1";
+    return false;
+  }
+  if (supersample_contrast >= 0.f && supersample <= 1) {
+    *err = "--supersample-contrast refines the edges of a supersampled frame; only with --supersample S, S >= 2";
     return false;
   }
   if (taa_alpha > 0.f && (reproject > 1 || supersample > 1)) {

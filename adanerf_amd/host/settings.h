@@ -57,6 +57,9 @@ class Settings {
                                 // (adanerf_reproject, fill on); 1: every frame is rendered
   int supersample = 1;          // --supersample S (1..8): every shown frame is S x S renders at the offsets of adanerf_host_subpixel_grid, accumulated and
                                 // resolved on the device (adanerf_set_pixel_offset / adanerf_accumulate / adanerf_resolve_mean); 1: one render per frame
+  float supersample_contrast = -1.f;   // --supersample-contrast T (0..1, with --supersample S >= 2): adaptive supersampling -- one render at the pixel centres, then
+                                // the S x S renders only for the pixels a neighbour of which differs by more than T in some channel's display value
+                                // (adanerf_contrast_mask / adanerf_render_masked / adanerf_accumulate_masked / adanerf_resolve_mean_masked); < 0: off
   float taa_alpha = 0.f;        // --taa ALPHA[:TOL]: temporal anti-aliasing (adanerf_temporal_resolve, clamp on): every frame is rendered at the next offset of
   float taa_tol = 0.02f;        // the --taa-grid cycle and blended with a history carried to its camera; ALPHA in (0, 1] the weight of the new frame, TOL >= 0
   int taa_grid = 2;             // the relative depth tolerance of the disocclusion test; --taa-grid S (1..8): the S x S cycle of adanerf_host_subpixel_grid.  0: off

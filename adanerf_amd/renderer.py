@@ -10,6 +10,7 @@ The product path is the HIP library.  Nothing here falls back to a CPU implement
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 from typing import Optional
@@ -82,7 +83,8 @@ EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_las
            "adanerf_set_pixel_offset", "adanerf_get_pixel_offset", "adanerf_accumulate", "adanerf_resolve_mean", "adanerf_host_subpixel_grid", "adanerf_temporal_resolve",
            "adanerf_temporal_upsample", "adanerf_render_masked",
            "adanerf_set_depth_limit", "adanerf_compact_depth_limit", "adanerf_blend_behind", "adanerf_host_sphere_zc",
-           "adanerf_foveate_density", "adanerf_fill_density", "adanerf_host_density_mask"]
+           "adanerf_foveate_density", "adanerf_fill_density", "adanerf_host_density_mask",
+           "adanerf_contrast_mask", "adanerf_accumulate_masked", "adanerf_resolve_mean_masked", "adanerf_host_contrast_mask"]
 
 _lib = None
 
@@ -115,6 +117,10 @@ def load_library(path: Optional[str] = None):
     lib.adanerf_foveate_density.argtypes = [vp, C.c_float, C.c_float, i32, C.POINTER(i32), C.POINTER(i32), vp]
     lib.adanerf_fill_density.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(i32)]
     lib.adanerf_host_density_mask.argtypes = [i32, i32, C.c_float, C.c_float, i32, C.POINTER(i32), C.POINTER(i32), vp]
+    lib.adanerf_contrast_mask.argtypes = [vp, vp, i32, i32, C.c_float, vp, C.POINTER(i32)]
+    lib.adanerf_accumulate_masked.argtypes = [vp, vp, vp, C.c_uint32, i32, vp, i32]
+    lib.adanerf_resolve_mean_masked.argtypes = [vp, vp, vp, C.c_uint32, i32, i32, vp, vp]
+    lib.adanerf_host_contrast_mask.argtypes = [vp, i32, i32, C.c_float, vp, C.POINTER(i32)]
     lib.adanerf_present.argtypes = [vp, vp, i32, i32, vp, i32, i32, i32]
     lib.adanerf_set_pixel_offset.argtypes = [vp, C.c_float, C.c_float]
     lib.adanerf_get_pixel_offset.argtypes = [vp, C.POINTER(C.c_float)]
@@ -380,6 +386,21 @@ def density_mask(width: int, height: int, gaze_xy, rings) -> np.ndarray:
     return out
 
 
+def host_contrast_mask(rgb, width: int, height: int, threshold: float):
+    """The mask of adanerf_contrast_mask on the host (adanerf_host_contrast_mask): ``rgb`` [height*width,3] fp32 -> (mask [height*width]
+    uint8, 0 = flagged: a neighbour's display value differs by more than ``threshold`` in some channel; n_flagged).  No device needed.
+    ValueError on what the library refuses (a side outside 1..16384, a threshold that is not finite or outside [0, 1])."""
+    ok = 1 <= int(width) <= 16384 and 1 <= int(height) <= 16384
+    a = np.ascontiguousarray(rgb, dtype=np.float32).reshape(-1)
+    if ok and a.size != 3 * int(width) * int(height):
+        raise ValueError("host_contrast_mask: %d values for a %d x %d image" % (a.size, width, height))
+    out = np.empty(int(width) * int(height) if ok else 1, dtype=np.uint8)
+    n = C.c_int32(0)
+    if load_library().adanerf_host_contrast_mask(a.ctypes.data, int(width), int(height), float(threshold), out.ctypes.data, C.byref(n)) != 0:
+        raise ValueError("adanerf_host_contrast_mask(%r x %r, threshold %r) refused" % (width, height, threshold))
+    return out, int(n.value)
+
+
 def choose_sampling(settings, pos=None, rot_c2w=None, precision="bf16", frames: int = 6, warmup: int = 2, margin: float = DEFAULT_RULE_MARGIN, **kw):
     """The default rule per workload: renders `frames` frames of this model / frame size / threshold in the split mode (exact by construction) and in
     the guarded mode (same frames while its measured band holds) and returns ("guarded" | "split", record): guarded only if it is >= margin faster
@@ -462,6 +483,7 @@ class NeuralRenderer:
         self._tu_hist = None          # (index of the history's buffer set, pos, rot) of the last render_upsampled since then
         self._dl_in_force = None      # what the last set_depth_limit installed; render_hybrid puts it back
         self._aux_in_force = (None, None)   # (depth_map, acc_map) of the last set_aux_outputs, likewise
+        self._disp_in_force = None    # the disp_map of the last set_disp_output; render_supersampled_adaptive puts it back
         self._fd = None               # foveate_density(): (gaze, rings, width, height) the device mask _fd_mask was filled for
 
     # -- lifecycle -------------------------------------------------------------------------------
@@ -537,7 +559,7 @@ class NeuralRenderer:
         self._check(self.lib.adanerf_set_frame_size(self.handle, 0 if width is None else int(width), 0 if height is None else int(height)))
         self.refresh_info()
         if self.info.rays_local != was_rays:      # the library dropped the per-ray buffers of the old rays_local
-            self._dl_in_force, self._aux_in_force = None, (None, None)
+            self._dl_in_force, self._aux_in_force, self._disp_in_force = None, (None, None), None
         self.settings.width, self.settings.height = self.info.width, self.info.height
         if hasattr(self, "_b_n") and self._b_n.shape[0] != self.info.rays_local:      # the library dropped the maps with the old rays_local
             self._drop_budget_buffers()
@@ -792,6 +814,88 @@ class NeuralRenderer:
         self.last_stats = total
         return self._o_rgb.numpy(), self._o_rgba.numpy(), total
 
+    # -- adaptive supersampling: the extra sub-pixel renders only at edges -------------------------------
+    host_contrast_mask = staticmethod(host_contrast_mask)
+
+    def contrast_mask(self, rgb, width: int, height: int, threshold: float, mask_out, count: bool = True):
+        """adanerf_contrast_mask over device images: ``mask_out`` [height*width] uint8 gets 0 where a neighbour of the pixel differs from
+        it by more than ``threshold`` in some channel's display value, 1 elsewhere.  Returns (code, n_flagged) instead of raising: tests
+        look at both; ``count=False`` passes no counter (asynchronous, n_flagged is None)."""
+        n = C.c_int32(-1)
+        rc = self.lib.adanerf_contrast_mask(self.handle, _ptr(rgb), int(width), int(height), float(threshold), _ptr(mask_out), C.byref(n) if count else None)
+        return rc, (int(n.value) if count else None)
+
+    def accumulate_masked_device(self, rgb, mask, values: int, n_rays: int, sum_out, first: bool):
+        """accumulate_device for the pixels ``mask`` selects (mask[p] < 32 and bit mask[p] of ``values``); every other pixel of sum_out
+        keeps its bytes (adanerf_accumulate_masked)"""
+        self._check(self.lib.adanerf_accumulate_masked(self.handle, _ptr(rgb), _ptr(mask), int(values) & 0xFFFFFFFF, int(n_rays), _ptr(sum_out), 1 if first else 0))
+
+    def resolve_mean_masked_device(self, sum_in, mask, values: int, n_rays: int, frames: int, rgba8_out=None, rgb_out=None):
+        """resolve_mean_device for the pixels ``mask`` selects; every other pixel of both outputs keeps its bytes
+        (adanerf_resolve_mean_masked)"""
+        self._check(self.lib.adanerf_resolve_mean_masked(self.handle, _ptr(sum_in), _ptr(mask), int(values) & 0xFFFFFFFF, int(n_rays), int(frames),
+                                                         _ptr(rgba8_out), _ptr(rgb_out)))
+
+    def render_supersampled_adaptive(self, s: int, threshold: float):
+        """One anti-aliased frame at the cost of its edges: a render at the pixel centres (the centre frame), adanerf_contrast_mask on its
+        fp32 colour, and -- if any pixel is flagged -- the s*s renders of subpixel_grid(s) for the flagged pixels alone
+        (adanerf_render_masked), summed and averaged over the centre frame (adanerf_accumulate_masked / adanerf_resolve_mean_masked).  A
+        flagged pixel carries the bytes render_supersampled(s) gives it, every other pixel the bytes of render_numpy().  s in
+        2..SUPERSAMPLE_MAX, threshold in [0, 1].  Returns (rgb [R,3] fp32, rgba8 [R,4] uint8, mask [R] uint8 with 0 = refined, n_refined,
+        Stats): the centre frame's record with the stage times summed over all passes.  The device copies stay in ``_o_rgb`` /
+        ``_o_rgba``; the pixel offset that was in force is restored, and the aux / disparity maps in force hold the centre frame (they are
+        switched off for the masked passes and put back)."""
+        if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 2 <= s <= SUPERSAMPLE_MAX:
+            raise ValueError("supersample: the adaptive form needs an integer S in 2..%d, got %r" % (SUPERSAMPLE_MAX, s))
+        thr = float(threshold)
+        if not (math.isfinite(thr) and 0.0 <= thr <= 1.0):
+            raise ValueError("supersample contrast: the threshold must lie in [0, 1], got %r" % (threshold,))
+        grid = subpixel_grid(s)
+        n, w, h = self.info.rays_local, self.info.width, self.info.height
+        if n != w * h:
+            raise AdaNeRFError("render_supersampled_adaptive: whole frames only (shard_world must be 1): the contrast rule reads a pixel's neighbours")
+        if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
+            self._o_rgb = self.empty((n, 3), np.float32)
+            self._o_rgba = self.empty((n, 4), np.uint8)
+        if not hasattr(self, "_ss_sum") or self._ss_sum.shape[0] != n:
+            if hasattr(self, "_ss_sum"):
+                self._ss_sum.free()
+                self._own.remove(self._ss_sum)
+            self._ss_sum = self.empty((n, 3), np.float32)
+        if not hasattr(self, "_sa_stage") or self._sa_stage.shape[0] != n:
+            for name in ("_sa_stage", "_sa_mask"):
+                if hasattr(self, name):
+                    a = getattr(self, name)
+                    a.free()
+                    self._own.remove(a)
+            self._sa_stage, self._sa_mask = self.empty((n, 3), np.float32), self.empty((n,), np.uint8)
+        was, was_aux, was_disp = self.pixel_offset, self._aux_in_force, self._disp_in_force
+        try:
+            self.set_pixel_offset(0.0, 0.0)
+            total = self.render(self._o_rgba, self._o_rgb, stats=True)
+            rc, flagged = self.contrast_mask(self._o_rgb, w, h, thr, self._sa_mask)
+            self._check(rc)
+            if flagged > 0:
+                self.set_aux_outputs(None, None)      # the maps belong to the centre frame
+                self.set_disp_output(None)
+                for k, (dx, dy) in enumerate(grid):
+                    self.set_pixel_offset(dx, dy)
+                    _, st = self.render_masked(self._sa_mask, 1, None, self._sa_stage)
+                    self.accumulate_masked_device(self._sa_stage, self._sa_mask, 1, n, self._ss_sum, first=k == 0)
+                    for name in ("ms_total", "ms_sample_mlp", "ms_compact", "ms_shade_mlp", "ms_composite"):
+                        setattr(total, name, getattr(total, name) + getattr(st, name))
+                self.resolve_mean_masked_device(self._ss_sum, self._sa_mask, 1, n, len(grid), self._o_rgba, self._o_rgb)
+        finally:
+            self.set_pixel_offset(*was)
+            if self._aux_in_force != was_aux:
+                self.set_aux_outputs(*was_aux)
+            if self._disp_in_force is not was_disp:
+                self.set_disp_output(was_disp)
+        self._last_frame = (self._o_rgba, w, h)
+        self._rp_frame = None      # the refined pixels have no single depth to warp by
+        self.last_stats = total
+        return self._o_rgb.numpy(), self._o_rgba.numpy(), self._sa_mask.numpy(), flagged, total
+
     def render(self, rgba8_out=None, rgb_out=None, stats: bool = False) -> Optional[Stats]:
         """One frame into caller-owned device buffers ([rays_local] uchar4 / [rays_local,3] fp32).
         ``stats=True`` synchronises and returns the per-stage timing record."""
@@ -822,6 +926,7 @@ class NeuralRenderer:
     def set_disp_output(self, disp_map=None):
         """Subsequent renders also fill [rays_local] fp32 disp_map = 1 / max(1e-10, depth_map / acc_map); None switches it off."""
         self._check(self.lib.adanerf_set_disp_output(self.handle, _ptr(disp_map)))
+        self._disp_in_force = disp_map
 
     def gather_from(self, dst, src_renderer: "NeuralRenderer", src, nbytes: int):
         """Stream-ordered copy of ``nbytes`` from ``src`` (on ``src_renderer``'s device / stream) into ``dst`` on this

@@ -801,6 +801,52 @@ int adanerf_present(adanerf_ctx* ctx, const void* d_src_rgba8, int32_t src_w, in
 int adanerf_accumulate(adanerf_ctx* ctx, const float* d_rgb_f32, int32_t n_rays, float* d_sum, int32_t first);
 int adanerf_resolve_mean(adanerf_ctx* ctx, const float* d_sum, int32_t n_rays, int32_t frames, void* d_rgba8_out, float* d_rgb_f32_out);
 
+/* Adaptive supersampling: the extra sub-pixel renders go only to the pixels that sit on an edge.  Three calls beside
+ * adanerf_render_masked, which renders an arbitrary pixel set at a cost that follows its size:
+ *
+ * adanerf_contrast_mask -- which pixels of a rendered fp32 frame need more rays.  One launch on the context's stream; width and height are
+ * arguments, independent of the context's frame size (as adanerf_present's are), sides in 1..16384.
+ *   d_rgb    [height*width,3] fp32, interleaved, row-major: the d_rgb_f32_out of a render
+ *   d_mask   [height*width] uint8, any alignment
+ * Definition, exact:
+ *   display value  v(p, ch) = fminf(fmaxf(d_rgb[3 p + ch], 0), 1), the clamp of adanerf_resolve_mean's byte contract: a NaN is 0, an
+ *                  infinity is 0 or 1
+ *   contrast       c(p, q) = max over ch of |v(p, ch) - v(q, ch)|, each difference one rounded fp32 subtraction
+ *   flagged        p iff some q among its up to 8 neighbours inside the image has c(p, q) > threshold; the comparison is strict and in
+ *                  fp32.  A 1 x 1 image flags nothing.  The relation is symmetric, so both sides of an edge are flagged and no dilation
+ *                  pass is needed
+ *   byte           d_mask[p] = 0 if flagged (render more), 1 otherwise: the convention of adanerf_reproject's holes and of the density
+ *                  mask's 0, so adanerf_render_masked(ctx, d_mask, 1, ..) selects the flagged pixels directly
+ *   n_flagged      a host pointer or NULL.  Given, it receives the number of 0 bytes, at the cost of one 4-byte read-back and one stream
+ *                  synchronisation (as adanerf_reproject's hole count); NULL keeps the call asynchronous
+ * With threshold 0 every pixel that differs from a neighbour at all is flagged; with 1 none is (no clamped difference exceeds 1).
+ * ADANERF_EINVAL, with nothing written: a NULL d_rgb or d_mask; a side outside 1..16384; a threshold that is not finite or lies outside
+ * [0, 1]; a d_rgb that is not 4-byte aligned; a d_mask that overlaps d_rgb.
+ *
+ * adanerf_accumulate_masked / adanerf_resolve_mean_masked -- adanerf_accumulate / adanerf_resolve_mean for the pixels a mask selects.
+ * The selection is adanerf_render_masked's, word for word: pixel p iff d_mask[p] < 32 and bit d_mask[p] of `values` is set
+ * (d_mask [n_rays] uint8).  A selected pixel gets exactly what the unmasked call computes: one rounded fp32 addition per value (or the
+ * copy, first != 0); one IEEE division by (float)frames and the byte contract above.  Every element of every other pixel -- in d_sum,
+ * d_rgb_f32_out and d_rgba8_out -- keeps its bytes and is not read.
+ * ADANERF_EINVAL, with nothing written: everything the unmasked call refuses; a NULL mask; values == 0; a mask that overlaps an image
+ * the call writes.
+ *
+ * The frame the hosts build from them (NeuralRenderer.render_supersampled_adaptive, --supersample S --supersample-contrast T): one render
+ * at offset (0, 0) fills the output images (the centre frame); adanerf_contrast_mask runs on its fp32 colour; if any pixel is flagged, the
+ * S * S offsets of adanerf_host_subpixel_grid(S, k) are walked in order, each adanerf_render_masked(values = 1) into a staging image and
+ * adanerf_accumulate_masked into the sum (first at k = 0); adanerf_resolve_mean_masked then writes the mean of the flagged pixels over the
+ * centre frame.  A flagged pixel carries, byte for byte, what the full S x S supersampling gives it; an unflagged pixel, byte for byte,
+ * what adanerf_render gives it (which is why the centre frame is a render of its own and not the grid's offset 0).  The aux and
+ * disparity maps are switched off for the masked passes, so they describe the centre frame whole.  Limits are adanerf_render_masked's.
+ * What it does not do: a depth or opacity criterion in the rule; progressive refinement (detecting again after each pass); coupling to
+ * adanerf_reproject or the temporal stages; launches sized on the device (the masked render reads its ray count back once per pass). */
+int adanerf_contrast_mask(adanerf_ctx* ctx, const float* d_rgb, int32_t width, int32_t height, float threshold, uint8_t* d_mask,
+                          int32_t* n_flagged);
+int adanerf_accumulate_masked(adanerf_ctx* ctx, const float* d_rgb_f32, const uint8_t* d_mask, uint32_t values, int32_t n_rays,
+                              float* d_sum, int32_t first);
+int adanerf_resolve_mean_masked(adanerf_ctx* ctx, const float* d_sum, const uint8_t* d_mask, uint32_t values, int32_t n_rays,
+                                int32_t frames, void* d_rgba8_out, float* d_rgb_f32_out);
+
 /* adanerf_reproject flags */
 enum { ADANERF_REPROJECT_FILL = 1 }; /* a destination pixel no source pixel lands in takes the farthest of its 8 neighbours' source pixels */
 
@@ -1048,6 +1094,11 @@ int adanerf_host_sphere_zc(int32_t width, int32_t height, float focal, const flo
  * ADANERF_EINVAL, with nothing written: everything adanerf_foveate_density refuses; a side outside 1..16384. */
 int adanerf_host_density_mask(int32_t width, int32_t height, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px,
                               const int32_t* stride, uint8_t* mask_out);
+
+/* The mask of adanerf_contrast_mask computed on the host: the same rule compiled from the same text (csrc/contrast_rule.hpp), byte for
+ * byte what the device writes.  rgb [height*width,3] fp32 and mask [height*width] uint8 in host memory; n_flagged may be NULL.
+ * ADANERF_EINVAL, with nothing written: everything adanerf_contrast_mask refuses. */
+int adanerf_host_contrast_mask(const float* rgb, int32_t width, int32_t height, float threshold, uint8_t* mask, int32_t* n_flagged);
 
 #ifdef __cplusplus
 }
