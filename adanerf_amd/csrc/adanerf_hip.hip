@@ -1404,6 +1404,86 @@ int adanerf_temporal_upsample(adanerf_ctx* c, int32_t scale, const float* d_cur_
   return ADANERF_OK;
 }
 
+int adanerf_temporal_resolve_sparse(adanerf_ctx* c, const uint8_t* d_mask, int32_t phase_x, int32_t phase_y, const float* d_cur_rgb, const float* d_cur_depth_map,
+                                    const float* d_cur_acc_map, const float cur_pos[3], const float cur_rot_c2w[9], const float* d_hist_rgb,
+                                    const float* d_hist_depth, const uint8_t* d_hist_count, const float prev_pos[3], const float prev_rot_c2w[9], float alpha,
+                                    float depth_tol, float acc_min, int32_t flags, float* d_out_rgb, float* d_out_depth, uint8_t* d_out_count, void* d_out_rgba8,
+                                    uint8_t* d_out_mask, int32_t* rejected_out) {
+  if (!c) return ADANERF_EINVAL;
+  if (!d_mask) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: NULL mask");
+  if (!d_cur_rgb || !d_cur_depth_map || !d_cur_acc_map || !d_out_rgb) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: NULL image");
+  if (!d_out_count) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: NULL d_out_count (without a count a placeholder cannot be told from a sample)");
+  if (d_hist_rgb && !d_hist_count) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: a history needs its count");
+  if (phase_x < 0 || phase_x > 7 || phase_y < 0 || phase_y > 7) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: phase_x and phase_y must be in 0..7");
+  if (!cur_pos || !cur_rot_c2w || (d_hist_rgb && (!prev_pos || !prev_rot_c2w))) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: NULL pose");
+  for (int k = 0; k < 9; ++k) {
+    if (!std::isfinite(cur_rot_c2w[k]) || (k < 3 && !std::isfinite(cur_pos[k])))
+      return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: a pose entry is not finite");
+    if (d_hist_rgb && (!std::isfinite(prev_rot_c2w[k]) || (k < 3 && !std::isfinite(prev_pos[k]))))      // without a history the previous pose is not read
+      return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: a pose entry is not finite");
+  }
+  if (!(alpha > 0.f && alpha <= 1.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: alpha must lie in (0, 1]");      // also a NaN
+  if (!(depth_tol >= 0.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: depth_tol must be >= 0");
+  if (!(acc_min >= 0.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: acc_min must be >= 0");
+  if (flags & ~ADANERF_TEMPORAL_CLAMP) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: flags must be 0 or ADANERF_TEMPORAL_CLAMP");
+  const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+  if ((at(d_cur_rgb) | at(d_cur_depth_map) | at(d_cur_acc_map) | at(d_hist_rgb) | at(d_hist_depth) | at(d_out_rgb) | at(d_out_depth) | at(d_out_rgba8)) & 3)
+    return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: fp32 and uchar4 images must be 4-byte aligned");
+  const int w = c->ms.info.width, h = c->ms.info.height, n = w * h;
+  const size_t n1 = static_cast<size_t>(n), b3 = n1 * 3 * sizeof(float), b1 = n1 * sizeof(float);
+  if ((d_hist_rgb && ranges_overlap(d_out_rgb, b3, d_hist_rgb, b3)) || ranges_overlap(d_out_rgb, b3, d_cur_rgb, b3) ||
+      (d_out_depth && d_hist_depth && ranges_overlap(d_out_depth, b1, d_hist_depth, b1)) ||
+      (d_hist_count && ranges_overlap(d_out_count, n1, d_hist_count, n1)))
+    return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: an output overlaps the image it is gathered from (the history is ping-ponged, not updated in place)");
+  if (ranges_overlap(d_mask, n1, d_out_rgb, b3) || (d_out_depth && ranges_overlap(d_mask, n1, d_out_depth, b1)) || ranges_overlap(d_mask, n1, d_out_count, n1) ||
+      (d_out_rgba8 && ranges_overlap(d_mask, n1, d_out_rgba8, b1)) || (d_out_mask && ranges_overlap(d_mask, n1, d_out_mask, n1)))
+    return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: the mask overlaps an output (a reconstructed pixel reads the bytes of its cell)");
+  if (c->ms.info.use_ndc) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_temporal_resolve_sparse: the depth_map of a useNDC model is NDC depth, not a distance along the ray");
+  if (c->ms.rg.world != 1) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_temporal_resolve_sparse: whole frames only (shard_world must be 1)");
+  BIND(c);
+  if (!c->reproj_holes.p) {      // the counter shared with adanerf_reproject and the other temporal stages: all run on the context's stream
+    if (int rc = dev_alloc(c, &c->reproj_holes, 64)) return rc;
+  }
+  const bool depth_test = d_hist_rgb && d_hist_depth;
+  if (depth_test && c->upsample_zp.bytes < b1) {      // the scratch adanerf_temporal_upsample keeps its pass A in
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // a call in flight may still use the smaller buffer
+    if (int rc = dev_alloc(c, &c->upsample_zp, b1)) return rc;
+  }
+  UpsampleParams a{};      // pass A is adanerf_temporal_upsample's with the context's generator at pixel centres; it reads nothing else of g_hi
+  a.g_lo = c->ms.rg;
+  std::memcpy(a.g_lo.pos, cur_pos, 3 * sizeof(float));
+  std::memcpy(a.g_lo.rot, cur_rot_c2w, 9 * sizeof(float));
+  TemporalParams p{};
+  p.g = a.g_lo;      // pixel centres: the offset of adanerf_set_pixel_offset is not applied
+  if (d_hist_rgb) {
+    std::memcpy(p.prev_pos, prev_pos, 3 * sizeof(float));
+    std::memcpy(p.prev_rot, prev_rot_c2w, 9 * sizeof(float));
+    std::memcpy(a.prev_pos, prev_pos, 3 * sizeof(float));
+    std::memcpy(a.prev_rot, prev_rot_c2w, 9 * sizeof(float));
+  }
+  p.alpha = alpha;
+  p.depth_tol = depth_tol;
+  p.acc_min = a.acc_min = acc_min;
+  p.origin_is_camera = a.origin_is_camera = c->ms.coarse_fine ? 1 : 0;
+  p.clamp = (flags & ADANERF_TEMPORAL_CLAMP) ? 1 : 0;
+  int32_t* rejected = reinterpret_cast<int32_t*>(c->reproj_holes.p);
+  float* zp = reinterpret_cast<float*>(c->upsample_zp.p);
+  HIP_TRY(c, hipMemsetAsync(rejected, 0, sizeof(int32_t), c->stream));
+  if (depth_test) {
+    hipLaunchKernelGGL(upsample_depth_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, a, d_cur_depth_map, d_cur_acc_map, zp);
+    HIP_TRY(c, hipGetLastError());
+  }
+  const dim3 grid((w + kTemporalTileW - 1) / kTemporalTileW, (h + kTemporalTileH - 1) / kTemporalTileH), block(256);
+  hipLaunchKernelGGL(sparse_resolve_kernel, grid, block, 0, c->stream, p, phase_x, phase_y, d_mask, d_cur_rgb, d_cur_depth_map, d_cur_acc_map, zp, d_hist_rgb,
+                     d_hist_depth, d_hist_count, d_out_rgb, d_out_depth, d_out_count, static_cast<uchar4*>(d_out_rgba8), d_out_mask, rejected);
+  HIP_TRY(c, hipGetLastError());
+  if (rejected_out) {
+    HIP_TRY(c, hipMemcpyAsync(rejected_out, rejected, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  return ADANERF_OK;
+}
+
 int adanerf_sync(adanerf_ctx* c) {
   BIND(c);
   HIP_RETURN(c, hipStreamSynchronize(c->stream));
@@ -2168,12 +2248,14 @@ int adanerf_blend_behind(adanerf_ctx* c, const float* d_rgb, const float* d_acc,
   HIP_RETURN(c, hipGetLastError());
 }
 
-int adanerf_foveate_density(adanerf_ctx* c, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* stride, uint8_t* d_mask) {
+// adanerf_foveate_density is phase (0, 0) of adanerf_foveate_density_phased; `who` names the entry point in the error text
+static int foveate_density_at(adanerf_ctx* c, const std::string& who, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* stride,
+                              int32_t phase_x, int32_t phase_y, uint8_t* d_mask) {
   if (!c) return ADANERF_EINVAL;
-  if (!d_mask) return fail(c, ADANERF_EINVAL, "adanerf_foveate_density: NULL mask");
+  if (!d_mask) return fail(c, ADANERF_EINVAL, who + ": NULL mask");
   DensityRule f;
-  if (const char* why = density_rule_fill(gaze_x, gaze_y, n_rings, radius_px, stride, &f)) return fail(c, ADANERF_EINVAL, std::string("adanerf_foveate_density: ") + why);
-  if (c->ms.rg.world != 1) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_foveate_density: whole frames only (shard_world must be 1): the reconstruction reads a pixel's neighbours");
+  if (const char* why = density_rule_fill(gaze_x, gaze_y, n_rings, radius_px, stride, &f, phase_x, phase_y)) return fail(c, ADANERF_EINVAL, who + ": " + why);
+  if (c->ms.rg.world != 1) return fail(c, ADANERF_EUNSUPPORTED, who + ": whole frames only (shard_world must be 1): the reconstruction reads a pixel's neighbours");
   BIND(c);
   const int w = c->ms.info.width, h = c->ms.info.height;
   const int64_t groups = (static_cast<int64_t>(w) * h + 3) / 4;      // four pixels per thread
@@ -2183,21 +2265,32 @@ int adanerf_foveate_density(adanerf_ctx* c, float gaze_x, float gaze_y, int32_t 
   HIP_RETURN(c, hipGetLastError());
 }
 
-int adanerf_fill_density(adanerf_ctx* c, const uint8_t* d_mask, int32_t width, int32_t height, float* d_rgb, float* d_depth_map, float* d_acc_map, void* d_rgba8,
-                         int32_t* unfilled_out) {
+int adanerf_foveate_density(adanerf_ctx* c, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* stride, uint8_t* d_mask) {
+  return foveate_density_at(c, "adanerf_foveate_density", gaze_x, gaze_y, n_rings, radius_px, stride, 0, 0, d_mask);
+}
+
+int adanerf_foveate_density_phased(adanerf_ctx* c, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* stride, int32_t phase_x,
+                                   int32_t phase_y, uint8_t* d_mask) {
+  return foveate_density_at(c, "adanerf_foveate_density_phased", gaze_x, gaze_y, n_rings, radius_px, stride, phase_x, phase_y, d_mask);
+}
+
+// adanerf_fill_density is phase (0, 0) of adanerf_fill_density_phased
+static int fill_density_at(adanerf_ctx* c, const std::string& who, const uint8_t* d_mask, int32_t width, int32_t height, int32_t phase_x, int32_t phase_y, float* d_rgb,
+                           float* d_depth_map, float* d_acc_map, void* d_rgba8, int32_t* unfilled_out) {
   if (!c) return ADANERF_EINVAL;
-  if (!d_mask || !d_rgb) return fail(c, ADANERF_EINVAL, "adanerf_fill_density: NULL mask or d_rgb");
+  if (!d_mask || !d_rgb) return fail(c, ADANERF_EINVAL, who + ": NULL mask or d_rgb");
   if (width < 1 || height < 1 || width > kPresentMaxSide || height > kPresentMaxSide)
-    return fail(c, ADANERF_EINVAL, "adanerf_fill_density: every side must be in 1.." + std::to_string(kPresentMaxSide));
+    return fail(c, ADANERF_EINVAL, who + ": every side must be in 1.." + std::to_string(kPresentMaxSide));
+  if (phase_x < 0 || phase_x > 7 || phase_y < 0 || phase_y > 7) return fail(c, ADANERF_EINVAL, who + ": phase_x and phase_y must be in 0..7");
   if ((reinterpret_cast<uintptr_t>(d_rgb) | reinterpret_cast<uintptr_t>(d_depth_map) | reinterpret_cast<uintptr_t>(d_acc_map) | reinterpret_cast<uintptr_t>(d_rgba8)) & 3)
-    return fail(c, ADANERF_EINVAL, "adanerf_fill_density: fp32 and uchar4 images must be 4-byte aligned");
+    return fail(c, ADANERF_EINVAL, who + ": fp32 and uchar4 images must be 4-byte aligned");
   const size_t n = static_cast<size_t>(width) * static_cast<size_t>(height);
   const void* const img[5] = {d_mask, d_rgb, d_depth_map, d_acc_map, d_rgba8};
   const size_t img_bytes[5] = {n, n * 3 * sizeof(float), n * sizeof(float), n * sizeof(float), n * 4};
   for (int i = 0; i < 5; ++i)
     for (int j = i + 1; j < 5; ++j)
       if (img[i] && img[j] && ranges_overlap(img[i], img_bytes[i], img[j], img_bytes[j]))
-        return fail(c, ADANERF_EINVAL, "adanerf_fill_density: the images overlap one another or the mask");
+        return fail(c, ADANERF_EINVAL, who + ": the images overlap one another or the mask");
   BIND(c);
   if (!c->reproj_holes.p) {      // the counter shared with adanerf_reproject and the temporal stages: all run on the context's stream
     if (int rc = dev_alloc(c, &c->reproj_holes, 64)) return rc;
@@ -2205,13 +2298,23 @@ int adanerf_fill_density(adanerf_ctx* c, const uint8_t* d_mask, int32_t width, i
   int32_t* unfilled = reinterpret_cast<int32_t*>(c->reproj_holes.p);
   HIP_TRY(c, hipMemsetAsync(unfilled, 0, sizeof(int32_t), c->stream));
   const DensityFill d{d_mask, d_rgb, d_depth_map, d_acc_map, static_cast<uchar4*>(d_rgba8), unfilled};
-  hipLaunchKernelGGL(density_fill_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, c->stream, d, width, height);
+  hipLaunchKernelGGL(density_fill_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, c->stream, d, width, height, phase_x, phase_y);
   HIP_TRY(c, hipGetLastError());
   if (unfilled_out) {
     HIP_TRY(c, hipMemcpyAsync(unfilled_out, unfilled, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   return ADANERF_OK;
+}
+
+int adanerf_fill_density(adanerf_ctx* c, const uint8_t* d_mask, int32_t width, int32_t height, float* d_rgb, float* d_depth_map, float* d_acc_map, void* d_rgba8,
+                         int32_t* unfilled_out) {
+  return fill_density_at(c, "adanerf_fill_density", d_mask, width, height, 0, 0, d_rgb, d_depth_map, d_acc_map, d_rgba8, unfilled_out);
+}
+
+int adanerf_fill_density_phased(adanerf_ctx* c, const uint8_t* d_mask, int32_t width, int32_t height, int32_t phase_x, int32_t phase_y, float* d_rgb,
+                                float* d_depth_map, float* d_acc_map, void* d_rgba8, int32_t* unfilled_out) {
+  return fill_density_at(c, "adanerf_fill_density_phased", d_mask, width, height, phase_x, phase_y, d_rgb, d_depth_map, d_acc_map, d_rgba8, unfilled_out);
 }
 
 int adanerf_contrast_mask(adanerf_ctx* c, const float* d_rgb, int32_t width, int32_t height, float threshold, uint8_t* d_mask, int32_t* n_flagged) {

@@ -1,4 +1,5 @@
-// N10: foveated ray density (adanerf_foveate_density / adanerf_fill_density) -- the two kernels either side of adanerf_render_masked.
+// N10: foveated ray density (adanerf_foveate_density / adanerf_fill_density and their _phased forms, of which the unphased ones are
+// phase (0, 0)) -- the two kernels either side of adanerf_render_masked.
 //   density_mask_kernel  the byte mask of a gaze point and rings of strides 1 / 2 / 4 / 8 (density_rule.hpp, shared with the host mirror):
 //                        0 = render this pixel, else the pixel's stride.  Four pixels and one 4-byte store per thread where the mask
 //                        pointer is 4-byte aligned (a wave then writes 256 contiguous bytes, not 64), single bytes otherwise and at the end.
@@ -56,22 +57,22 @@ __device__ __forceinline__ float density_blend(float c00, float c01, float c10, 
   return __fadd_rn(top, __fmul_rn(fy, __fsub_rn(bot, top)));
 }
 
-__global__ __launch_bounds__(256) void density_fill_kernel(DensityFill d, int w, int h) {
+__global__ __launch_bounds__(256) void density_fill_kernel(DensityFill d, int w, int h, int phase_x, int phase_y) {
   const int n = w * h;      // <= 2^28 (sides <= 16384): 3 n values fit 32 bits too
   const int p = static_cast<int>(blockIdx.x) * 256 + static_cast<int>(threadIdx.x);
   const int s = p < n ? d.mask[p] : 0;
   bool missing = false;
   if (s == 2 || s == 4 || s == 8) {
     const int y = static_cast<int>(static_cast<uint32_t>(p) / static_cast<uint32_t>(w)), x = p - y * w;
-    const int x0 = x & ~(s - 1), y0 = y & ~(s - 1);
-    const bool two_x = x != x0 && x0 + s < w, two_y = y != y0 && y0 + s < h;
-    const int x1 = two_x ? x0 + s : x0, y1 = two_y ? y0 + s : y0;
-    const int i00 = y0 * w + x0, i01 = y0 * w + x1, i10 = y1 * w + x0, i11 = y1 * w + x1;
+    const DensityAxis ax = density_cell_axis(x, phase_x, s, w), ay = density_cell_axis(y, phase_y, s, h);
+    const bool two_x = ax.c1 != ax.c0, two_y = ay.c1 != ay.c0;
+    missing = ax.none || ay.none;      // a frame narrower than the stride: no corner on that axis, nothing is read
+    const int i00 = ay.c0 * w + ax.c0, i01 = ay.c0 * w + ax.c1, i10 = ay.c1 * w + ax.c0, i11 = ay.c1 * w + ax.c1;
     // the corners that are not distinct repeat one that is: their bytes are looked at twice, nothing more
-    missing = (d.mask[i00] | d.mask[i01] | d.mask[i10] | d.mask[i11]) != 0;
+    if (!missing) missing = (d.mask[i00] | d.mask[i01] | d.mask[i10] | d.mask[i11]) != 0;
     if (!missing) {
-      const float inv_s = s == 2 ? 0.5f : (s == 4 ? 0.25f : 0.125f);      // (x - x0) / s, exact: s is a power of two
-      const float fx = static_cast<float>(x - x0) * inv_s, fy = static_cast<float>(y - y0) * inv_s;
+      const float inv_s = s == 2 ? 0.5f : (s == 4 ? 0.25f : 0.125f);      // m / s, exact: s is a power of two
+      const float fx = static_cast<float>(ax.m) * inv_s, fy = static_cast<float>(ay.m) * inv_s;
       float out[3];
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch)

@@ -15,6 +15,7 @@
 //   N8        mask_bits_kernel / mask_scatter_kernel   a byte mask as bit words for refine_list_kernel; the pixels of a listed batch to their places (masked rendering)
 //   N9        blend_behind_kernel   the rasterised colour behind a depth-limited frame, through the transmittance that is left (hybrid rendering)
 //   N10       density_mask_kernel / density_fill_kernel   the render mask of a gaze and rings of strides; the pixels between the rendered ones, bilinear (foveated ray density)
+//   N12       sparse_resolve_kernel   the temporal resolve of a foveated frame: rendered pixels refresh the history, reconstructed ones keep it (phased lattice)
 //   N11       contrast_mask_kernel / accumulate_masked_kernel / resolve_mean_masked_kernel   the pixels on an edge of a rendered frame; sum and mean of the sub-pixel renders of those alone (adaptive supersampling)
 // plus explicit-feature debug kernels (ray_features_kernel, shade_features_kernel) that materialise
 // what the reference launchers wrote to memory, for parity tests only.
@@ -40,4 +41,5 @@
 #include "k_depth_limit.hip.hpp"
 #include "k_blend.hip.hpp"
 #include "k_density.hip.hpp"
+#include "k_sparse_temporal.hip.hpp"
 #include "k_contrast.hip.hpp"

@@ -481,14 +481,31 @@ int adanerf_host_sphere_zc(int32_t width, int32_t height, float focal, const flo
   return ADANERF_OK;
 }
 
-int adanerf_host_density_mask(int32_t width, int32_t height, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* stride,
-                              uint8_t* mask_out) {
-  if (!mask_out) return fail(ADANERF_EINVAL, "adanerf_host_density_mask: NULL mask");
-  if (width < 1 || width > 16384 || height < 1 || height > 16384) return fail(ADANERF_EINVAL, "adanerf_host_density_mask: width and height must be in 1..16384");
+// adanerf_host_density_mask is phase (0, 0) of adanerf_host_density_mask_phased
+static int host_density_mask_at(const std::string& who, int32_t width, int32_t height, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px,
+                                const int32_t* stride, int32_t phase_x, int32_t phase_y, uint8_t* mask_out) {
+  if (!mask_out) return fail(ADANERF_EINVAL, who + ": NULL mask");
+  if (width < 1 || width > 16384 || height < 1 || height > 16384) return fail(ADANERF_EINVAL, who + ": width and height must be in 1..16384");
   DensityRule f;
-  if (const char* why = density_rule_fill(gaze_x, gaze_y, n_rings, radius_px, stride, &f)) return fail(ADANERF_EINVAL, std::string("adanerf_host_density_mask: ") + why);
+  if (const char* why = density_rule_fill(gaze_x, gaze_y, n_rings, radius_px, stride, &f, phase_x, phase_y)) return fail(ADANERF_EINVAL, who + ": " + why);
   for (int y = 0; y < height; ++y)
     for (int x = 0; x < width; ++x) mask_out[static_cast<size_t>(y) * width + x] = density_mask_byte(f, x, y, width, height);
+  return ADANERF_OK;
+}
+
+int adanerf_host_density_mask(int32_t width, int32_t height, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* stride,
+                              uint8_t* mask_out) {
+  return host_density_mask_at("adanerf_host_density_mask", width, height, gaze_x, gaze_y, n_rings, radius_px, stride, 0, 0, mask_out);
+}
+
+int adanerf_host_density_mask_phased(int32_t width, int32_t height, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* stride,
+                                     int32_t phase_x, int32_t phase_y, uint8_t* mask_out) {
+  return host_density_mask_at("adanerf_host_density_mask_phased", width, height, gaze_x, gaze_y, n_rings, radius_px, stride, phase_x, phase_y, mask_out);
+}
+
+int adanerf_host_density_phase(int32_t k, int32_t* phase_x, int32_t* phase_y) {
+  if (!phase_x || !phase_y) return fail(ADANERF_EINVAL, "adanerf_host_density_phase: NULL output");
+  density_phase(k, phase_x, phase_y);
   return ADANERF_OK;
 }
 

@@ -7,7 +7,7 @@ reference's second default metric (``metrics = ["flip", "psnr"]`` :613-615): the
     python -m adanerf_amd.evaluate <model_dir> <dataset_dir> [--set test] [--out DIR] [--video out.y4m] [--precision bf16]
                                    [--metrics psnr flip] [--sweep-thresholds T ...] [--sweep-samples N ...] [--sweep-scales S ...]
                                    [--reproject-stride K [--rerender holes|unsourced]] [--supersample S] [--present-filter nearest|linear|area]
-                                   [--fovea-density R:S[,R:S...],S] [--supersample-contrast T]
+                                   [--fovea-density R:S[,R:S...],S [--fovea-temporal ALPHA] [--fovea-temporal-still K]] [--supersample-contrast T]
 
 ``--sweep-thresholds`` / ``--sweep-samples`` render the set once per (N, threshold) of their cross product on ONE context
 (``NeuralRenderer.set_selection``: an AdaNeRF network is trained once and rendered at any sample budget) -- the two axes of a quality
@@ -32,7 +32,10 @@ the flagged pixels alone through ``adanerf_render_masked``); the summary gains `
 
 ``--fovea-density SPEC`` scores, beside every full frame, the same pose rendered at a foveated ray density around a gaze at the frame
 centre (``NeuralRenderer.render_foveated``: the lattice of ``adanerf_foveate_density`` rendered, the pixels in between rebuilt by
-``adanerf_fill_density``), on the same context.
+``adanerf_fill_density``), on the same context.  ``--fovea-temporal ALPHA`` adds, beside that fill-only frame, the same pose through
+``NeuralRenderer.render_foveated_temporal`` (the lattice at the next phase of its 64-phase cycle, resolved against a history by
+``adanerf_temporal_resolve_sparse``), the set in order as one sequence; ``--fovea-temporal-still K`` scores per pose the frame after K
+such frames at rest from a cut instead.
 
 Dataset layout (src/datasets.py:146-213, 361-365, 480-542): ``dataset_info.json`` (``resolution``,
 ``camera_angle_x``, ``view_cell_center``, ``view_cell_size`` ...), ``transforms_<set>.json`` with
@@ -111,7 +114,7 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
              precision: str = "bf16", batch_size: int = -1, max_frames: int = 0, quiet: bool = False,
              video: Optional[str] = None, fps: int = 30, metrics=("psnr",), fovea=None, sweep_thresholds=None, sweep_samples=None, reproject_stride=None,
              supersample=None, present_filter=None, temporal=None, temporal_still=None, temporal_upsample=None, temporal_upsample_frames=None,
-             rerender=None, fovea_density=None, supersample_contrast=None, sweep_scales=None):
+             rerender=None, fovea_density=None, fovea_temporal=None, fovea_temporal_still=None, supersample_contrast=None, sweep_scales=None):
     """metrics: "psnr" (always reported where a ground-truth image exists) and / or "flip": each record gains ``flip``, the summary
     ``mean_flip``, and with out_dir the error map is written as an 8-bit greyscale ``%05d_flip.png``.
 
@@ -178,7 +181,15 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     ``rendered_fraction`` (rays rendered, of w h), ``ms_foveated`` (the masked render's own time; the fill is not in it) and, with "flip",
     ``flip_foveated``; the summary ``mean_psnr_foveated``, ``mean_rendered_fraction``, ``mean_ms_foveated`` and ``mean_flip_foveated``;
     out_dir gets ``%05d_foveated.png``.  The plain keys are those of a run without the option.  Not with fovea (the masked render refuses
-    budget maps), reproject_stride, supersample, sweep_scales, temporal, temporal_still or temporal_upsample."""
+    budget maps), reproject_stride, supersample, sweep_scales, temporal, temporal_still or temporal_upsample.
+
+    fovea_temporal (ALPHA in (0, 1] or None; needs fovea_density): beside the fill-only frame, the same pose once more through
+    NeuralRenderer.render_foveated_temporal -- the lattice at the next phase of its 64-phase cycle, resolved against a history that knows
+    which pixels were rendered (adanerf_temporal_resolve_sparse) -- the set in order as one sequence.  Records gain
+    ``psnr_foveated_temporal`` / ``mse_foveated_temporal``, ``foveated_temporal_rejected_fraction`` and, with "flip",
+    ``flip_foveated_temporal``; the summary their means; out_dir gets ``%05d_foveated_temporal.png``.
+    fovea_temporal_still (K >= 1 or None): per pose instead, the frame after K such frames at rest from a cut; ALPHA is ``fovea_temporal``
+    or, without it, 0.1; the summary carries ``fovea_temporal_still``."""
     if isinstance(fovea, str):
         fovea = parse_fovea(fovea)
     if fovea_density is not None:
@@ -231,6 +242,14 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     if fovea_density and (fovea or stride or ss or sweep_scales or ta or tu):
         raise ValueError("fovea_density renders a lattice of whole frames at the dataset's resolution without budget maps: not together with "
                          "fovea, reproject_stride, supersample, sweep_scales, temporal, temporal_still or temporal_upsample")
+    ft_still = int(fovea_temporal_still) if fovea_temporal_still is not None else 0
+    if fovea_temporal_still is not None and (ft_still != fovea_temporal_still or ft_still < 1):
+        raise ValueError("fovea_temporal_still must be an integer >= 1, got %s" % (fovea_temporal_still,))
+    ft = (0.1 if fovea_temporal is None else float(fovea_temporal)) if (fovea_temporal is not None or ft_still) else 0.0
+    if fovea_temporal is not None and not 0.0 < ft <= 1.0:
+        raise ValueError("fovea_temporal must lie in (0, 1], got %s" % (fovea_temporal,))
+    if ft and not fovea_density:
+        raise ValueError("fovea_temporal / fovea_temporal_still resolve the frames of a moving lattice: they need fovea_density")
     if present_filter not in PRESENT_FILTERS:
         raise ValueError("present_filter must be None, 'nearest', 'linear' or 'area', got %r" % (present_filter,))
     want_flip = "flip" in metrics
@@ -248,7 +267,7 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
         vid = Y4mWriter(video, w, h, fps) if video else None
         d_ref = r.empty((w * h, 3), np.float32) if want_flip else None
         d_map = r.empty((w * h,), np.float32) if want_flip and out_dir else None
-        d_pres = r.empty((w * h, 3), np.float32) if want_flip and (sweep_scales or stride or ta or tu) else None      # (the foveated frame is scored in place)
+        d_pres = r.empty((w * h, 3), np.float32) if want_flip and (sweep_scales or stride or ta or tu or ft) else None      # (the foveated frame is scored in place)
         if stride:
             r.enable_reprojection()
         if ta:
@@ -269,6 +288,8 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                 r.reset_temporal()      # a pass over the set is one sequence
             if fovea_density:      # again for every setting: the mask belongs to the frame size
                 r.foveate_density((0.5 * rw, 0.5 * rh), fovea_density)
+            if ft:      # a pass over the set is one sequence, from a cut
+                r.enable_foveated_temporal(alpha=ft)
             for i, fr in enumerate(frames):
                 ref = None
                 warped = bool(stride) and i % stride != 0
@@ -349,6 +370,19 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                             rec.update(flip_foveated=r.flip_device(r._o_rgb, d_ref, w, h))
                     if out_dir:
                         write_png(os.path.join(out_dir, "%05d_foveated.png" % i), f_rgba[:, :3].reshape(h, w, 3))
+                if ft:      # the same pose once more on the lattice of the next phase, resolved against the history (or K times from a cut)
+                    if ft_still:
+                        r.reset_foveated_temporal()
+                    for _ in range(ft_still or 1):
+                        s_rgb, s_rgba, _, s_rejected, _, _ = r.render_foveated_temporal()
+                    rec.update(foveated_temporal_rejected_fraction=s_rejected / float(w * h))
+                    if ref is not None:
+                        s_mse = float(np.mean((s_rgb.astype(np.float64) - ref) ** 2))
+                        rec.update(mse_foveated_temporal=s_mse, psnr_foveated_temporal=psnr_from_mse(s_mse))
+                        if want_flip:
+                            rec.update(flip_foveated_temporal=r.flip_device(d_pres.upload(s_rgb), d_ref, w, h))
+                    if out_dir:
+                        write_png(os.path.join(out_dir, "%05d_foveated_temporal.png" % i), s_rgba[:, :3].reshape(h, w, 3))
                 if out_dir:
                     write_png(os.path.join(out_dir, "%05d.png" % i), rgba[:, :3].reshape(h, w, 3))
                 if vid:
@@ -377,7 +411,8 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     if sweep:
         return dict(frames=len(frames), sweep=sweep, **(dict(supersample=ss) if ss else {}), **(dict(temporal_still=still) if still else {})), results
     return dict(summarise(results, want_flip), **(dict(supersample=ss) if ss else {}), **(dict(temporal_still=still) if still else {}),
-                **(dict(temporal_upsample=tu, temporal_upsample_frames=tu_frames) if tu else {})), results
+                **(dict(temporal_upsample=tu, temporal_upsample_frames=tu_frames) if tu else {}),
+                **(dict(fovea_temporal_still=ft_still) if ft_still else {})), results
 
 
 def summarise(results: List[dict], want_flip: bool) -> dict:
@@ -420,6 +455,13 @@ def summarise(results: List[dict], want_flip: bool) -> dict:
             summary["mean_flip_foveated"] = float(np.mean([x["flip_foveated"] for x in part])) if part else None
         summary["mean_rendered_fraction"] = float(np.mean([x["rendered_fraction"] for x in results if "rendered_fraction" in x]))
         summary["mean_ms_foveated"] = float(np.mean([x["ms_foveated"] for x in results if "ms_foveated" in x]))
+    if any("foveated_temporal_rejected_fraction" in x for x in results):      # fovea_temporal: the resolved frames beside the fill-only ones
+        part = [x for x in results if "psnr_foveated_temporal" in x]
+        summary["mean_psnr_foveated_temporal"] = float(np.mean([x["psnr_foveated_temporal"] for x in part])) if part else None
+        if want_flip:
+            summary["mean_flip_foveated_temporal"] = float(np.mean([x["flip_foveated_temporal"] for x in part])) if part else None
+        summary["mean_foveated_temporal_rejected_fraction"] = float(np.mean([x["foveated_temporal_rejected_fraction"] for x in results
+                                                                             if "foveated_temporal_rejected_fraction" in x]))
     if any("refined_fraction" in x for x in results):      # supersample_contrast: the share of the pixels that got the S x S renders
         summary["mean_refined_fraction"] = float(np.mean([x["refined_fraction"] for x in results if "refined_fraction" in x]))
     return summary
@@ -477,6 +519,12 @@ def build_parser():
                          "stride outside them; every pose is rendered once more on that lattice and reconstructed (adanerf_foveate_density / "
                          "adanerf_render_masked / adanerf_fill_density); the summary gains mean_psnr_foveated / mean_rendered_fraction / "
                          "mean_ms_foveated (and mean_flip_foveated with --metrics flip)")
+    ap.add_argument("--fovea-temporal", type=float, default=None, metavar="ALPHA",
+                    help="with --fovea-density: every pose once more on the lattice of the next phase of its 64-phase cycle, resolved against a "
+                         "history that knows which pixels were rendered (adanerf_temporal_resolve_sparse, rendered-pixel weight ALPHA in (0, 1]); "
+                         "the summary gains mean_psnr_foveated_temporal / mean_foveated_temporal_rejected_fraction beside mean_psnr_foveated")
+    ap.add_argument("--fovea-temporal-still", type=int, default=None, metavar="K",
+                    help="per pose, score the frame after K such frames at rest from a cut instead (ALPHA of --fovea-temporal, default 0.1)")
     ap.add_argument("--supersample-contrast", type=float, default=None, metavar="T",
                     help="with --supersample S >= 2: adaptive supersampling -- one render at the pixel centres, the S x S renders only for the "
                          "pixels a neighbour of which differs by more than T (0..1) in some channel (adanerf_contrast_mask / "
@@ -504,6 +552,12 @@ def main(argv=None):
         if (a.fovea is not None or a.reproject_stride is not None or a.supersample is not None or a.sweep_scales or a.temporal is not None or
                 a.temporal_still is not None or a.temporal_upsample is not None):
             ap.error("--fovea-density cannot be combined with --fovea, --reproject-stride, --supersample, --sweep-scales or the --temporal options")
+    if (a.fovea_temporal is not None or a.fovea_temporal_still is not None) and a.fovea_density is None:
+        ap.error("--fovea-temporal / --fovea-temporal-still need --fovea-density")
+    if a.fovea_temporal is not None and not 0.0 < a.fovea_temporal <= 1.0:
+        ap.error("--fovea-temporal ALPHA: ALPHA must lie in (0, 1]")
+    if a.fovea_temporal_still is not None and a.fovea_temporal_still < 1:
+        ap.error("--fovea-temporal-still K: K must be >= 1")
     if a.supersample_contrast is not None:
         if a.supersample is None or a.supersample < 2:
             ap.error("--supersample-contrast requires --supersample S with S >= 2")
@@ -516,7 +570,7 @@ def main(argv=None):
                           fovea=a.fovea, reproject_stride=a.reproject_stride, rerender=a.rerender, supersample=a.supersample, present_filter=a.present_filter,
                           temporal=a.temporal, temporal_still=a.temporal_still, temporal_upsample=a.temporal_upsample,
                           temporal_upsample_frames=a.temporal_upsample_frames, fovea_density=a.fovea_density,
-                          supersample_contrast=a.supersample_contrast)
+                          supersample_contrast=a.supersample_contrast, fovea_temporal=a.fovea_temporal, fovea_temporal_still=a.fovea_temporal_still)
     print(json.dumps(summary))
 
 

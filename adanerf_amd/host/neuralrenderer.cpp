@@ -171,6 +171,10 @@ bool NeuralRenderer::init() {
     err = "--taau: the depth of a useNDC model is NDC depth";
     return false;
   }
+  if (settings.fovea_temporal_alpha > 0.f && info_.use_ndc) {
+    err = "--fovea-temporal: the depth of a useNDC model is NDC depth";
+    return false;
+  }
   if (!allocFrameBuffers()) return false;
   if (settings.write_window &&
       adanerf_malloc(ctx, static_cast<size_t>(settings.window_width) * settings.window_height * 4, &d_window) != ADANERF_OK) {
@@ -228,6 +232,17 @@ bool NeuralRenderer::allocFrameBuffers() {
       if (*bufs[k] && adanerf_free(ctx, *bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
       *bufs[k] = nullptr;
       if (adanerf_malloc(ctx, bytes[k], bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+    }
+    if (settings.fovea_temporal_alpha > 0.f) {      // the aux outputs and the history belong to the frame size too
+      taa_have = false;
+      void** more[] = {&d_depth, &d_acc, &d_hist[0][0], &d_hist[0][1], &d_hist[0][2], &d_hist[1][0], &d_hist[1][1], &d_hist[1][2]};
+      const size_t more_bytes[] = {n * 4, n * 4, n * 12, n * 4, n, n * 12, n * 4, n};
+      for (int k = 0; k < 8; ++k) {
+        if (*more[k] && adanerf_free(ctx, *more[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+        *more[k] = nullptr;
+        if (adanerf_malloc(ctx, more_bytes[k], more[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+      }
+      if (adanerf_set_aux_outputs(ctx, static_cast<float*>(d_depth), static_cast<float*>(d_acc)) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
     }
   }
   if (settings.supersample > 1) {
@@ -384,6 +399,44 @@ bool NeuralRenderer::renderFoveated(adanerf_stats* st) {
   return true;
 }
 
+// --fovea-density with --fovea-temporal: frame k takes the phase adanerf_host_density_phase(k); the mask of the gaze in force at that phase,
+// its lattice rendered into d_rgb and the aux maps, the pixels in between rebuilt in all three (adanerf_fill_density_phased), then
+// adanerf_temporal_resolve_sparse (clamp on) against the history, which the result replaces; d_frame gets the resolved frame.  The history's
+// depth is tested only when the pose differs from the history's (as renderer.py).
+bool NeuralRenderer::renderFoveatedTemporal(adanerf_stats* st, const float rot[9]) {
+  int32_t m = 0, px = 0, py = 0, rejected = 0;
+  adanerf_host_density_phase(ft_k, &px, &py);
+  ft_k = (ft_k + 1) % 64;
+  const uint8_t* mask = static_cast<const uint8_t*>(d_dmask);
+  const int out = taa_have ? 1 - taa_side : 0;
+  void* const* hist = d_hist[taa_side];
+  const bool at_rest = taa_have && std::memcmp(prev_pos, camera.getPosition(), sizeof(prev_pos)) == 0 && std::memcmp(prev_rot, rot, sizeof(prev_rot)) == 0;
+  if (adanerf_foveate_density_phased(ctx, gaze_x, gaze_y, static_cast<int32_t>(settings.density_radius.size()), settings.density_radius.data(),
+                                     settings.density_stride.data(), px, py, static_cast<uint8_t*>(d_dmask)) != ADANERF_OK ||
+      adanerf_render_masked(ctx, mask, 1u, nullptr, static_cast<float*>(d_rgb), st, &m) != ADANERF_OK ||
+      adanerf_fill_density_phased(ctx, mask, info_.width, info_.height, px, py, static_cast<float*>(d_rgb), static_cast<float*>(d_depth), static_cast<float*>(d_acc),
+                                  nullptr, nullptr) != ADANERF_OK ||
+      adanerf_temporal_resolve_sparse(ctx, mask, px, py, static_cast<const float*>(d_rgb), static_cast<const float*>(d_depth), static_cast<const float*>(d_acc),
+                                      camera.getPosition(), rot, taa_have ? static_cast<const float*>(hist[0]) : nullptr,
+                                      taa_have && !at_rest ? static_cast<const float*>(hist[1]) : nullptr,
+                                      taa_have ? static_cast<const uint8_t*>(hist[2]) : nullptr, prev_pos, prev_rot, settings.fovea_temporal_alpha, 0.02f, 0.5f,
+                                      ADANERF_TEMPORAL_CLAMP, static_cast<float*>(d_hist[out][0]), static_cast<float*>(d_hist[out][1]),
+                                      static_cast<uint8_t*>(d_hist[out][2]), d_frame, nullptr, &rejected) != ADANERF_OK) {
+    err = adanerf_last_error(ctx);
+    return false;
+  }
+  std::memcpy(prev_pos, camera.getPosition(), sizeof(prev_pos));
+  std::memcpy(prev_rot, rot, sizeof(prev_rot));
+  taa_side = out;
+  taa_have = true;
+  s_rejected += rejected;
+  s_density_rendered += m;
+  if (settings.log_camera)
+    std::printf("foveated %d phase %d %d rendered %d of %u rejected %d\n", sample_count, static_cast<int>(px), static_cast<int>(py), static_cast<int>(m),
+                settings.total_size, static_cast<int>(rejected));
+  return true;
+}
+
 bool NeuralRenderer::render() {
   float rot[9];
   camera.getRotMatrix(rot);
@@ -467,7 +520,7 @@ bool NeuralRenderer::render() {
   } else if (!settings.occluders.empty()) {
     if (!renderHybrid(&st, rot)) return false;
   } else if (!settings.density_stride.empty()) {
-    if (!renderFoveated(&st)) return false;
+    if (settings.fovea_temporal_alpha > 0.f ? !renderFoveatedTemporal(&st, rot) : !renderFoveated(&st)) return false;
   } else if (settings.supersample > 1 ? !renderSupersampled(&st) : adanerf_render(ctx, d_frame, nullptr, &st) != ADANERF_OK) {
     if (settings.supersample <= 1) err = adanerf_last_error(ctx);
     return false;
@@ -727,6 +780,7 @@ void NeuralRenderer::logInterval() {
   if (settings.taau_scale > 0)
     std::cout << ", taau rejected: " << s_rejected / static_cast<double>(logging_interval) / settings.total_size / (settings.taau_scale * settings.taau_scale);
   if (settings.reproject > 1) std::cout << ", holes: " << s_holes / static_cast<double>(std::max(s_warped, 1)) << " (" << s_warped << " warped frames)";
+  if (settings.fovea_temporal_alpha > 0.f) std::cout << ", fovea-temporal rejected: " << s_rejected / static_cast<double>(logging_interval) / settings.total_size;
   if (!settings.density_stride.empty()) std::cout << ", rendered fraction: " << s_density_rendered / static_cast<double>(logging_interval) / settings.total_size;
   if (!settings.rerender.empty()) std::cout << ", rerendered: " << s_rerendered / static_cast<double>(std::max(s_warped, 1));
   std::cout << std::endl;

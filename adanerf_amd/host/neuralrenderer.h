@@ -119,6 +119,10 @@ class NeuralRenderer {
   long long s_density_rendered = 0;  // rays rendered in the running interval's frames
   bool applyFoveaDensity();          // the mask filled again: at start, after "gaze", after "size" (fovea_pending, shared with --fovea: the two are exclusive)
   bool renderFoveated(adanerf_stats* st);   // adanerf_render_masked over the lattice, adanerf_fill_density for the rest, into d_frame
+  // --fovea-temporal: the frame number of the phase cycle; the aux maps (d_depth, d_acc), the history sets and their state are --taa's
+  // (d_hist, taa_have, taa_side, prev_*, s_rejected: --fovea-density excludes --taa and --taau)
+  int ft_k = 0;
+  bool renderFoveatedTemporal(adanerf_stats* st, const float rot[9]);   // phased mask, masked render, phased fill, sparse resolve into d_frame
   void* d_window = nullptr;          // --write-window: uchar4 [window_height*window_width], the frame as adanerf_present shows it
   int world_ = 1, strip_rows_ = 8;   // share layout chosen at init; a live context keeps its strip height
   bool allocFrameBuffers();          // d_frame, d_gathered, d_payload for the size in info_ (again after a size change)

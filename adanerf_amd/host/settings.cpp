@@ -16,6 +16,9 @@ const char* Settings::usage() {
          "                                                  entry outside them; the gaze starts at the frame centre\n"
          "               [--fovea-density R:S[,R:S...],S]   foveated ray density: rings around the gaze (radius px : stride 1|2|4|8), then the\n"
          "                                                  stride outside them; every S-th pixel per axis is rendered, the rest rebuilt\n"
+         "               [--fovea-temporal ALPHA]           with --fovea-density: the lattice moves through a 64-phase cycle and every frame is\n"
+         "                                                  resolved against a history; rendered pixels refresh it with weight ALPHA in (0, 1],\n"
+         "                                                  reconstructed pixels keep what they have\n"
          "               [--occluder cx,cy,cz,r[,R,G,B]]    hybrid rendering (repeatable): every ray stops at the nearest of these spheres and its\n"
          "                                                  flat colour (0..1, default 0.5 grey) shows through what the volume in front leaves\n"
          "               [--script FILE] [--log-camera] [--dry-run]     input replay: one line of events per frame\n"
@@ -23,7 +26,7 @@ const char* Settings::usage() {
          "                                                              sample budget N / threshold from that frame on;\n"
          "                                                              size <W> <H>: frame size from that frame on, the window stays;\n"
          "                                                              gaze <X> <Y>: the --fovea / --fovea-density gaze, px;\n"
-         "                                                              cut: --taa / --taau start a new history with that frame)\n"
+         "                                                              cut: --taa / --taau / --fovea-temporal start a new history with that frame)\n"
          "               [--reproject K]      of every K frames render the first and warp it to the camera of the next K - 1 (depth\n"
          "                                    reprojection, holes filled from their neighbours); -w / --write-window write what was shown\n"
          "               [--rerender holes|unsourced]     with --reproject K: render the warped frames' holes (unsourced: the pixels filled from a\n"
@@ -223,6 +226,16 @@ bool Settings::init(int argc, char** argv, std::string* err) {
     } else if (a == "--fovea-density") {
       if (!need(i, 1)) return false;
       if (!parseFoveaDensity(argv[++i], &density_radius, &density_stride, err)) return false;
+    } else if (a == "--fovea-temporal") {
+      if (!need(i, 1)) return false;
+      const std::string as = argv[++i];
+      char* ea = nullptr;
+      const float al = std::strtof(as.c_str(), &ea);
+      if (as.empty() || *ea != 0 || !(al > 0.f && al <= 1.f)) {
+        *err = "--fovea-temporal ALPHA: ALPHA must lie in (0, 1]";
+        return false;
+      }
+      fovea_temporal_alpha = al;
     } else if (a == "--occluder") {
       if (!need(i, 1)) return false;
       Occluder o;
@@ -377,6 +390,10 @@ bool Settings::init(int argc, char** argv, std::string* err) {
       *err = std::string("--fovea-density: ") + why;
       return false;
     }
+  }
+  if (fovea_temporal_alpha > 0.f && density_stride.empty()) {
+    *err = "--fovea-temporal resolves the frames of a moving lattice; only with --fovea-density";
+    return false;
   }
   total_size = width * height;
   if (sampling.empty()) sampling = "split";      // exact by construction; guarded / fp16 are opt-in (the default rule)

@@ -43,6 +43,10 @@ class Settings {
   // ring.  Empty density_stride: off
   std::vector<int> density_radius, density_stride;
   static bool parseFoveaDensity(const std::string& spec, std::vector<int>* radius, std::vector<int>* stride, std::string* err);
+  // --fovea-temporal ALPHA (with --fovea-density): the lattice moves through the 64 phases of adanerf_host_density_phase and every frame is
+  // resolved against a history that knows which pixels were rendered (adanerf_temporal_resolve_sparse, clamp on, depth tolerance 0.02);
+  // ALPHA in (0, 1] the weight of a rendered pixel once its history is older than 1 / ALPHA samples.  0: off
+  float fovea_temporal_alpha = 0.f;
   // --occluder cx,cy,cz,r[,R,G,B] (repeatable): hybrid rendering against sphere occluders -- the frame is rendered under the depth limit of
   // the spheres' camera-space depth (per-pixel minimum, adanerf_host_sphere_zc / adanerf_set_depth_limit) and the nearest sphere's flat colour
   // (0..1 per channel, default 0.5 grey) is let through with the transmittance left (adanerf_blend_behind).  Empty: off

@@ -84,6 +84,8 @@ EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_las
            "adanerf_temporal_upsample", "adanerf_render_masked",
            "adanerf_set_depth_limit", "adanerf_compact_depth_limit", "adanerf_blend_behind", "adanerf_host_sphere_zc",
            "adanerf_foveate_density", "adanerf_fill_density", "adanerf_host_density_mask",
+           "adanerf_foveate_density_phased", "adanerf_fill_density_phased", "adanerf_host_density_mask_phased", "adanerf_host_density_phase",
+           "adanerf_temporal_resolve_sparse",
            "adanerf_contrast_mask", "adanerf_accumulate_masked", "adanerf_resolve_mean_masked", "adanerf_host_contrast_mask"]
 
 _lib = None
@@ -117,6 +119,13 @@ def load_library(path: Optional[str] = None):
     lib.adanerf_foveate_density.argtypes = [vp, C.c_float, C.c_float, i32, C.POINTER(i32), C.POINTER(i32), vp]
     lib.adanerf_fill_density.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(i32)]
     lib.adanerf_host_density_mask.argtypes = [i32, i32, C.c_float, C.c_float, i32, C.POINTER(i32), C.POINTER(i32), vp]
+    lib.adanerf_foveate_density_phased.argtypes = [vp, C.c_float, C.c_float, i32, C.POINTER(i32), C.POINTER(i32), i32, i32, vp]
+    lib.adanerf_fill_density_phased.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, C.POINTER(i32)]
+    lib.adanerf_host_density_mask_phased.argtypes = [i32, i32, C.c_float, C.c_float, i32, C.POINTER(i32), C.POINTER(i32), i32, i32, vp]
+    lib.adanerf_host_density_phase.argtypes = [i32, C.POINTER(i32), C.POINTER(i32)]
+    fp = C.POINTER(C.c_float)
+    lib.adanerf_temporal_resolve_sparse.argtypes = [vp, vp, i32, i32, vp, vp, vp, fp, fp, vp, vp, vp, fp, fp, C.c_float, C.c_float, C.c_float, i32,
+                                                    vp, vp, vp, vp, vp, C.POINTER(i32)]
     lib.adanerf_contrast_mask.argtypes = [vp, vp, i32, i32, C.c_float, vp, C.POINTER(i32)]
     lib.adanerf_accumulate_masked.argtypes = [vp, vp, vp, C.c_uint32, i32, vp, i32]
     lib.adanerf_resolve_mean_masked.argtypes = [vp, vp, vp, C.c_uint32, i32, i32, vp, vp]
@@ -386,6 +395,30 @@ def density_mask(width: int, height: int, gaze_xy, rings) -> np.ndarray:
     return out
 
 
+def density_phase(k: int):
+    """(phase_x, phase_y) of frame k of the lattice's 64-phase cycle (adanerf_host_density_phase): any L * L consecutive frames put
+    every residue pair mod L on the lattice of level L exactly once, for L = 2, 4 and 8 at the same time."""
+    px, py = C.c_int32(-1), C.c_int32(-1)
+    k = ((int(k) + (1 << 31)) % (1 << 32)) - (1 << 31)      # as an int32; the cycle only reads k mod 64
+    if load_library().adanerf_host_density_phase(k, C.byref(px), C.byref(py)) != 0:
+        raise ValueError("adanerf_host_density_phase(%r) refused" % (k,))
+    return int(px.value), int(py.value)
+
+
+def density_mask_phased(width: int, height: int, gaze_xy, rings, phase_xy) -> np.ndarray:
+    """density_mask with the lattice at phase (phase_x, phase_y), each 0..7 (adanerf_host_density_mask_phased); phase (0, 0) is
+    density_mask.  ValueError on what the library refuses."""
+    if isinstance(rings, str):
+        rings = parse_fovea_density(rings)
+    nr, radius, stride = _density_arrays(rings)
+    ok = 1 <= int(width) <= 16384 and 1 <= int(height) <= 16384
+    out = np.empty(int(width) * int(height) if ok else 1, dtype=np.uint8)
+    if load_library().adanerf_host_density_mask_phased(int(width), int(height), float(gaze_xy[0]), float(gaze_xy[1]), nr, radius, stride,
+                                                       int(phase_xy[0]), int(phase_xy[1]), out.ctypes.data) != 0:
+        raise ValueError("adanerf_host_density_mask_phased(%r x %r, gaze %r, %r, phase %r) refused" % (width, height, tuple(gaze_xy), rings, tuple(phase_xy)))
+    return out
+
+
 def host_contrast_mask(rgb, width: int, height: int, threshold: float):
     """The mask of adanerf_contrast_mask on the host (adanerf_host_contrast_mask): ``rgb`` [height*width,3] fp32 -> (mask [height*width]
     uint8, 0 = flagged: a neighbour's display value differs by more than ``threshold`` in some channel; n_flagged).  No device needed.
@@ -481,6 +514,8 @@ class NeuralRenderer:
         self._ta_hist = None          # (index of the history's buffer set, pos, rot) of the last render_temporal since then
         self._tu = None               # enable_temporal_upsample(): scale, alpha, depth_tol, clamp, the offset cycle and the place in it
         self._tu_hist = None          # (index of the history's buffer set, pos, rot) of the last render_upsampled since then
+        self._ft = None               # enable_foveated_temporal(): alpha, depth_tol, clamp and the frame number k of the phase cycle
+        self._ft_hist = None          # (index of the history's buffer set, pos, rot) of the last render_foveated_temporal since then
         self._dl_in_force = None      # what the last set_depth_limit installed; render_hybrid puts it back
         self._aux_in_force = (None, None)   # (depth_map, acc_map) of the last set_aux_outputs, likewise
         self._disp_in_force = None    # the disp_map of the last set_disp_output; render_supersampled_adaptive puts it back
@@ -566,6 +601,7 @@ class NeuralRenderer:
         self._rp_frame = None      # a frame of the old size cannot be warped with the new size's ray generator
         self._ta_hist = None       # nor can a history of the old size be gathered from
         self._tu_hist = None
+        self._ft_hist = None
         self._fd = None            # the density mask is per frame size: foveate_density() fills it again
         for name in ("_o_rgb", "_o_rgba"):
             if hasattr(self, name):
@@ -684,6 +720,125 @@ class NeuralRenderer:
         self._last_frame = (self._o_rgba, w, h)
         self._rp_frame = None      # the depth between the rendered pixels is interpolated, not the volume's own
         return self._o_rgb.numpy(), self._o_rgba.numpy(), rendered, st
+
+    # -- foveated density over time: the lattice moves through 64 phases, the sparse temporal resolve keeps what was rendered ----
+    density_phase = staticmethod(density_phase)
+    density_mask_phased = staticmethod(density_mask_phased)
+
+    def foveate_density_phased_device(self, gaze_xy, rings, phase_xy, mask) -> int:
+        """adanerf_foveate_density_phased into a device buffer: foveate_density_device with the lattice at phase (phase_x, phase_y).
+        Returns the library's code instead of raising."""
+        nr, radius, stride = _density_arrays(rings)
+        return self.lib.adanerf_foveate_density_phased(self.handle, float(gaze_xy[0]), float(gaze_xy[1]), nr, radius, stride, int(phase_xy[0]),
+                                                       int(phase_xy[1]), _ptr(mask))
+
+    def fill_density_phased_device(self, mask, width: int, height: int, phase_xy, rgb, depth_map=None, acc_map=None, rgba8=None, count: bool = True):
+        """adanerf_fill_density_phased over device images, in place: fill_density_device with the cells of the lattice at phase
+        (phase_x, phase_y).  Returns (code, unfilled); ``count=False`` passes no counter (asynchronous, unfilled is None)."""
+        u = C.c_int32(-1)
+        rc = self.lib.adanerf_fill_density_phased(self.handle, _ptr(mask), int(width), int(height), int(phase_xy[0]), int(phase_xy[1]), _ptr(rgb),
+                                                  _ptr(depth_map), _ptr(acc_map), _ptr(rgba8), C.byref(u) if count else None)
+        return rc, (int(u.value) if count else None)
+
+    def temporal_resolve_sparse_device(self, mask, phase_xy, cur_rgb, cur_depth, cur_acc, cur_pos, cur_rot, hist_rgb, hist_depth, hist_count, prev_pos,
+                                       prev_rot, out_rgb, out_depth, out_count, out_rgba8=None, out_mask=None, alpha: float = 0.1,
+                                       depth_tol: float = 0.02, acc_min: float = 0.5, clamp: bool = True, rejected: bool = True) -> Optional[int]:
+        """adanerf_temporal_resolve_sparse on device images of the context's frame size: temporal_resolve_device told by ``mask`` (the
+        frame's density mask, phase ``phase_xy``) which pixels were rendered (they refresh the history) and which the fill reconstructed
+        (they keep the history they have).  out_count is required, and hist_count with a history.  out_mask: 1 the history was used, 2 it
+        held only a placeholder, 0 rejected.  Returns the number of rejected pixels (synchronous); with rejected=False nothing is read
+        back and the outputs are complete after sync()."""
+        f = [None if v is None else np.ascontiguousarray(v, dtype=np.float32).reshape(k) for v, k in ((cur_pos, 3), (cur_rot, 9), (prev_pos, 3), (prev_rot, 9))]
+        fp = [None if v is None else v.ctypes.data_as(C.POINTER(C.c_float)) for v in f]
+        n = C.c_int32(0)
+        self._check(self.lib.adanerf_temporal_resolve_sparse(self.handle, _ptr(mask), int(phase_xy[0]), int(phase_xy[1]), _ptr(cur_rgb), _ptr(cur_depth),
+                                                             _ptr(cur_acc), fp[0], fp[1], _ptr(hist_rgb), _ptr(hist_depth), _ptr(hist_count), fp[2], fp[3],
+                                                             float(alpha), float(depth_tol), float(acc_min), TEMPORAL_CLAMP if clamp else 0, _ptr(out_rgb),
+                                                             _ptr(out_depth), _ptr(out_count), _ptr(out_rgba8), _ptr(out_mask),
+                                                             C.byref(n) if rejected else None))
+        return int(n.value) if rejected else None
+
+    def _foveated_temporal_buffers(self):
+        """two history sets (rgb, depth, count) to ping-pong, the verdict mask, the 8-bit image of the resolved frame and the density mask of
+        the phase (render_foveated's own mask stays at phase (0, 0)), made on first use
+        and again after a frame size that changes rays_local; the frame's depth_map / acc_map are the aux buffers reproject() uses too"""
+        n = self.info.rays_local
+        self._reproject_buffers()
+        if not hasattr(self, "_ft_sets") or self._ft_mask.shape[0] != n:
+            if hasattr(self, "_ft_sets"):
+                for a in [b for st in self._ft_sets for b in st] + [self._ft_mask, self._ft_rgba, self._ft_dmask]:
+                    if self._last_frame is not None and self._last_frame[0] is a:
+                        self._last_frame = None
+                    a.free()
+                    self._own.remove(a)
+            self._ft_sets = [(self.empty((n, 3), np.float32), self.empty((n,), np.float32), self.empty((n,), np.uint8)) for _ in range(2)]
+            self._ft_mask, self._ft_rgba, self._ft_dmask = self.empty((n,), np.uint8), self.empty((n, 4), np.uint8), self.empty((n,), np.uint8)
+            self._ft_hist = None
+
+    def enable_foveated_temporal(self, alpha: float = 0.1, depth_tol: float = 0.02, clamp: bool = True):
+        """Foveated density over time from now on through render_foveated_temporal(): the lattice of foveate_density() -- which must have
+        set the gaze and rings -- moves through the 64 phases of density_phase, and every frame is resolved against a history kept on the
+        device (adanerf_temporal_resolve_sparse): rendered pixels refresh it, reconstructed pixels keep what they have.  alpha, depth_tol,
+        clamp: as enable_temporal's (the depth test is over a rendered pixel's 3 x 3 neighbourhood, a reconstructed pixel's corners; the
+        clamp applies to rendered pixels).  Whole frames of models without useNDC only.  The depth_map / acc_map aux outputs become the
+        renderer's own."""
+        if self.info.use_ndc or self.info.rays_local != self.info.width * self.info.height:
+            raise AdaNeRFError("foveated density over time needs a whole frame of a model without useNDC")
+        if self._fd is None:
+            raise AdaNeRFError("enable_foveated_temporal: call foveate_density first (it sets the gaze and the rings)")
+        if not 0.0 < float(alpha) <= 1.0:
+            raise ValueError("enable_foveated_temporal: alpha must lie in (0, 1], got %r" % (alpha,))
+        if not float(depth_tol) >= 0.0:
+            raise ValueError("enable_foveated_temporal: depth_tol must be >= 0, got %r" % (depth_tol,))
+        self._ft = dict(alpha=float(alpha), depth_tol=float(depth_tol), clamp=bool(clamp), k=0)
+        self._ft_hist = None
+        self._foveated_temporal_buffers()
+
+    def reset_foveated_temporal(self):
+        """Drops the history (a cut): the next render_foveated_temporal shows its frame as render_foveated would at that phase.  The
+        phase cycle goes on."""
+        self._ft_hist = None
+
+    def render_foveated_temporal(self):
+        """One frame at the camera of the last set_camera: frame k takes the phase density_phase(k), fills the mask of foveate_density()'s
+        gaze and rings at that phase, renders its lattice (adanerf_render_masked), rebuilds the pixels in between
+        (adanerf_fill_density_phased) and resolves the frame against the history, which it then replaces (two buffer sets ping-pong on the
+        device).  Returns (rgb fp32 [R,3], rgba8 [R,4] uint8, mask [R] uint8, rejected, rendered, Stats of the rendered rays): mask 1
+        where the history was used, 2 where it held only a placeholder; rejected counts mask 0 (every pixel on the first frame and after
+        reset_foveated_temporal / set_frame_size).  While the pose is bit for bit the one of the call before, the history's depth is not
+        tested (nothing is uncovered while the camera rests).  render_foveated() and its mask are untouched: the phased mask is a buffer
+        of this path's own (``_ft_dmask``).  present() shows the resolved frame."""
+        if getattr(self, "_ft", None) is None:
+            raise AdaNeRFError("render_foveated_temporal: call enable_foveated_temporal first")
+        if self._pose is None:
+            raise AdaNeRFError("render_foveated_temporal needs the pose of the frame: call set_camera first")
+        w, h = self.info.width, self.info.height
+        if self._fd is None or self._fd[2:] != (w, h):
+            raise AdaNeRFError("render_foveated_temporal: no density mask for %d x %d (call foveate_density first, and again after set_frame_size)" % (w, h))
+        n = self.info.rays_local
+        self._foveated_temporal_buffers()
+        if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
+            self._o_rgb = self.empty((n, 3), np.float32)
+            self._o_rgba = self.empty((n, 4), np.uint8)
+        ft = self._ft
+        phase = density_phase(ft["k"])
+        ft["k"] += 1
+        self._check(self.foveate_density_phased_device(self._fd[0], self._fd[1], phase, self._ft_dmask))
+        rendered, st = self.render_masked(self._ft_dmask, 1, None, self._o_rgb)
+        rc, _ = self.fill_density_phased_device(self._ft_dmask, w, h, phase, self._o_rgb, self._rp_depth, self._rp_acc, None, count=False)
+        self._check(rc)
+        side = 0 if self._ft_hist is None else 1 - self._ft_hist[0]
+        out = self._ft_sets[side]
+        hist = (None, None, None) if self._ft_hist is None else self._ft_sets[self._ft_hist[0]]
+        prev = (None, None) if self._ft_hist is None else self._ft_hist[1:]
+        at_rest = self._ft_hist is not None and np.array_equal(prev[0], self._pose[0]) and np.array_equal(prev[1], self._pose[1])
+        rejected = self.temporal_resolve_sparse_device(self._ft_dmask, phase, self._o_rgb, self._rp_depth, self._rp_acc, self._pose[0], self._pose[1], hist[0],
+                                                       None if at_rest else hist[1], hist[2], prev[0], prev[1], out[0], out[1], out[2], self._ft_rgba,
+                                                       self._ft_mask, alpha=ft["alpha"], depth_tol=ft["depth_tol"], clamp=ft["clamp"])
+        self._ft_hist = (side, self._pose[0], self._pose[1])
+        self._last_frame = (self._ft_rgba, w, h)
+        self._rp_frame = None      # the depth between the rendered pixels is interpolated, not the volume's own
+        return out[0].numpy(), self._ft_rgba.numpy(), self._ft_mask.numpy(), rejected, rendered, st
 
     # -- hybrid rendering: depth limits, the rasterised colour behind --------------------------------------
     def set_depth_limit(self, limit_zc=None):

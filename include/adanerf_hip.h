@@ -525,13 +525,30 @@ int adanerf_foveate_density(adanerf_ctx* ctx, float gaze_x, float gaze_y, int32_
  * render and fill -- 1.12 ms where adanerf_render takes 4.91 ms.
  * ADANERF_EINVAL, with nothing written: a NULL mask or d_rgb; a side outside 1..16384; an fp32 or uchar4 pointer that is not 4-byte
  * aligned; images that overlap one another or the mask.
- * What it does not do: combine with budget maps (the hosts refuse the pair: a ray's budget would have to be reconstructed too); rotate the
- * lattice from frame to frame or couple it to the temporal stages (adanerf_temporal_resolve sees a reconstructed frame as any other); an
+ * What it does not do: combine with budget maps (the hosts refuse the pair: a ray's budget would have to be reconstructed too); an
  * edge-aware or depth-aware filter (the blend is bilinear across depth edges); anything specific to useNDC models (their depth_map is
  * interpolated as a number like any other); sizing launches on the device (the ray count of the masked render is read back once per frame,
  * as adanerf_render_masked does). */
 int adanerf_fill_density(adanerf_ctx* ctx, const uint8_t* d_mask, int32_t width, int32_t height, float* d_rgb, float* d_depth_map,
                          float* d_acc_map, void* d_rgba8, int32_t* unfilled_out);
+
+/* The lattice with a phase: the two calls above are phase (0, 0) of these and write the same bytes.  phase_x, phase_y in 0..7.
+ *   lattice   pixel (x, y) lies on the lattice of level L iff ((x - phase_x) & (L - 1)) == 0 and ((y - phase_y) & (L - 1)) == 0 (two's
+ *             complement: the residue of x - phase_x mod L, also where the difference is negative).  The rest of the rule -- the ring
+ *             test, the box of L - 1 around the point clipped to the frame, its pixel nearest the gaze having stride <= L -- is unchanged.
+ *   cell      of a pixel with byte s: m = (x - phase_x) & (s - 1), x0 = x - m, x1 = x0 + s.  Two taps iff m != 0, x0 >= 0 and x1 < width,
+ *             with fx = (float)m / (float)s; otherwise one tap: x0 if m == 0, else x0 if x0 >= 0, else x1 if x1 < width.  If neither
+ *             exists (a frame narrower than the stride) the pixel is left untouched and counted in *unfilled_out.  y alike.  The used
+ *             corners are the distinct ones among the taps; the blend is adanerf_fill_density's.
+ * A corner lies within s - 1 of every pixel that uses it (m <= s - 1; x1 - x = s - m <= s - 1 where m != 0), so the closure above holds for
+ * every phase: every corner the fill uses is a rendered pixel.
+ * adanerf_host_density_phase gives the phase of frame k; over its 64 phases every pixel of a frame is rendered at least once, and a pixel
+ * whose ring has stride L at least once in any L^2 consecutive frames.
+ * ADANERF_EINVAL / ADANERF_EUNSUPPORTED, with nothing written: what the unphased calls refuse; a phase outside 0..7. */
+int adanerf_foveate_density_phased(adanerf_ctx* ctx, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* stride,
+                                   int32_t phase_x, int32_t phase_y, uint8_t* d_mask);
+int adanerf_fill_density_phased(adanerf_ctx* ctx, const uint8_t* d_mask, int32_t width, int32_t height, int32_t phase_x, int32_t phase_y,
+                                float* d_rgb, float* d_depth_map, float* d_acc_map, void* d_rgba8, int32_t* unfilled_out);
 
 /* De-interleaves the gathered shard payloads ([shard_world][rays_local_max] uchar4, rank-major)
  * into the full row-major image [h*w] uchar4. */
@@ -1005,6 +1022,59 @@ int adanerf_temporal_upsample(adanerf_ctx* ctx, int32_t scale, const float* d_cu
                               float alpha, float depth_tol, float acc_min, int32_t flags, float* d_out_rgb, float* d_out_depth,
                               uint8_t* d_out_count, void* d_out_rgba8, uint8_t* d_out_mask, int32_t* rejected_out);
 
+/* The temporal resolve of a foveated frame: adanerf_temporal_resolve told which pixels were rendered and which only reconstructed.
+ * Rendered pixels refresh the history; reconstructed pixels keep the history they have and show the fill only where they have none.  With
+ * the lattice moving through adanerf_host_density_phase's 64 phases the periphery converges on the full render while the camera rests,
+ * at the price of the foveated frame; in motion every pixel is re-rendered at least once per s^2 frames of its ring.
+ *   d_mask, phase_x, phase_y   the mask and phase of this frame.  d_cur_* are what adanerf_render_masked(d_mask, 1, ..) followed by
+ *                              adanerf_fill_density_phased(d_mask, .., phase_x, phase_y, ..) left: dense colour, depth and acc at the
+ *                              context's current frame size.  Byte 0: the pixel was rendered; 2, 4 or 8: reconstructed with that stride;
+ *                              any other byte: the pixel is rejected -- out = cur with the bits copied, count 0, mask 0, no history read.
+ *   every other argument, image shape, alignment rule and the meaning of rejected_out are adanerf_temporal_resolve's, except that
+ *   d_hist_count is required whenever d_hist_rgb is given and d_out_count always: without a count a placeholder (count 0, a fill nobody
+ *   rendered) could not be told from a sample.
+ * Two launches on the context's stream; a gather: the same inputs give the same bits on every call.  Every operation below is one
+ * rounded fp32 operation in the stated order, never fused.
+ * Pass A (only with d_hist_rgb and d_hist_depth), over every pixel i: zp[i], the camera depth of i's surface at the previous pose --
+ *   pass A of adanerf_temporal_upsample with G_lo the context's generator at pixel centres (the offset of adanerf_set_pixel_offset is
+ *   ignored, as adanerf_temporal_resolve ignores it): +inf for a far pixel or a value that is not finite.  The scratch is the context's
+ *   own, shared with adanerf_temporal_upsample and grown on demand.
+ * Pass B, per pixel j:
+ *   1-3  adanerf_temporal_resolve's steps unchanged: the surface from j's own depth and acc, zc_cur -> d_out_depth[j], the projection into
+ *        the previous camera, the nearest tap.  A pixel that misses the previous frame is rejected.
+ *   4    disocclusion (only with d_hist_depth): hd = d_hist_depth[tap] against a set Z of zp values.  Rendered pixel: the zp of j's 3 x 3
+ *        neighbourhood that exists.  Reconstructed pixel: the zp of its used corners, the corners adanerf_fill_density_phased used (none
+ *        on a frame narrower than the stride: Z is empty).  zmin / zmax the smallest / largest finite value of Z, any_far: some value is
+ *        +inf.  The rule is step 4 of adanerf_temporal_upsample verbatim: hd == +inf: accepted iff any_far; hd finite: accepted iff a finite
+ *        zp exists and zmin - tol zmin <= hd <= zmax + tol zmax; anything else rejected.  Why the corners: a filled depth is a blend of its
+ *        corners' depths, so a history surface that any corner explains is not a disocclusion, and the 3 x 3 of a blend would reject every
+ *        cell that straddles an edge.  The corners' mask bytes are not looked at.
+ *   5    history colour hst: adanerf_temporal_resolve's four bilinear taps.
+ *   6    clamp (ADANERF_TEMPORAL_CLAMP), rendered pixels only: hst to the minimum / maximum of the current (filled) colour over the 3 x 3
+ *        neighbourhood, by adanerf_temporal_resolve's order rules.  A reconstructed pixel's own colour is an interpolation and no
+ *        evidence against its history: not clamped.
+ *   7    hc = d_hist_count[tap]; live = accepted and hc >= 1.  Count n': rendered and live min(hc + 1, 255), with a_eff = fmaxf(alpha,
+ *        1.0f / (float)n'); rendered and not live 1; reconstructed and live hc; reconstructed and not live 0, a placeholder.
+ *   8    rendered and live: out = hst + a_eff (cur - hst); reconstructed and live: out = hst; not live: out = cur, the bits copied.
+ *        d_out_mask: 1 live; 2 accepted with hc == 0 (a placeholder replaced by a sample, or kept as the new fill); 0 rejected, counted in
+ *        rejected_out.  d_out_rgba8 follows adanerf_resolve_mean's byte contract.
+ * Without a history every pixel is rejected: rendered pixels start at count 1, reconstructed ones at 0.
+ * Measured (profiles/foveated_temporal_measured.md): the call 58 us at 800 x 800 and 128 us at 1920 x 1080 with the history's depth tested
+ * (adanerf_temporal_resolve on the same images: 52 us and 112 us), 33 us and 57 us without; the whole frame -- phased mask, masked render,
+ * phased fill, this call -- 1.20 ms and 3.15 ms at rest where the fill-only frame takes 1.13 ms and 3.05 ms.  At rest the result reaches the
+ * full render (above 90 dB) once every pixel has been rendered; on a moving camera it can score below the fill-only frame (same note).
+ * ADANERF_EINVAL, with nothing written: everything adanerf_temporal_resolve refuses; a NULL mask; a phase outside 0..7; a history without
+ * a count; a NULL d_out_count; the mask overlapping an output.  ADANERF_EUNSUPPORTED, with nothing written: useNDC models; shards.
+ * What it does not do: sub-pixel jitter on top (the stage ignores the offset as its siblings do; a host may still set one); budget maps;
+ * variance clipping; ageing out reconstructed history faster than alpha; re-rendering the rejected pixels (d_out_mask == 0 selects them
+ * for adanerf_render_masked, but neither host does it); launches sized on the device; NDC models and shards. */
+int adanerf_temporal_resolve_sparse(adanerf_ctx* ctx, const uint8_t* d_mask, int32_t phase_x, int32_t phase_y, const float* d_cur_rgb,
+                                    const float* d_cur_depth_map, const float* d_cur_acc_map, const float cur_pos[3],
+                                    const float cur_rot_c2w[9], const float* d_hist_rgb, const float* d_hist_depth,
+                                    const uint8_t* d_hist_count, const float prev_pos[3], const float prev_rot_c2w[9], float alpha,
+                                    float depth_tol, float acc_min, int32_t flags, float* d_out_rgb, float* d_out_depth,
+                                    uint8_t* d_out_count, void* d_out_rgba8, uint8_t* d_out_mask, int32_t* rejected_out);
+
 /* ---- measurement hook (bench.py's roofline) ---- */
 
 /* What dense 16-bit MFMA rate does the context's device sustain on live operands, and at which clock?  Runs register-only loops of
@@ -1094,6 +1164,17 @@ int adanerf_host_sphere_zc(int32_t width, int32_t height, float focal, const flo
  * ADANERF_EINVAL, with nothing written: everything adanerf_foveate_density refuses; a side outside 1..16384. */
 int adanerf_host_density_mask(int32_t width, int32_t height, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px,
                               const int32_t* stride, uint8_t* mask_out);
+
+/* The mask of adanerf_foveate_density_phased computed on the host, compiled from the same text (csrc/density_rule.hpp).
+ * ADANERF_EINVAL, with nothing written: everything adanerf_host_density_mask refuses; a phase outside 0..7. */
+int adanerf_host_density_mask_phased(int32_t width, int32_t height, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px,
+                                     const int32_t* stride, int32_t phase_x, int32_t phase_y, uint8_t* mask_out);
+
+/* The phase of frame k, a cycle of 64: k is taken mod 64 (a negative k too); d_i = (k >> 2 i) & 3 for i = 0, 1, 2; with bx = {0, 1, 1, 0}
+ * and by = {0, 1, 0, 1}, phase_x = sum bx[d_i] << i and phase_y = sum by[d_i] << i.  k mod L^2 fixes (phase_x mod L, phase_y mod L) one to
+ * one, so any L^2 consecutive frames put every residue pair mod L on the lattice exactly once, for L = 2, 4 and 8 at the same time.
+ * ADANERF_EINVAL, with nothing written: a NULL output. */
+int adanerf_host_density_phase(int32_t k, int32_t* phase_x, int32_t* phase_y);
 
 /* The mask of adanerf_contrast_mask computed on the host: the same rule compiled from the same text (csrc/contrast_rule.hpp), byte for
  * byte what the device writes.  rgb [height*width,3] fp32 and mask [height*width] uint8 in host memory; n_flagged may be NULL.
