@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstring>
 #include <exception>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -706,6 +707,8 @@ int launch_shade_mlp(adanerf_ctx* c, const float* d_rays, const uint32_t* d_key,
   a.total = d_total;
   a.max_samples = max_samples;
   a.raw_out = d_raw;
+  // a position that is not finite, or beyond what the scaled bf16 packing was proved for, comes out as NaN (k_mlp16.hip.hpp position_outside)
+  a.pos_limit = prec == ADANERF_PREC_BF16 ? static_cast<float>(kPosIdentityBound) : std::numeric_limits<float>::max();
   const int enc = coarse ? enc_layout(c->ms.fp0, c->ms.fd0, false) : c->enc1;      // generic nets only: kEnc10_4, or the catch-all 16-band layout
   auto for_elem = [&](auto&& f) { return prec == ADANERF_PREC_BF16 ? f(Bf16{}) : f(Fp16{}); };
   if (generic && prec != ADANERF_PREC_FP32) {

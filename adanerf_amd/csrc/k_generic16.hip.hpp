@@ -288,6 +288,7 @@ __global__ __launch_bounds__(256, OCC) void shade_mlp16_gen_staged_kernel(ShadeA
     // where it is consumed -- neither lives in registers across the layer stack
     uint32_t hA[NB * IA], hB[NB * IB];
     float dpe[NB][3];
+    uint64_t outside[NB];      // position_outside per block
     // k-steps (= KiB) of a tile of hidden layer l (1 <= l < depth), of the feature layer at l == depth
     auto ks_of = [&](int l) { return (l < t.depth && ((t.cat_mask >> l) & 1)) ? QP / 8 + KW : KW; };
     {
@@ -297,7 +298,7 @@ __global__ __launch_bounds__(256, OCC) void shade_mlp16_gen_staged_kernel(ShadeA
         float x[3];
         // past the end: the last sample again.  (The opaque zero keeps `total - 1` a per-pass scalar: as a loop invariant hipcc parked it
         // in a VGPR, spilled that, and re-loaded it from scratch at the head of every pass.)
-        load_sample(a, tile * TILE + (wave * NB + nb) * 32 + j, total + bias_launder(), x, dpe[nb]);
+        outside[nb] = load_sample(a, tile * TILE + (wave * NB + nb) * 32 + j, total + bias_launder(), x, dpe[nb]);
         pe_pack<ET, FP>(x, h, pts + nb * IP);
 #pragma unroll
         for (int g = 0; g < QP / 8; ++g) {
@@ -353,7 +354,7 @@ __global__ __launch_bounds__(256, OCC) void shade_mlp16_gen_staged_kernel(ShadeA
     for (int nb = 0; nb < NB; ++nb) {
       const int s = tile * TILE + (wave * NB + nb) * 32 + j;
       if (h == 0 && s < total)
-        store_raw(a, s, rgb_tile[nb][0], rgb_tile[nb][1], rgb_tile[nb][2], alpha_tile[nb][0]);
+        store_raw(a, s, rgb_tile[nb][0], rgb_tile[nb][1], rgb_tile[nb][2], alpha_tile[nb][0], outside_lane(outside[nb]));
     }
   }
   // no LDS-DMA may outlive the workgroup's LDS allocation.  (Nothing is in flight here -- the last pass issues no copy for a next one and

@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256) void shade_mlp32_gen_kernel(ShadeArgs a, Gener
     if (tile * TILE + wave * 32 >= total) continue;
     asm volatile("" : "+v"(w), "+v"(b));
     float x[3], dpe[3];
-    load_sample(a, s, total, x, dpe);
+    const uint64_t outside = load_sample(a, s, total, x, dpe);
     float pts[QP], dirs[QD], hA[QW], hB[QW + 16];      // hB also receives the (MT + 1)-tile feature (+ alpha) layer
     pe_eval<FP, true>(x, h, pts);
     pe_eval<FD, true>(dpe, h, dirs);
@@ -167,8 +167,7 @@ __global__ __launch_bounds__(256) void shade_mlp32_gen_kernel(ShadeArgs a, Gener
     layer_f32<QW, QD, MT / 2, true>(w + a.net.w_off[lf + 1], b + a.net.b_off[lf + 1], lane, hB, dirs, hA);   // cat([feature, dir])
     float rgb[16];
     layer_f32<QW / 2, 0, 1, false>(w + a.net.w_off[lf + 2], b + a.net.b_off[lf + 2], lane, hA, hA, rgb);
-    if (h == 0 && s < total)
-      *reinterpret_cast<float4*>(a.raw_out + static_cast<size_t>(s) * 4) = make_float4(rgb[0], rgb[1], rgb[2], alpha);
+    if (h == 0 && s < total) store_raw_f32(a, s, rgb[0], rgb[1], rgb[2], alpha, outside_lane(outside));
   }
 }
 
@@ -298,7 +297,7 @@ __global__ __launch_bounds__(256) void shade_mlp32_gen_wide_kernel(ShadeArgs a, 
     if (tile * TILE + wave * 16 >= total) continue;
     asm volatile("" : "+v"(w), "+v"(b));
     float x[3], dpe[3];
-    load_sample(a, s, total, x, dpe);
+    const uint64_t outside = load_sample(a, s, total, x, dpe);
     float hA[QW], hB[QW + 4];      // hB also receives the (MT + 1)-tile feature (+ alpha) layer
     {
       float pts[QP];
@@ -328,8 +327,7 @@ __global__ __launch_bounds__(256) void shade_mlp32_gen_wide_kernel(ShadeArgs a, 
     }
     float rgb[4];
     layer_f32_wide<QW / 2, 0, 1, false>(w + a.net.w_off[lf + 2], b + a.net.b_off[lf + 2], lane, hA, hA, rgb);
-    if (g == 0 && s < total)
-      *reinterpret_cast<float4*>(a.raw_out + static_cast<size_t>(s) * 4) = make_float4(rgb[0], rgb[1], rgb[2], alpha);
+    if (g == 0 && s < total) store_raw_f32(a, s, rgb[0], rgb[1], rgb[2], alpha, outside_lane(outside));
   }
 }
 

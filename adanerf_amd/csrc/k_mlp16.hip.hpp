@@ -22,12 +22,37 @@ struct ShadeArgs {
   const int32_t* total;       // device S (may be null -> max_samples)
   int32_t max_samples;
   float* raw_out;             // [S,4]
+  float pos_limit;            // largest |x_i| of a (normalised) sample position the engine answers for: kPosIdentityBound on the scaled bf16
+                              // packing, FLT_MAX otherwise (launch_shade_mlp); see position_outside
 };
 
-// one sample's raw outputs, back in the network's own scale (NetParams::out_scale: 1, or the exact power of two the bf16 packing took out)
-__device__ __forceinline__ void store_raw(const ShadeArgs& a, int s, float r, float g, float b, float alpha) {
-  const float ks = a.net.out_scale[1];
-  *reinterpret_cast<float4*>(a.raw_out + static_cast<size_t>(s) * 4) = make_float4(r * ks, g * ks, b * ks, alpha * a.net.out_scale[0]);
+// The position contract of adanerf_shade_mlp (include/adanerf_hip.h): a sample whose position is not finite -- or, on the bf16 engine, lies beyond
+// kPosIdentityBound, the premise the packing's layer scaling was proved under -- comes out as four NaNs.  The layers themselves cannot be
+// trusted with it: the bf16 kernels' clamped conversion turns a NaN accumulator into 0 and cuts an activation above 1, and the fp32 kernels'
+// fmaxf(NaN, 0) is 0, so such a sample would leave as the finite colour of an all-zero trunk.  One predicate per sample where the position is
+// formed, !(max |x_i| <= limit) with the IEEE 754-2019 maximum, which keeps a NaN (so the predicate is true for one), carried to the store as the
+// wave's lane mask in a scalar register pair -- no vector register across the layer stack; the store selects straight from the mask
+// (outside_lane).  The mask is made opaque where it is formed: left as a plain bool, hipcc sinks the comparison to the store and keeps the
+// three coordinates alive across the layers instead (the 256-register instantiations then spill).
+__device__ __forceinline__ uint64_t position_outside(const ShadeArgs& a, const float x[3]) {
+  const float m = __builtin_elementwise_maximum(__builtin_elementwise_maximum(fabsf(x[0]), fabsf(x[1])), fabsf(x[2]));
+  uint64_t mask = __builtin_amdgcn_ballot_w64(!(m <= a.pos_limit));
+  asm volatile("" : "+s"(mask));
+  return mask;
+}
+__device__ __forceinline__ bool outside_lane(uint64_t mask) { return __builtin_amdgcn_inverse_ballot_w64(mask); }
+
+// one sample's raw outputs, back in the network's own scale (NetParams::out_scale: 1, or the exact power of two the bf16 packing took out);
+// outside (position_outside): NaN instead
+__device__ __forceinline__ void store_raw(const ShadeArgs& a, int s, float r, float g, float b, float alpha, bool outside) {
+  const float ks = a.net.out_scale[1], q = __builtin_nanf("");
+  *reinterpret_cast<float4*>(a.raw_out + static_cast<size_t>(s) * 4) =
+      make_float4(outside ? q : r * ks, outside ? q : g * ks, outside ? q : b * ks, outside ? q : alpha * a.net.out_scale[0]);
+}
+// the fp32 engines: nothing to un-scale
+__device__ __forceinline__ void store_raw_f32(const ShadeArgs& a, int s, float r, float g, float b, float alpha, bool outside) {
+  const float q = __builtin_nanf("");
+  *reinterpret_cast<float4*>(a.raw_out + static_cast<size_t>(s) * 4) = make_float4(outside ? q : r, outside ? q : g, outside ? q : b, outside ? q : alpha);
 }
 
 // kClampRelu: ReLU + conversion of a pair is ONE instruction, `v_cvt_pk_bf16_f32 ... clamp` (clamps to [0, 1]; gfx950 honours the modifier on
@@ -421,8 +446,8 @@ __device__ __forceinline__ void layer_16(WS& st, uint32_t bias_addr, int lane, c
   }
 }
 
-// Loads the sample's ray record and evaluates position (+ optional unit direction).
-__device__ __forceinline__ void load_sample(const ShadeArgs& a, int s, int total, float x[3], float dpe[3]) {
+// Loads the sample's ray record and evaluates position (+ optional unit direction).  Returns position_outside of the wave's samples.
+__device__ __forceinline__ uint64_t load_sample(const ShadeArgs& a, int s, int total, float x[3], float dpe[3]) {
   const int si = (s < total) ? s : (total > 0 ? total - 1 : 0);
   const uint32_t key = a.sample_key ? a.sample_key[si] : static_cast<uint32_t>(si);      // null: dense mode, sample i = (ray i >> 7, bin i & 127)
   const uint32_t ray = key >> 7;
@@ -437,6 +462,7 @@ __device__ __forceinline__ void load_sample(const ShadeArgs& a, int s, int total
     dpe[1] = d[1];
     dpe[2] = d[2];
   }
+  return position_outside(a, x);
 }
 
 // Wave-private LDS stash for packed PE slots (hand-issued so hipcc neither orders them against the LDS-DMA
@@ -632,15 +658,16 @@ __global__ __launch_bounds__(256) void shade_mlp16x2_kernel(ShadeArgs a) {
     const int s0 = tile * TILE + wave * 64 + j, s1 = s0 + 32;
     uint32_t hA0[64], hB0[64], hA1[64], hB1[64];
     PendingTile2 pend;      // a layer's last tile, converted under the next layer's first MFMAs
+    uint64_t outside0, outside1;      // position_outside of the two blocks
     {
       float x[3], dpe[3];
       uint32_t pts0[QP / 2], pts1[QP / 2], dirs[QD / 2];
-      load_sample(a, s0, total, x, dpe);
+      outside0 = load_sample(a, s0, total, x, dpe);
       pe_pack<ET, FP>(x, h, pts0);
       pe_pack<ET, FD>(dpe, h, dirs);
       lds_stash_write<QP / 8>(stash, pts0);
       lds_stash_write<QD / 8>(stash + (QP / 8) * 1024, dirs);
-      load_sample(a, s1, total, x, dpe);
+      outside1 = load_sample(a, s1, total, x, dpe);
       pe_pack<ET, FP>(x, h, pts1);
       pe_pack<ET, FD>(dpe, h, dirs);
       lds_stash_write<QP / 8>(stash + kStashPerBlock, pts1);
@@ -674,9 +701,9 @@ __global__ __launch_bounds__(256) void shade_mlp16x2_kernel(ShadeArgs a) {
     // that read them -- tests/test_host_cpu.py test_asm_conversions_are_two_wait_states_ahead_of_the_mfma_that_reads_them)
     layer_16x2<ET, WS, 8, 0, 1, false, (32 + 4 * 128 + 160 + 2 * 128 + 144 + 72) % CF, 0>(st, bias0 + bo[10] * 4, hB0, hB0, hB1, hB1, hA0, hA1, pend, nullptr, nullptr, &rgb0, &rgb1);
     if (h == 0 && s0 < total)
-      store_raw(a, s0, rgb0[0], rgb0[1], rgb0[2], alpha0[0]);
+      store_raw(a, s0, rgb0[0], rgb0[1], rgb0[2], alpha0[0], outside_lane(outside0));
     if (h == 0 && s1 < total)
-      store_raw(a, s1, rgb1[0], rgb1[1], rgb1[2], alpha1[0]);
+      store_raw(a, s1, rgb1[0], rgb1[1], rgb1[2], alpha1[0], outside_lane(outside1));
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may outlive the workgroup's LDS allocation
 }
@@ -701,7 +728,7 @@ __global__ __launch_bounds__(256) void shade_mlp32_kernel(ShadeArgs a) {
     // load out of the tile loop (loop-invariant code motion) and spills thousands of registers
     asm volatile("" : "+v"(w), "+v"(b));
     float x[3], dpe[3];
-    load_sample(a, s, total, x, dpe);
+    const uint64_t outside = load_sample(a, s, total, x, dpe);
     float pts[QP], dirs[QD], hA[144], hB[128];      // hA also receives the 9-tile feature(+alpha) layer
     pe_eval<FP, true>(x, h, pts);
     pe_eval<FD, true>(dpe, h, dirs);
@@ -719,8 +746,7 @@ __global__ __launch_bounds__(256) void shade_mlp32_kernel(ShadeArgs a) {
     layer_f32<128, QD, 4, true>(w + a.net.w_off[9], b + a.net.b_off[9], lane, hA, dirs, hB);       // cat([feature, dir])
     float rgb[16];
     layer_f32<64, 0, 1, false>(w + a.net.w_off[10], b + a.net.b_off[10], lane, hB, hB, rgb);
-    if (h == 0 && s < total)
-      *reinterpret_cast<float4*>(a.raw_out + static_cast<size_t>(s) * 4) = make_float4(rgb[0], rgb[1], rgb[2], alpha);
+    if (h == 0 && s < total) store_raw_f32(a, s, rgb[0], rgb[1], rgb[2], alpha, outside_lane(outside));
   }
 }
 

@@ -669,12 +669,19 @@ int adanerf_shade_features(adanerf_ctx* ctx, const float* d_rays, const uint32_t
 
 /* Fused PE + shading MLP over compacted samples -> raw [rgb, alpha] fp32 [n_samples,4].
  * d_total (device int32) bounds the work without a host sync; max_samples bounds the launch.
- * precision: ADANERF_PREC_*, or -1 for the context's. */
+ * precision: ADANERF_PREC_*, or -1 for the context's.
+ * Positions: a sample whose (normalised) position o + d z is not finite in every component -- a NaN or an infinity in the ray record
+ * or in the depth -- gets NaN in all four raw outputs, in every precision (the compositing stages then make the ray non-finite); every
+ * other sample of the launch is unaffected.  ADANERF_PREC_BF16 runs a packing whose per-layer scaling is proved for |x_i| <= 4096 only
+ * (what adanerf_create and adanerf_set_camera check for a bf16 context's own samples): a finite position beyond that also gets four
+ * NaNs there, never a clamped value; fp16 and fp32 evaluate it like any other. */
 int adanerf_shade_mlp(adanerf_ctx* ctx, const float* d_rays, const uint32_t* d_sample_key,
                       const int32_t* d_total, int32_t max_samples, int32_t precision, float* d_raw_out);
 
 /* As adanerf_shade_mlp with an explicit world depth per sample (d_sample_z [S] fp32, may be NULL -> the bin
- * centre of sample_key's bin): the inverse-CDF sampler places samples anywhere inside a bin. */
+ * centre of sample_key's bin): the inverse-CDF sampler places samples anywhere inside a bin.  The depths are the caller's: one that
+ * is NaN or infinite, or (ADANERF_PREC_BF16) takes the position beyond |x_i| <= 4096, gives that sample four NaNs as stated at
+ * adanerf_shade_mlp -- also when the call names bf16 in a context created with another precision, where nothing checked the scene. */
 int adanerf_shade_mlp_z(adanerf_ctx* ctx, const float* d_rays, const uint32_t* d_sample_key, const float* d_sample_z,
                         const int32_t* d_total, int32_t max_samples, int32_t precision, float* d_raw_out);
 

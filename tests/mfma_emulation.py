@@ -78,6 +78,7 @@ class PackedNet:
         if self.scaled:
             self.lay = lay[:-1]
         self.max_relu_out = 0.0
+        self.max_relu_out_of = {}      # per layer record: the largest scaled ReLU output seen (how far the rows fill the packer's premise)
 
     def unscale(self, rgb_rows, alpha):
         """the kernels' store_raw: outputs back in the network's own scale (exact powers of two)"""
@@ -136,8 +137,28 @@ class PackedNet:
             out = np.maximum(out, 0)
             if self.scaled:
                 self.max_relu_out = max(self.max_relu_out, float(out.max()))
+                self.max_relu_out_of[l] = max(self.max_relu_out_of.get(l, 0.0), float(out.max()))
                 assert out.max() <= 1.0, "a scaled ReLU layer exceeds 1: the kernels' clamped conversion would cut it off"
         return out
+
+
+def scale_exponents(scaled: PackedNet, plain: PackedNet):
+    """The power of two the bf16 packer chose per layer record (pack.cpp scale_layer): `scaled` computes y 2^-e where `plain` (the same
+    network packed without the scaling, host hook precision 4) computes y, so e is read off any nonzero bias, b_scaled = b 2^-e exactly
+    (layers without an activation carry their input's exponent).  None for a layer whose biases are all zero."""
+    assert scaled.scaled and not plain.scaled and scaled.lay.shape == plain.lay.shape
+    out = []
+    for l in range(scaled.lay.shape[0]):
+        b_off, MT = int(scaled.lay[l][1]), int(scaled.lay[l][3])
+        bs, bp = scaled.b[b_off:b_off + MT * 32].astype(np.float64), plain.b[b_off:b_off + MT * 32].astype(np.float64)
+        nz = np.flatnonzero(bp)
+        if nz.size == 0:
+            out.append(None)
+            continue
+        e = -np.log2(bs[nz] / bp[nz])
+        assert (e == np.round(e)).all() and (e == e[0]).all(), (l, e[:8])
+        out.append(int(e[0]))
+    return out
 
 
 def run_sampling_net(net: PackedNet, dir_unit, p, fp, fd):

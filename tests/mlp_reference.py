@@ -6,11 +6,14 @@ Networks come as the oracle's weight dicts (``O.Weights.net0`` / ``.net1``), inp
 - ``bf16`` / ``fp16``: every operand of a matrix product is rounded to the MFMA operand type (RNE, ``mfma_emulation.quantize``): the
   weights, the encoded inputs (identity slots included), every ReLU output, the skip concatenation (which reuses the rounded
   encoding) and ``feature_linear``'s output feeding ``views_linears.0``.  Biases and accumulation stay exact.  The bf16 packer's
-  per-layer powers of two (pack.cpp scale_layer) commute with every rounding on the way and are not modelled.
+  per-layer powers of two (pack.cpp scale_layer) commute with every rounding on the way and are not modelled; ``rescale`` below builds
+  the networks that put exactly that under test (tests/test_shading_ranges_cpu.py, tests/test_gpu_shading_ranges.py).
 - ``split``: every operand is ``hi + 2^-11 lo'`` with both parts fp16 (pack.cpp F16_SPLIT, k_sampling16.hip.hpp split_pack), and a
   product keeps ``hi*hi + hi*lo' + lo'*hi`` (the ``lo'*lo'`` term, 2^-22 relative, is dropped as the kernels drop it).
 
 Faults (``fault=(kind, layer)``) are the emulated kernel bugs the CPU suite shows the comparator rejects (tests/test_mlp_reference_cpu.py).
+``("clamp", layer, e)``: the ReLU output of that layer is cut at 2^(e - 1), half the power of two 2^e the bf16 packer chose for it
+(mfma_emulation.scale_exponents): what the kernels' clamped conversion does to a layer whose scale exponent came out one too small.
 """
 import numpy as np
 
@@ -83,11 +86,13 @@ def linear(x, w, b, model, fault_here=None, f32=False):
     return fin(mm(_round(x, m), _round(w, m)) + bb)
 
 
-def _act(y, model, fault_here=None):
+def _act(y, model, fault_here=None, cut=None):
     """ReLU output as the next layer's operand is formed from it (fp32 in the kernels' accumulators; the rounding happens in linear)"""
     y = np.maximum(y, 0.0)
     if fault_here == "rtz":
         return _rtz(y, model)
+    if fault_here == "clamp":
+        y = np.minimum(y, cut)
     return np.asarray(y, np.float32).astype(np.float64) if model != "exact" else y
 
 
@@ -100,6 +105,11 @@ def _bias(net, name, fault, layer):
 
 def _here(fault, layer):
     return fault[0] if fault is not None and fault[1] == layer else None
+
+
+def _cut(fault):
+    """("clamp", layer, e): the value the layer's ReLU output is cut at, 2^(e - 1)"""
+    return float(np.ldexp(1.0, int(fault[2]) - 1)) if fault is not None and fault[0] == "clamp" else None
 
 
 def sampling_mlp64(x, net0, model="exact", fault=None, f32=False):
@@ -124,7 +134,7 @@ def shading_mlp64(x, net1, n_pos, model="exact", fault=None, f32=False):
     h = pts
     for i in range(depth):
         h = _act(linear(h, net1["pts_linears.%d.weight" % i], _bias(net1, "pts_linears.%d.bias" % i, fault, i), model, _here(fault, i), f32),
-                 model, _here(fault, i))
+                 model, _here(fault, i), _cut(fault))
         if i in skips:
             p = np.roll(pts, 1, axis=1) if _here(fault, i) == "skip_shift" else pts
             h = np.concatenate([p, h], axis=1)
@@ -134,9 +144,61 @@ def shading_mlp64(x, net1, n_pos, model="exact", fault=None, f32=False):
         feat = np.asarray(feat, np.float32).astype(np.float64)
     h = np.concatenate([feat, views], axis=1)
     h = _act(linear(h, net1["views_linears.0.weight"], _bias(net1, "views_linears.0.bias", fault, depth + 1), model, _here(fault, depth + 1),
-                    f32), model, _here(fault, depth + 1))
+                    f32), model, _here(fault, depth + 1), _cut(fault))
     rgb = linear(h, net1["rgb_linear.weight"], net1["rgb_linear.bias"], model, _here(fault, depth + 2), f32)
     return np.concatenate([rgb, alpha], axis=1)
+
+
+def shading_layer_names(net1):
+    """the shading net's layers in the order of `rescale`'s exponents: the trunk, then feature_linear, alpha_linear, views_linears.0, rgb_linear"""
+    depth = len([k for k in net1 if k.startswith("pts_linears.") and k.endswith(".weight")])
+    return ["pts_linears.%d" % i for i in range(depth)] + ["feature_linear", "alpha_linear", "views_linears.0", "rgb_linear"]
+
+
+def rescale(net1, n_pos, E):
+    """The shading network with the OUTPUT of every layer times 2^E[layer] (E: one integer per layer, in shading_layer_names order).  ReLU is
+    positively homogeneous, so it is enough to multiply every weight column block by 2^(E_layer - E_source) -- E_source is the exponent of the
+    layer the columns read, 0 for encoding columns (layer 0, the skip concatenation, the direction columns of views_linears.0) -- and every
+    bias by 2^E_layer.  The layers without an activation take their own E like the others.  In real arithmetic the result is the base network
+    with alpha times 2^Ea and rgb times 2^Ec (Ea = E[alpha_linear], Ec = E[rgb_linear]); in fp32 every factor is an exact power of two, and the
+    function refuses a schedule under which a weight or bias would leave fp32's normal range (the scaling would round)."""
+    names = shading_layer_names(net1)
+    depth = len(names) - 4
+    E = [int(e) for e in E]
+    assert len(E) == len(names), (len(E), names)
+    e_of = dict(zip(names, E))
+    width = net1["pts_linears.0.weight"].shape[0]
+
+    def scaled(a, k):
+        a = np.asarray(a, np.float32)
+        out = np.ldexp(a, k).astype(np.float32)
+        nz = a != 0
+        assert np.isfinite(out).all() and (np.abs(out[nz]) >= np.finfo(np.float32).tiny).all(), "rescale: 2^%s leaves fp32's normal range" % (k,)
+        return out
+
+    out = {}
+    for i in range(depth):
+        nm = "pts_linears.%d" % i
+        w = np.asarray(net1[nm + ".weight"], np.float32)
+        e, src = e_of[nm], (e_of["pts_linears.%d" % (i - 1)] if i else 0)
+        if i == 0:
+            cols = np.full(w.shape[1], e, np.int64)                     # encoding columns only
+        elif w.shape[1] == width + n_pos:
+            cols = np.concatenate([np.full(n_pos, e, np.int64), np.full(width, e - src, np.int64)])      # cat([input_pts, h])
+        else:
+            cols = np.full(w.shape[1], e - src, np.int64)
+        out[nm + ".weight"] = scaled(w, cols[None, :])
+        out[nm + ".bias"] = scaled(net1[nm + ".bias"], e)
+    eh, ef, ev = e_of["pts_linears.%d" % (depth - 1)], e_of["feature_linear"], e_of["views_linears.0"]
+    for nm, src in (("feature_linear", eh), ("alpha_linear", eh), ("rgb_linear", ev)):
+        out[nm + ".weight"] = scaled(net1[nm + ".weight"], e_of[nm] - src)
+        out[nm + ".bias"] = scaled(net1[nm + ".bias"], e_of[nm])
+    w = np.asarray(net1["views_linears.0.weight"], np.float32)
+    cols = np.concatenate([np.full(width, ev - ef, np.int64), np.full(w.shape[1] - width, ev, np.int64)])      # cat([feature, input_views])
+    out["views_linears.0.weight"] = scaled(w, cols[None, :])
+    out["views_linears.0.bias"] = scaled(net1["views_linears.0.bias"], ev)
+    assert set(out) == set(net1)
+    return out
 
 
 def pad_with_garbage(net, prefix, layer, value=0.05, seed=0):
@@ -164,6 +226,35 @@ def sampling_hidden_max(x, net0):
         h = np.maximum(linear(h, net0["layers.%d.weight" % i], net0["layers.%d.bias" % i], "exact"), 0.0)
         m = np.maximum(m, h.max(axis=1))
     return m
+
+
+def shading_hidden_max(x, net1, n_pos):
+    """the largest trunk activation of the shading network over all rows (fp64): what an fp16 engine would have to hold"""
+    x = np.asarray(x, np.float32).astype(np.float64)
+    pts = x[:, :n_pos]
+    depth = len([k for k in net1 if k.startswith("pts_linears.") and k.endswith(".weight")])
+    width = net1["pts_linears.0.weight"].shape[0]
+    h, m = pts, 0.0
+    for i in range(depth):
+        w = net1["pts_linears.%d.weight" % i]
+        if i and w.shape[1] == width + n_pos:
+            h = np.concatenate([pts, h], axis=1)
+        h = np.maximum(linear(h, w, net1["pts_linears.%d.bias" % i], "exact"), 0.0)
+        m = max(m, float(h.max()))
+    return m
+
+
+def emulation_bounds(x, net1, n_pos, engine, ref64, refq):
+    """check_engine bounds for a 16-bit engine on rows whose errors are not the Kaiming nets' errors (positions far from the origin, other
+    normalisations): per quantity the larger of BOUNDS[engine] and 1.5 x what the emulated correct kernel (f32=True: the model's operands,
+    fp32 products summed in another order) shows on the same rows.  Computed from the reference alone, never from a kernel's output.
+    Returns (bounds, shown)."""
+    emu = shading_mlp64(x, net1, n_pos, engine, f32=True)
+    e = engine_errors(emu, ref64, refq)
+    shown = dict(rms_frac=float((e["rms_kq"] / np.maximum(e["rms_q64"], 1e-300)).max()),
+                 max_mult=float((e["max_kq"] / np.maximum(e["max_q64"], 1e-300)).max()), mean_z=float(e["mean_z"].max()),
+                 intrinsic=float((e["max_k64"] / e["scale"]).max()))
+    return {k: max(BOUNDS[engine][k], 1.5 * v) for k, v in shown.items()}, shown
 
 
 def _cols(a):
