@@ -24,7 +24,8 @@ Instantiations and the cases that reach them:
     shade_mlp32_gen_kernel <10, 4 | 16, 16, W = 64 / 128 / 256>        the same cases in fp32
     shade_mlp32_gen_wide_kernel <10, 4 | 16, 16>                       [w257_d3_skip1], [w512_d8_skip4], [w512_d2_catchall] in fp32
     the 16-band catch-all at widths 64 / 256 is the same template as 128 / 512 at another width; not run separately.
-  launch_sample_mlp (stage calls: no fused selection; the fused forms are covered by the frame tests in test_gpu_parity.py)
+  launch_sample_mlp (stage calls: no fused selection; the fused forms on tie, fallback, at-threshold and non-finite rows, bit for bit:
+                     test_gpu_fused_selection_edges.py; on frames of trained and random networks: test_gpu_parity.py)
     sample_mlp16x3_kernel <10, 4 | 2, 2>                               test_sampling_engines[fixed_split], [fixed_split_2_2]
     sample_mlp16_kernel<10, 4>                                         [fixed_fp16] (three laps of its persistent grid)
     sample_mlp_kernel<10, 4> (fp32 MFMA)                               [fixed_fp32]
