@@ -9,7 +9,7 @@ CSRC = os.path.join(HERE, "csrc")
 HOST = os.path.join(HERE, "host")
 LIBDIR = os.path.join(HERE, "lib")
 BINDIR = os.path.join(HERE, "bin")
-LIB_SOURCES = ["adanerf_hip.hip", "launch_f32.hip", "model_setup.cpp", "guard_record.cpp", "flip_tables.cpp", "format.cpp", "pack.cpp"]
+LIB_SOURCES = ["adanerf_hip.hip", "stages.hip", "launch_f32.hip", "model_setup.cpp", "guard_record.cpp", "flip_tables.cpp", "format.cpp", "pack.cpp"]
 _INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
 
 
@@ -44,6 +44,7 @@ HIPCC_FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-ffp-contract=off
 # Per translation unit: the main one keeps MFMA accumulators in architectural VGPRs, so the VALU epilogues of the 16-bit
 # kernels read them without v_accvgpr_read copies (split-precision sampling kernel 1.48 -> 1.35 ms); the fp32-MFMA
 # kernels (launch_f32.hip) are slower that way and keep the compiler's default (AGPR accumulators).
+# stages.hip has no entry: no MFMA in it, and its kernels come out the same with the flag or without (profiles/stages_split_isa_identity.md).
 TU_FLAGS = {"adanerf_hip.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 
@@ -97,14 +98,17 @@ def build_library(force=False, verbose=False, out=None, extra_flags=(), tu_flags
     objdir = os.path.join(LIBDIR, "obj" if not variant else "obj_" + os.path.splitext(os.path.basename(out))[0])
     os.makedirs(objdir, exist_ok=True)
     procs, objs = [], []
+    plain = not (force or variant or extra_flags or tu_flags)
     for src in LIB_SOURCES:
         obj = os.path.join(objdir, src + ".o")
+        objs.append(obj)
+        if plain and not _stale(obj, [os.path.join(CSRC, d) for d in include_closure([src])]):
+            continue      # nothing this unit includes is newer than its object: an edit to a stage header compiles stages.hip alone
         exp = ["-I", os.path.join(os.path.dirname(HERE), "tools", "experiments")] if "-DADN_EXPERIMENT" in extra_flags else []
         cmd = [_hipcc()] + HIPCC_FLAGS + TU_FLAGS.get(src, []) + exp + list(extra_flags) + list((tu_flags or {}).get(src, [])) + ["-fPIC", "-c", os.path.join(CSRC, src), "-o", obj]
         if verbose:
             print(" ".join(cmd))
         procs.append((cmd, subprocess.Popen(cmd, cwd=CSRC)))
-        objs.append(obj)
     for cmd, p in procs:
         if p.wait() != 0:
             raise subprocess.CalledProcessError(p.returncode, cmd)

@@ -1,9 +1,7 @@
-// C ABI of libadanerf_hip.so (see include/adanerf_hip.h).  Host side: the context, weight upload, buffer ownership, every launcher
-// of the 16-bit kernels and the per-frame launch sequence on the context's own HIP stream.  The device-free parts live in
-// model_setup.cpp, guard_record.cpp and flip_tables.cpp; the fp32-MFMA kernels in launch_f32.hip.
-#include "../../include/adanerf_hip.h"
-
-#include <hip/hip_runtime.h>
+// C ABI of libadanerf_hip.so (see include/adanerf_hip.h).  Host side of the render path: the context (context.hpp), weight upload, buffer ownership,
+// every launcher of the 16-bit kernels and the per-frame launch sequence on the context's own HIP stream.  The entry points that work on finished
+// images live in stages.hip; the device-free parts in model_setup.cpp, guard_record.cpp and flip_tables.cpp; the fp32-MFMA kernels in launch_f32.hip.
+#include "context.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -14,139 +12,15 @@
 #include <string>
 #include <vector>
 
-#include "flip_tables.hpp"
-#include "format.hpp"
 #include "guard_record.hpp"
 #include "kernels.hip.hpp"
 #include "launch_f32.hpp"
-#include "model_setup.hpp"
-#include "k_generic_f32.hip.hpp"   // GenericTopo (the kernels themselves live in launch_f32.hip)
+#include "k_generic_f32.hip.hpp"   // (the kernels themselves live in launch_f32.hip)
 #include "k_generic16.hip.hpp"     // the 16-bit form of the run-time-shaped shading kernel
-#include "pack.hpp"
 
 using namespace adanerf;
 
-namespace {
-
-// int32 slots of the `total` block (64 B on the device, imaged to pinned memory after every recorded batch): samples of the batch, rays
-// re-evaluated by the guarded selection, its monitor (SelectOut::guard_seen: kGuardSeenSlots running values, indexed by kSeen*)
-enum { kTotalSamples = 0, kTotalRefined = 4, kTotalGuardSeen = 8, kTotalSlots = 16 };
-enum { kSeenMax = 0, kSeenViolations = 1, kSeenPair = 2, kSeenAuditMismatch = 3, kSeenAudited = 4, kGuardSeenSlots = 5 };
-
-// A device allocation and its owner: move-only, freed with it.
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  DevBuf() = default;
-  DevBuf(DevBuf&& o) noexcept { *this = std::move(o); }
-  DevBuf& operator=(DevBuf&& o) noexcept { return std::swap(p, o.p), std::swap(bytes, o.bytes), *this; }
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-struct PackedDev {
-  DevBuf w, b;
-  NetParams params{};
-};
-
-}  // namespace
-
-struct adanerf_ctx {
-  adanerf_options opt{};
-  ModelSetup ms;                      // what the model directory and the options say (model_setup.hpp); info, rg and sp move on from there
-  std::string err;
-  hipStream_t stream = nullptr;       // stream in use
-  hipStream_t own_stream = nullptr;   // the context's own stream
-  GridCache grids;                    // resident workgroups of every persistent kernel launched so far
-  std::vector<hipEvent_t> events;     // pool; 5 per batch
-  size_t events_used = 0;
-  bool profiling = false;
-  int prof_frames = 0;
-  std::vector<int32_t*> pinned_totals;   // one pinned int32 per recorded batch
-  // always-on monitor of the guarded selection (ADANERF_SAMPLING_GUARDED): the device's running {largest difference seen, violations,
-  // largest pair error seen, audit mismatches, audited rays} copied to pinned memory after every frame and looked at before the next
-  // one -- a violated band (or a failed audit) widens it (poll_guard)
-  int32_t* guard_host = nullptr;
-  hipEvent_t guard_ev = nullptr;
-  bool guard_ev_pending = false;
-  int guard_viol_seen = 0;
-  int guard_mism_seen = 0;
-  bool guard_ev_stale = false;           // the copy in flight was taken under another (N, threshold): it must not widen the band in force
-  int guard_widened = 0;
-  uint32_t guard_frame = 0;              // frames rendered in guarded mode: the audit's rotating phase
-  int debug_guard = 0;                   // $ADANERF_DEBUG_GUARD at create (measurement knobs, bit 0: no whole-row monitor; bits 1 / 2: which plain-fp16 sampling kernel)
-  std::string model_dir;
-  uint64_t model0_hash = 0;              // FNV-1a 64 of model0.onnx: key of the calibration record
-  adanerf_stats folded{};                // profiling record folded out of a full event pool (see adanerf_render)
-
-  NetTopology topo0, topo1;       // read off the ONNX initializers
-  bool generic0 = false, generic1 = false;   // not the 8 x 256 (/ skip 4) topology or not a 10-4 (2-2) encoding: the run-time-shaped fp32 kernels (k_generic_f32.hip.hpp)
-  int enc0 = kEnc10_4, enc1 = kEnc10_4;      // slot layout of the two networks' encodings (launch_f32.hpp)
-  GenericTopo gen0{}, gen1{};
-  DevBuf rsi_z;                   // [ray_samples] world depths of the raySampleInput points
-
-  PackedDev net0;                 // sampling net, fp32 fragments (exact engine)
-  PackedDev net0_split;           // sampling net, fp16 hi/lo' fragment pairs (split-precision engine)
-  PackedDev net0_f16;             // sampling net, plain fp16 fragments (ADANERF_SAMPLING_FP16, packed on first use)
-  TensorMap net0_host;
-  int sampling_mode = 0;          // ADANERF_SAMPLING_*
-  DevBuf overflow;                // int32 counter: rays whose oracle values came out non-finite
-  PackedDev net1[3];              // shading net per precision (packed lazily)
-  TensorMap net1_host;
-  DevBuf ztab;                    // [2][128]: the sampler's bin centres, the dense mode's depths (depth_table); ms.sp.ztab is the one in force
-  // vanilla NeRF (ADANERF_SAMPLER_COARSE_FINE): model0.onnx is a NeRF net as well, evaluated at n_coarse uniform depths
-  PackedDev netc[3];              // coarse net per precision (packed lazily)
-  NetTopology topoc;
-  bool genericc = false;
-  GenericTopo genc{};
-  ShadeParams spc{};              // its sample positions: uniform depth table, rayMarchNormalization[0]
-  DevBuf ztab_coarse, raw_coarse, key_coarse;
-
-  // per-batch buffers
-  int cap_rays = 0, cap_nmax = 0;
-  DevBuf rays, oracle, ray_offsets, ray_counts, selbin, selw, block_total, block_offset, total;
-  DevBuf sample_key, sample_w, raw, sample_z;
-  DevBuf guard_mask, refine_list, guard_probe;   // ADANERF_SAMPLING_GUARDED: undecided bit per ray (one word per 32), ids of the
-                                                 // rays to re-evaluate, first-pass top value of each undecided ray (monitor)
-  float guard_eps = 0.f;             // the band in raw-output units; 0: not calibrated yet
-  float guard_eps_pair = 0.f;        // bound on the error of a (kept - candidate) difference, raw-output units; 0: 2 x guard_eps
-  int guard_audit_period = 0;        // 0: no audit; else a power of two <= 32
-  int device = 0;                 // HIP device ordinal this context lives on
-  float* aux_depth = nullptr;        // adanerf_set_aux_outputs: caller-owned [rays_local] buffers filled by adanerf_render
-  float* aux_acc = nullptr;
-  float* aux_disp = nullptr;         // adanerf_set_disp_output
-  const uint8_t* budget_n = nullptr;  // adanerf_set_budget_map: caller-owned [rays_local] per-ray N / threshold, read by the trim kernels of every render
-  const float* budget_thr = nullptr;
-  const float* depth_limit = nullptr; // adanerf_set_depth_limit: caller-owned [rays_local] camera-space depths, read by the depth trim of every render
-  DevBuf disp_scratch;               // [2, batch] depth / accumulation of the batch when the caller asked for disparity only
-  // adanerf_flip: filter tables of the last pixels-per-degree value, per-tile sums, the mean; grown on demand
-  DevBuf flip_tab, flip_partial, flip_mean;
-  double flip_ppd = 0.0;             // what flip_tab holds (0: nothing yet)
-  FlipParams flip_params{};
-  bool flip_lds_raised = false;      // flip_kernel may use more than 64 KB of dynamic LDS
-  DevBuf reproj_zbuf, reproj_holes;  // adanerf_reproject: [width*height] uint64 z-buffer, the hole count; grown on demand
-  DevBuf upsample_zp;                // adanerf_temporal_upsample: [width*height] fp32 depths at the previous pose; grown on demand
-  // adanerf_render_masked: the mask as bit words, the ascending ray list and its count (for the frame), staged pixels of one listed batch
-  // (rgba8 [cap], rgb [cap,3], depth / acc / disp [3,cap]); grown on demand
-  DevBuf mask_bits, ray_list, ray_list_count, stage_rgba8, stage_rgb, stage_aux;
-  int stage_cap = 0;
-  float px_dx = 0.f, px_dy = 0.f;    // adanerf_set_pixel_offset: kept here, not in ms.rg (calibrate_guard and adanerf_set_frame_size derive from / rewrite that)
-  hipEvent_t peer_event = nullptr;   // adanerf_gather_to: orders the destination stream behind the copy
-  uint64_t peer_tried = 0;           // bit d: peer access to device d has been requested once
-};
-
-namespace {
-
-// ADANERF_EDEVICE and the message "<what>: <HIP's error string>" unless e is hipSuccess
-int hip_rc(adanerf_ctx* c, hipError_t e, const char* what);
-#define HIP_TRY(ctx, call) do { if (int rc_ = hip_rc(ctx, (call), #call)) return rc_; } while (0)
-#define HIP_RETURN(ctx, call) return hip_rc(ctx, (call), #call)
-constexpr const char* kOccupancyQuery = "hipOccupancyMaxActiveBlocksPerMultiprocessor";      // where launch_persistent() can fail
-
-// Every entry point that touches the device first makes the context's device current: one host thread may drive
-// several contexts on different GPUs (adanerf_amd/host --gpus N), and a launch on another device's stream fails.
-#define BIND(ctx) do { if (!(ctx)) return ADANERF_EINVAL; HIP_TRY(ctx, hipSetDevice((ctx)->device)); } while (0)
+namespace adanerf {      // declared in context.hpp: stages.hip calls them too
 
 int fail(adanerf_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;
@@ -167,6 +41,17 @@ int dev_alloc(adanerf_ctx* c, DevBuf* b, size_t bytes) {
   b->bytes = bytes;
   return ADANERF_OK;
 }
+
+}  // namespace adanerf
+
+namespace {
+
+// int32 slots of the `total` block (64 B on the device, imaged to pinned memory after every recorded batch): samples of the batch, rays
+// re-evaluated by the guarded selection, its monitor (SelectOut::guard_seen: kGuardSeenSlots running values, indexed by kSeen*)
+enum { kTotalSamples = 0, kTotalRefined = 4, kTotalGuardSeen = 8, kTotalSlots = 16 };
+enum { kSeenMax = 0, kSeenViolations = 1, kSeenPair = 2, kSeenAuditMismatch = 3, kSeenAudited = 4, kGuardSeenSlots = 5 };
+
+constexpr const char* kOccupancyQuery = "hipOccupancyMaxActiveBlocksPerMultiprocessor";      // where launch_persistent() can fail
 
 int upload_net(adanerf_ctx* c, const PackedNet& pn, PackedDev* d) {
   int rc;
@@ -813,53 +698,6 @@ int launch_composite(adanerf_ctx* c, const float* d_raw, const float* d_w, const
   HIP_RETURN(c, hipGetLastError());
 }
 
-int flip_prepare(adanerf_ctx* c, double ppd) {
-  if (c->flip_tab.p && c->flip_ppd == ppd) return ADANERF_OK;
-  std::vector<float> tab;
-  if (!flip_tables(ppd, &tab, &c->flip_params))
-    return fail(c, ADANERF_EINVAL, "adanerf_flip: filter radius outside 1.." + std::to_string(kFlipMaxRadius) + " at this pixels_per_degree");
-  if (int rc = dev_alloc(c, &c->flip_tab, tab.size() * sizeof(float))) return rc;
-  c->flip_ppd = 0.0;
-  HIP_TRY(c, hipMemcpyAsync(c->flip_tab.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-  HIP_TRY(c, hipStreamSynchronize(c->stream));      // `tab` leaves scope
-  c->flip_ppd = ppd;
-  return ADANERF_OK;
-}
-
-int launch_flip(adanerf_ctx* c, const float* d_test, const float* d_ref, int width, int height, double ppd, float* d_map, float* mean_out) {
-  int rc = flip_prepare(c, ppd);
-  if (rc) return rc;
-  FlipParams p = c->flip_params;
-  p.tiles_x = (width + kFlipTile - 1) / kFlipTile;
-  const int tiles = p.tiles_x * ((height + kFlipTile - 1) / kFlipTile);
-  if ((rc = dev_alloc(c, &c->flip_partial, static_cast<size_t>(tiles) * sizeof(double)))) return rc;
-  if ((rc = dev_alloc(c, &c->flip_mean, sizeof(float)))) return rc;
-  p.test = d_test;
-  p.ref = d_ref;
-  p.map = d_map;
-  p.partial = reinterpret_cast<double*>(c->flip_partial.p);
-  p.tab = reinterpret_cast<const float*>(c->flip_tab.p);
-  p.width = width;
-  p.height = height;
-  const int S = kFlipTile + 2 * p.halo;
-  const size_t lds = static_cast<size_t>(6) * S * S * sizeof(float);      // >= 24 KB: also holds the 2 KB reduction tree
-  if (lds > 64 * 1024 && !c->flip_lds_raised) {
-    constexpr int Smax = kFlipTile + 2 * kFlipMaxRadius;
-    HIP_TRY(c, hipFuncSetAttribute(reinterpret_cast<const void*>(flip_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 6 * Smax * Smax * static_cast<int>(sizeof(float))));
-    c->flip_lds_raised = true;
-  }
-  hipLaunchKernelGGL(flip_kernel, dim3(tiles), dim3(kFlipThreads), lds, c->stream, p);
-  HIP_TRY(c, hipGetLastError());
-  hipLaunchKernelGGL(flip_mean_kernel, dim3(1), dim3(kFlipThreads), 0, c->stream, reinterpret_cast<const double*>(c->flip_partial.p), tiles,
-                     static_cast<double>(width) * height, reinterpret_cast<float*>(c->flip_mean.p));
-  HIP_TRY(c, hipGetLastError());
-  if (mean_out) {
-    HIP_TRY(c, hipMemcpyAsync(mean_out, c->flip_mean.p, sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  return ADANERF_OK;
-}
-
 }  // namespace
 
 // =============================================================================================
@@ -1097,393 +935,6 @@ int adanerf_get_pixel_offset(const adanerf_ctx* c, float out[2]) {
   if (!c || !out) return ADANERF_EINVAL;
   out[0] = c->px_dx;
   out[1] = c->px_dy;
-  return ADANERF_OK;
-}
-
-namespace {
-
-// byte ranges [a, a + na) and [b, b + nb) share a byte
-bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
-  const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
-  return a0 < b0 + nb && b0 < a0 + na;
-}
-
-}  // namespace
-
-int adanerf_accumulate(adanerf_ctx* c, const float* d_rgb, int32_t n_rays, float* d_sum, int32_t first) {
-  if (!c) return ADANERF_EINVAL;
-  if (!d_rgb || !d_sum) return fail(c, ADANERF_EINVAL, "adanerf_accumulate: NULL image");
-  if (n_rays < 0 || n_rays > 0x7fffffff / 3) return fail(c, ADANERF_EINVAL, "adanerf_accumulate: n_rays must be >= 0 and n_rays * 3 <= 2^31 - 1");
-  if ((reinterpret_cast<uintptr_t>(d_rgb) | reinterpret_cast<uintptr_t>(d_sum)) & 3) return fail(c, ADANERF_EINVAL, "adanerf_accumulate: images must be 4-byte aligned");
-  const size_t bytes = static_cast<size_t>(n_rays) * 3 * sizeof(float);
-  if (d_rgb != d_sum && ranges_overlap(d_rgb, bytes, d_sum, bytes)) return fail(c, ADANERF_EINVAL, "adanerf_accumulate: frame and sum overlap without being the same image");
-  BIND(c);
-  if (n_rays == 0) return ADANERF_OK;
-  const int n = n_rays * 3;
-  const int grid = std::min((n + 255) / 256, 65536);      // grid-stride beyond 2^24 values
-  hipLaunchKernelGGL(accumulate_kernel, dim3(grid), dim3(256), 0, c->stream, d_rgb, d_sum, n, first != 0 ? 1 : 0);
-  HIP_RETURN(c, hipGetLastError());
-}
-
-int adanerf_resolve_mean(adanerf_ctx* c, const float* d_sum, int32_t n_rays, int32_t frames, void* d_rgba8, float* d_rgb) {
-  if (!c) return ADANERF_EINVAL;
-  if (!d_sum || (!d_rgba8 && !d_rgb)) return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean: NULL sum, or both outputs NULL");
-  if (n_rays < 0 || n_rays > 0x7fffffff / 3) return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean: n_rays must be >= 0 and n_rays * 3 <= 2^31 - 1");
-  if (frames < 1 || frames > 65536) return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean: frames must be in 1..65536");
-  if ((reinterpret_cast<uintptr_t>(d_sum) | reinterpret_cast<uintptr_t>(d_rgba8) | reinterpret_cast<uintptr_t>(d_rgb)) & 3)
-    return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean: images must be 4-byte aligned");
-  const size_t bytes = static_cast<size_t>(n_rays) * 3 * sizeof(float), bytes8 = static_cast<size_t>(n_rays) * 4;
-  if ((d_rgb && d_rgb != d_sum && ranges_overlap(d_sum, bytes, d_rgb, bytes)) ||
-      (d_rgba8 && (ranges_overlap(d_sum, bytes, d_rgba8, bytes8) || (d_rgb && ranges_overlap(d_rgb, bytes, d_rgba8, bytes8)))))
-    return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean: images overlap (only d_rgb_f32_out may be d_sum itself)");
-  BIND(c);
-  if (n_rays == 0) return ADANERF_OK;
-  hipLaunchKernelGGL(resolve_mean_kernel, dim3((n_rays + 255) / 256), dim3(256), 0, c->stream, d_sum, n_rays, static_cast<float>(frames), d_rgb,
-                     static_cast<uchar4*>(d_rgba8));
-  HIP_RETURN(c, hipGetLastError());
-}
-
-int adanerf_accumulate_masked(adanerf_ctx* c, const float* d_rgb, const uint8_t* d_mask, uint32_t values, int32_t n_rays, float* d_sum, int32_t first) {
-  if (!c) return ADANERF_EINVAL;
-  if (!d_rgb || !d_sum) return fail(c, ADANERF_EINVAL, "adanerf_accumulate_masked: NULL image");
-  if (!d_mask || values == 0) return fail(c, ADANERF_EINVAL, "adanerf_accumulate_masked: NULL mask, or values == 0 selects no mask byte");
-  if (n_rays < 0 || n_rays > 0x7fffffff / 3) return fail(c, ADANERF_EINVAL, "adanerf_accumulate_masked: n_rays must be >= 0 and n_rays * 3 <= 2^31 - 1");
-  if ((reinterpret_cast<uintptr_t>(d_rgb) | reinterpret_cast<uintptr_t>(d_sum)) & 3) return fail(c, ADANERF_EINVAL, "adanerf_accumulate_masked: images must be 4-byte aligned");
-  const size_t bytes = static_cast<size_t>(n_rays) * 3 * sizeof(float);
-  if (d_rgb != d_sum && ranges_overlap(d_rgb, bytes, d_sum, bytes))
-    return fail(c, ADANERF_EINVAL, "adanerf_accumulate_masked: frame and sum overlap without being the same image");
-  if (ranges_overlap(d_mask, static_cast<size_t>(n_rays), d_sum, bytes)) return fail(c, ADANERF_EINVAL, "adanerf_accumulate_masked: the mask overlaps the sum");
-  BIND(c);
-  if (n_rays == 0) return ADANERF_OK;
-  const int n = n_rays * 3;
-  const int grid = std::min((n + 255) / 256, 65536);      // grid-stride beyond 2^24 values
-  hipLaunchKernelGGL(accumulate_masked_kernel, dim3(grid), dim3(256), 0, c->stream, d_rgb, d_mask, values, d_sum, n, first != 0 ? 1 : 0);
-  HIP_RETURN(c, hipGetLastError());
-}
-
-int adanerf_resolve_mean_masked(adanerf_ctx* c, const float* d_sum, const uint8_t* d_mask, uint32_t values, int32_t n_rays, int32_t frames, void* d_rgba8,
-                                float* d_rgb) {
-  if (!c) return ADANERF_EINVAL;
-  if (!d_sum || (!d_rgba8 && !d_rgb)) return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean_masked: NULL sum, or both outputs NULL");
-  if (!d_mask || values == 0) return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean_masked: NULL mask, or values == 0 selects no mask byte");
-  if (n_rays < 0 || n_rays > 0x7fffffff / 3) return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean_masked: n_rays must be >= 0 and n_rays * 3 <= 2^31 - 1");
-  if (frames < 1 || frames > 65536) return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean_masked: frames must be in 1..65536");
-  if ((reinterpret_cast<uintptr_t>(d_sum) | reinterpret_cast<uintptr_t>(d_rgba8) | reinterpret_cast<uintptr_t>(d_rgb)) & 3)
-    return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean_masked: images must be 4-byte aligned");
-  const size_t bytes = static_cast<size_t>(n_rays) * 3 * sizeof(float), bytes8 = static_cast<size_t>(n_rays) * 4;
-  if ((d_rgb && d_rgb != d_sum && ranges_overlap(d_sum, bytes, d_rgb, bytes)) ||
-      (d_rgba8 && (ranges_overlap(d_sum, bytes, d_rgba8, bytes8) || (d_rgb && ranges_overlap(d_rgb, bytes, d_rgba8, bytes8)))))
-    return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean_masked: images overlap (only d_rgb_f32_out may be d_sum itself)");
-  if ((d_rgb && ranges_overlap(d_mask, static_cast<size_t>(n_rays), d_rgb, bytes)) || (d_rgba8 && ranges_overlap(d_mask, static_cast<size_t>(n_rays), d_rgba8, bytes8)))
-    return fail(c, ADANERF_EINVAL, "adanerf_resolve_mean_masked: the mask overlaps an output");
-  BIND(c);
-  if (n_rays == 0) return ADANERF_OK;
-  hipLaunchKernelGGL(resolve_mean_masked_kernel, dim3((n_rays + 255) / 256), dim3(256), 0, c->stream, d_sum, d_mask, values, n_rays, static_cast<float>(frames),
-                     d_rgb, static_cast<uchar4*>(d_rgba8));
-  HIP_RETURN(c, hipGetLastError());
-}
-
-int adanerf_present(adanerf_ctx* c, const void* d_src_rgba8, int32_t src_w, int32_t src_h, void* d_dst_rgba8, int32_t dst_w, int32_t dst_h,
-                    int32_t flags) {
-  if (!c) return ADANERF_EINVAL;
-  if (!d_src_rgba8 || !d_dst_rgba8) return fail(c, ADANERF_EINVAL, "adanerf_present: NULL image");
-  if (src_w < 1 || src_h < 1 || dst_w < 1 || dst_h < 1 || src_w > kPresentMaxSide || src_h > kPresentMaxSide || dst_w > kPresentMaxSide ||
-      dst_h > kPresentMaxSide)
-    return fail(c, ADANERF_EINVAL, "adanerf_present: every side must be in 1.." + std::to_string(kPresentMaxSide));
-  constexpr int32_t kFilters = ADANERF_PRESENT_NEAREST | ADANERF_PRESENT_LINEAR | ADANERF_PRESENT_AREA;
-  if ((flags & ~(ADANERF_PRESENT_FLIP_Y | kFilters)) || ((flags & kFilters) & ((flags & kFilters) - 1)))
-    return fail(c, ADANERF_EINVAL, "adanerf_present: flags must be ADANERF_PRESENT_FLIP_Y with at most one of _NEAREST / _LINEAR / _AREA");
-  const bool area = (flags & ADANERF_PRESENT_AREA) != 0;
-  if (area && (src_w > 8 * dst_w || src_h > 8 * dst_h))      // bounds the kernel's loop at 9 taps per axis
-    return fail(c, ADANERF_EINVAL, "adanerf_present: ADANERF_PRESENT_AREA reduces by at most 8 per axis (reduce in two steps)");
-  const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src_rgba8), d0 = reinterpret_cast<uintptr_t>(d_dst_rgba8);
-  const uintptr_t s1 = s0 + static_cast<size_t>(src_w) * src_h * 4, d1 = d0 + static_cast<size_t>(dst_w) * dst_h * 4;
-  if ((s0 | d0) & 3) return fail(c, ADANERF_EINVAL, "adanerf_present: images must be 4-byte aligned (uchar4)");
-  if (s0 < d1 && d0 < s1) return fail(c, ADANERF_EINVAL, "adanerf_present: source and destination overlap");
-  BIND(c);
-  if (area) {
-    const uint64_t den_a = 2ull * static_cast<uint64_t>(src_w) * static_cast<uint64_t>(src_h);      // 2 S
-    hipLaunchKernelGGL(present_area_kernel, dim3((dst_w * dst_h + 255) / 256), dim3(256), 0, c->stream, static_cast<const uchar4*>(d_src_rgba8),
-                       static_cast<uchar4*>(d_dst_rgba8), src_w, src_h, dst_w, dst_h, (flags & ADANERF_PRESENT_FLIP_Y) ? 1 : 0, den_a, ~0ull / den_a);
-    HIP_RETURN(c, hipGetLastError());
-  }
-  const bool linear = (flags & kFilters) ? (flags & ADANERF_PRESENT_LINEAR) != 0 : dst_w > src_w;      // the reference's rule
-  const uint64_t den = 8ull * static_cast<uint64_t>(dst_w) * static_cast<uint64_t>(dst_h);               // 2 D E
-  const int threads = (1 + (dst_w + 3) / 4) * dst_h;
-  hipLaunchKernelGGL(present_kernel, dim3((threads + 255) / 256), dim3(256), 0, c->stream, static_cast<const uchar4*>(d_src_rgba8),
-                     static_cast<uchar4*>(d_dst_rgba8), src_w, src_h, dst_w, dst_h, linear ? 1 : 0, (flags & ADANERF_PRESENT_FLIP_Y) ? 1 : 0,
-                     static_cast<uint32_t>((d0 >> 2) & 3), den, ~0ull / den);
-  HIP_RETURN(c, hipGetLastError());
-}
-
-int adanerf_reproject(adanerf_ctx* c, const void* d_src_rgba8, const float* d_src_depth_map, const float* d_src_acc_map, const float src_pos[3],
-                      const float src_rot_c2w[9], const float dst_pos[3], const float dst_rot_c2w[9], float acc_min, uint32_t hole_rgba8,
-                      int32_t flags, void* d_dst_rgba8, float* d_dst_depth, uint8_t* d_dst_mask, int32_t* holes_out) {
-  if (!c) return ADANERF_EINVAL;
-  if (!d_src_rgba8 || !d_src_depth_map || !d_src_acc_map || !d_dst_rgba8) return fail(c, ADANERF_EINVAL, "adanerf_reproject: NULL image");
-  if (!src_pos || !src_rot_c2w || !dst_pos || !dst_rot_c2w) return fail(c, ADANERF_EINVAL, "adanerf_reproject: NULL pose");
-  for (int k = 0; k < 9; ++k)
-    if (!std::isfinite(src_rot_c2w[k]) || !std::isfinite(dst_rot_c2w[k]) || (k < 3 && (!std::isfinite(src_pos[k]) || !std::isfinite(dst_pos[k]))))
-      return fail(c, ADANERF_EINVAL, "adanerf_reproject: a pose entry is not finite");
-  if (!(acc_min >= 0.f)) return fail(c, ADANERF_EINVAL, "adanerf_reproject: acc_min must be >= 0");      // also a NaN
-  if (flags & ~ADANERF_REPROJECT_FILL) return fail(c, ADANERF_EINVAL, "adanerf_reproject: flags must be 0 or ADANERF_REPROJECT_FILL");
-  const int w = c->ms.info.width, h = c->ms.info.height, n = w * h;
-  const uintptr_t s0 = reinterpret_cast<uintptr_t>(d_src_rgba8), d0 = reinterpret_cast<uintptr_t>(d_dst_rgba8);
-  if ((s0 | d0) & 3) return fail(c, ADANERF_EINVAL, "adanerf_reproject: colour images must be 4-byte aligned (uchar4)");
-  if (s0 < d0 + static_cast<size_t>(n) * 4 && d0 < s0 + static_cast<size_t>(n) * 4)      // the resolve pass reads the source colour while it writes
-    return fail(c, ADANERF_EINVAL, "adanerf_reproject: source and destination colour overlap");
-  if (c->ms.info.use_ndc) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_reproject: the depth_map of a useNDC model is NDC depth, not a distance along the ray");
-  if (c->ms.rg.world != 1) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_reproject: whole frames only (shard_world must be 1)");
-  BIND(c);
-  if (c->reproj_zbuf.bytes < static_cast<size_t>(n) * sizeof(uint64_t) || !c->reproj_holes.p) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));      // a warp in flight may still use the smaller z-buffer
-    if (int rc = dev_alloc(c, &c->reproj_zbuf, static_cast<size_t>(n) * sizeof(uint64_t))) return rc;
-    if (int rc = dev_alloc(c, &c->reproj_holes, 64)) return rc;
-  }
-  ReprojectParams p{};
-  p.g = c->ms.rg;
-  std::memcpy(p.g.pos, src_pos, 3 * sizeof(float));
-  std::memcpy(p.g.rot, src_rot_c2w, 9 * sizeof(float));
-  std::memcpy(p.dst_pos, dst_pos, 3 * sizeof(float));
-  std::memcpy(p.dst_rot, dst_rot_c2w, 9 * sizeof(float));
-  p.acc_min = acc_min;
-  p.origin_is_camera = c->ms.coarse_fine ? 1 : 0;      // what the render path writes to ADANERF_BUF_RAYS (camera_rays_kernel)
-  unsigned long long* zbuf = reinterpret_cast<unsigned long long*>(c->reproj_zbuf.p);
-  int32_t* holes = reinterpret_cast<int32_t*>(c->reproj_holes.p);
-  const dim3 grid((n + 255) / 256), block(256);
-  hipLaunchKernelGGL(reproject_clear_kernel, grid, block, 0, c->stream, zbuf, n, holes);
-  HIP_TRY(c, hipGetLastError());
-  hipLaunchKernelGGL(reproject_splat_kernel, grid, block, 0, c->stream, p, d_src_depth_map, d_src_acc_map, zbuf);
-  HIP_TRY(c, hipGetLastError());
-  hipLaunchKernelGGL(reproject_resolve_kernel, grid, block, 0, c->stream, zbuf, static_cast<const uint32_t*>(d_src_rgba8), w, h,
-                     (flags & ADANERF_REPROJECT_FILL) ? 1 : 0, hole_rgba8, static_cast<uint32_t*>(d_dst_rgba8), d_dst_depth, d_dst_mask, holes);
-  HIP_TRY(c, hipGetLastError());
-  if (holes_out) {
-    HIP_TRY(c, hipMemcpyAsync(holes_out, holes, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  return ADANERF_OK;
-}
-
-int adanerf_temporal_resolve(adanerf_ctx* c, const float* d_cur_rgb, const float* d_cur_depth_map, const float* d_cur_acc_map, const float cur_pos[3],
-                             const float cur_rot_c2w[9], const float* d_hist_rgb, const float* d_hist_depth, const uint8_t* d_hist_count,
-                             const float prev_pos[3], const float prev_rot_c2w[9], float alpha, float depth_tol, float acc_min, int32_t flags,
-                             float* d_out_rgb, float* d_out_depth, uint8_t* d_out_count, void* d_out_rgba8, uint8_t* d_out_mask,
-                             int32_t* rejected_out) {
-  if (!c) return ADANERF_EINVAL;
-  if (!d_cur_rgb || !d_cur_depth_map || !d_cur_acc_map || !d_out_rgb) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: NULL image");
-  if (!cur_pos || !cur_rot_c2w || (d_hist_rgb && (!prev_pos || !prev_rot_c2w))) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: NULL pose");
-  for (int k = 0; k < 9; ++k) {
-    if (!std::isfinite(cur_rot_c2w[k]) || (k < 3 && !std::isfinite(cur_pos[k])))
-      return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: a pose entry is not finite");
-    if (d_hist_rgb && (!std::isfinite(prev_rot_c2w[k]) || (k < 3 && !std::isfinite(prev_pos[k]))))      // without a history the previous pose is not read
-      return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: a pose entry is not finite");
-  }
-  if (!(alpha > 0.f && alpha <= 1.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: alpha must lie in (0, 1]");      // also a NaN
-  if (!(depth_tol >= 0.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: depth_tol must be >= 0");
-  if (!(acc_min >= 0.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: acc_min must be >= 0");
-  if (flags & ~ADANERF_TEMPORAL_CLAMP) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: flags must be 0 or ADANERF_TEMPORAL_CLAMP");
-  const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-  if ((at(d_cur_rgb) | at(d_cur_depth_map) | at(d_cur_acc_map) | at(d_hist_rgb) | at(d_hist_depth) | at(d_out_rgb) | at(d_out_depth) | at(d_out_rgba8)) & 3)
-    return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: fp32 and uchar4 images must be 4-byte aligned");
-  const int w = c->ms.info.width, h = c->ms.info.height, n = w * h;
-  const size_t b3 = static_cast<size_t>(n) * 3 * sizeof(float), b1 = static_cast<size_t>(n) * sizeof(float);
-  if ((d_hist_rgb && ranges_overlap(d_out_rgb, b3, d_hist_rgb, b3)) || ranges_overlap(d_out_rgb, b3, d_cur_rgb, b3) ||
-      (d_out_depth && d_hist_depth && ranges_overlap(d_out_depth, b1, d_hist_depth, b1)) ||
-      (d_out_count && d_hist_count && ranges_overlap(d_out_count, static_cast<size_t>(n), d_hist_count, static_cast<size_t>(n))))
-    return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve: an output overlaps the image it is gathered from (the history is ping-ponged, not updated in place)");
-  if (c->ms.info.use_ndc) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_temporal_resolve: the depth_map of a useNDC model is NDC depth, not a distance along the ray");
-  if (c->ms.rg.world != 1) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_temporal_resolve: whole frames only (shard_world must be 1)");
-  BIND(c);
-  if (!c->reproj_holes.p) {      // the counter adanerf_reproject keeps its hole count in: both run on the context's stream, one after the other
-    if (int rc = dev_alloc(c, &c->reproj_holes, 64)) return rc;
-  }
-  TemporalParams p{};
-  p.g = c->ms.rg;      // pixel centres: the offset of adanerf_set_pixel_offset is not applied
-  std::memcpy(p.g.pos, cur_pos, 3 * sizeof(float));
-  std::memcpy(p.g.rot, cur_rot_c2w, 9 * sizeof(float));
-  if (d_hist_rgb) {
-    std::memcpy(p.prev_pos, prev_pos, 3 * sizeof(float));
-    std::memcpy(p.prev_rot, prev_rot_c2w, 9 * sizeof(float));
-  }
-  p.alpha = alpha;
-  p.depth_tol = depth_tol;
-  p.acc_min = acc_min;
-  p.origin_is_camera = c->ms.coarse_fine ? 1 : 0;
-  p.clamp = (flags & ADANERF_TEMPORAL_CLAMP) ? 1 : 0;
-  int32_t* rejected = reinterpret_cast<int32_t*>(c->reproj_holes.p);
-  HIP_TRY(c, hipMemsetAsync(rejected, 0, sizeof(int32_t), c->stream));
-  const dim3 grid((w + kTemporalTileW - 1) / kTemporalTileW, (h + kTemporalTileH - 1) / kTemporalTileH), block(256);
-  hipLaunchKernelGGL(temporal_resolve_kernel, grid, block, 0, c->stream, p, d_cur_rgb, d_cur_depth_map, d_cur_acc_map, d_hist_rgb, d_hist_depth, d_hist_count, d_out_rgb,
-                     d_out_depth, d_out_count, static_cast<uchar4*>(d_out_rgba8), d_out_mask, rejected);
-  HIP_TRY(c, hipGetLastError());
-  if (rejected_out) {
-    HIP_TRY(c, hipMemcpyAsync(rejected_out, rejected, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  return ADANERF_OK;
-}
-
-int adanerf_temporal_upsample(adanerf_ctx* c, int32_t scale, const float* d_cur_rgb, const float* d_cur_depth_map, const float* d_cur_acc_map, float cur_dx,
-                              float cur_dy, const float cur_pos[3], const float cur_rot_c2w[9], const float* d_hist_rgb, const float* d_hist_depth,
-                              const uint8_t* d_hist_count, const float prev_pos[3], const float prev_rot_c2w[9], float alpha, float depth_tol,
-                              float acc_min, int32_t flags, float* d_out_rgb, float* d_out_depth, uint8_t* d_out_count, void* d_out_rgba8,
-                              uint8_t* d_out_mask, int32_t* rejected_out) {
-  if (!c) return ADANERF_EINVAL;
-  if (!d_cur_rgb || !d_cur_depth_map || !d_cur_acc_map || !d_out_rgb) return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: NULL image");
-  if (!cur_pos || !cur_rot_c2w || (d_hist_rgb && (!prev_pos || !prev_rot_c2w))) return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: NULL pose");
-  for (int k = 0; k < 9; ++k) {
-    if (!std::isfinite(cur_rot_c2w[k]) || (k < 3 && !std::isfinite(cur_pos[k])))
-      return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: a pose entry is not finite");
-    if (d_hist_rgb && (!std::isfinite(prev_rot_c2w[k]) || (k < 3 && !std::isfinite(prev_pos[k]))))      // without a history the previous pose is not read
-      return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: a pose entry is not finite");
-  }
-  if (scale < 1 || scale > kUpsampleMaxScale) return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: scale must lie in 1..4");
-  if (!(std::fabs(cur_dx) <= 1.f && std::fabs(cur_dy) <= 1.f))      // also a NaN
-    return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: the pixel offset must lie in [-1, 1] on both axes");
-  if (!(alpha > 0.f && alpha <= 1.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: alpha must lie in (0, 1]");      // also a NaN
-  if (!(depth_tol >= 0.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: depth_tol must be >= 0");
-  if (!(acc_min >= 0.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: acc_min must be >= 0");
-  if (flags & ~ADANERF_TEMPORAL_CLAMP) return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: flags must be 0 or ADANERF_TEMPORAL_CLAMP");
-  const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-  if ((at(d_cur_rgb) | at(d_cur_depth_map) | at(d_cur_acc_map) | at(d_hist_rgb) | at(d_hist_depth) | at(d_out_rgb) | at(d_out_depth) | at(d_out_rgba8)) & 3)
-    return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: fp32 and uchar4 images must be 4-byte aligned");
-  const int w = c->ms.info.width, h = c->ms.info.height, n = w * h;
-  const int64_t N64 = static_cast<int64_t>(n) * scale * scale;
-  if (N64 >= (1ll << 25)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: the output's width*height must be < 2^25");
-  const int W = w * scale, H = h * scale;
-  const size_t N = static_cast<size_t>(N64), sf = sizeof(float);
-  if ((d_hist_rgb && ranges_overlap(d_out_rgb, N * 3 * sf, d_hist_rgb, N * 3 * sf)) || ranges_overlap(d_out_rgb, N * 3 * sf, d_cur_rgb, n * 3 * sf) ||
-      (d_out_depth && ((d_hist_depth && ranges_overlap(d_out_depth, N * sf, d_hist_depth, N * sf)) || ranges_overlap(d_out_depth, N * sf, d_cur_depth_map, n * sf) ||
-                       ranges_overlap(d_out_depth, N * sf, d_cur_acc_map, n * sf))) ||
-      (d_out_count && d_hist_count && ranges_overlap(d_out_count, N, d_hist_count, N)))
-    return fail(c, ADANERF_EINVAL, "adanerf_temporal_upsample: an output overlaps the image it is gathered from (the history is ping-ponged, not updated in place)");
-  if (c->ms.info.use_ndc) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_temporal_upsample: the depth_map of a useNDC model is NDC depth, not a distance along the ray");
-  if (c->ms.rg.world != 1) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_temporal_upsample: whole frames only (shard_world must be 1)");
-  BIND(c);
-  if (!c->reproj_holes.p) {      // the counter shared with adanerf_reproject and adanerf_temporal_resolve: all run on the context's stream
-    if (int rc = dev_alloc(c, &c->reproj_holes, 64)) return rc;
-  }
-  const bool depth_test = d_hist_rgb && d_hist_depth;
-  if (depth_test && c->upsample_zp.bytes < static_cast<size_t>(n) * sf) {
-    HIP_TRY(c, hipStreamSynchronize(c->stream));      // a call in flight may still use the smaller buffer
-    if (int rc = dev_alloc(c, &c->upsample_zp, static_cast<size_t>(n) * sf)) return rc;
-  }
-  UpsampleParams p{};
-  p.g_lo = with_pixel_offset(c->ms.rg, cur_dx, cur_dy);      // the offset handed in, never the context's own
-  p.g_hi = c->ms.rg;
-  ray_geometry(c->ms.cfg.fov, W, H, c->ms.rg.strip_rows, 1, 0, &p.g_hi);      // what frame_geometry yields for (W, H); its focal as fp32 is read in the kernel
-  std::memcpy(p.g_lo.pos, cur_pos, 3 * sizeof(float));
-  std::memcpy(p.g_lo.rot, cur_rot_c2w, 9 * sizeof(float));
-  std::memcpy(p.g_hi.pos, cur_pos, 3 * sizeof(float));
-  std::memcpy(p.g_hi.rot, cur_rot_c2w, 9 * sizeof(float));
-  if (d_hist_rgb) {
-    std::memcpy(p.prev_pos, prev_pos, 3 * sizeof(float));
-    std::memcpy(p.prev_rot, prev_rot_c2w, 9 * sizeof(float));
-  }
-  p.alpha = alpha;
-  p.depth_tol = depth_tol;
-  p.acc_min = acc_min;
-  p.cur_dx = cur_dx;
-  p.cur_dy = cur_dy;
-  p.scale = scale;
-  p.origin_is_camera = c->ms.coarse_fine ? 1 : 0;
-  p.clamp = (flags & ADANERF_TEMPORAL_CLAMP) ? 1 : 0;
-  int32_t* rejected = reinterpret_cast<int32_t*>(c->reproj_holes.p);
-  float* zp = reinterpret_cast<float*>(c->upsample_zp.p);
-  HIP_TRY(c, hipMemsetAsync(rejected, 0, sizeof(int32_t), c->stream));
-  if (depth_test) {
-    hipLaunchKernelGGL(upsample_depth_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, p, d_cur_depth_map, d_cur_acc_map, zp);
-    HIP_TRY(c, hipGetLastError());
-  }
-  const dim3 grid((W + kTemporalTileW - 1) / kTemporalTileW, (H + kTemporalTileH - 1) / kTemporalTileH), block(256);
-  hipLaunchKernelGGL(upsample_resolve_kernel, grid, block, 0, c->stream, p, d_cur_rgb, d_cur_depth_map, d_cur_acc_map, zp, d_hist_rgb, d_hist_depth, d_hist_count,
-                     d_out_rgb, d_out_depth, d_out_count, static_cast<uchar4*>(d_out_rgba8), d_out_mask, rejected);
-  HIP_TRY(c, hipGetLastError());
-  if (rejected_out) {
-    HIP_TRY(c, hipMemcpyAsync(rejected_out, rejected, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  return ADANERF_OK;
-}
-
-int adanerf_temporal_resolve_sparse(adanerf_ctx* c, const uint8_t* d_mask, int32_t phase_x, int32_t phase_y, const float* d_cur_rgb, const float* d_cur_depth_map,
-                                    const float* d_cur_acc_map, const float cur_pos[3], const float cur_rot_c2w[9], const float* d_hist_rgb,
-                                    const float* d_hist_depth, const uint8_t* d_hist_count, const float prev_pos[3], const float prev_rot_c2w[9], float alpha,
-                                    float depth_tol, float acc_min, int32_t flags, float* d_out_rgb, float* d_out_depth, uint8_t* d_out_count, void* d_out_rgba8,
-                                    uint8_t* d_out_mask, int32_t* rejected_out) {
-  if (!c) return ADANERF_EINVAL;
-  if (!d_mask) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: NULL mask");
-  if (!d_cur_rgb || !d_cur_depth_map || !d_cur_acc_map || !d_out_rgb) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: NULL image");
-  if (!d_out_count) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: NULL d_out_count (without a count a placeholder cannot be told from a sample)");
-  if (d_hist_rgb && !d_hist_count) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: a history needs its count");
-  if (phase_x < 0 || phase_x > 7 || phase_y < 0 || phase_y > 7) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: phase_x and phase_y must be in 0..7");
-  if (!cur_pos || !cur_rot_c2w || (d_hist_rgb && (!prev_pos || !prev_rot_c2w))) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: NULL pose");
-  for (int k = 0; k < 9; ++k) {
-    if (!std::isfinite(cur_rot_c2w[k]) || (k < 3 && !std::isfinite(cur_pos[k])))
-      return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: a pose entry is not finite");
-    if (d_hist_rgb && (!std::isfinite(prev_rot_c2w[k]) || (k < 3 && !std::isfinite(prev_pos[k]))))      // without a history the previous pose is not read
-      return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: a pose entry is not finite");
-  }
-  if (!(alpha > 0.f && alpha <= 1.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: alpha must lie in (0, 1]");      // also a NaN
-  if (!(depth_tol >= 0.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: depth_tol must be >= 0");
-  if (!(acc_min >= 0.f)) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: acc_min must be >= 0");
-  if (flags & ~ADANERF_TEMPORAL_CLAMP) return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: flags must be 0 or ADANERF_TEMPORAL_CLAMP");
-  const auto at = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
-  if ((at(d_cur_rgb) | at(d_cur_depth_map) | at(d_cur_acc_map) | at(d_hist_rgb) | at(d_hist_depth) | at(d_out_rgb) | at(d_out_depth) | at(d_out_rgba8)) & 3)
-    return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: fp32 and uchar4 images must be 4-byte aligned");
-  const int w = c->ms.info.width, h = c->ms.info.height, n = w * h;
-  const size_t n1 = static_cast<size_t>(n), b3 = n1 * 3 * sizeof(float), b1 = n1 * sizeof(float);
-  if ((d_hist_rgb && ranges_overlap(d_out_rgb, b3, d_hist_rgb, b3)) || ranges_overlap(d_out_rgb, b3, d_cur_rgb, b3) ||
-      (d_out_depth && d_hist_depth && ranges_overlap(d_out_depth, b1, d_hist_depth, b1)) ||
-      (d_hist_count && ranges_overlap(d_out_count, n1, d_hist_count, n1)))
-    return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: an output overlaps the image it is gathered from (the history is ping-ponged, not updated in place)");
-  if (ranges_overlap(d_mask, n1, d_out_rgb, b3) || (d_out_depth && ranges_overlap(d_mask, n1, d_out_depth, b1)) || ranges_overlap(d_mask, n1, d_out_count, n1) ||
-      (d_out_rgba8 && ranges_overlap(d_mask, n1, d_out_rgba8, b1)) || (d_out_mask && ranges_overlap(d_mask, n1, d_out_mask, n1)))
-    return fail(c, ADANERF_EINVAL, "adanerf_temporal_resolve_sparse: the mask overlaps an output (a reconstructed pixel reads the bytes of its cell)");
-  if (c->ms.info.use_ndc) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_temporal_resolve_sparse: the depth_map of a useNDC model is NDC depth, not a distance along the ray");
-  if (c->ms.rg.world != 1) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_temporal_resolve_sparse: whole frames only (shard_world must be 1)");
-  BIND(c);
-  if (!c->reproj_holes.p) {      // the counter shared with adanerf_reproject and the other temporal stages: all run on the context's stream
-    if (int rc = dev_alloc(c, &c->reproj_holes, 64)) return rc;
-  }
-  const bool depth_test = d_hist_rgb && d_hist_depth;
-  if (depth_test && c->upsample_zp.bytes < b1) {      // the scratch adanerf_temporal_upsample keeps its pass A in
-    HIP_TRY(c, hipStreamSynchronize(c->stream));      // a call in flight may still use the smaller buffer
-    if (int rc = dev_alloc(c, &c->upsample_zp, b1)) return rc;
-  }
-  UpsampleParams a{};      // pass A is adanerf_temporal_upsample's with the context's generator at pixel centres; it reads nothing else of g_hi
-  a.g_lo = c->ms.rg;
-  std::memcpy(a.g_lo.pos, cur_pos, 3 * sizeof(float));
-  std::memcpy(a.g_lo.rot, cur_rot_c2w, 9 * sizeof(float));
-  TemporalParams p{};
-  p.g = a.g_lo;      // pixel centres: the offset of adanerf_set_pixel_offset is not applied
-  if (d_hist_rgb) {
-    std::memcpy(p.prev_pos, prev_pos, 3 * sizeof(float));
-    std::memcpy(p.prev_rot, prev_rot_c2w, 9 * sizeof(float));
-    std::memcpy(a.prev_pos, prev_pos, 3 * sizeof(float));
-    std::memcpy(a.prev_rot, prev_rot_c2w, 9 * sizeof(float));
-  }
-  p.alpha = alpha;
-  p.depth_tol = depth_tol;
-  p.acc_min = a.acc_min = acc_min;
-  p.origin_is_camera = a.origin_is_camera = c->ms.coarse_fine ? 1 : 0;
-  p.clamp = (flags & ADANERF_TEMPORAL_CLAMP) ? 1 : 0;
-  int32_t* rejected = reinterpret_cast<int32_t*>(c->reproj_holes.p);
-  float* zp = reinterpret_cast<float*>(c->upsample_zp.p);
-  HIP_TRY(c, hipMemsetAsync(rejected, 0, sizeof(int32_t), c->stream));
-  if (depth_test) {
-    hipLaunchKernelGGL(upsample_depth_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, a, d_cur_depth_map, d_cur_acc_map, zp);
-    HIP_TRY(c, hipGetLastError());
-  }
-  const dim3 grid((w + kTemporalTileW - 1) / kTemporalTileW, (h + kTemporalTileH - 1) / kTemporalTileH), block(256);
-  hipLaunchKernelGGL(sparse_resolve_kernel, grid, block, 0, c->stream, p, phase_x, phase_y, d_mask, d_cur_rgb, d_cur_depth_map, d_cur_acc_map, zp, d_hist_rgb,
-                     d_hist_depth, d_hist_count, d_out_rgb, d_out_depth, d_out_count, static_cast<uchar4*>(d_out_rgba8), d_out_mask, rejected);
-  HIP_TRY(c, hipGetLastError());
-  if (rejected_out) {
-    HIP_TRY(c, hipMemcpyAsync(rejected_out, rejected, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
   return ADANERF_OK;
 }
 
@@ -2228,121 +1679,6 @@ int adanerf_compact_depth_limit(adanerf_ctx* c, const float* d_oracle, int32_t n
   return launch_compact(c, d_oracle, n_rays, n_max, thr, d_off, d_cnt, d_key, d_w, d_total, nullptr, &dl);
 }
 
-int adanerf_blend_behind(adanerf_ctx* c, const float* d_rgb, const float* d_acc, const float* d_behind_rgb, int32_t n, float* d_out_rgb, void* d_out_rgba8) {
-  if (!c) return ADANERF_EINVAL;
-  if (!d_rgb || !d_acc || !d_behind_rgb) return fail(c, ADANERF_EINVAL, "adanerf_blend_behind: NULL input image");
-  if (!d_out_rgb && !d_out_rgba8) return fail(c, ADANERF_EINVAL, "adanerf_blend_behind: both outputs NULL");
-  if (n < 0 || n > 0x7fffffff / 3) return fail(c, ADANERF_EINVAL, "adanerf_blend_behind: n must be >= 0 and n * 3 <= 2^31 - 1");
-  if ((reinterpret_cast<uintptr_t>(d_rgb) | reinterpret_cast<uintptr_t>(d_acc) | reinterpret_cast<uintptr_t>(d_behind_rgb) | reinterpret_cast<uintptr_t>(d_out_rgb) |
-       reinterpret_cast<uintptr_t>(d_out_rgba8)) & 3)
-    return fail(c, ADANERF_EINVAL, "adanerf_blend_behind: images must be 4-byte aligned");
-  const size_t bytes = static_cast<size_t>(n) * 3 * sizeof(float), bytes1 = static_cast<size_t>(n) * 4;
-  const void* const in[3] = {d_rgb, d_acc, d_behind_rgb};
-  const size_t in_bytes[3] = {bytes, bytes1, bytes};
-  for (int i = 0; i < 3; ++i) {
-    if (d_out_rgb && !(i == 0 && d_out_rgb == d_rgb) && ranges_overlap(in[i], in_bytes[i], d_out_rgb, bytes))
-      return fail(c, ADANERF_EINVAL, "adanerf_blend_behind: d_out_rgb overlaps an input (only d_rgb itself may be the output)");
-    if (d_out_rgba8 && ranges_overlap(in[i], in_bytes[i], d_out_rgba8, bytes1)) return fail(c, ADANERF_EINVAL, "adanerf_blend_behind: d_out_rgba8 overlaps an input");
-  }
-  if (d_out_rgb && d_out_rgba8 && ranges_overlap(d_out_rgb, bytes, d_out_rgba8, bytes1)) return fail(c, ADANERF_EINVAL, "adanerf_blend_behind: the two outputs overlap");
-  BIND(c);
-  if (n == 0) return ADANERF_OK;
-  hipLaunchKernelGGL(blend_behind_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, d_rgb, d_acc, d_behind_rgb, n, d_out_rgb, static_cast<uchar4*>(d_out_rgba8));
-  HIP_RETURN(c, hipGetLastError());
-}
-
-// adanerf_foveate_density is phase (0, 0) of adanerf_foveate_density_phased; `who` names the entry point in the error text
-static int foveate_density_at(adanerf_ctx* c, const std::string& who, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* stride,
-                              int32_t phase_x, int32_t phase_y, uint8_t* d_mask) {
-  if (!c) return ADANERF_EINVAL;
-  if (!d_mask) return fail(c, ADANERF_EINVAL, who + ": NULL mask");
-  DensityRule f;
-  if (const char* why = density_rule_fill(gaze_x, gaze_y, n_rings, radius_px, stride, &f, phase_x, phase_y)) return fail(c, ADANERF_EINVAL, who + ": " + why);
-  if (c->ms.rg.world != 1) return fail(c, ADANERF_EUNSUPPORTED, who + ": whole frames only (shard_world must be 1): the reconstruction reads a pixel's neighbours");
-  BIND(c);
-  const int w = c->ms.info.width, h = c->ms.info.height;
-  const int64_t groups = (static_cast<int64_t>(w) * h + 3) / 4;      // four pixels per thread
-  if (groups <= 0) return ADANERF_OK;
-  hipLaunchKernelGGL(density_mask_kernel, dim3(static_cast<unsigned>((groups + 255) / 256)), dim3(256), 0, c->stream, f, w, h,
-                     (reinterpret_cast<uintptr_t>(d_mask) & 3) == 0 ? 1 : 0, d_mask);
-  HIP_RETURN(c, hipGetLastError());
-}
-
-int adanerf_foveate_density(adanerf_ctx* c, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* stride, uint8_t* d_mask) {
-  return foveate_density_at(c, "adanerf_foveate_density", gaze_x, gaze_y, n_rings, radius_px, stride, 0, 0, d_mask);
-}
-
-int adanerf_foveate_density_phased(adanerf_ctx* c, float gaze_x, float gaze_y, int32_t n_rings, const int32_t* radius_px, const int32_t* stride, int32_t phase_x,
-                                   int32_t phase_y, uint8_t* d_mask) {
-  return foveate_density_at(c, "adanerf_foveate_density_phased", gaze_x, gaze_y, n_rings, radius_px, stride, phase_x, phase_y, d_mask);
-}
-
-// adanerf_fill_density is phase (0, 0) of adanerf_fill_density_phased
-static int fill_density_at(adanerf_ctx* c, const std::string& who, const uint8_t* d_mask, int32_t width, int32_t height, int32_t phase_x, int32_t phase_y, float* d_rgb,
-                           float* d_depth_map, float* d_acc_map, void* d_rgba8, int32_t* unfilled_out) {
-  if (!c) return ADANERF_EINVAL;
-  if (!d_mask || !d_rgb) return fail(c, ADANERF_EINVAL, who + ": NULL mask or d_rgb");
-  if (width < 1 || height < 1 || width > kPresentMaxSide || height > kPresentMaxSide)
-    return fail(c, ADANERF_EINVAL, who + ": every side must be in 1.." + std::to_string(kPresentMaxSide));
-  if (phase_x < 0 || phase_x > 7 || phase_y < 0 || phase_y > 7) return fail(c, ADANERF_EINVAL, who + ": phase_x and phase_y must be in 0..7");
-  if ((reinterpret_cast<uintptr_t>(d_rgb) | reinterpret_cast<uintptr_t>(d_depth_map) | reinterpret_cast<uintptr_t>(d_acc_map) | reinterpret_cast<uintptr_t>(d_rgba8)) & 3)
-    return fail(c, ADANERF_EINVAL, who + ": fp32 and uchar4 images must be 4-byte aligned");
-  const size_t n = static_cast<size_t>(width) * static_cast<size_t>(height);
-  const void* const img[5] = {d_mask, d_rgb, d_depth_map, d_acc_map, d_rgba8};
-  const size_t img_bytes[5] = {n, n * 3 * sizeof(float), n * sizeof(float), n * sizeof(float), n * 4};
-  for (int i = 0; i < 5; ++i)
-    for (int j = i + 1; j < 5; ++j)
-      if (img[i] && img[j] && ranges_overlap(img[i], img_bytes[i], img[j], img_bytes[j]))
-        return fail(c, ADANERF_EINVAL, who + ": the images overlap one another or the mask");
-  BIND(c);
-  if (!c->reproj_holes.p) {      // the counter shared with adanerf_reproject and the temporal stages: all run on the context's stream
-    if (int rc = dev_alloc(c, &c->reproj_holes, 64)) return rc;
-  }
-  int32_t* unfilled = reinterpret_cast<int32_t*>(c->reproj_holes.p);
-  HIP_TRY(c, hipMemsetAsync(unfilled, 0, sizeof(int32_t), c->stream));
-  const DensityFill d{d_mask, d_rgb, d_depth_map, d_acc_map, static_cast<uchar4*>(d_rgba8), unfilled};
-  hipLaunchKernelGGL(density_fill_kernel, dim3(static_cast<unsigned>((n + 255) / 256)), dim3(256), 0, c->stream, d, width, height, phase_x, phase_y);
-  HIP_TRY(c, hipGetLastError());
-  if (unfilled_out) {
-    HIP_TRY(c, hipMemcpyAsync(unfilled_out, unfilled, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  return ADANERF_OK;
-}
-
-int adanerf_fill_density(adanerf_ctx* c, const uint8_t* d_mask, int32_t width, int32_t height, float* d_rgb, float* d_depth_map, float* d_acc_map, void* d_rgba8,
-                         int32_t* unfilled_out) {
-  return fill_density_at(c, "adanerf_fill_density", d_mask, width, height, 0, 0, d_rgb, d_depth_map, d_acc_map, d_rgba8, unfilled_out);
-}
-
-int adanerf_fill_density_phased(adanerf_ctx* c, const uint8_t* d_mask, int32_t width, int32_t height, int32_t phase_x, int32_t phase_y, float* d_rgb,
-                                float* d_depth_map, float* d_acc_map, void* d_rgba8, int32_t* unfilled_out) {
-  return fill_density_at(c, "adanerf_fill_density_phased", d_mask, width, height, phase_x, phase_y, d_rgb, d_depth_map, d_acc_map, d_rgba8, unfilled_out);
-}
-
-int adanerf_contrast_mask(adanerf_ctx* c, const float* d_rgb, int32_t width, int32_t height, float threshold, uint8_t* d_mask, int32_t* n_flagged) {
-  if (!c) return ADANERF_EINVAL;
-  if (!d_rgb || !d_mask) return fail(c, ADANERF_EINVAL, "adanerf_contrast_mask: NULL image or mask");
-  if (const char* why = contrast_rule_check(width, height, threshold)) return fail(c, ADANERF_EINVAL, std::string("adanerf_contrast_mask: ") + why);
-  if (reinterpret_cast<uintptr_t>(d_rgb) & 3) return fail(c, ADANERF_EINVAL, "adanerf_contrast_mask: d_rgb must be 4-byte aligned");
-  const size_t n = static_cast<size_t>(width) * static_cast<size_t>(height);
-  if (ranges_overlap(d_rgb, n * 3 * sizeof(float), d_mask, n)) return fail(c, ADANERF_EINVAL, "adanerf_contrast_mask: the mask overlaps the image");
-  BIND(c);
-  if (!c->reproj_holes.p) {      // the counter shared with adanerf_reproject, the temporal stages and adanerf_fill_density: all run on the context's stream
-    if (int rc = dev_alloc(c, &c->reproj_holes, 64)) return rc;
-  }
-  int32_t* flagged = reinterpret_cast<int32_t*>(c->reproj_holes.p);
-  if (n_flagged) HIP_TRY(c, hipMemsetAsync(flagged, 0, sizeof(int32_t), c->stream));
-  const dim3 grid(static_cast<unsigned>((width + kContrastTileW - 1) / kContrastTileW), static_cast<unsigned>((height + kContrastTileH - 1) / kContrastTileH));
-  hipLaunchKernelGGL(contrast_mask_kernel, grid, dim3(256), 0, c->stream, d_rgb, width, height, threshold, d_mask, n_flagged ? flagged : nullptr);
-  HIP_TRY(c, hipGetLastError());
-  if (n_flagged) {
-    HIP_TRY(c, hipMemcpyAsync(n_flagged, flagged, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  return ADANERF_OK;
-}
-
 int adanerf_set_stream(adanerf_ctx* c, void* hip_stream) {
   BIND(c);
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2402,23 +1738,6 @@ int adanerf_gather_to(adanerf_ctx* dst, void* d_dst, adanerf_ctx* src, const voi
   c = dst;
   BIND(dst);
   HIP_RETURN(c, hipStreamWaitEvent(dst->stream, src->peer_event, 0));
-}
-
-int adanerf_flip(adanerf_ctx* c, const float* d_test_rgb, const float* d_ref_rgb, int32_t width, int32_t height, float pixels_per_degree,
-                 float* d_error_map, float* mean_out) {
-  if (!c) return ADANERF_EINVAL;
-  if (!d_test_rgb || !d_ref_rgb) return fail(c, ADANERF_EINVAL, "adanerf_flip: NULL image");
-  if (width < 1 || height < 1) return fail(c, ADANERF_EINVAL, "adanerf_flip: width and height must be >= 1");
-  if (static_cast<int64_t>(width) * height > (1ll << 30)) return fail(c, ADANERF_EINVAL, "adanerf_flip: width * height exceeds 2^30");
-  const double ppd = pixels_per_degree <= 0.f ? kFlipDefaultPpd : static_cast<double>(pixels_per_degree);
-  if (!(ppd >= kFlipPpdMin && ppd <= kFlipPpdMax)) {      // also a NaN; a filter is never truncated to fit
-    char msg[160];
-    std::snprintf(msg, sizeof(msg), "adanerf_flip: pixels_per_degree %.6g outside the supported %.0f..%.0f (<= 0 selects the reference's %.4f)",
-                  ppd, kFlipPpdMin, kFlipPpdMax, kFlipDefaultPpd);
-    return fail(c, ADANERF_EINVAL, msg);
-  }
-  BIND(c);
-  return launch_flip(c, d_test_rgb, d_ref_rgb, width, height, ppd, d_error_map, mean_out);
 }
 
 int adanerf_probe_mfma(adanerf_ctx* c, int32_t operands, int32_t f16, float target_ms, float* tflops, float* clock_mhz) {

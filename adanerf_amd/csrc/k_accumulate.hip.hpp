@@ -6,7 +6,6 @@
 // Bandwidth-bound and tiny beside a frame's two networks: grid-stride over the values, a thread per pixel in the resolve.  No LDS.
 #pragma once
 #include "k_common.hip.hpp"
-#include "k_mask.hip.hpp"
 
 namespace adanerf {
 
@@ -44,7 +43,7 @@ __global__ __launch_bounds__(256) void resolve_mean_kernel(const float* sum, int
   if (rgba8_out) rgba8_out[r] = rgba8_of(m0, m1, m2);
 }
 
-// N11 (adaptive supersampling): accumulate_kernel for the pixels the mask selects (mask_selects, k_mask.hip.hpp: the test of
+// N11 (adaptive supersampling): accumulate_kernel for the pixels the mask selects (mask_selects, k_common.hip.hpp: the test of
 // adanerf_render_masked).  Value i belongs to pixel i / 3; nothing of any other pixel is read or written.  A thread per value as there, so
 // the loads and stores of a wave stay contiguous where the mask selects a run of pixels.
 __global__ __launch_bounds__(256) void accumulate_masked_kernel(const float* rgb, const uint8_t* __restrict__ mask, uint32_t values, float* sum, int n, int first) {

@@ -38,6 +38,9 @@ struct NetParams {
 
 __device__ __forceinline__ int lane_id() { return static_cast<int>(threadIdx.x) & 63; }
 
+// a byte mask's test (k_mask.hip.hpp, k_accumulate.hip.hpp): pixel p is selected iff mask[p] < 32 and bit mask[p] of `values` is set
+__device__ __forceinline__ uint32_t mask_selects(uint32_t byte, uint32_t values) { return byte < 32u ? (values >> byte) & 1u : 0u; }
+
 // local ray index -> (col, row) under round-robin row-strip sharding
 __device__ __forceinline__ void ray_pixel(const RayGenParams& g, int i, int* col, int* row) {
   const int per_strip = g.w * g.strip_rows;

@@ -6,7 +6,7 @@
 // (The first form, every wave fetching its fragments straight from global memory, was the baseline of profiles/r03_generic_staged.md.)
 // Device code only (gfx950, wave64); part of kernels.hip.hpp (main translation unit: accumulators in architectural VGPRs).
 #pragma once
-#include "k_generic_f32.hip.hpp"      // GenericTopo
+#include "k_generic_f32.hip.hpp"      // the fp32 form (GenericTopo itself: params.hpp)
 #include "k_mlp16.hip.hpp"
 #include "k_sampling16.hip.hpp"   // split_pack, epilogue_pair_16x3
 

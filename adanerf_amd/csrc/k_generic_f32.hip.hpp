@@ -12,15 +12,6 @@
 
 namespace adanerf {
 
-struct GenericTopo {
-  int32_t depth;        // Linear layers of the trunk (sampling net: all layers)
-  int32_t cat_mask;     // shading trunk: bit l set <=> layer l takes cat([pts, h]) (l - 1 in the reference's `skips`, src/models.py:226-228, 260-261); 0 none
-  int32_t ray_samples;  // sampling net: raySampleInput
-  uint32_t rsi_w_off;   // 16-byte offset of the raySampleInput fragments of layer 0, [a][s4][m][lane]
-  const float* rsi_z;   // [ray_samples] world depth of every extra point
-  float rsi_d1;         // upper end of the warped depth range
-};
-
 // Layer 0 of a sampling net with raySampleInput: K = [dir PE | pos PE | A x PE(point a)].  The A points are walked in a
 // run-time loop with all MT accumulators live (K-major fragments, pack.cpp emit_ray_samples); the first part is the usual
 // tile-major block.  PE(point) = encode((p + d z_a) / d1) with the identity slots scaled back by d1, as the reference does.

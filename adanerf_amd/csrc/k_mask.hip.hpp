@@ -10,9 +10,6 @@
 
 namespace adanerf {
 
-// pixel p is selected iff mask[p] < 32 and bit mask[p] of `values` is set
-__device__ __forceinline__ uint32_t mask_selects(uint32_t byte, uint32_t values) { return byte < 32u ? (values >> byte) & 1u : 0u; }
-
 // One thread per 16 pixels: a 16-byte load where the 16 bytes exist and are aligned (aligned16: the mask pointer is), single bytes for a
 // partial last group and for a misaligned mask; the thread's 16 bits are half a word of `bits` (little-endian: pixel 32 w + b is bit b of
 // word w).  Launched over 2 x n_words threads, so the bits behind the last pixel of the last word are written too, as zeros.

@@ -48,6 +48,15 @@ constexpr int kMaxCoarse = 128;      // coarse samples per ray (their depths are
 // 2-2 (sampling network); kEncMax is the catch-all kMaxBands-band layout of the run-time-shaped kernels (any posEncArgs)
 enum { kEnc10_4 = 0, kEnc2_2 = 1, kEncMax = 2 };
 
+struct GenericTopo {      // a network on the run-time-shaped kernels (k_generic_f32.hip.hpp, k_generic16.hip.hpp)
+  int32_t depth;        // Linear layers of the trunk (sampling net: all layers)
+  int32_t cat_mask;     // shading trunk: bit l set <=> layer l takes cat([pts, h]) (l - 1 in the reference's `skips`, src/models.py:226-228, 260-261); 0 none
+  int32_t ray_samples;  // sampling net: raySampleInput
+  uint32_t rsi_w_off;   // 16-byte offset of the raySampleInput fragments of layer 0, [a][s4][m][lane]
+  const float* rsi_z;   // [ray_samples] world depth of every extra point
+  float rsi_d1;         // upper end of the warped depth range
+};
+
 constexpr int kFlipMaxRadius = 19;     // colour radius at 140 pixels per degree: (32 + 38)^2 x 6 planes x 4 B = 117.6 KB of the CU's 160 KB
 
 struct FlipParams {

@@ -1,7 +1,7 @@
 // TEST INFRASTRUCTURE (tools/host_abi_sanitize.sh builds it; tests/test_host_cpu.py runs it): the library's HOST-ONLY entry points --
 // adanerf_host_parse_model (model_setup.cpp setup_model: every check adanerf_create makes on a model directory), adanerf_host_depth_table,
 // adanerf_host_pack_weights -- called through the C ABI on randomly damaged model directories, with the library's own host code
-// (adanerf_hip.hip and launch_f32.hip compiled --cuda-host-only; model_setup.cpp, where these entry points live, guard_record.cpp,
+// (adanerf_hip.hip, stages.hip and launch_f32.hip compiled --cuda-host-only; model_setup.cpp, where these entry points live, guard_record.cpp,
 // flip_tables.cpp, format.cpp, pack.cpp) built with -fsanitize=address,undefined.
 // An audit build: it contains no device code (an empty fat-binary stub satisfies the linker), launches nothing and is never shipped.
 //   host_abi_fuzz <model_dir> <work_dir> <iterations> <seed>

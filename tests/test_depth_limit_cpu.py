@@ -157,6 +157,11 @@ def test_header_declares_and_library_exports_the_hybrid_calls(lib, tmp_path):
         assert name in dir(R.NeuralRenderer)
     header = open(os.path.join(ROOT, "include", "adanerf_hip.h")).read()
     assert all("int %s(" % name in header for name in NAMES)
-    # the two kernels are part of the code object's source, through the one header every build includes
+    # the two kernels are part of the code object's source: the depth trim through the header of the render path's unit, the blend through
+    # the unit of the image-space stages, and both units are built into the library
+    from adanerf_amd import build as B
     kernels = open(os.path.join(ROOT, "adanerf_amd", "csrc", "kernels.hip.hpp")).read()
-    assert '#include "k_depth_limit.hip.hpp"' in kernels and '#include "k_blend.hip.hpp"' in kernels
+    stages = open(os.path.join(ROOT, "adanerf_amd", "csrc", "stages.hip")).read()
+    assert '#include "k_depth_limit.hip.hpp"' in kernels and '#include "k_blend.hip.hpp"' in stages
+    assert "k_depth_limit.hip.hpp" in B.include_closure(["adanerf_hip.hip"]) and "k_blend.hip.hpp" in B.include_closure(["stages.hip"])
+    assert {"adanerf_hip.hip", "stages.hip"} <= set(B.LIB_SOURCES)

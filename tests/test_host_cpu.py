@@ -62,7 +62,7 @@ def test_dependency_list_is_the_include_closure():
     every_header = {f for f in os.listdir(csrc) if f.endswith((".hpp", ".h"))}
     assert every_header <= set(B.LIB_DEPS), "headers in csrc/ that no translation unit includes: %s" % sorted(every_header - set(B.LIB_DEPS))
     assert not any(f.startswith("x_") for f in os.listdir(csrc)), "experiment-only headers belong in tools/experiments/"
-    for src in B.LIB_SOURCES:      # device code stays in the two .hip units the ISA tests below compile
+    for src in B.LIB_SOURCES:      # device code stays in the .hip units, all of which the ISA tests below compile
         if src.endswith(".cpp"):
             reached = [d for d in B.include_closure([src]) if d.endswith(".hip.hpp")]
             assert not reached, "%s reaches device headers: %s" % (src, reached)
@@ -94,7 +94,7 @@ def test_no_kernel_goes_through_the_lds_crossbar_for_lane_exchanges():
 
 
 def _device_assembly():
-    """gfx950 assembly of the library's two translation units with the shipped flags, cached in /tmp under the source hash (one ~60 s
+    """gfx950 assembly of every .hip translation unit of the library (build.LIB_SOURCES) with the shipped flags, cached in /tmp under the source hash (one ~60 s
     compile per change of the sources); None without hipcc."""
     import shutil
     import subprocess
@@ -103,7 +103,7 @@ def _device_assembly():
     if not os.path.exists(hipcc):
         return None
     texts = []
-    for src in ("adanerf_hip.hip", "launch_f32.hip"):
+    for src in (s for s in B.LIB_SOURCES if s.endswith(".hip")):
         out = "/tmp/adanerf_isa_%s_%s.s" % (B.source_hash(), src)
         if not os.path.exists(out):
             tmp = out + ".tmp%d" % os.getpid()
@@ -1277,7 +1277,7 @@ def test_host_loader_under_sanitizers_on_mutated_model_directories(tmp_path):
 
 
 def test_host_only_entry_points_under_sanitizers(tmp_path):
-    """tools/host_abi_sanitize.sh: the library's own host code (both .hip translation units compiled --cuda-host-only, the five .cpp ones as they are)
+    """tools/host_abi_sanitize.sh: the library's own host code (the three .hip translation units compiled --cuda-host-only, the five .cpp ones as they are)
     with -fsanitize=address,undefined, and adanerf_host_parse_model / _depth_table / _pack_weights called through the C ABI on 200 randomly
     damaged model directories (tests/host_abi_fuzz.cpp).  Covers what the g++ harness above cannot: setup_model (csrc/model_setup.cpp), i.e. every check
     adanerf_create makes on config.ini / dataset_info.txt, and the shape adanerf_host_pack_weights derives from them (round 6: a saturated

@@ -7,7 +7,7 @@ out = "/tmp/adanerf_all.s"
 sys.path.insert(0, root)
 from adanerf_amd import build as B
 parts = []
-for src in ("adanerf_hip.hip", "launch_f32.hip"):          # same per-translation-unit flags as the shipped build
+for src in (s for s in B.LIB_SOURCES if s.endswith(".hip")):          # every unit that holds kernels, with the shipped build's per-unit flags
     tmp = "/tmp/adanerf_%s.s" % src
     subprocess.run(["hipcc"] + B.HIPCC_FLAGS + B.TU_FLAGS.get(src, []) + ["-S", "--cuda-device-only", os.path.join(root, "adanerf_amd/csrc", src), "-o", tmp],
                    check=True, stderr=subprocess.DEVNULL)

@@ -2,7 +2,7 @@
 """Did a source change move the device code?  python tools/isa_diff.py OLD.s NEW.s compares two gfx950 assembly files kernel by kernel.
 
 The files are what tests/test_host_cpu.py::_device_assembly compiles: hipcc + build.HIPCC_FLAGS + build.TU_FLAGS[src] + -S
---cuda-device-only, one per translation unit (adanerf_hip.hip, launch_f32.hip).
+--cuda-device-only, one per .hip entry of build.LIB_SOURCES (python -c "from adanerf_amd import build; print(build.LIB_SOURCES)").
 
 Per kernel the text from its .globl line to .end_amdhsa_kernel (the kernel descriptor included) is normalised: comments (from `;`) and
 empty lines go, and every .L label is renamed to its order of first appearance inside the kernel (labels carry a function ordinal that
