@@ -19,20 +19,24 @@ __device__ __forceinline__ uchar4 rgba8_of(float r, float g, float b) {
   return px;
 }
 
-// sum[i] = rgb[i] (first) or sum[i] + rgb[i], i < n; rgb may be sum itself
-__global__ __launch_bounds__(256) void accumulate_kernel(const float* rgb, float* sum, int n, int first) {
-  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;      // 64-bit: i + stride passes 2^31 at the largest n
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const float v = rgb[i];
-    sum[i] = first ? v : __fadd_rn(sum[i], v);
-  }
+// Each pair of kernels below is one body: Masked adds the test of a byte mask (mask_selects, k_common.hip.hpp: the test of
+// adanerf_render_masked), and nothing of a pixel the mask does not select is read or written.
+
+// sum[i] = rgb[i] (first) or sum[i] + rgb[i]; rgb may be sum itself.  Value i belongs to pixel i / 3.
+template <bool Masked>
+__device__ __forceinline__ void accumulate_value(int64_t i, const float* rgb, const uint8_t* __restrict__ mask, uint32_t values, float* sum, int first) {
+  if (Masked && !mask_selects(mask[static_cast<uint32_t>(i) / 3u], values)) return;
+  const float v = rgb[i];
+  sum[i] = first ? v : __fadd_rn(sum[i], v);
 }
 
 // pixel r: m = sum / frames per channel -> rgb_out [n_rays,3] (may be sum itself: a thread reads its three values before it writes them)
-// and rgba8_out [n_rays]; either may be null
-__global__ __launch_bounds__(256) void resolve_mean_kernel(const float* sum, int n_rays, float frames, float* rgb_out, uchar4* __restrict__ rgba8_out) {
+// and rgba8_out [n_rays]; either may be null.  Every element of a pixel the mask does not select keeps its bytes in both outputs.
+template <bool Masked>
+__device__ __forceinline__ void resolve_mean_pixel(const float* sum, const uint8_t* __restrict__ mask, uint32_t values, int n_rays, float frames,
+                                                   float* rgb_out, uchar4* __restrict__ rgba8_out) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n_rays) return;
+  if (r >= n_rays || (Masked && !mask_selects(mask[r], values))) return;
   const size_t o = 3 * static_cast<size_t>(r);
   const float m0 = __fdiv_rn(sum[o], frames), m1 = __fdiv_rn(sum[o + 1], frames), m2 = __fdiv_rn(sum[o + 2], frames);
   if (rgb_out) {
@@ -43,31 +47,23 @@ __global__ __launch_bounds__(256) void resolve_mean_kernel(const float* sum, int
   if (rgba8_out) rgba8_out[r] = rgba8_of(m0, m1, m2);
 }
 
-// N11 (adaptive supersampling): accumulate_kernel for the pixels the mask selects (mask_selects, k_common.hip.hpp: the test of
-// adanerf_render_masked).  Value i belongs to pixel i / 3; nothing of any other pixel is read or written.  A thread per value as there, so
-// the loads and stores of a wave stay contiguous where the mask selects a run of pixels.
+// A thread per value, i < n, masked or not, so the loads and stores of a wave stay contiguous where the mask selects a run of pixels.  The
+// grid-stride loop is written out in both kernels: inside a device function its blockDim.x costs a load and a select that a kernel folds away.
+__global__ __launch_bounds__(256) void accumulate_kernel(const float* rgb, float* sum, int n, int first) {
+  const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;      // 64-bit: i + stride passes 2^31 at the largest n
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) accumulate_value<false>(i, rgb, nullptr, 0, sum, first);
+}
+__global__ __launch_bounds__(256) void resolve_mean_kernel(const float* sum, int n_rays, float frames, float* rgb_out, uchar4* __restrict__ rgba8_out) {
+  resolve_mean_pixel<false>(sum, nullptr, 0, n_rays, frames, rgb_out, rgba8_out);
+}
+// N11 (adaptive supersampling): the two for the pixels the mask selects
 __global__ __launch_bounds__(256) void accumulate_masked_kernel(const float* rgb, const uint8_t* __restrict__ mask, uint32_t values, float* sum, int n, int first) {
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) {
-    if (!mask_selects(mask[static_cast<uint32_t>(i) / 3u], values)) continue;
-    const float v = rgb[i];
-    sum[i] = first ? v : __fadd_rn(sum[i], v);
-  }
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += stride) accumulate_value<true>(i, rgb, mask, values, sum, first);
 }
-
-// resolve_mean_kernel for the pixels the mask selects; every element of every other pixel keeps its bytes in both outputs
 __global__ __launch_bounds__(256) void resolve_mean_masked_kernel(const float* sum, const uint8_t* __restrict__ mask, uint32_t values, int n_rays, float frames,
                                                                   float* rgb_out, uchar4* __restrict__ rgba8_out) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n_rays || !mask_selects(mask[r], values)) return;
-  const size_t o = 3 * static_cast<size_t>(r);
-  const float m0 = __fdiv_rn(sum[o], frames), m1 = __fdiv_rn(sum[o + 1], frames), m2 = __fdiv_rn(sum[o + 2], frames);
-  if (rgb_out) {
-    rgb_out[o] = m0;
-    rgb_out[o + 1] = m1;
-    rgb_out[o + 2] = m2;
-  }
-  if (rgba8_out) rgba8_out[r] = rgba8_of(m0, m1, m2);
+  resolve_mean_pixel<true>(sum, mask, values, n_rays, frames, rgb_out, rgba8_out);
 }
 
 }  // namespace adanerf

@@ -11,9 +11,10 @@
 // Every floating-point operation is a single rounded fp32 operation in a fixed order (the library is built with -ffp-contract=off), so
 // the stage is exact against a numpy float32 restatement (tests/reproject_reference.py).  The source reads are coalesced, the scatter is
 // what it is: one 8-byte atomic per source pixel, 5.1 MB of them for an 800 x 800 frame.
-// Device code only (gfx950, wave64); part of kernels.hip.hpp.
+// The rotation into the destination camera, the image coordinates and the block's count are k_pose_core.hip.hpp's.
+// Device code only (gfx950, wave64); part of stages.hip.
 #pragma once
-#include "k_common.hip.hpp"
+#include "k_pose_core.hip.hpp"
 
 namespace adanerf {
 
@@ -53,15 +54,13 @@ __global__ __launch_bounds__(256) void reproject_splat_kernel(ReprojectParams p,
   float q[3];
 #pragma unroll
   for (int k = 0; k < 3; ++k) q[k] = near ? __fsub_rn(__fadd_rn(o[k], __fmul_rn(nds[k], t)), p.dst_pos[k]) : nds[k];      // far: direction only
-  float v[3];      // camera space of the destination: the transpose of its c2w
-#pragma unroll
-  for (int k = 0; k < 3; ++k)
-    v[k] = __fadd_rn(__fadd_rn(__fmul_rn(p.dst_rot[k], q[0]), __fmul_rn(p.dst_rot[3 + k], q[1])), __fmul_rn(p.dst_rot[6 + k], q[2]));
+  float v[3];      // camera space of the destination
+  to_camera(p.dst_rot, q, v);
   const float zc = -v[2];
   if (!(zc > 0.f && zc < INFINITY)) return;
   const float focal = static_cast<float>(p.g.focal), fw = static_cast<float>(w), fh = static_cast<float>(h);
-  const float u = __fadd_rn(__fmul_rn(focal, v[0]) / zc, __fmul_rn(0.5f, fw));
-  const float vv = __fadd_rn(__fmul_rn(focal, -v[1]) / zc, __fmul_rn(0.5f, fh));
+  const float u = image_coord(focal, v[0], zc, fw);
+  const float vv = image_coord(focal, -v[1], zc, fh);
   if (!(u >= 0.f && u < fw && vv >= 0.f && vv < fh)) return;      // floorf(u) <= u < w: the pixel is inside
   const int X = static_cast<int>(floorf(u)), Y = static_cast<int>(floorf(vv));
   const unsigned long long key =
@@ -74,7 +73,6 @@ __global__ __launch_bounds__(256) void reproject_resolve_kernel(const unsigned l
                                                                 int h, int fill, uint32_t hole_rgba8, uint32_t* __restrict__ dst,
                                                                 float* __restrict__ dst_depth, uint8_t* __restrict__ dst_mask,
                                                                 int32_t* __restrict__ holes) {
-  __shared__ int wave_holes[4];
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
   const bool inside = j < w * h;
   int is_hole = 0;
@@ -105,13 +103,7 @@ __global__ __launch_bounds__(256) void reproject_resolve_kernel(const unsigned l
     if (dst_mask) dst_mask[j] = static_cast<uint8_t>(mask);
     is_hole = mask == 0;
   }
-  const int in_wave = wave_sum_dpp_i32(is_hole);
-  if (lane_id() == 0) wave_holes[threadIdx.x >> 6] = in_wave;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int in_block = (wave_holes[0] + wave_holes[1]) + (wave_holes[2] + wave_holes[3]);
-    if (in_block) atomicAdd(holes, in_block);
-  }
+  count_in_block(is_hole, holes);
 }
 
 }  // namespace adanerf

@@ -21,7 +21,8 @@
 // (32 400) adds on one address made the call 0.133 ms (0.362 ms) where this form takes 0.059 ms (0.125 ms).
 // Every floating-point operation is a single rounded fp32 operation in a fixed order (-ffp-contract=off and the _rn intrinsics), so the
 // stage is exact against a numpy float32 restatement (tests/sparse_temporal_reference.py).
-// Device code only (gfx950, wave64); part of kernels.hip.hpp.
+// The expressions shared with the other stages that change pose are k_pose_core.hip.hpp's.
+// Device code only (gfx950, wave64); part of stages.hip.
 #pragma once
 #include "k_upsample.hip.hpp"
 
@@ -71,11 +72,7 @@ __global__ __launch_bounds__(256) void sparse_resolve_kernel(TemporalParams p, i
     float P[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) P[k] = __fadd_rn(o[k], __fmul_rn(nds[k], t));
-    float zc_cur = INFINITY;
-    if (near) {
-      const float q0 = __fsub_rn(P[0], p.g.pos[0]), q1 = __fsub_rn(P[1], p.g.pos[1]), q2 = __fsub_rn(P[2], p.g.pos[2]);
-      zc_cur = -__fadd_rn(__fadd_rn(__fmul_rn(p.g.rot[2], q0), __fmul_rn(p.g.rot[5], q1)), __fmul_rn(p.g.rot[8], q2));
-    }
+    const float zc_cur = near ? camera_depth(p.g.pos, p.g.rot, P) : INFINITY;
     const float c0 = cur_rgb[3 * j], c1 = cur_rgb[3 * j + 1], c2 = cur_rgb[3 * j + 2];
     float r0 = c0, r1 = c1, r2 = c2;      // not live: the bits copied
     int count = rendered ? 1 : 0;
@@ -85,17 +82,15 @@ __global__ __launch_bounds__(256) void sparse_resolve_kernel(TemporalParams p, i
       float q[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) q[k] = near ? __fsub_rn(P[k], p.prev_pos[k]) : nds[k];      // far: direction only
-      float v[3];      // camera space of the history: the transpose of its c2w
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        v[k] = __fadd_rn(__fadd_rn(__fmul_rn(p.prev_rot[k], q[0]), __fmul_rn(p.prev_rot[3 + k], q[1])), __fmul_rn(p.prev_rot[6 + k], q[2]));
+      float v[3];      // camera space of the history
+      to_camera(p.prev_rot, q, v);
       const float zc = -v[2];
       if (zc > 0.f && zc < INFINITY) {
         const float focal = static_cast<float>(p.g.focal), fw = static_cast<float>(w), fh = static_cast<float>(h);
-        const float u = __fadd_rn(__fmul_rn(focal, v[0]) / zc, __fmul_rn(0.5f, fw));
-        const float vv = __fadd_rn(__fmul_rn(focal, -v[1]) / zc, __fmul_rn(0.5f, fh));
+        const float u = image_coord(focal, v[0], zc, fw);
+        const float vv = image_coord(focal, -v[1], zc, fh);
         if (u >= 0.f && u < fw && vv >= 0.f && vv < fh) {      // floorf(u) <= u < w: every tap below is inside
-          const int tap = static_cast<int>(floorf(vv)) * w + static_cast<int>(floorf(u));
+          const int tap = nearest_tap(u, vv, w);
           bool accepted = true;
           // 4 disocclusion: the history's depth against the range of zp over the 3 x 3 neighbourhood or the cell's used corners
           if (hist_depth) {
@@ -135,22 +130,8 @@ __global__ __launch_bounds__(256) void sparse_resolve_kernel(TemporalParams p, i
             verdict = live ? 1 : 2;
             if (live) {
               // 5 history colour
-              const float fx = __fsub_rn(u, 0.5f), fy = __fsub_rn(vv, 0.5f);
-              const float x0f = floorf(fx), y0f = floorf(fy);
-              const float wx = __fsub_rn(fx, x0f), wy = __fsub_rn(fy, y0f);
-              const int x0 = static_cast<int>(x0f), y0 = static_cast<int>(y0f);      // -1 .. w - 1
-              const int xa = max(x0, 0), xb = min(x0 + 1, w - 1), ya = max(y0, 0), yb = min(y0 + 1, h - 1);
-              const float* h00 = hist_rgb + 3 * (ya * w + xa);
-              const float* h01 = hist_rgb + 3 * (ya * w + xb);
-              const float* h10 = hist_rgb + 3 * (yb * w + xa);
-              const float* h11 = hist_rgb + 3 * (yb * w + xb);
               float hst[3];
-#pragma unroll
-              for (int k = 0; k < 3; ++k) {
-                const float top = __fadd_rn(h00[k], __fmul_rn(wx, __fsub_rn(h01[k], h00[k])));
-                const float bot = __fadd_rn(h10[k], __fmul_rn(wx, __fsub_rn(h11[k], h10[k])));
-                hst[k] = __fadd_rn(top, __fmul_rn(wy, __fsub_rn(bot, top)));
-              }
+              bilinear_history(hist_rgb, w, h, u, vv, hst);
               if (rendered) {
                 // 6 clamp: a reconstructed pixel's own colour is an interpolation and no evidence against its history
                 if (p.clamp) {
@@ -176,9 +157,9 @@ __global__ __launch_bounds__(256) void sparse_resolve_kernel(TemporalParams p, i
                 // 8 blend
                 count = min(hc + 1, 255);
                 const float a_eff = fmaxf(p.alpha, 1.0f / static_cast<float>(count));
-                r0 = __fadd_rn(hst[0], __fmul_rn(a_eff, __fsub_rn(c0, hst[0])));
-                r1 = __fadd_rn(hst[1], __fmul_rn(a_eff, __fsub_rn(c1, hst[1])));
-                r2 = __fadd_rn(hst[2], __fmul_rn(a_eff, __fsub_rn(c2, hst[2])));
+                r0 = blend_toward(hst[0], c0, a_eff);
+                r1 = blend_toward(hst[1], c1, a_eff);
+                r2 = blend_toward(hst[2], c2, a_eff);
               } else {
                 count = hc;
                 r0 = hst[0];

@@ -12,10 +12,11 @@
 // rule skips NaNs, so the border needs no second case.  The history taps depend on the data and stay plain global loads.
 // Every floating-point operation is a single rounded fp32 operation in a fixed order (the library is built with -ffp-contract=off), so
 // the stage is exact against a numpy float32 restatement (tests/temporal_reference.py).  The rejected pixels are counted in integers.
-// Device code only (gfx950, wave64); part of kernels.hip.hpp.
+// The expressions this stage shares with the others that change pose -- a point's camera depth, the rotation into a camera, image
+// coordinates and tap, the history's bilinear taps, the clamp's order, the blend, the block's count -- are k_pose_core.hip.hpp's.
+// Device code only (gfx950, wave64); part of stages.hip.
 #pragma once
-#include "k_accumulate.hip.hpp"
-#include "k_common.hip.hpp"
+#include "k_pose_core.hip.hpp"
 
 namespace adanerf {
 
@@ -32,23 +33,6 @@ struct TemporalParams {
   int32_t clamp;            // ADANERF_TEMPORAL_CLAMP
 };
 
-// The order of the clamp: a NaN is skipped (both NaN: a NaN), otherwise the floats order as sign-magnitude integers, so -0 < +0.
-// v_min_f32 / v_max_f32 do not promise the signed-zero order, hence integers.
-__device__ __forceinline__ int32_t temporal_order_key(float f) {
-  const int32_t b = __float_as_int(f);
-  return b ^ ((b >> 31) & 0x7FFFFFFF);
-}
-__device__ __forceinline__ float temporal_min(float a, float b) {
-  if (a != a) return b;
-  if (b != b) return a;
-  return temporal_order_key(b) < temporal_order_key(a) ? b : a;
-}
-__device__ __forceinline__ float temporal_max(float a, float b) {
-  if (a != a) return b;
-  if (b != b) return a;
-  return temporal_order_key(b) > temporal_order_key(a) ? b : a;
-}
-
 __global__ __launch_bounds__(256) void temporal_resolve_kernel(TemporalParams p, const float* __restrict__ cur_rgb, const float* __restrict__ cur_depth,
                                                                const float* __restrict__ cur_acc, const float* __restrict__ hist_rgb,
                                                                const float* __restrict__ hist_depth, const uint8_t* __restrict__ hist_count,
@@ -56,7 +40,6 @@ __global__ __launch_bounds__(256) void temporal_resolve_kernel(TemporalParams p,
                                                                uint8_t* __restrict__ out_count, uchar4* __restrict__ out_rgba8,
                                                                uint8_t* __restrict__ out_mask, int32_t* __restrict__ rejected) {
   __shared__ float tile[kTemporalTileFloats];
-  __shared__ int wave_rejected[4];
   const int w = p.g.w, h = p.g.h;      // w * h < 2^25 (frame_geometry): 3 * w * h fits an int
   const int tid = static_cast<int>(threadIdx.x);
   const int tx = tid & (kTemporalTileW - 1), ty = tid >> 5;
@@ -91,11 +74,7 @@ __global__ __launch_bounds__(256) void temporal_resolve_kernel(TemporalParams p,
     float P[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) P[k] = __fadd_rn(o[k], __fmul_rn(nds[k], t));
-    float zc_cur = INFINITY;
-    if (near) {
-      const float q0 = __fsub_rn(P[0], p.g.pos[0]), q1 = __fsub_rn(P[1], p.g.pos[1]), q2 = __fsub_rn(P[2], p.g.pos[2]);
-      zc_cur = -__fadd_rn(__fadd_rn(__fmul_rn(p.g.rot[2], q0), __fmul_rn(p.g.rot[5], q1)), __fmul_rn(p.g.rot[8], q2));
-    }
+    const float zc_cur = near ? camera_depth(p.g.pos, p.g.rot, P) : INFINITY;
     const float c0 = cur_rgb[3 * j], c1 = cur_rgb[3 * j + 1], c2 = cur_rgb[3 * j + 2];
     float r0 = c0, r1 = c1, r2 = c2;      // a rejected pixel: the bits copied
     int count = 1;
@@ -104,39 +83,23 @@ __global__ __launch_bounds__(256) void temporal_resolve_kernel(TemporalParams p,
       float q[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) q[k] = near ? __fsub_rn(P[k], p.prev_pos[k]) : nds[k];      // far: direction only
-      float v[3];      // camera space of the history: the transpose of its c2w
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        v[k] = __fadd_rn(__fadd_rn(__fmul_rn(p.prev_rot[k], q[0]), __fmul_rn(p.prev_rot[3 + k], q[1])), __fmul_rn(p.prev_rot[6 + k], q[2]));
+      float v[3];      // camera space of the history
+      to_camera(p.prev_rot, q, v);
       const float zc = -v[2];
       if (zc > 0.f && zc < INFINITY) {
         const float focal = static_cast<float>(p.g.focal), fw = static_cast<float>(w), fh = static_cast<float>(h);
-        const float u = __fadd_rn(__fmul_rn(focal, v[0]) / zc, __fmul_rn(0.5f, fw));
-        const float vv = __fadd_rn(__fmul_rn(focal, -v[1]) / zc, __fmul_rn(0.5f, fh));
+        const float u = image_coord(focal, v[0], zc, fw);
+        const float vv = image_coord(focal, -v[1], zc, fh);
         if (u >= 0.f && u < fw && vv >= 0.f && vv < fh) {      // floorf(u) <= u < w: every tap below is inside
-          const int tap = static_cast<int>(floorf(vv)) * w + static_cast<int>(floorf(u));
+          const int tap = nearest_tap(u, vv, w);
           accepted = true;
           if (hist_depth) {
             const float hd = hist_depth[tap];
             accepted = near ? (fabsf(hd) < INFINITY && fabsf(__fsub_rn(zc, hd)) <= __fmul_rn(p.depth_tol, zc)) : hd == INFINITY;
           }
           if (accepted) {
-            const float fx = __fsub_rn(u, 0.5f), fy = __fsub_rn(vv, 0.5f);
-            const float x0f = floorf(fx), y0f = floorf(fy);
-            const float wx = __fsub_rn(fx, x0f), wy = __fsub_rn(fy, y0f);
-            const int x0 = static_cast<int>(x0f), y0 = static_cast<int>(y0f);      // -1 .. w - 1
-            const int xa = max(x0, 0), xb = min(x0 + 1, w - 1), ya = max(y0, 0), yb = min(y0 + 1, h - 1);
-            const float* h00 = hist_rgb + 3 * (ya * w + xa);
-            const float* h01 = hist_rgb + 3 * (ya * w + xb);
-            const float* h10 = hist_rgb + 3 * (yb * w + xa);
-            const float* h11 = hist_rgb + 3 * (yb * w + xb);
             float hst[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-              const float top = __fadd_rn(h00[k], __fmul_rn(wx, __fsub_rn(h01[k], h00[k])));
-              const float bot = __fadd_rn(h10[k], __fmul_rn(wx, __fsub_rn(h11[k], h10[k])));
-              hst[k] = __fadd_rn(top, __fmul_rn(wy, __fsub_rn(bot, top)));
-            }
+            bilinear_history(hist_rgb, w, h, u, vv, hst);
             if (p.clamp) {
               const float qnan = __int_as_float(0x7FC00000);
               float lo[3] = {qnan, qnan, qnan}, hi[3] = {qnan, qnan, qnan};
@@ -160,9 +123,9 @@ __global__ __launch_bounds__(256) void temporal_resolve_kernel(TemporalParams p,
               count = min(static_cast<int>(hist_count[tap]) + 1, 255);
               a_eff = fmaxf(p.alpha, 1.0f / static_cast<float>(count));
             }
-            r0 = __fadd_rn(hst[0], __fmul_rn(a_eff, __fsub_rn(c0, hst[0])));
-            r1 = __fadd_rn(hst[1], __fmul_rn(a_eff, __fsub_rn(c1, hst[1])));
-            r2 = __fadd_rn(hst[2], __fmul_rn(a_eff, __fsub_rn(c2, hst[2])));
+            r0 = blend_toward(hst[0], c0, a_eff);
+            r1 = blend_toward(hst[1], c1, a_eff);
+            r2 = blend_toward(hst[2], c2, a_eff);
           }
         }
       }
@@ -176,13 +139,7 @@ __global__ __launch_bounds__(256) void temporal_resolve_kernel(TemporalParams p,
     if (out_mask) out_mask[j] = accepted ? 1 : 0;
     is_rejected = accepted ? 0 : 1;
   }
-  const int in_wave = wave_sum_dpp_i32(is_rejected);
-  if (lane_id() == 0) wave_rejected[tid >> 6] = in_wave;
-  __syncthreads();
-  if (tid == 0) {
-    const int in_block = (wave_rejected[0] + wave_rejected[1]) + (wave_rejected[2] + wave_rejected[3]);
-    if (in_block) atomicAdd(rejected, in_block);
-  }
+  count_in_block(is_rejected, rejected);
 }
 
 }  // namespace adanerf

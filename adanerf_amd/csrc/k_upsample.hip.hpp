@@ -16,7 +16,8 @@
 // 1 at the first pixel, cx + 31 can round up to 32 -- so the footprint is ceil(31 / s) + 4 columns and ceil(7 / s) + 4 rows with the halo.
 // A pixel outside the image is staged as a NaN: the clamp's rule skips it, and zp (finite or +inf by definition) reads it as "no such pixel".
 // Every floating-point operation is a single rounded fp32 operation in a fixed order (-ffp-contract=off): exact against
-// tests/upsample_reference.py.  Device code only (gfx950, wave64); part of kernels.hip.hpp.
+// tests/upsample_reference.py.  The expressions shared with the other stages that change pose are k_pose_core.hip.hpp's; pass A and
+// step 5 keep their own text (profiles/pose_core_isa_identity.md).  Device code only (gfx950, wave64); part of stages.hip.
 #pragma once
 #include "k_temporal.hip.hpp"
 
@@ -80,7 +81,6 @@ __global__ __launch_bounds__(256) void upsample_resolve_kernel(UpsampleParams p,
                                                                int32_t* __restrict__ rejected) {
   __shared__ float tile[kUpsampleMaxPixels * 3];
   __shared__ float ztile[kUpsampleMaxPixels];
-  __shared__ int wave_rejected[4];
   const int w = p.g_lo.w, h = p.g_lo.h, W = p.g_hi.w, H = p.g_hi.h;      // W * H < 2^25: 3 * W * H fits an int
   const int s = p.scale;
   const float fs = static_cast<float>(s);
@@ -141,11 +141,7 @@ __global__ __launch_bounds__(256) void upsample_resolve_kernel(UpsampleParams p,
     float P[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) P[k] = __fadd_rn(o[k], __fmul_rn(nds[k], t));
-    float zc_cur = INFINITY;
-    if (near) {
-      const float q0 = __fsub_rn(P[0], p.g_hi.pos[0]), q1 = __fsub_rn(P[1], p.g_hi.pos[1]), q2 = __fsub_rn(P[2], p.g_hi.pos[2]);
-      zc_cur = -__fadd_rn(__fadd_rn(__fmul_rn(p.g_hi.rot[2], q0), __fmul_rn(p.g_hi.rot[5], q1)), __fmul_rn(p.g_hi.rot[8], q2));
-    }
+    const float zc_cur = near ? camera_depth(p.g_hi.pos, p.g_hi.rot, P) : INFINITY;
     float r0 = c0, r1 = c1, r2 = c2;      // not live: the bits copied
     int count = inside;
     int mask = 0;
@@ -154,17 +150,15 @@ __global__ __launch_bounds__(256) void upsample_resolve_kernel(UpsampleParams p,
       float q[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) q[k] = near ? __fsub_rn(P[k], p.prev_pos[k]) : nds[k];      // far: direction only
-      float v[3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-        v[k] = __fadd_rn(__fadd_rn(__fmul_rn(p.prev_rot[k], q[0]), __fmul_rn(p.prev_rot[3 + k], q[1])), __fmul_rn(p.prev_rot[6 + k], q[2]));
+      float v[3];      // camera space of the history
+      to_camera(p.prev_rot, q, v);
       const float zc = -v[2];
       if (zc > 0.f && zc < INFINITY) {
         const float focal = static_cast<float>(p.g_hi.focal), fw = static_cast<float>(W), fh = static_cast<float>(H);
-        const float u = __fadd_rn(__fmul_rn(focal, v[0]) / zc, __fmul_rn(0.5f, fw));
-        const float vv = __fadd_rn(__fmul_rn(focal, -v[1]) / zc, __fmul_rn(0.5f, fh));
+        const float u = image_coord(focal, v[0], zc, fw);
+        const float vv = image_coord(focal, -v[1], zc, fh);
         if (u >= 0.f && u < fw && vv >= 0.f && vv < fh) {      // floorf(u) <= u < W: every tap below is inside
-          const int tap = static_cast<int>(floorf(vv)) * W + static_cast<int>(floorf(u));
+          const int tap = nearest_tap(u, vv, W);
           bool accepted = true;
           // 4 disocclusion: the history's depth against the range of zp over i's 3 x 3 neighbourhood
           if (hist_depth) {
@@ -252,9 +246,9 @@ __global__ __launch_bounds__(256) void upsample_resolve_kernel(UpsampleParams p,
               r1 = hst[1];
               r2 = hst[2];
               if (kw > 0.f) {
-                r0 = __fadd_rn(hst[0], __fmul_rn(a_eff, __fsub_rn(c0, hst[0])));
-                r1 = __fadd_rn(hst[1], __fmul_rn(a_eff, __fsub_rn(c1, hst[1])));
-                r2 = __fadd_rn(hst[2], __fmul_rn(a_eff, __fsub_rn(c2, hst[2])));
+                r0 = blend_toward(hst[0], c0, a_eff);
+                r1 = blend_toward(hst[1], c1, a_eff);
+                r2 = blend_toward(hst[2], c2, a_eff);
               }
             }
           }
@@ -270,13 +264,7 @@ __global__ __launch_bounds__(256) void upsample_resolve_kernel(UpsampleParams p,
     if (out_mask) out_mask[J] = static_cast<uint8_t>(mask);
     is_rejected = mask == 0 ? 1 : 0;
   }
-  const int in_wave = wave_sum_dpp_i32(is_rejected);
-  if (lane_id() == 0) wave_rejected[tid >> 6] = in_wave;
-  __syncthreads();
-  if (tid == 0) {
-    const int in_block = (wave_rejected[0] + wave_rejected[1]) + (wave_rejected[2] + wave_rejected[3]);
-    if (in_block) atomicAdd(rejected, in_block);
-  }
+  count_in_block(is_rejected, rejected);
 }
 
 }  // namespace adanerf

@@ -8,7 +8,8 @@
 //   A5+A6     shade_mlp16x2_kernel / shade_mlp32_kernel   fused PE + 8x256 shading MLP (bf16/f16/f32 MFMA)
 //   A7        composite_kernel       sigmoid + alpha * oracle weight, front-to-back
 //   N8        mask_bits_kernel / mask_scatter_kernel   a byte mask as bit words for refine_list_kernel; the pixels of a listed batch to their places (masked rendering)
-// stages.hip (k_flip, k_present, k_reproject, k_accumulate, k_temporal, k_upsample, k_blend, k_density, k_sparse_temporal, k_contrast):
+// stages.hip (k_flip, k_present, k_reproject, k_accumulate, k_temporal, k_upsample, k_blend, k_density, k_sparse_temporal, k_contrast;
+// k_pose_core: the arithmetic N4, N6, N7 and N12 share):
 //   N1        flip_kernel / flip_mean_kernel   FLIP error map and mean of an image pair (the evaluator's second metric)
 //   N3        present_kernel / present_area_kernel   the frame at the window's size (the viewer's blit: linear / nearest, y flip; exact area filter)
 //   N4        reproject_clear_kernel / reproject_splat_kernel / reproject_resolve_kernel   a rendered frame warped to another pose by its depth
