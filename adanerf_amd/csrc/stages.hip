@@ -14,6 +14,7 @@
 #include "k_flip.hip.hpp"
 #include "k_present.hip.hpp"
 #include "k_reproject.hip.hpp"
+#include "k_reproject_gather.hip.hpp"
 #include "k_accumulate.hip.hpp"
 #include "k_temporal.hip.hpp"
 #include "k_upsample.hip.hpp"
@@ -348,6 +349,61 @@ int adanerf_reproject(adanerf_ctx* c, const void* d_src_rgba8, const float* d_sr
   HIP_TRY(c, hipGetLastError());
   hipLaunchKernelGGL(reproject_resolve_kernel, grid, block, 0, c->stream, zbuf, static_cast<const uint32_t*>(d_src_rgba8), w, h,
                      (flags & ADANERF_REPROJECT_FILL) ? 1 : 0, hole_rgba8, static_cast<uint32_t*>(d_dst_rgba8), d_dst_depth, d_dst_mask, holes);
+  HIP_TRY(c, hipGetLastError());
+  return read_count(c, holes, holes_out);
+}
+
+int adanerf_reproject_gather(adanerf_ctx* c, const float* d_src_rgb, const float* d_src_depth_map, const float* d_src_acc_map, const float src_pos[3],
+                             const float src_rot_c2w[9], const float dst_pos[3], const float dst_rot_c2w[9], float acc_min, float depth_tol,
+                             int32_t iterations, uint32_t hole_rgba8, int32_t flags, float* d_dst_rgb, void* d_dst_rgba8, float* d_dst_depth,
+                             uint8_t* d_dst_mask, int32_t* holes_out) {
+  constexpr const char* who = "adanerf_reproject_gather";
+  if (!c) return ADANERF_EINVAL;
+  if (!d_src_rgb || !d_src_depth_map || !d_src_acc_map || !d_dst_rgb) return reject(c, ADANERF_EINVAL, who, "NULL image");
+  if (int rc = check_poses(c, who, src_pos, src_rot_c2w, dst_pos, dst_rot_c2w, true)) return rc;
+  if (!(acc_min >= 0.f)) return reject(c, ADANERF_EINVAL, who, "acc_min must be >= 0");      // every comparison also refuses a NaN
+  if (!(depth_tol >= 0.f)) return reject(c, ADANERF_EINVAL, who, "depth_tol must be >= 0");
+  if (iterations < 1 || iterations > kGatherMaxIterations) return reject(c, ADANERF_EINVAL, who, "iterations must lie in 1..8");
+  if (flags & ~ADANERF_GATHER_GUESS) return reject(c, ADANERF_EINVAL, who, "flags must be 0 or ADANERF_GATHER_GUESS");
+  if (misaligned4({d_src_rgb, d_src_depth_map, d_src_acc_map, d_dst_rgb, d_dst_rgba8, d_dst_depth}))
+    return reject(c, ADANERF_EINVAL, who, "fp32 and uchar4 images must be 4-byte aligned");
+  const int w = c->ms.info.width, h = c->ms.info.height, n = w * h;
+  const size_t b1 = static_cast<size_t>(n) * sizeof(float);
+  struct Range { const void* p; size_t bytes; };
+  const Range in[3] = {{d_src_rgb, 3 * b1}, {d_src_depth_map, b1}, {d_src_acc_map, b1}};
+  const Range out[4] = {{d_dst_rgb, 3 * b1}, {d_dst_rgba8, b1}, {d_dst_depth, b1}, {d_dst_mask, static_cast<size_t>(n)}};
+  for (int a = 0; a < 4; ++a) {      // both passes read the sources while the second writes; no output may be another's or a source's bytes
+    if (!out[a].p) continue;
+    for (const Range& r : in)
+      if (ranges_overlap(out[a].p, out[a].bytes, r.p, r.bytes)) return reject(c, ADANERF_EINVAL, who, "an output overlaps a source image");
+    for (int b = a + 1; b < 4; ++b)
+      if (out[b].p && ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) return reject(c, ADANERF_EINVAL, who, "two outputs overlap");
+  }
+  if (int rc = check_depth_frames(c, who)) return rc;
+  BIND(c);
+  if (int rc = grow_in_use(c, &c->stages.gather_surface, static_cast<size_t>(n) * sizeof(float4))) return rc;      // a warp in flight may still use the smaller table
+  int32_t* holes = nullptr;
+  if (int rc = stage_count(c, &holes)) return rc;
+  GatherSurfaceParams ps{};
+  ps.g = c->ms.rg;
+  copy_pose(ps.g.pos, ps.g.rot, src_pos, src_rot_c2w);
+  ps.acc_min = acc_min;
+  ps.origin_is_camera = c->ms.coarse_fine ? 1 : 0;      // what the render path writes to ADANERF_BUF_RAYS (camera_rays_kernel)
+  GatherWarpParams pw{};
+  pw.g = c->ms.rg;
+  copy_pose(pw.g.pos, pw.g.rot, dst_pos, dst_rot_c2w);
+  copy_pose(pw.src_pos, pw.src_rot, src_pos, src_rot_c2w);
+  pw.depth_tol = depth_tol;
+  pw.iterations = iterations;
+  pw.guess = (flags & ADANERF_GATHER_GUESS) ? 1 : 0;
+  pw.hole_rgba8 = hole_rgba8;
+  float4* surface = reinterpret_cast<float4*>(c->stages.gather_surface.p);
+  HIP_TRY(c, hipMemsetAsync(holes, 0, sizeof(int32_t), c->stream));
+  hipLaunchKernelGGL(gather_surface_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, ps, d_src_depth_map, d_src_acc_map, surface);
+  HIP_TRY(c, hipGetLastError());
+  const dim3 grid((w + kGatherTileW - 1) / kGatherTileW, (h + kGatherTileH - 1) / kGatherTileH);
+  hipLaunchKernelGGL(gather_warp_kernel, grid, dim3(256), 0, c->stream, pw, surface, d_src_rgb, d_dst_rgb, static_cast<uchar4*>(d_dst_rgba8), d_dst_depth,
+                     d_dst_mask, holes);
   HIP_TRY(c, hipGetLastError());
   return read_count(c, holes, holes_out);
 }

@@ -6,7 +6,7 @@ reference's second default metric (``metrics = ["flip", "psnr"]`` :613-615): the
 
     python -m adanerf_amd.evaluate <model_dir> <dataset_dir> [--set test] [--out DIR] [--video out.y4m] [--precision bf16]
                                    [--metrics psnr flip] [--sweep-thresholds T ...] [--sweep-samples N ...] [--sweep-scales S ...]
-                                   [--reproject-stride K [--rerender holes|unsourced]] [--supersample S] [--present-filter nearest|linear|area]
+                                   [--reproject-stride K [--reproject-warp splat|gather] [--rerender holes|unsourced]] [--supersample S] [--present-filter nearest|linear|area]
                                    [--fovea-density R:S[,R:S...],S [--fovea-temporal ALPHA] [--fovea-temporal-still K]] [--supersample-contrast T]
 
 ``--sweep-thresholds`` / ``--sweep-samples`` render the set once per (N, threshold) of their cross product on ONE context
@@ -19,7 +19,8 @@ dataset's ``w x h`` on the GPU (``adanerf_present``, the viewer's blit) and scor
 ``--reproject-stride K`` renders the poses with ``i % K == 0`` and warps the others from the nearest rendered pose before them
 (``adanerf_reproject``, holes filled from their neighbours): what a host that renders every K-th frame shows in between, scored against
 the same ground truth.  ``--rerender holes|unsourced`` scores every warped frame once more with its holes (unsourced: the filled pixels too)
-rendered at its own pose (``adanerf_render_masked``).
+rendered at its own pose (``adanerf_render_masked``).  ``--reproject-warp gather`` makes the warped frames with ``adanerf_reproject_gather``
+(``--reproject-iterations N``, ``--reproject-tol T``: its two dials) instead of the splat.
 
 ``--supersample S`` makes every image the mean of S x S renders at the sub-pixel offsets of ``adanerf_host_subpixel_grid``, accumulated
 and resolved on the GPU (``NeuralRenderer.render_supersampled``) and scored from the fp32 mean: anti-aliasing in time, against the
@@ -53,7 +54,7 @@ from typing import List, Optional
 import numpy as np
 
 from .png import read_png, write_png
-from .renderer import PRESENT_FILTERS, RERENDER_VALUES, SUPERSAMPLE_MAX, NeuralRenderer, Settings, parse_fovea, parse_fovea_density
+from .renderer import GATHER_DEPTH_TOL, GATHER_ITERATIONS, PRESENT_FILTERS, RERENDER_VALUES, SUPERSAMPLE_MAX, NeuralRenderer, Settings, parse_fovea, parse_fovea_density
 
 
 def load_dataset(dataset_dir: str, set_name: str = "test"):
@@ -114,7 +115,8 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
              precision: str = "bf16", batch_size: int = -1, max_frames: int = 0, quiet: bool = False,
              video: Optional[str] = None, fps: int = 30, metrics=("psnr",), fovea=None, sweep_thresholds=None, sweep_samples=None, reproject_stride=None,
              supersample=None, present_filter=None, temporal=None, temporal_still=None, temporal_upsample=None, temporal_upsample_frames=None,
-             rerender=None, fovea_density=None, fovea_temporal=None, fovea_temporal_still=None, supersample_contrast=None, sweep_scales=None):
+             rerender=None, fovea_density=None, reproject_warp="splat", reproject_iterations=None, reproject_tol=None, fovea_temporal=None,
+             fovea_temporal_still=None, supersample_contrast=None, sweep_scales=None):
     """metrics: "psnr" (always reported where a ground-truth image exists) and / or "flip": each record gains ``flip``, the summary
     ``mean_flip``, and with out_dir the error map is written as an 8-bit greyscale ``%05d_flip.png``.
 
@@ -138,6 +140,9 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     ``psnr_rerendered`` / ``mse_rerendered`` and ``rerendered_fraction`` (pixels rendered, of w h), the summary
     ``mean_psnr_warped_rerendered`` and ``mean_rerendered_fraction``; out_dir gets ``%05d_rerendered.png``.  Every other key is that of a run
     without the option.
+    reproject_warp ("splat", the default, or "gather"; gather needs reproject_stride): the warped frames come from
+    NeuralRenderer.reproject_gather (adanerf_reproject_gather; reproject_iterations / reproject_tol: its two dials, None = the renderer's
+    defaults) and rerender uses reproject_gather_rerender.  Warped records carry ``warp``; the summary keys are unchanged.
 
     supersample (S in 1..8 or None): every image is the mean of S x S renders at the offsets of the regular sub-pixel grid
     (NeuralRenderer.render_supersampled), scored from the fp32 mean; ms is the sum over the S x S renders, samples_per_ray is per rendered
@@ -205,6 +210,12 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
         raise ValueError("reproject_stride must be >= 1, got %s" % (reproject_stride,))
     if rerender not in RERENDER_VALUES:
         raise ValueError("rerender must be None, 'holes' or 'unsourced', got %r" % (rerender,))
+    if reproject_warp not in ("splat", "gather"):
+        raise ValueError("reproject_warp must be 'splat' or 'gather', got %r" % (reproject_warp,))
+    if (reproject_warp == "gather" or reproject_iterations is not None or reproject_tol is not None) and not stride:
+        raise ValueError("reproject_warp / reproject_iterations / reproject_tol choose how warped frames are made: they need reproject_stride")
+    gather_kw = dict(iterations=GATHER_ITERATIONS if reproject_iterations is None else int(reproject_iterations),
+                     depth_tol=GATHER_DEPTH_TOL if reproject_tol is None else float(reproject_tol))
     if rerender and not stride:
         raise ValueError("rerender re-renders the holes of warped frames: it needs reproject_stride")
     if stride and sweep_scales:
@@ -294,11 +305,17 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                 ref = None
                 warped = bool(stride) and i % stride != 0
                 if warped:      # the last rendered frame at this pose: what a host that renders every K-th frame shows here
-                    rgba, _, holes = r.reproject(fr["pose"], fr["rot"])
+                    if reproject_warp == "gather":
+                        _, rgba, _, holes = r.reproject_gather(fr["pose"], fr["rot"], **gather_kw)
+                    else:
+                        rgba, _, holes = r.reproject(fr["pose"], fr["rot"])
                     rgb = rgba[:, :3].astype(np.float32) / 255.0
-                    rec = dict(extra, frame=i, image=fr["image"], warped=True, hole_fraction=holes / float(w * h))
+                    rec = dict(extra, frame=i, image=fr["image"], warped=True, warp=reproject_warp, hole_fraction=holes / float(w * h))
                     if rerender:      # the same warp with its holes rendered at this pose
-                        rr_rgba, _, _, rerendered = r.reproject_rerender(fr["pose"], fr["rot"], rerender)
+                        if reproject_warp == "gather":
+                            rr_rgba, _, _, rerendered = r.reproject_gather_rerender(fr["pose"], fr["rot"], rerender, **gather_kw)
+                        else:
+                            rr_rgba, _, _, rerendered = r.reproject_rerender(fr["pose"], fr["rot"], rerender)
                         rec.update(rerendered_fraction=rerendered / float(w * h))
                         if out_dir:
                             os.makedirs(out_dir, exist_ok=True)
@@ -490,6 +507,12 @@ def build_parser():
     ap.add_argument("--reproject-stride", type=int, default=None, metavar="K",
                     help="render the poses with i %% K == 0 and warp the others from the nearest rendered pose before them (adanerf_reproject); "
                          "the summary gains mean_psnr_rendered / mean_psnr_warped / mean_hole_fraction (and mean_flip_* with --metrics flip)")
+    ap.add_argument("--reproject-warp", default=None, choices=["splat", "gather"],
+                    help="with --reproject-stride: how the warped frames are made -- splat (default, adanerf_reproject) or gather "
+                         "(adanerf_reproject_gather: every pixel iterates along its ray to the source surface); warped records carry `warp`")
+    ap.add_argument("--reproject-iterations", type=int, default=None, metavar="N", help="with --reproject-warp gather: steps per pixel, 1..8 (default %d)" % GATHER_ITERATIONS)
+    ap.add_argument("--reproject-tol", type=float, default=None, metavar="T",
+                    help="with --reproject-warp gather: relative depth tolerance of the consistency test (default %g)" % GATHER_DEPTH_TOL)
     ap.add_argument("--rerender", default=None, choices=["holes", "unsourced"],
                     help="with --reproject-stride: score every warped frame once more with its holes (unsourced: the filled pixels too) rendered at "
                          "its own pose (adanerf_render_masked); the summary gains mean_psnr_warped_rerendered / mean_rerendered_fraction")
@@ -535,6 +558,8 @@ def build_parser():
 def main(argv=None):
     ap = build_parser()
     a = ap.parse_args(argv)
+    if (a.reproject_warp is not None or a.reproject_iterations is not None or a.reproject_tol is not None) and a.reproject_stride is None:
+        ap.error("--reproject-warp / --reproject-iterations / --reproject-tol need --reproject-stride")
     if a.rerender is not None and a.reproject_stride is None:
         ap.error("--rerender needs --reproject-stride")
     if a.supersample is not None and a.reproject_stride is not None:
@@ -567,7 +592,8 @@ def main(argv=None):
         ap.error("--temporal-upsample-frames goes with --temporal-upsample")
     summary, _ = evaluate(a.model_dir, a.dataset_dir, a.set, a.out, a.precision, a.batch_size, a.max_frames, video=a.video, fps=a.fps,
                           metrics=tuple(a.metrics), sweep_thresholds=a.sweep_thresholds, sweep_samples=a.sweep_samples, sweep_scales=a.sweep_scales,
-                          fovea=a.fovea, reproject_stride=a.reproject_stride, rerender=a.rerender, supersample=a.supersample, present_filter=a.present_filter,
+                          fovea=a.fovea, reproject_stride=a.reproject_stride, reproject_warp=a.reproject_warp or "splat", reproject_iterations=a.reproject_iterations,
+                          reproject_tol=a.reproject_tol, rerender=a.rerender, supersample=a.supersample, present_filter=a.present_filter,
                           temporal=a.temporal, temporal_still=a.temporal_still, temporal_upsample=a.temporal_upsample,
                           temporal_upsample_frames=a.temporal_upsample_frames, fovea_density=a.fovea_density,
                           supersample_contrast=a.supersample_contrast, fovea_temporal=a.fovea_temporal, fovea_temporal_still=a.fovea_temporal_still)

@@ -24,7 +24,7 @@ NeuralRenderer::~NeuralRenderer() {
   if (ctx) {
     if (d_gathered) adanerf_free(ctx, d_gathered);
     if (d_frame) adanerf_free(ctx, d_frame);
-    for (void* p : {d_depth, d_acc, d_warp, d_wmask, d_rgb, d_sum, d_hist[0][0], d_hist[0][1], d_hist[0][2], d_hist[1][0], d_hist[1][1], d_hist[1][2], d_up, d_limit, d_behind, d_dmask, d_stage, d_cmask})
+    for (void* p : {d_depth, d_acc, d_warp, d_wmask, d_src_rgb, d_warp_rgb, d_rgb, d_sum, d_hist[0][0], d_hist[0][1], d_hist[0][2], d_hist[1][0], d_hist[1][1], d_hist[1][2], d_up, d_limit, d_behind, d_dmask, d_stage, d_cmask})
       if (p) adanerf_free(ctx, p);
     if (d_window) adanerf_free(ctx, d_window);
     adanerf_destroy(ctx);
@@ -282,6 +282,13 @@ bool NeuralRenderer::allocFrameBuffers() {
       *p = nullptr;
       if (adanerf_malloc(ctx, n * 4, p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
     }
+    if (settings.reproject_gather) {
+      for (void** p : {&d_src_rgb, &d_warp_rgb}) {
+        if (*p && adanerf_free(ctx, *p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+        *p = nullptr;
+        if (adanerf_malloc(ctx, n * 12, p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+      }
+    }
     if (adanerf_set_aux_outputs(ctx, static_cast<float*>(d_depth), static_cast<float*>(d_acc)) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
   }
   if (world_ > 1) {
@@ -521,7 +528,8 @@ bool NeuralRenderer::render() {
     if (!renderHybrid(&st, rot)) return false;
   } else if (!settings.density_stride.empty()) {
     if (settings.fovea_temporal_alpha > 0.f ? !renderFoveatedTemporal(&st, rot) : !renderFoveated(&st)) return false;
-  } else if (settings.supersample > 1 ? !renderSupersampled(&st) : adanerf_render(ctx, d_frame, nullptr, &st) != ADANERF_OK) {
+  } else if (settings.supersample > 1 ? !renderSupersampled(&st)
+                                      : adanerf_render(ctx, d_frame, static_cast<float*>(settings.reproject_gather ? d_src_rgb : nullptr), &st) != ADANERF_OK) {
     if (settings.supersample <= 1) err = adanerf_last_error(ctx);
     return false;
   }
@@ -733,11 +741,17 @@ bool NeuralRenderer::renderUpsampled(adanerf_stats* st, const float rot[9]) {
   return true;
 }
 
-// --reproject K: the last rendered frame at this frame's camera (adanerf_reproject, holes filled from their neighbours, the rest black)
+// --reproject K: the last rendered frame at this frame's camera (adanerf_reproject, holes filled from their neighbours, the rest black;
+// --reproject-warp gather: adanerf_reproject_gather, unverified pixels keep their gathered colour, the rest black)
 bool NeuralRenderer::warp(const float rot[9]) {
   int32_t holes = 0;
-  if (adanerf_reproject(ctx, d_frame, static_cast<const float*>(d_depth), static_cast<const float*>(d_acc), src_pos, src_rot, camera.getPosition(), rot,
-                        0.5f, 0xFF000000u, ADANERF_REPROJECT_FILL, d_warp, nullptr, static_cast<uint8_t*>(d_wmask), &holes) != ADANERF_OK) {
+  const int rc = settings.reproject_gather
+                     ? adanerf_reproject_gather(ctx, static_cast<const float*>(d_src_rgb), static_cast<const float*>(d_depth), static_cast<const float*>(d_acc), src_pos,
+                                                src_rot, camera.getPosition(), rot, 0.5f, settings.reproject_tol, settings.reproject_iterations, 0xFF000000u,
+                                                ADANERF_GATHER_GUESS, static_cast<float*>(d_warp_rgb), d_warp, nullptr, static_cast<uint8_t*>(d_wmask), &holes)
+                     : adanerf_reproject(ctx, d_frame, static_cast<const float*>(d_depth), static_cast<const float*>(d_acc), src_pos, src_rot, camera.getPosition(),
+                                         rot, 0.5f, 0xFF000000u, ADANERF_REPROJECT_FILL, d_warp, nullptr, static_cast<uint8_t*>(d_wmask), &holes);
+  if (rc != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;
   }

@@ -75,6 +75,8 @@ class NeuralRenderer {
   void* d_acc = nullptr;
   void* d_warp = nullptr;            // uchar4 [h*w]
   void* d_wmask = nullptr;           // --rerender: adanerf_reproject's mask of the warped frame, uint8 [h*w]
+  void* d_src_rgb = nullptr;         // --reproject-warp gather: the rendered frame's fp32 colour, float [h*w*3]
+  void* d_warp_rgb = nullptr;        // --reproject-warp gather: the gathered fp32 colour, float [h*w*3]
   const void* d_shown = nullptr;     // what the last frame presented: d_frame or d_warp (-w / --write-window write it)
   bool have_source = false;          // d_frame, d_depth, d_acc and src_* describe one rendered frame of the size and selection in force
   int since_render = 0;              // warped frames since it

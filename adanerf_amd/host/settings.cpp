@@ -29,8 +29,12 @@ const char* Settings::usage() {
          "                                                              cut: --taa / --taau / --fovea-temporal start a new history with that frame)\n"
          "               [--reproject K]      of every K frames render the first and warp it to the camera of the next K - 1 (depth\n"
          "                                    reprojection, holes filled from their neighbours); -w / --write-window write what was shown\n"
+         "               [--reproject-warp splat|gather]  with --reproject K: splat (default) scatters source pixels (adanerf_reproject); gather\n"
+         "                                    iterates each shown pixel along its ray to the source surface (adanerf_reproject_gather: no cracks)\n"
+         "               [--reproject-iterations N] [--reproject-tol T]   the gather's steps per pixel (1..8, default 4) and the relative depth\n"
+         "                                    tolerance of its consistency test (default 0.05)\n"
          "               [--rerender holes|unsourced]     with --reproject K: render the warped frames' holes (unsourced: the pixels filled from a\n"
-         "                                    neighbour too) at their own camera instead of leaving the fill\n"
+         "                                    neighbour, or gathered but unverified, too) at their own camera instead of leaving them\n"
          "               [--supersample S]    every shown frame is S x S renders (S in 1..8) at the offsets of a regular sub-pixel grid, summed and\n"
          "                                    averaged on the device (anti-aliasing in time); -w / --write-window write the resolved image\n"
          "               [--supersample-contrast T]   with --supersample S >= 2: one render at the pixel centres, then the S x S renders only for\n"
@@ -250,6 +254,36 @@ bool Settings::init(int argc, char** argv, std::string* err) {
         return false;
       }
       reproject = static_cast<int>(k);
+    } else if (a == "--reproject-warp") {
+      if (!need(i, 1)) return false;
+      const std::string v = argv[++i];
+      if (v != "splat" && v != "gather") {
+        *err = "--reproject-warp must be splat or gather";
+        return false;
+      }
+      reproject_gather = v == "gather";
+      reproject_warp_set = true;
+    } else if (a == "--reproject-iterations") {
+      if (!need(i, 1)) return false;
+      char* end = nullptr;
+      const long k = std::strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end != 0 || k < 1 || k > 8) {
+        *err = "--reproject-iterations N: N must be an integer in 1..8";
+        return false;
+      }
+      reproject_iterations = static_cast<int>(k);
+      reproject_warp_set = true;
+    } else if (a == "--reproject-tol") {
+      if (!need(i, 1)) return false;
+      const std::string ts = argv[++i];
+      char* et = nullptr;
+      const float t = std::strtof(ts.c_str(), &et);
+      if (ts.empty() || *et != 0 || !(t >= 0.f) || !(t < 1e30f)) {
+        *err = "--reproject-tol T: T must be a number >= 0";
+        return false;
+      }
+      reproject_tol = t;
+      reproject_warp_set = true;
     } else if (a == "--rerender") {
       if (!need(i, 1)) return false;
       rerender = argv[++i];
@@ -353,6 +387,10 @@ bool Settings::init(int argc, char** argv, std::string* err) {
   }
   if (!rerender.empty() && reproject <= 1) {
     *err = "--rerender re-renders the holes of warped frames; only with --reproject K, K > 1";
+    return false;
+  }
+  if (reproject_warp_set && reproject <= 1) {
+    *err = "--reproject-warp / --reproject-iterations / --reproject-tol choose how warped frames are made; only with --reproject K, K > 1";
     return false;
   }
   if (supersample_contrast >= 0.f && supersample <= 1) {

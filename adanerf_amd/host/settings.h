@@ -59,6 +59,10 @@ class Settings {
                                 // of its own) are rendered at the frame's camera (adanerf_render_masked); empty: they stay filled from neighbours
   int reproject = 1;            // --reproject K: of every K frames the first is rendered, the next K - 1 are that frame warped to their own camera
                                 // (adanerf_reproject, fill on); 1: every frame is rendered
+  bool reproject_warp_set = false;      // --reproject-warp / --reproject-iterations / --reproject-tol was given (an error without --reproject K > 1)
+  bool reproject_gather = false;        // --reproject-warp gather: the warped frames come from adanerf_reproject_gather; splat (the default): adanerf_reproject
+  int reproject_iterations = 4;         // --reproject-iterations N (1..8) and --reproject-tol T (>= 0): the gather's two dials
+  float reproject_tol = 0.05f;
   int supersample = 1;          // --supersample S (1..8): every shown frame is S x S renders at the offsets of adanerf_host_subpixel_grid, accumulated and
                                 // resolved on the device (adanerf_set_pixel_offset / adanerf_accumulate / adanerf_resolve_mean); 1: one render per frame
   float supersample_contrast = -1.f;   // --supersample-contrast T (0..1, with --supersample S >= 2): adaptive supersampling -- one render at the pixel centres, then

@@ -30,6 +30,8 @@ PRESENT_FLIP_Y, PRESENT_NEAREST, PRESENT_LINEAR, PRESENT_AREA = 1, 2, 4, 8      
 PRESENT_FILTERS = {None: 0, "nearest": PRESENT_NEAREST, "linear": PRESENT_LINEAR, "area": PRESENT_AREA}
 SUPERSAMPLE_MAX = 8                                            # adanerf_host_subpixel_grid: s in 1..8
 REPROJECT_FILL = 1                                             # adanerf_reproject flag
+GATHER_GUESS = 1                                               # adanerf_reproject_gather flag
+GATHER_ITERATIONS, GATHER_DEPTH_TOL = 4, 0.05                  # the hosts' defaults (profiles/reproject_gather_measured.md)
 RERENDER_VALUES = {None: 0, "holes": 1, "unsourced": 5}        # adanerf_render_masked `values` over adanerf_reproject's mask bytes (0 hole, 2 filled)
 TEMPORAL_CLAMP = 1                                          # adanerf_temporal_resolve flag
 ABI_VERSION = 4
@@ -73,6 +75,7 @@ class Stats(C.Structure):
 
 
 EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_last_error", "adanerf_abi_version", "adanerf_struct_sizes", "adanerf_set_camera", "adanerf_set_selection", "adanerf_set_frame_size", "adanerf_present", "adanerf_reproject",
+           "adanerf_reproject_gather",
            "adanerf_set_budget_map", "adanerf_foveate", "adanerf_compact_budget",
            "adanerf_render", "adanerf_set_aux_outputs", "adanerf_set_disp_output", "adanerf_assemble_strips", "adanerf_sync", "adanerf_set_stream", "adanerf_set_profiling",
            "adanerf_collect_stats", "adanerf_ray_features", "adanerf_sample_mlp",
@@ -138,6 +141,7 @@ def load_library(path: Optional[str] = None):
     lib.adanerf_host_subpixel_grid.argtypes = [i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     fp = C.POINTER(C.c_float)
     lib.adanerf_reproject.argtypes = [vp, vp, vp, vp, fp, fp, fp, fp, C.c_float, C.c_uint32, i32, vp, vp, vp, C.POINTER(i32)]
+    lib.adanerf_reproject_gather.argtypes = [vp, vp, vp, vp, fp, fp, fp, fp, C.c_float, C.c_float, i32, C.c_uint32, i32, vp, vp, vp, vp, C.POINTER(i32)]
     lib.adanerf_temporal_resolve.argtypes = [vp, vp, vp, vp, fp, fp, vp, vp, vp, fp, fp, C.c_float, C.c_float, C.c_float, i32, vp, vp, vp, vp, vp,
                                              C.POINTER(i32)]
     lib.adanerf_temporal_upsample.argtypes = [vp, i32, vp, vp, vp, C.c_float, C.c_float, fp, fp, vp, vp, vp, fp, fp, C.c_float, C.c_float, C.c_float, i32,
@@ -1109,6 +1113,7 @@ class NeuralRenderer:
             if self._pose is None:
                 raise AdaNeRFError("reprojection needs the pose of the frame: call set_camera before render_numpy")
             self._rp_frame = (self._o_rgba, self._rp_depth, self._rp_acc, self._pose[0], self._pose[1], n)
+            self.gather_from(self._rp_rgb, self, self._o_rgb, n * 12)      # the fp32 colour reproject_gather() taps, stream-ordered
         return self._o_rgb.numpy(), self._o_rgba.numpy(), st
 
     # -- the last frame at the pose of the moment --------------------------------------------------------
@@ -1117,13 +1122,14 @@ class NeuralRenderer:
         (the library drops the aux outputs then); installed as the context's aux outputs"""
         n = self.info.rays_local
         if not hasattr(self, "_rp_depth") or self._rp_depth.shape[0] != n:
-            for name in ("_rp_depth", "_rp_acc", "_rp_rgba", "_rp_mask"):
+            for name in ("_rp_depth", "_rp_acc", "_rp_rgba", "_rp_mask", "_rp_rgb", "_rp_wrgb"):
                 if hasattr(self, name):
                     a = getattr(self, name)
                     a.free()
                     self._own.remove(a)
             self._rp_depth, self._rp_acc = self.empty((n,), np.float32), self.empty((n,), np.float32)
             self._rp_rgba, self._rp_mask = self.empty((n, 4), np.uint8), self.empty((n,), np.uint8)
+            self._rp_rgb, self._rp_wrgb = self.empty((n, 3), np.float32), self.empty((n, 3), np.float32)      # the frame's fp32 colour; the gathered one
             self._rp_frame = None
             self.set_aux_outputs(self._rp_depth, self._rp_acc)
 
@@ -1169,6 +1175,51 @@ class NeuralRenderer:
         if rerender not in ("holes", "unsourced"):
             raise AdaNeRFError("reproject_rerender: rerender must be 'holes' or 'unsourced'")
         _, mask, holes = self.reproject(dst_pos, dst_rot, fill=fill, acc_min=acc_min)
+        self.set_camera(dst_pos, dst_rot)
+        self.set_aux_outputs(None, None)
+        try:
+            rerendered, _ = self.render_masked(self._rp_mask, RERENDER_VALUES[rerender], rgba8=self._rp_rgba)
+        finally:
+            self.set_aux_outputs(self._rp_depth, self._rp_acc)
+        return self._rp_rgba.numpy(), mask, holes, rerendered
+
+    # -- the same warp as a gather (adanerf_reproject_gather) ------------------------------------------------
+    def reproject_gather_device(self, src_rgb, src_depth, src_acc, src_pos, src_rot, dst_pos, dst_rot, dst_rgb, dst_rgba8=None, dst_depth=None,
+                                dst_mask=None, acc_min: float = 0.5, depth_tol: float = GATHER_DEPTH_TOL, iterations: int = GATHER_ITERATIONS,
+                                hole_rgba8: int = 0xFF000000, guess: bool = True, holes: bool = True) -> Optional[int]:
+        """adanerf_reproject_gather on device images of the context's frame size: the frame (fp32 rgb, depth_map, acc_map) rendered at
+        (src_pos, src_rot) gathered at (dst_pos, dst_rot) into dst_rgb (fp32) and, if given, dst_rgba8 (uchar4) / dst_depth (fp32) /
+        dst_mask (uint8: 1 a verified source surface, 2 an unverified one (guess), 0 hole).  Returns the number of holes (synchronous);
+        with holes=False nothing is read back and the outputs are complete after sync()."""
+        f = [np.ascontiguousarray(v, dtype=np.float32).reshape(k) for v, k in ((src_pos, 3), (src_rot, 9), (dst_pos, 3), (dst_rot, 9))]
+        fp = [v.ctypes.data_as(C.POINTER(C.c_float)) for v in f]
+        n = C.c_int32(0)
+        self._check(self.lib.adanerf_reproject_gather(self.handle, _ptr(src_rgb), _ptr(src_depth), _ptr(src_acc), fp[0], fp[1], fp[2], fp[3],
+                                                      float(acc_min), float(depth_tol), int(iterations), int(hole_rgba8) & 0xFFFFFFFF,
+                                                      GATHER_GUESS if guess else 0, _ptr(dst_rgb), _ptr(dst_rgba8), _ptr(dst_depth),
+                                                      _ptr(dst_mask), C.byref(n) if holes else None))
+        return int(n.value) if holes else None
+
+    def reproject_gather(self, dst_pos, dst_rot, iterations: int = GATHER_ITERATIONS, depth_tol: float = GATHER_DEPTH_TOL, guess: bool = True,
+                         acc_min: float = 0.5):
+        """The last render_numpy frame (after enable_reprojection) gathered at the pose (dst_pos, dst_rot): returns (rgb [R,3] float32,
+        rgba8 [R,4] uint8, mask [R] uint8, holes).  Holes come out opaque black.  The camera in force does not change."""
+        if self._rp_frame is None or self._rp_frame[5] != self.info.rays_local:
+            raise AdaNeRFError("reproject_gather: no frame to warp -- enable_reprojection(), set_camera, then render_numpy")
+        _, depth, acc, pos, rot, _ = self._rp_frame
+        holes = self.reproject_gather_device(self._rp_rgb, depth, acc, pos, rot, dst_pos, dst_rot, self._rp_wrgb, self._rp_rgba, None, self._rp_mask,
+                                             acc_min=acc_min, depth_tol=depth_tol, iterations=iterations, guess=guess)
+        return self._rp_wrgb.numpy(), self._rp_rgba.numpy(), self._rp_mask.numpy(), holes
+
+    def reproject_gather_rerender(self, dst_pos, dst_rot, rerender: str = "holes", iterations: int = GATHER_ITERATIONS,
+                                  depth_tol: float = GATHER_DEPTH_TOL, guess: bool = True, acc_min: float = 0.5):
+        """reproject_gather(), then the pixels the gather could not source rendered at the destination pose into the 8-bit colour, as
+        reproject_rerender does for the splat: ``rerender="holes"`` the mask-0 pixels, ``"unsourced"`` the unverified ones (mask 2) as
+        well.  The camera moves to (dst_pos, dst_rot) and stays there; the frame kept for warping is untouched.  Returns (rgba8, mask,
+        holes, rerendered)."""
+        if rerender not in ("holes", "unsourced"):
+            raise AdaNeRFError("reproject_gather_rerender: rerender must be 'holes' or 'unsourced'")
+        _, _, mask, holes = self.reproject_gather(dst_pos, dst_rot, iterations=iterations, depth_tol=depth_tol, guess=guess, acc_min=acc_min)
         self.set_camera(dst_pos, dst_rot)
         self.set_aux_outputs(None, None)
         try:

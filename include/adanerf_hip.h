@@ -19,6 +19,7 @@
  *                                        ADANERF_PRESENT_AREA replaces its nearest decimation by an exact area filter
  *   adanerf_reproject                    none: the viewer presents the frame it rendered (src/neuralrenderer.cpp:146-182 ->
  *                                        src/interoprenderbuffer.cpp:87); this stage sits in front of that step
+ *   adanerf_reproject_gather             none, as adanerf_reproject: the same warp as a gather, without cracks
  *   adanerf_temporal_resolve             none: the viewer shows each frame as rendered, without a history (src/neuralrenderer.cpp:146-182 ->
  *                                        src/interoprenderbuffer.cpp:87); temporal anti-aliasing between the render and that step
  *   adanerf_temporal_upsample            none: the viewer blits the frame it rendered (src/interoprenderbuffer.cpp:87), at whatever size it
@@ -913,6 +914,65 @@ int adanerf_reproject(adanerf_ctx* ctx, const void* d_src_rgba8, const float* d_
                       const float src_pos[3], const float src_rot_c2w[9], const float dst_pos[3], const float dst_rot_c2w[9],
                       float acc_min, uint32_t hole_rgba8, int32_t flags, void* d_dst_rgba8, float* d_dst_depth, uint8_t* d_dst_mask,
                       int32_t* holes_out);
+
+/* adanerf_reproject_gather flags */
+enum { ADANERF_GATHER_GUESS = 1 }; /* a pixel whose iteration stayed inside the source frame but failed the consistency test keeps its gathered colour, mask 2 */
+
+/* Gather reprojection: adanerf_reproject's warp done from the destination's side, with only the source frame's depth.  Each destination
+ * pixel searches its own ray for the source surface by a fixed-point iteration -- guess a depth on the ray, look where that point lies in
+ * the source frame, take the surface found there as the next guess -- so a pixel is a hole only where the source frame has nothing (a
+ * disocclusion, the frame's border), never because no splat happened to land on it, and the colour is a bilinear tap of the fp32 frame.
+ * adanerf_reproject is unchanged and stays every host's default.  Inputs are what one adanerf_render of this context wrote.
+ *   d_src_rgb [height*width,3] fp32 (d_rgb_f32_out), d_src_depth_map / d_src_acc_map [height*width] fp32 (adanerf_set_aux_outputs);
+ *                           src_pos / src_rot_c2w: the pose of that frame
+ *   dst_pos / dst_rot_c2w   the pose to warp to (conventions of adanerf_set_camera; the camera in force is neither read nor changed)
+ *   acc_min                 as adanerf_reproject's; depth_tol >= 0: relative tolerance of the consistency test; iterations in 1..8
+ *   hole_rgba8              as adanerf_reproject's: the four bytes of a mask-0 pixel in d_dst_rgba8
+ *   flags                   0 or ADANERF_GATHER_GUESS
+ *   d_dst_rgb [height*width,3] fp32; d_dst_rgba8 [height*width] uchar4, d_dst_depth [height*width] fp32, d_dst_mask [height*width] uint8:
+ *                           each may be NULL
+ *   holes_out               host pointer or NULL: the number of pixels with mask 0; non-NULL makes the call synchronous (as holes_out of
+ *                           adanerf_reproject), with NULL the outputs are complete after adanerf_sync()
+ * All images have the context's CURRENT frame size and are indexed as adanerf_render's output is; fp32 and uchar4 images are 4-byte aligned;
+ * no output may overlap a source image or another output.
+ * Definition (every operation a single rounded fp32 operation in this order, over the float64 ray table; a gather: the same inputs give
+ * the same bits on every call):
+ *   1 source surface, source pixel i   (nds, p) = this context's ray of the pixel at the source pose through the pixel centre; o = p, or
+ *               src_pos (ADANERF_SAMPLER_COARSE_FINE).  a = acc_map[i], t = depth_map[i] / a; near by adanerf_reproject's test (a >= acc_min,
+ *               t finite, t > 0; NaNs are far).  near: S_i = o + nds t, q = S_i - src_pos, zs_i = -((R[2] q_0 + R[5] q_1) + R[8] q_2),
+ *               R = src_rot_c2w.  far: no point, zs_i = +inf (a near pixel whose zs comes out +inf counts as far from here on).
+ *   2 destination ray, destination pixel j   d = the nds of this context's ray of j at the destination pose through the pixel centre (the
+ *               offset of adanerf_set_pixel_offset is ignored, as adanerf_reproject ignores it).
+ *   3 iteration   tap_0 = j.  For k = 0 .. iterations - 1: if tap_k is near, s = ((S_x - dst_x) d_x + (S_y - dst_y) d_y) + (S_z - dst_z) d_z
+ *               with S = S_tap_k; the pixel dies unless s is finite and > 0; P = dst_pos + d s, q = P - src_pos.  If tap_k is far, q = d
+ *               (direction only: the sky follows the rotation alone).  v_k = (R[k] q_0 + R[3+k] q_1) + R[6+k] q_2 with R = src_rot_c2w,
+ *               zc = -v_2, u = (focal v_0) / zc + 0.5 width, vv = (focal (-v_1)) / zc + 0.5 height; the pixel dies unless zc is finite
+ *               and > 0, 0 <= u < width and 0 <= vv < height.  tap_k+1 = floor(vv) width + floor(u).  A dead pixel stays dead.
+ *   4 consistency, against the last zc and the final tap   a near estimate (the last tap_k was near) is consistent iff the final tap is near
+ *               and |zc - zs_tap| <= depth_tol * zc; a far estimate iff the final tap is far.
+ *   5 result    the colour tap is adanerf_temporal_resolve's step 5 on d_src_rgb at the last (u, vv).  Alive and consistent: that colour,
+ *               mask 1, depth = -((D[2] r_0 + D[5] r_1) + D[8] r_2) with r = P - dst_pos, D = dst_rot_c2w (+inf for a far estimate).
+ *               Alive, not consistent, ADANERF_GATHER_GUESS: the same colour and depth, mask 2.  Everything else: fp32 (0, 0, 0), hole_rgba8,
+ *               mask 0, depth 0.  d_dst_rgba8 of a mask 1 / 2 pixel follows adanerf_resolve_mean's byte contract.
+ * The mask bytes mean to adanerf_render_masked what adanerf_reproject's mean: values 1 re-renders the holes, 5 the unverified pixels too.
+ * What it does not do: a thin foreground object that the start guess (the same pixel) never sees can be missed; bilinear taps blend across
+ * depth edges; view-dependent colour stays that of the source pose; the scene is static; no depth limit; no useNDC models, no shards.
+ * A depth_tol below the relative depth step per pixel of a sloped surface cannot verify it (the iteration ends in a 2-cycle between two
+ * taps).  And on a trained network's noisy depth it does not beat the splat (profiles/reproject_gather_measured.md, 800 x 800, 4 iterations,
+ * depth_tol 0.05): not in PSNR as warped (19.99 against 20.09 dB), not in pixels left to re-render once the unverified ones count (32.9 %
+ * both); it leaves fewer holes (11.1 against 14.0 %) but is 1.3 dB worse once those are re-rendered, at two thirds of the splat's time.
+ * At 1920 x 1080 it is 0.3 dB better as warped.  The iteration follows the depth's noise: one iteration scores highest as warped.
+ * Runs on the context's stream in two launches (source surfaces, warp); the surface table (16 bytes per pixel) lives in context-owned
+ * scratch beside the hole count, grown on demand (the stream is synchronised only then), never shrunk, freed by adanerf_destroy;
+ * adanerf_render never allocates for it.
+ * ADANERF_EINVAL, with nothing written: a NULL source image, pose or d_dst_rgb; a pose entry that is not finite; acc_min or depth_tol NaN
+ * or negative; iterations outside 1..8; an unknown flag; a misaligned fp32 or uchar4 pointer; an output overlapping a source image or
+ * another output.
+ * ADANERF_EUNSUPPORTED, with nothing written: a useNDC model (its depth_map is NDC depth); a context with shard_world != 1. */
+int adanerf_reproject_gather(adanerf_ctx* ctx, const float* d_src_rgb, const float* d_src_depth_map, const float* d_src_acc_map,
+                             const float src_pos[3], const float src_rot_c2w[9], const float dst_pos[3], const float dst_rot_c2w[9],
+                             float acc_min, float depth_tol, int32_t iterations, uint32_t hole_rgba8, int32_t flags, float* d_dst_rgb,
+                             void* d_dst_rgba8, float* d_dst_depth, uint8_t* d_dst_mask, int32_t* holes_out);
 
 /* adanerf_temporal_resolve flags */
 enum { ADANERF_TEMPORAL_CLAMP = 1 }; /* the history colour is clamped to the min / max of the current colour over the pixel's 3 x 3 neighbourhood */
