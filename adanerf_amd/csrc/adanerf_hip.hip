@@ -208,8 +208,8 @@ int launch_sample_mlp(adanerf_ctx* c, int first_ray, int n_rays, float* d_oracle
   }
   // Guarded two-precision selection: plain fp16 for every ray, then the split engine on the rays the guard band flagged.
   // Only where the selection is fused; otherwise this mode is the split-precision engine.
-  // Nor under a budget map: unrefined rays keep the fp16 engine's values in selw, and a trim by them would not be the exact selection.
-  const bool guarded = c->sampling_mode == ADANERF_SAMPLING_GUARDED && sel != nullptr && !has_budget_map(c) && !list;
+  // Nor under a budget map or a sample cap: unrefined rays keep the fp16 engine's values in selw, and a trim by them would not be the exact selection.
+  const bool guarded = c->sampling_mode == ADANERF_SAMPLING_GUARDED && sel != nullptr && !has_budget_map(c) && !(c->sample_cap > 0.f) && !list;
   if (list) {      // guard_mask, guard_rows, guard_seen and sel.refine_list stay null: guard_flush has nothing to write
     a.ray_list = list->ids;
     a.n_list = list->count;
@@ -350,12 +350,66 @@ int launch_depth_limit(adanerf_ctx* c, const DepthLimit& dl, int n_rays, int n_m
   HIP_RETURN(c, hipGetLastError());
 }
 
+// A bound on the batch's samples (adanerf_set_sample_cap, k_cap.hip.hpp): after the selection, the budget trim and the depth limit, before
+// launch_expand.  Three histogram passes over the rows, each followed by its one-workgroup digit search; then t* goes into the context's
+// threshold map and the unchanged trim kernels run at (n_max, t*).  Nothing is read back; when the batch fits, the later passes return at once
+// and the trim changes no row.
+bool has_sample_cap(const adanerf_ctx* c) { return c->sample_cap > 0.f; }
+
+// a cap at or above N cannot trim: nothing is launched for it
+bool cap_trims(const adanerf_ctx* c) { return has_sample_cap(c) && c->sample_cap < static_cast<float>(c->ms.info.num_samples); }
+
+int64_t cap_total_of(const adanerf_ctx* c, int n_rays) { return static_cast<int64_t>(std::floor(static_cast<double>(c->sample_cap) * n_rays)); }
+
+constexpr size_t kCapStateBytes = sizeof(CapState) + static_cast<size_t>(kCapLevels) * 2 * kCapBins * sizeof(uint32_t);
+
+// scratch of the cap for batches of n_rays; grown on demand, freed with the context
+int ensure_cap_buffers(adanerf_ctx* c, int n_rays) {
+  const size_t map_bytes = static_cast<size_t>(std::max(n_rays, 1)) * sizeof(float);
+  if (c->cap_state.p && c->cap_record.p && c->cap_map.bytes >= map_bytes) return ADANERF_OK;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));      // an enqueued batch may still read the smaller map
+  int rc;
+  if ((rc = dev_alloc(c, &c->cap_state, kCapStateBytes))) return rc;
+  if ((rc = dev_alloc(c, &c->cap_map, map_bytes))) return rc;
+  if (!c->cap_record.p) {
+    if ((rc = dev_alloc(c, &c->cap_record, sizeof(CapRecord)))) return rc;
+    hipLaunchKernelGGL(cap_reset_kernel, dim3(1), dim3(1), 0, c->stream, reinterpret_cast<CapRecord*>(c->cap_record.p));
+    HIP_TRY(c, hipGetLastError());
+  }
+  return ADANERF_OK;
+}
+
+int launch_cap(adanerf_ctx* c, int n_rays, int n_max, float thr, int seg_shift, int32_t* d_cnt, int64_t cap_total) {
+  if (n_rays <= 0) return ADANERF_OK;
+  CapState* st = reinterpret_cast<CapState*>(c->cap_state.p);
+  uint32_t* hist = reinterpret_cast<uint32_t*>(st + 1);
+  CapRecord* rec = reinterpret_cast<CapRecord*>(c->cap_record.p);
+  float* map = reinterpret_cast<float*>(c->cap_map.p);
+  const float* selw = reinterpret_cast<const float*>(c->selw.p);
+  HIP_TRY(c, hipMemsetAsync(st, 0, kCapStateBytes, c->stream));
+  const bool wave = n_max > kCapThreadMaxN;
+  // few workgroups, each over many rays: a workgroup flushes every occupied bin of its private histograms with one global atomic, and where the
+  // values share their leading bits every workgroup adds to the same few words (measured at 640 000 rays: 194 us for the first pass with 2 048
+  // workgroups and a wave's counters added straight to global memory, profiles/sample_cap_measured.md)
+  const int cus = std::max(c->ms.info.compute_units, 1);
+  const dim3 grid(wave ? std::min((n_rays + 3) / 4, 4 * cus) : std::min((n_rays + 255) / 256, 2 * cus));
+  for (int level = 0; level < kCapLevels; ++level) {
+    uint32_t* h = hist + static_cast<size_t>(level) * 2 * kCapBins;
+    hipLaunchKernelGGL(wave ? cap_hist_kernel<true> : cap_hist_kernel<false>, grid, dim3(256), 0, c->stream, d_cnt, selw, n_rays, n_max, level, st, h);
+    hipLaunchKernelGGL(cap_search_kernel, dim3(1), dim3(1024), 0, c->stream, level, static_cast<long long>(cap_total), st, h, rec);
+  }
+  hipLaunchKernelGGL(cap_fill_kernel, dim3((n_rays + 255) / 256), dim3(256), 0, c->stream, rec, n_rays, map);
+  HIP_TRY(c, hipGetLastError());
+  return launch_trim(c, BudgetMaps{nullptr, map, 0}, n_rays, n_max, thr, seg_shift, d_cnt);
+}
+
 // the pair selection keeps its sorted candidate lists in registers: n_max <= kPairMaxN; ADANERF_FLAG_WAVE_SELECT forces the
 // wave-per-ray select_kernel (any n_max)
 bool use_pair_select(const adanerf_ctx* c, int n_max) { return n_max <= kPairMaxN && !(c->opt.flags & ADANERF_FLAG_WAVE_SELECT); }
 
 int launch_compact(adanerf_ctx* c, const float* d_oracle, int n_rays, int n_max, float thr, int32_t* d_off, int32_t* d_cnt,
-                   uint32_t* d_key, float* d_w, int32_t* d_total, const BudgetMaps* bm = nullptr, const DepthLimit* dl = nullptr) {
+                   uint32_t* d_key, float* d_w, int32_t* d_total, const BudgetMaps* bm = nullptr, const DepthLimit* dl = nullptr,
+                   const int64_t* cap_total = nullptr) {
   if (n_rays <= 0) return ADANERF_OK;
   if (thr == 0.0f) {
     const size_t n = static_cast<size_t>(n_rays) * kBins;
@@ -370,6 +424,8 @@ int launch_compact(adanerf_ctx* c, const float* d_oracle, int n_rays, int n_max,
       if (int rc = launch_trim(c, *bm, n_rays, n_max, thr, kPairSegShift, d_cnt)) return rc;
     if (dl)
       if (int rc = launch_depth_limit(c, *dl, n_rays, n_max, kPairSegShift, d_cnt)) return rc;
+    if (cap_total)
+      if (int rc = launch_cap(c, n_rays, n_max, thr, kPairSegShift, d_cnt, *cap_total)) return rc;
     return launch_expand(c, n_rays, n_max, kPairSegShift, d_off, d_cnt, d_key, d_w, d_total);
   }
   const int nblk = (n_rays + kSelRaysPerBlock - 1) / kSelRaysPerBlock;
@@ -380,6 +436,8 @@ int launch_compact(adanerf_ctx* c, const float* d_oracle, int n_rays, int n_max,
     if (int rc = launch_trim(c, *bm, n_rays, n_max, thr, kSelSegShift, d_cnt)) return rc;
   if (dl)
     if (int rc = launch_depth_limit(c, *dl, n_rays, n_max, kSelSegShift, d_cnt)) return rc;
+  if (cap_total)
+    if (int rc = launch_cap(c, n_rays, n_max, thr, kSelSegShift, d_cnt, *cap_total)) return rc;
   return launch_expand(c, n_rays, n_max, kSelSegShift, d_off, d_cnt, d_key, d_w, d_total);
 }
 
@@ -883,6 +941,8 @@ int adanerf_set_selection(adanerf_ctx* c, int32_t num_samples, float threshold) 
     return fail(c, ADANERF_EUNSUPPORTED, "threshold 0 (dense) keeps every bin: remove the budget map first (adanerf_set_budget_map with two NULLs)");
   if (threshold == 0.f && c->depth_limit)
     return fail(c, ADANERF_EUNSUPPORTED, "threshold 0 (dense) keeps every bin with implicit keys: remove the depth limit first (adanerf_set_depth_limit with NULL)");
+  if (threshold == 0.f && has_sample_cap(c))
+    return fail(c, ADANERF_EUNSUPPORTED, "threshold 0 (dense) keeps every bin: remove the sample cap first (adanerf_set_sample_cap with 0)");
   ModelSetup& ms = c->ms;
   const adanerf_info was = ms.info;
   const ModelSetup::PosBound was_bound = ms.pos_bound;
@@ -1381,6 +1441,9 @@ int render_batch(adanerf_ctx* c, int first, int n, const RayList* list, const Ba
   const BudgetMaps bm{c->budget_n, c->budget_thr, first};
   // adaptive sampler, threshold > 0, no NDC (adanerf_set_depth_limit / adanerf_set_selection see to it); the pose in force reaches the kernel by value
   const bool limited = c->depth_limit != nullptr;
+  // adaptive sampler, threshold > 0 (adanerf_set_sample_cap / adanerf_set_selection see to it); the bound is on this batch's own rays
+  const bool capped = cap_trims(c) && !pdf && thr > 0.f;
+  const int64_t cap_total = capped ? cap_total_of(c, n) : 0;
   const DepthLimit dl{c->depth_limit, first, list ? list->ids : nullptr, rays, c->ms.sp.ztab, depth_pose(c->ms.rg.pos, c->ms.rg.rot)};
   if (!cfm && (rc = launch_sample_mlp(c, first, n, fused ? nullptr : oracle, rays, fused ? &so : nullptr, list))) return rc;
   if (ev && !cfm) HIP_TRY(c, hipEventRecord(ev[1], c->stream));
@@ -1390,12 +1453,13 @@ int render_batch(adanerf_ctx* c, int first, int n, const RayList* list, const Ba
   else if (fused) {
     rc = budget ? launch_trim(c, bm, n, N, thr, kPairSegShift, cnt) : ADANERF_OK;
     if (!rc && limited) rc = launch_depth_limit(c, dl, n, N, kPairSegShift, cnt);
+    if (!rc && capped) rc = launch_cap(c, n, N, thr, kPairSegShift, cnt, cap_total);
     if (!rc) rc = launch_expand(c, n, N, kPairSegShift, off, cnt, key, sw, total);
   }
   else if (thr == 0.f) {      // dense: implicit keys, the oracle buffer is the weight array (dense_offsets_kernel)
     hipLaunchKernelGGL(dense_offsets_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, off, cnt, total);
     HIP_TRY(c, hipGetLastError());
-  } else rc = launch_compact(c, oracle, n, N, thr, off, cnt, key, sw, total, budget ? &bm : nullptr, limited ? &dl : nullptr);
+  } else rc = launch_compact(c, oracle, n, N, thr, off, cnt, key, sw, total, budget ? &bm : nullptr, limited ? &dl : nullptr, capped ? &cap_total : nullptr);
   if (rc) return rc;
   const bool dense_implicit = !cfm && !pdf && !fused && thr == 0.f;
   const uint32_t* key_s = dense_implicit ? nullptr : key;
@@ -1450,9 +1514,15 @@ int adanerf_render(adanerf_ctx* c, void* d_rgba8, float* d_rgb, adanerf_stats* s
   poll_guard(c);
   const int R = c->ms.info.rays_local, B = c->ms.info.batch_rays, N = c->ms.info.num_samples;
   const int n_batches = R > 0 ? (R + B - 1) / B : 0;
-  const bool budget = has_budget_map(c);
+  const bool budget = has_budget_map(c) || has_sample_cap(c);      // the trims that read values: a guarded context renders as the split engine
   int rc = ensure_batch_buffers(c, std::min(B, std::max(R, 1)), N);
   if (rc) return rc;
+  if (has_sample_cap(c)) c->cap_record_live = cap_trims(c);      // a cap at or above N launches nothing: its report is the empty one
+  if (cap_trims(c)) {      // the report covers this frame
+    if ((rc = ensure_cap_buffers(c, std::min(B, std::max(R, 1))))) return rc;
+    hipLaunchKernelGGL(cap_reset_kernel, dim3(1), dim3(1), 0, c->stream, reinterpret_cast<CapRecord*>(c->cap_record.p));
+    HIP_TRY(c, hipGetLastError());
+  }
   bool record = false;
   if ((rc = begin_record(c, stats, n_batches, &record))) return rc;
   int32_t* total = reinterpret_cast<int32_t*>(c->total.p);
@@ -1462,7 +1532,7 @@ int adanerf_render(adanerf_ctx* c, void* d_rgba8, float* d_rgb, adanerf_stats* s
                        c->aux_depth ? c->aux_depth + first : nullptr, c->aux_acc ? c->aux_acc + first : nullptr, c->aux_disp ? c->aux_disp + first : nullptr};
     if ((rc = render_batch(c, first, n, nullptr, out, record))) return rc;
   }
-  // under a budget map the guarded mode renders as the split engine: no audit to move on, no monitor to read
+  // under a budget map or a sample cap the guarded mode renders as the split engine: no audit to move on, no monitor to read
   if (c->sampling_mode == ADANERF_SAMPLING_GUARDED && c->guard_mask.p && n_batches > 0 && !budget) ++c->guard_frame;      // the audit moves on
   if (c->sampling_mode == ADANERF_SAMPLING_GUARDED && c->guard_mask.p && n_batches > 0 && !budget && !c->guard_ev_pending) {
     if (!c->guard_host) {
@@ -1516,6 +1586,7 @@ int adanerf_render_masked(adanerf_ctx* c, const uint8_t* d_mask, uint32_t values
   if (!use_pair_select(c, N) || (c->opt.flags & ADANERF_FLAG_KEEP_ORACLE))
     return refuse("the ray list needs the fused selection (N <= 16, neither ADANERF_FLAG_KEEP_ORACLE nor ADANERF_FLAG_WAVE_SELECT)");
   if (has_budget_map(c)) return refuse("a budget map is installed: its maps are indexed by frame position (remove it first)");
+  if (has_sample_cap(c)) return refuse("a sample cap is installed: its threshold depends on which rays share a batch (adanerf_set_sample_cap(ctx, 0) removes it)");
   if (c->ms.rg.world != 1) return refuse("whole frames only (shard_world must be 1)");
   BIND(c);
   if (n_rendered) *n_rendered = 0;
@@ -1677,6 +1748,68 @@ int adanerf_compact_depth_limit(adanerf_ctx* c, const float* d_oracle, int32_t n
   if (int rc = ensure_compact_scratch(c, n_rays, n_max)) return rc;
   const DepthLimit dl{d_limit_zc, 0, nullptr, d_rays, c->ms.sp.ztab, depth_pose(pos, rot)};
   return launch_compact(c, d_oracle, n_rays, n_max, thr, d_off, d_cnt, d_key, d_w, d_total, nullptr, &dl);
+}
+
+int adanerf_set_sample_cap(adanerf_ctx* c, float mean_samples_per_ray) {
+  BIND(c);
+  const float cap = mean_samples_per_ray;
+  if (cap != 0.f && !(std::isfinite(cap) && cap >= 1.f))
+    return fail(c, ADANERF_EINVAL, "adanerf_set_sample_cap: the cap must be 0 (off) or a finite mean of at least 1 sample per ray");
+  if (cap != 0.f) {
+    if (c->ms.coarse_fine || c->ms.info.sampler_mode != ADANERF_SAMPLER_ADAPTIVE)
+      return fail(c, ADANERF_EUNSUPPORTED, "adanerf_set_sample_cap: a cap trims the adaptive selection: this model's sampler has none");
+    if (c->ms.info.dense) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_set_sample_cap: threshold 0 (dense) keeps every bin: there is no selection to trim");
+  }
+  // a guarded context renders as the split engine while a cap is installed: the per-frame count of re-evaluated rays goes back to 0 in
+  // stream order (only a guarded frame writes it), as in adanerf_set_budget_map
+  if (c->sampling_mode == ADANERF_SAMPLING_GUARDED && cap != 0.f && !has_sample_cap(c) && c->total.p)
+    HIP_TRY(c, hipMemsetAsync(reinterpret_cast<int32_t*>(c->total.p) + kTotalRefined, 0, sizeof(int32_t), c->stream));
+  c->sample_cap = cap == 0.f ? 0.f : cap;
+  return ADANERF_OK;
+}
+
+int adanerf_sample_cap_report(adanerf_ctx* c, adanerf_cap_report* out) {
+  BIND(c);
+  if (!out) return fail(c, ADANERF_EINVAL, "adanerf_sample_cap_report: out == NULL");
+  CapRecord r{};
+  r.thr_max = -INFINITY;
+  if (c->cap_record.p && c->cap_record_live) {
+    HIP_TRY(c, hipMemcpyAsync(&r, c->cap_record.p, sizeof(r), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  out->threshold_max = r.thr_max;
+  out->batches_trimmed = r.batches_trimmed;
+  out->samples_selected = r.selected;
+  out->samples_kept = r.kept;
+  return ADANERF_OK;
+}
+
+int adanerf_compact_cap(adanerf_ctx* c, const float* d_oracle, int32_t n_rays, int32_t n_max, float thr, const uint8_t* d_n_map, const float* d_thr_map,
+                        const float* d_rays, const float* d_limit_zc, const float pos[3], const float rot[9], int64_t cap_total, int32_t* d_off,
+                        int32_t* d_cnt, uint32_t* d_key, float* d_w, int32_t* d_total, float* d_tstar) {
+  BIND(c);
+  if (!d_oracle || !d_off || !d_cnt || !d_key || !d_w || !d_total || !d_tstar) return fail(c, ADANERF_EINVAL, "NULL buffer");
+  if (n_rays < 0 || n_max < 1 || n_max > kBins || !(thr > 0.f)) return fail(c, ADANERF_EINVAL, "n_rays/n_max/thr out of range (thr must be > 0: the dense mode selects nothing)");
+  if (static_cast<int64_t>(n_rays) >= (1ll << 25)) return fail(c, ADANERF_EINVAL, "n_rays must be < 2^25 per batch");
+  if (static_cast<int64_t>(n_rays) * n_max > 0x7fffffffll) return fail(c, ADANERF_EINVAL, "n_rays * n_max exceeds 2^31 - 1");
+  if (cap_total < n_rays) return fail(c, ADANERF_EINVAL, "adanerf_compact_cap: cap_total must be at least n_rays (every non-empty row keeps one entry)");
+  if (d_limit_zc) {
+    if (!d_rays || !pos || !rot) return fail(c, ADANERF_EINVAL, "adanerf_compact_cap: a depth limit needs d_rays, pos and rot");
+    if ((reinterpret_cast<uintptr_t>(d_rays) & 15) || (reinterpret_cast<uintptr_t>(d_limit_zc) & 3))
+      return fail(c, ADANERF_EINVAL, "d_rays must be 16-byte aligned, d_limit_zc 4-byte aligned");
+    if (!c->ms.sp.ztab) return fail(c, ADANERF_EUNSUPPORTED, "adanerf_compact_cap: this context has no depth table");
+  }
+  if (int rc = ensure_compact_scratch(c, n_rays, n_max)) return rc;
+  if (int rc = ensure_cap_buffers(c, n_rays)) return rc;
+  c->cap_record_live = true;
+  const BudgetMaps bm{d_n_map, d_thr_map, 0};
+  const DepthLimit dl = d_limit_zc ? DepthLimit{d_limit_zc, 0, nullptr, d_rays, c->ms.sp.ztab, depth_pose(pos, rot)} : DepthLimit{};
+  hipLaunchKernelGGL(cap_reset_kernel, dim3(1), dim3(1), 0, c->stream, reinterpret_cast<CapRecord*>(c->cap_record.p));      // -inf for n_rays == 0 too
+  HIP_TRY(c, hipGetLastError());
+  if (int rc = launch_compact(c, d_oracle, n_rays, n_max, thr, d_off, d_cnt, d_key, d_w, d_total, (d_n_map || d_thr_map) ? &bm : nullptr,
+                              d_limit_zc ? &dl : nullptr, &cap_total))
+    return rc;
+  HIP_RETURN(c, hipMemcpyAsync(d_tstar, c->cap_record.p, sizeof(float), hipMemcpyDeviceToDevice, c->stream));
 }
 
 int adanerf_set_stream(adanerf_ctx* c, void* hip_stream) {

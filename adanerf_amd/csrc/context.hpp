@@ -117,6 +117,11 @@ struct adanerf_ctx {
   const uint8_t* budget_n = nullptr;  // adanerf_set_budget_map: caller-owned [rays_local] per-ray N / threshold, read by the trim kernels of every render
   const float* budget_thr = nullptr;
   const float* depth_limit = nullptr; // adanerf_set_depth_limit: caller-owned [rays_local] camera-space depths, read by the depth trim of every render
+  float sample_cap = 0.f;             // adanerf_set_sample_cap: mean samples per ray a batch may shade, 0: no cap
+  adanerf::DevBuf cap_state;          // k_cap.hip.hpp: CapState + the histograms of the three radix levels (zeroed per batch)
+  adanerf::DevBuf cap_record;         // CapRecord: t* and totals of the last batch, running figures of the last frame
+  bool cap_record_live = false;       // the record describes the last render (false: that render's cap could not trim and launched nothing)
+  adanerf::DevBuf cap_map;            // [batch] the threshold map the unchanged trim kernels read t* from
   adanerf::DevBuf disp_scratch;      // [2, batch] depth / accumulation of the batch when the caller asked for disparity only
   adanerf::StageScratch stages;      // what the image-space stages (stages.hip) keep between calls
   // adanerf_render_masked: the mask as bit words, the ascending ray list and its count (for the frame), staged pixels of one listed batch

@@ -5,6 +5,7 @@
 //   A4        select_kernel / scan_blocks_kernel / expand_kernel   top-N + threshold, deterministic compaction
 //   A4b       trim_rows_kernel / trim_rows_wave_kernel / foveate_kernel   per-ray budgets: the selection trimmed to (n_r, thr_r), the maps of a gaze
 //   A4c       depth_limit_kernel     per-ray depth limits: the selection trimmed to the samples in front of a rasterised surface
+//   A4d       cap_hist_kernel / cap_search_kernel / cap_fill_kernel   a bound on the batch's samples: the threshold t* that meets it, by an exact radix selection
 //   A5+A6     shade_mlp16x2_kernel / shade_mlp32_kernel   fused PE + 8x256 shading MLP (bf16/f16/f32 MFMA)
 //   A7        composite_kernel       sigmoid + alpha * oracle weight, front-to-back
 //   N8        mask_bits_kernel / mask_scatter_kernel   a byte mask as bit words for refine_list_kernel; the pixels of a listed batch to their places (masked rendering)
@@ -37,3 +38,4 @@
 #include "k_budget.hip.hpp"
 #include "k_mask.hip.hpp"
 #include "k_depth_limit.hip.hpp"
+#include "k_cap.hip.hpp"

@@ -8,6 +8,11 @@ reference's second default metric (``metrics = ["flip", "psnr"]`` :613-615): the
                                    [--metrics psnr flip] [--sweep-thresholds T ...] [--sweep-samples N ...] [--sweep-scales S ...]
                                    [--reproject-stride K [--reproject-warp splat|gather] [--rerender holes|unsourced]] [--supersample S] [--present-filter nearest|linear|area]
                                    [--fovea-density R:S[,R:S...],S [--fovea-temporal ALPHA] [--fovea-temporal-still K]] [--supersample-contrast T]
+                                   [--sweep-sample-caps C ...]
+
+``--sweep-sample-caps`` renders the set once per sample cap on one context (``NeuralRenderer.set_sample_cap``: a hard bound on the mean
+samples per ray of every frame, met on the device by raising the threshold): the quality a frame-time guarantee costs; the summary's
+``sweep`` entries carry ``sample_cap`` and ``mean_cap_threshold``.
 
 ``--sweep-thresholds`` / ``--sweep-samples`` render the set once per (N, threshold) of their cross product on ONE context
 (``NeuralRenderer.set_selection``: an AdaNeRF network is trained once and rendered at any sample budget) -- the two axes of a quality
@@ -115,8 +120,8 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
              precision: str = "bf16", batch_size: int = -1, max_frames: int = 0, quiet: bool = False,
              video: Optional[str] = None, fps: int = 30, metrics=("psnr",), fovea=None, sweep_thresholds=None, sweep_samples=None, reproject_stride=None,
              supersample=None, present_filter=None, temporal=None, temporal_still=None, temporal_upsample=None, temporal_upsample_frames=None,
-             rerender=None, fovea_density=None, reproject_warp="splat", reproject_iterations=None, reproject_tol=None, fovea_temporal=None,
-             fovea_temporal_still=None, supersample_contrast=None, sweep_scales=None):
+             rerender=None, fovea_density=None, reproject_warp="splat", reproject_iterations=None, reproject_tol=None, sweep_sample_caps=None,
+             fovea_temporal=None, fovea_temporal_still=None, supersample_contrast=None, sweep_scales=None):
     """metrics: "psnr" (always reported where a ground-truth image exists) and / or "flip": each record gains ``flip``, the summary
     ``mean_flip``, and with out_dir the error map is written as an 8-bit greyscale ``%05d_flip.png``.
 
@@ -194,7 +199,19 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     ``psnr_foveated_temporal`` / ``mse_foveated_temporal``, ``foveated_temporal_rejected_fraction`` and, with "flip",
     ``flip_foveated_temporal``; the summary their means; out_dir gets ``%05d_foveated_temporal.png``.
     fovea_temporal_still (K >= 1 or None): per pose instead, the frame after K such frames at rest from a cut; ALPHA is ``fovea_temporal``
-    or, without it, 0.1; the summary carries ``fovea_temporal_still``."""
+    or, without it, 0.1; the summary carries ``fovea_temporal_still``.
+
+    sweep_sample_caps (list of caps C or None): the set is rendered once per cap on the one context (NeuralRenderer.set_sample_cap: no
+    frame shades more than C samples per ray on average; 0 = no cap), in the shape of sweep_samples.  The summary is ``{"frames": n,
+    "sweep": [...]}`` with one ``{sample_cap, mean_psnr, mean_mse, mean_samples_per_ray, mean_cap_threshold, mean_ms[, mean_flip]}`` per cap;
+    ``mean_cap_threshold`` is the mean over the trimmed frames of the largest threshold the cap chose (None if no frame was trimmed);
+    records carry ``sample_cap`` and ``cap_threshold`` (None: not trimmed); out_dir gets ``cap<C>/``.  With metrics and fovea only; the cap
+    is removed afterwards."""
+    if sweep_sample_caps and (sweep_thresholds or sweep_samples or sweep_scales or reproject_stride is not None or supersample is not None or
+                              temporal is not None or temporal_still is not None or temporal_upsample is not None or fovea_density is not None):
+        raise ValueError("sweep_sample_caps goes with metrics and fovea only")
+    if sweep_sample_caps and not all(c == 0 or (math.isfinite(c) and c >= 1) for c in sweep_sample_caps):
+        raise ValueError("sweep_sample_caps: every cap must be 0 or a finite value >= 1, got %s" % (list(sweep_sample_caps),))
     if isinstance(fovea, str):
         fovea = parse_fovea(fovea)
     if fovea_density is not None:
@@ -330,6 +347,9 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                         rgba = r.present(w, h, filter="linear" if tu else present_filter).reshape(-1, 4)
                         rgb = rgba[:, :3].astype(np.float32) / 255.0
                     rec = dict(extra, frame=i, image=fr["image"], samples_per_ray=st.total_samples / float(rw * rh), ms=st.ms_total)
+                    if "sample_cap" in extra:      # the largest threshold the cap chose over the frame's batches
+                        t_cap = float(r.sample_cap_report().threshold_max)
+                        rec.update(cap_threshold=t_cap if math.isfinite(t_cap) or t_cap > 0 else None)
                     if stride:
                         rec.update(warped=False)
                     if ss:
@@ -421,6 +441,18 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                 recs = render_set(os.path.join(out_dir, sweep_dir_name(**key)) if out_dir else None, key, sc)
                 sweep.append(dict(key, **{k: v for k, v in summarise(recs, want_flip).items() if k != "frames"}, **(dict(supersample=ss) if ss else {})))
                 results.extend(recs)
+        elif sweep_sample_caps:
+            try:
+                for cap in sweep_sample_caps:
+                    r.set_sample_cap(cap)
+                    key = dict(sample_cap=float(cap))
+                    recs = render_set(os.path.join(out_dir, "cap%g" % cap) if out_dir else None, key)
+                    trimmed = [x["cap_threshold"] for x in recs if x.get("cap_threshold") is not None]
+                    sweep.append(dict(key, **{k: v for k, v in summarise(recs, want_flip).items() if k != "frames"},
+                                      mean_cap_threshold=float(np.mean(trimmed)) if trimmed else None))
+                    results.extend(recs)
+            finally:
+                r.set_sample_cap(0)
         else:
             results = render_set(out_dir, {})
         if vid:
@@ -501,6 +533,9 @@ def build_parser():
                     help="render the set once per threshold (x --sweep-samples) on one context; summary gains `sweep`, --out gets n<N>_t<T>/")
     ap.add_argument("--sweep-samples", nargs="+", type=int, default=None, metavar="N",
                     help="render the set once per sample budget N (x --sweep-thresholds)")
+    ap.add_argument("--sweep-sample-caps", nargs="+", type=float, default=None, metavar="C",
+                    help="render the set once per sample cap C (mean samples per ray no frame may exceed; 0 = none) on one context; summary "
+                         "gains `sweep` with mean_cap_threshold, --out gets cap<C>/")
     ap.add_argument("--sweep-scales", nargs="+", type=float, default=None, metavar="S",
                     help="render the set once per scale S of the dataset's resolution (x the other sweeps) on the same context, present it "
                          "to the full size on the GPU and score that 8-bit image; entries gain `scale`, --out directories _s<S>")
@@ -596,7 +631,8 @@ def main(argv=None):
                           reproject_tol=a.reproject_tol, rerender=a.rerender, supersample=a.supersample, present_filter=a.present_filter,
                           temporal=a.temporal, temporal_still=a.temporal_still, temporal_upsample=a.temporal_upsample,
                           temporal_upsample_frames=a.temporal_upsample_frames, fovea_density=a.fovea_density,
-                          supersample_contrast=a.supersample_contrast, fovea_temporal=a.fovea_temporal, fovea_temporal_still=a.fovea_temporal_still)
+                          supersample_contrast=a.supersample_contrast, fovea_temporal=a.fovea_temporal, fovea_temporal_still=a.fovea_temporal_still,
+                          sweep_sample_caps=a.sweep_sample_caps)
     print(json.dumps(summary))
 
 

@@ -92,6 +92,14 @@ bool InputHandler::replay(const char* line) {
         if (end == val.c_str() || *end != 0 || !(x - x == 0.f)) return false;      // finite
       }
       renderer.setGaze(v[0], v[1]);
+    } else if (tok == "cap") {
+      // one value, read whole: "cap 4.5"; 0 removes the cap; the library validates it when the frame is rendered
+      std::string val;
+      if (!(in >> val)) return false;
+      char* end = nullptr;
+      const float x = std::strtof(val.c_str(), &end);
+      if (end == val.c_str() || *end != 0 || !(x == 0.f || (x >= 1.f && x - x == 0.f))) return false;
+      renderer.setSampleCap(x);
     } else if (tok == "cut") {
       renderer.cutHistory();
     } else if (tok == "size") {

@@ -22,7 +22,7 @@ class InputHandler {
   // one script line = the events in front of one frame: "+w" "-w" (key down / up: w a s d q e o f esc), "b+ x y" / "b- x y"
   // (left button), "m x y" (mouse position), "n <int>" / "thr <float>" (sample budget N / selection threshold from this line's frame
   // on: NeuralRenderer::setSelection), "size <W> <H>" (frame size from this line's frame on, the window size stays:
-  // NeuralRenderer::setFrameSize), "gaze <X> <Y>" (the --fovea gaze point in pixels from this line's frame on:
+  // NeuralRenderer::setFrameSize), "cap <X>" (the --sample-cap bound from this line's frame on, 0 removes it), "gaze <X> <Y>" (the --fovea gaze point in pixels from this line's frame on:
   // NeuralRenderer::setGaze), "cut" (--taa: this line's frame starts a new history: NeuralRenderer::cutHistory); returns false on a
   // malformed line
   bool replay(const char* line);

@@ -188,6 +188,7 @@ bool NeuralRenderer::init() {
     return false;
   }
   render_oracle = settings.render_oracle;
+  if (settings.sample_cap > 0.f) setSampleCap(settings.sample_cap);      // installed before the first frame; the library validates it there
   return true;
 }
 
@@ -463,6 +464,19 @@ bool NeuralRenderer::render() {
     have_source = false;      // a new selection shows from this frame on: render it
     taa_have = false;         // and --taa does not blend it with frames of the old one
   }
+  if (cap_pending) {      // --sample-cap / script token "cap": every context (--gpus / --sub-shares) gets the same bound before this frame
+    cap_pending = false;
+    std::vector<adanerf_ctx*> all(1, ctx);
+    all.insert(all.end(), peers.begin(), peers.end());
+    for (adanerf_ctx* c : all)
+      if (adanerf_set_sample_cap(c, want_cap) != ADANERF_OK) {
+        err = adanerf_last_error(c);
+        return false;
+      }
+    cap_in_force = want_cap;
+    have_source = false;      // the bound shows from this frame on: render it
+    taa_have = false;
+  }
   if (!applyFovea()) return false;
   if (!applyFoveaDensity()) return false;
   if (adanerf_set_camera(ctx, camera.getPosition(), rot) != ADANERF_OK) {
@@ -541,6 +555,16 @@ bool NeuralRenderer::render() {
                 << ", largest pair error " << st.guard_pair_seen << "), audit: " << st.guard_audit_mismatch << " of " << st.guard_audited
                 << " decided rays selected differently; bounds widened to " << now.guard_eps << " / " << now.guard_eps_pair
                 << " for the following frames" << std::endl;
+  }
+  if (cap_in_force > 0.f) {      // the frame is finished (stats synchronise): what the cap did to its last render
+    adanerf_cap_report rep;
+    if (adanerf_sample_cap_report(ctx, &rep) != ADANERF_OK) {
+      err = adanerf_last_error(ctx);
+      return false;
+    }
+    if (rep.threshold_max > s_cap_thr) s_cap_thr = rep.threshold_max;
+    s_cap_selected += rep.samples_selected;
+    s_cap_kept += rep.samples_kept;
   }
   s_inference1 += st.ms_sample_mlp;
   s_inference2 += st.ms_shade_mlp;
@@ -796,6 +820,8 @@ void NeuralRenderer::logInterval() {
   if (settings.reproject > 1) std::cout << ", holes: " << s_holes / static_cast<double>(std::max(s_warped, 1)) << " (" << s_warped << " warped frames)";
   if (settings.fovea_temporal_alpha > 0.f) std::cout << ", fovea-temporal rejected: " << s_rejected / static_cast<double>(logging_interval) / settings.total_size;
   if (!settings.density_stride.empty()) std::cout << ", rendered fraction: " << s_density_rendered / static_cast<double>(logging_interval) / settings.total_size;
+  if (cap_in_force > 0.f)
+    std::cout << ", sample cap: " << cap_in_force << ", cap threshold max: " << s_cap_thr << ", cap kept / selected: " << s_cap_kept << " / " << s_cap_selected;
   if (!settings.rerender.empty()) std::cout << ", rerendered: " << s_rerendered / static_cast<double>(std::max(s_warped, 1));
   std::cout << std::endl;
   s_inference1 = s_inference2 = s_fc2 = s_rm = s_total = 0;
@@ -806,6 +832,8 @@ void NeuralRenderer::logInterval() {
   s_refined = 0;
   s_rejected = 0;
   s_rendered = s_warped = 0;
+  s_cap_thr = -1.f / 0.f;
+  s_cap_selected = s_cap_kept = 0;
 }
 
 // -w: the frame at its render size, exactly as before; --write-window: the frame as the viewer's blit would show it in a window of

@@ -30,6 +30,15 @@ class NeuralRenderer {
     *thr = want_threshold;
     return selection_pending;
   }
+  // --sample-cap: the bound from the next frame on (script token "cap X", 0 removes it); reaches every context in render()
+  void setSampleCap(float cap) {
+    want_cap = cap;
+    cap_pending = true;
+  }
+  bool pendingSampleCap(float* cap) const {      // what the next frame will ask of the library
+    *cap = want_cap;
+    return cap_pending;
+  }
   // frame size from the next frame on ("size W H"); the window size stays.  Reaches every context in render()
   void setFrameSize(int w, int h) {
     want_width = w;
@@ -139,6 +148,10 @@ class NeuralRenderer {
   bool fovea_pending = true;         // the maps are to be filled before the next frame: at start, after "gaze", after "size"
   bool gaze_set = false;             // a "gaze" token has moved it from the frame centre
   float gaze_x = 0.f, gaze_y = 0.f;
+  bool cap_pending = false;          // setSampleCap since the last frame (init: --sample-cap)
+  float want_cap = 0.f, cap_in_force = 0.f;
+  float s_cap_thr = -1.f / 0.f;      // --sample-cap: largest threshold the cap chose, samples before / after it, over the running interval's frames
+  long long s_cap_selected = 0, s_cap_kept = 0;
   bool size_pending = false;         // setFrameSize since the last frame
   int want_width = 0, want_height = 0;
   // 100-frame running sums

@@ -12,6 +12,8 @@ const char* Settings::usage() {
          "               [--frames N] [--precision bf16|fp16|fp32] [--sampling auto|guarded|split|fp32|fp16]\n"
          "               [--yaw DEG] [--pitch DEG]\n"
          "               [--samples N] [--threshold T] [--oracle]\n"
+         "               [--sample-cap X]                   a hard bound on the samples of every frame: at most X per ray on average (X >= 1);\n"
+         "                                                  the threshold is raised on the device by exactly as much as that needs\n"
          "               [--fovea R:N:T[,R:N:T...],N:T]     per-ray budgets: rings around the gaze (radius px : N : threshold), then the\n"
          "                                                  entry outside them; the gaze starts at the frame centre\n"
          "               [--fovea-density R:S[,R:S...],S]   foveated ray density: rings around the gaze (radius px : stride 1|2|4|8), then the\n"
@@ -26,6 +28,7 @@ const char* Settings::usage() {
          "                                                              sample budget N / threshold from that frame on;\n"
          "                                                              size <W> <H>: frame size from that frame on, the window stays;\n"
          "                                                              gaze <X> <Y>: the --fovea / --fovea-density gaze, px;\n"
+         "                                                              cap <X>: the --sample-cap bound from that frame on, cap 0 removes it;\n"
          "                                                              cut: --taa / --taau / --fovea-temporal start a new history with that frame)\n"
          "               [--reproject K]      of every K frames render the first and warp it to the camera of the next K - 1 (depth\n"
          "                                    reprojection, holes filled from their neighbours); -w / --write-window write what was shown\n"
@@ -300,6 +303,15 @@ bool Settings::init(int argc, char** argv, std::string* err) {
         return false;
       }
       supersample = static_cast<int>(k);
+    } else if (a == "--sample-cap") {
+      if (!need(i, 1)) return false;
+      char* end = nullptr;
+      const float x = std::strtof(argv[++i], &end);
+      if (end == argv[i] || *end != 0 || !(x == 0.f || (x >= 1.f && x - x == 0.f))) {
+        *err = "--sample-cap X: X must be 0 (off) or a finite number >= 1";
+        return false;
+      }
+      sample_cap = x;
     } else if (a == "--supersample-contrast") {
       if (!need(i, 1)) return false;
       char* end = nullptr;
@@ -428,6 +440,12 @@ bool Settings::init(int argc, char** argv, std::string* err) {
       *err = std::string("--fovea-density: ") + why;
       return false;
     }
+  }
+  if (sample_cap > 0.f && (!density_stride.empty() || !rerender.empty() || supersample_contrast >= 0.f || render_oracle)) {
+    *err = render_oracle ? "--sample-cap bounds rendered frames; not with --oracle"
+                         : "--sample-cap: the masked render refuses a cap (its threshold depends on which rays share a batch); not with --fovea-density, "
+                           "--rerender or --supersample-contrast";
+    return false;
   }
   if (fovea_temporal_alpha > 0.f && density_stride.empty()) {
     *err = "--fovea-temporal resolves the frames of a moving lattice; only with --fovea-density";

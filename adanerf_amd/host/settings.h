@@ -65,6 +65,7 @@ class Settings {
   float reproject_tol = 0.05f;
   int supersample = 1;          // --supersample S (1..8): every shown frame is S x S renders at the offsets of adanerf_host_subpixel_grid, accumulated and
                                 // resolved on the device (adanerf_set_pixel_offset / adanerf_accumulate / adanerf_resolve_mean); 1: one render per frame
+  float sample_cap = 0.f;       // --sample-cap X: no frame shades more than X samples per ray on average (adanerf_set_sample_cap; script token `cap X`); 0: off
   float supersample_contrast = -1.f;   // --supersample-contrast T (0..1, with --supersample S >= 2): adaptive supersampling -- one render at the pixel centres, then
                                 // the S x S renders only for the pixels a neighbour of which differs by more than T in some channel's display value
                                 // (adanerf_contrast_mask / adanerf_render_masked / adanerf_accumulate_masked / adanerf_resolve_mean_masked); < 0: off

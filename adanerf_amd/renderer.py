@@ -74,6 +74,11 @@ class Stats(C.Structure):
                 ("guard_audit_mismatch", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
+class CapReport(C.Structure):
+    """adanerf_cap_report: what the sample cap did to the last render."""
+    _fields_ = [("threshold_max", C.c_float), ("batches_trimmed", C.c_int32), ("samples_selected", C.c_int64), ("samples_kept", C.c_int64)]
+
+
 EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_last_error", "adanerf_abi_version", "adanerf_struct_sizes", "adanerf_set_camera", "adanerf_set_selection", "adanerf_set_frame_size", "adanerf_present", "adanerf_reproject",
            "adanerf_reproject_gather",
            "adanerf_set_budget_map", "adanerf_foveate", "adanerf_compact_budget",
@@ -89,7 +94,8 @@ EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_las
            "adanerf_foveate_density", "adanerf_fill_density", "adanerf_host_density_mask",
            "adanerf_foveate_density_phased", "adanerf_fill_density_phased", "adanerf_host_density_mask_phased", "adanerf_host_density_phase",
            "adanerf_temporal_resolve_sparse",
-           "adanerf_contrast_mask", "adanerf_accumulate_masked", "adanerf_resolve_mean_masked", "adanerf_host_contrast_mask"]
+           "adanerf_contrast_mask", "adanerf_accumulate_masked", "adanerf_resolve_mean_masked", "adanerf_host_contrast_mask",
+           "adanerf_set_sample_cap", "adanerf_sample_cap_report", "adanerf_compact_cap"]
 
 _lib = None
 
@@ -118,6 +124,10 @@ def load_library(path: Optional[str] = None):
     lib.adanerf_set_depth_limit.argtypes = [vp, vp]
     lib.adanerf_compact_depth_limit.argtypes = [vp, vp, i32, i32, C.c_float, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp, vp, vp, vp, vp]
     lib.adanerf_blend_behind.argtypes = [vp, vp, vp, vp, i32, vp, vp]
+    lib.adanerf_set_sample_cap.argtypes = [vp, C.c_float]
+    lib.adanerf_sample_cap_report.argtypes = [vp, C.POINTER(CapReport)]
+    lib.adanerf_compact_cap.argtypes = [vp, vp, i32, i32, C.c_float, vp, vp, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int64,
+                                        vp, vp, vp, vp, vp, vp]
     lib.adanerf_host_sphere_zc.argtypes = [i32, i32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float)]
     lib.adanerf_foveate_density.argtypes = [vp, C.c_float, C.c_float, i32, C.POINTER(i32), C.POINTER(i32), vp]
     lib.adanerf_fill_density.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, C.POINTER(i32)]
@@ -652,6 +662,19 @@ class NeuralRenderer:
                 m = buf
             ptrs.append(_ptr(m))
         self._check(self.lib.adanerf_set_budget_map(self.handle, ptrs[0], ptrs[1]))
+
+    def set_sample_cap(self, mean: float = 0.0):
+        """A hard upper bound on the samples of the frames rendered from now on (adanerf_set_sample_cap): a batch of n rays shades at most
+        floor(mean * n) samples; the threshold is raised on the device, in the same frame, by exactly as much as that needs.  0 removes the
+        cap; otherwise ``mean`` is finite and >= 1.  Survives set_selection and set_frame_size."""
+        self._check(self.lib.adanerf_set_sample_cap(self.handle, float(mean)))
+
+    def sample_cap_report(self) -> CapReport:
+        """What the cap did to the last render (adanerf_sample_cap_report; synchronises once): threshold_max (-inf: no batch was trimmed),
+        batches_trimmed, samples_selected, samples_kept."""
+        rep = CapReport()
+        self._check(self.lib.adanerf_sample_cap_report(self.handle, C.byref(rep)))
+        return rep
 
     def foveate_device(self, gaze_xy, rings, n_map=None, thr_map=None) -> int:
         """adanerf_foveate into device buffers (either may be None): rings as parse_fovea returns them, [(R, N, T), ..., (N, T)].
@@ -1534,6 +1557,18 @@ class NeuralRenderer:
         r = np.ascontiguousarray(rot_c2w, dtype=np.float32).reshape(9)
         return self.lib.adanerf_compact_depth_limit(self.handle, _ptr(oracle), n_rays, n_max, thr, _ptr(rays), _ptr(limit_zc), p.ctypes.data_as(fp),
                                                     r.ctypes.data_as(fp), _ptr(ray_offsets), _ptr(ray_counts), _ptr(sample_key), _ptr(sample_w), _ptr(total))
+
+    def compact_cap(self, oracle, n_rays: int, n_max: int, thr: float, cap_total: int, ray_offsets, ray_counts, sample_key, sample_w, total, tstar,
+                    n_map=None, thr_map=None, rays=None, limit_zc=None, pos=None, rot_c2w=None) -> int:
+        """adanerf_compact_cap: the selection at (n_max, thr), the budget trim (n_map / thr_map) and the depth trim (rays, limit_zc, pos,
+        rot_c2w) where given, the sample cap at C = cap_total, then the compaction; ``tstar`` [1] fp32 on the device gets t* (-inf: nothing
+        trimmed).  Returns the library's code instead of raising: tests look at both."""
+        fp = C.POINTER(C.c_float)
+        p = None if pos is None else np.ascontiguousarray(pos, dtype=np.float32).reshape(3)
+        r = None if rot_c2w is None else np.ascontiguousarray(rot_c2w, dtype=np.float32).reshape(9)
+        return self.lib.adanerf_compact_cap(self.handle, _ptr(oracle), n_rays, n_max, thr, _ptr(n_map), _ptr(thr_map), _ptr(rays), _ptr(limit_zc),
+                                            None if p is None else p.ctypes.data_as(fp), None if r is None else r.ctypes.data_as(fp), int(cap_total),
+                                            _ptr(ray_offsets), _ptr(ray_counts), _ptr(sample_key), _ptr(sample_w), _ptr(total), _ptr(tstar))
 
     def compact_budget(self, oracle, n_rays: int, n_max: int, thr: float, n_map, thr_map, ray_offsets, ray_counts, sample_key, sample_w, total):
         self._check(self.lib.adanerf_compact_budget(self.handle, _ptr(oracle), n_rays, n_max, thr, _ptr(n_map), _ptr(thr_map), _ptr(ray_offsets),

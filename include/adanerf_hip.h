@@ -466,6 +466,60 @@ int adanerf_foveate(adanerf_ctx* ctx, float gaze_x, float gaze_y, int32_t n_ring
  * reprojection stages (their depth is the volume's own); an evaluator mode. */
 int adanerf_set_depth_limit(adanerf_ctx* ctx, const float* d_limit_zc);
 
+/* A hard upper bound on the samples a batch may shade: the guarantee "this frame will not cost more than X" that no other dial gives.
+ * Frame time is shading time and shading time is linear in the selected samples, whose number follows the view; every other dial
+ * (adanerf_set_selection, budget maps, depth limits, the frame size) fixes the inputs of the selection and takes whatever total comes out.
+ * The cap is enforced on the device in the same frame, with no read-back, by raising the threshold -- AdaNeRF's own quality knob -- by
+ * exactly as much as the bound needs.
+ *   mean_samples_per_ray   0 turns the cap off.  Otherwise finite and >= 1, else ADANERF_EINVAL.  A batch of n rays may shade
+ *                          C = (int64) floor((double) mean_samples_per_ray * n) samples (>= n: every non-empty row keeps one entry).
+ *                          A cap at or above the context's N cannot trim and launches nothing.
+ * Rule (exact, in integers on the values' bits), per batch, after the selection -- fused, pair or wave --, the budget trim and the depth
+ * limit, immediately before the compaction: row r has c_r entries (0..N; 0 only under a depth limit) with kept values v_rk.  For a
+ * threshold t, kept_r(t) = 0 if c_r == 0, else max(1, #{k < c_r : v_rk >= t}) -- an fp32 >=, so a NaN never passes and -0 equals +0;
+ * T(t) = sum_r kept_r(t); T_now = sum_r c_r.  If T_now <= C nothing is written: rows, counts and segment totals keep their bytes.
+ * Otherwise t* is the smallest non-NaN value present in the batch's rows with T(t*) <= C (-0 taken as +0; +inf if no present value
+ * satisfies it: T(+inf) <= n <= C unless a row holds +inf more than once -- such a row keeps every +inf, the one way past C), and every row with more than one entry is trimmed as the budget trim trims a row at (N, t*): the
+ * entries with v >= t* survive, the first of the order (value descending, lower bin first) alone if none does; survivors stay in
+ * ascending bin order with their values untouched.  Ties at t* make T jump: the rule takes the smallest t that fits, so the result may lie
+ * well under C, never above it.  t* >= the context's threshold always.  Trims compose (the kept set of a row is a prefix of one order):
+ * with a budget map installed ray r ends with the selection at (n_r, max(thr_r, t*)).
+ * Contract: a capped batch is byte for byte the batch the same context renders with no cap and a threshold map filled with t*
+ * (adanerf_set_budget_map(ctx, NULL, map)): counts, offsets, keys, kept values, total and image.
+ * Mechanism: an exact radix selection of t* over the order-preserving 32-bit keys of the values, 11 + 11 + 10 bits in three passes over the
+ * rows; per pass two integer histograms (entries, row maxima: T(t) = entries >= t + non-empty rows - rows whose maximum is >= t), privatised in
+ * LDS and flushed with integer atomic adds -- integer sums do not depend on their order, so the same inputs give the same bits; no
+ * floating-point atomic -- and a one-workgroup digit search.  Every pass is its own launch, ordered by the stream; t*, T_now and the new
+ * total stay in a context-owned device record; the scratch is context-owned, grown on demand and freed by adanerf_destroy.  t* then goes
+ * into a context-owned threshold map and the unchanged budget-trim kernels run.  When a batch fits, the later passes return at once.
+ * Without a cap nothing new is launched: every frame is byte for byte what it was.  After a render adanerf_stats.total_samples and
+ * ADANERF_BUF_RAY_COUNTS / _RAY_OFFSETS / _SAMPLE_KEY / _SAMPLE_W / _TOTAL describe the trimmed selection.
+ *   Ordering is that of adanerf_set_camera.  The cap is a scalar, not a per-ray buffer: it survives adanerf_set_selection and
+ *   adanerf_set_frame_size.  While a cap is installed adanerf_set_selection refuses threshold 0.
+ *   Shards and batches (options.batch_rays): each batch is capped on its own rays, so the bound holds per batch and therefore per frame
+ *   (sum of floor(cap * n_b) <= cap * rays_local); t* may differ between batches.
+ *   ADANERF_SAMPLING_GUARDED: as under a budget map, the context renders as an ADANERF_SAMPLING_SPLIT_FP16 context while a cap is installed
+ *   (the trim reads values, and unrefined rays hold fp16 values): no first pass, no audit, rays_refined 0.  The band, the audit's phase and
+ *   the monitor are left untouched; removing the cap resumes guarded rendering.
+ * ADANERF_EUNSUPPORTED, with nothing changed: a context with threshold 0 (dense); ADANERF_SAMPLER_PDF and _COARSE_FINE.
+ * What it does not do: adanerf_render_masked returns ADANERF_EUNSUPPORTED while a cap is installed (its byte-identity contract with
+ * adanerf_render cannot hold when t* depends on which rays are in the batch); one cap across the batches of a frame; spreading the cut by
+ * anything other than one threshold per batch; a closed-loop frame-time controller (a few host lines on top of this). */
+int adanerf_set_sample_cap(adanerf_ctx* ctx, float mean_samples_per_ray);
+
+/* What the cap did to the last adanerf_render (synchronises the context's stream once):
+ *   threshold_max      largest t* over the frame's batches; -inf when no batch was trimmed
+ *   batches_trimmed    batches whose T_now exceeded their C
+ *   samples_selected   sum of T_now over the batches the cap examined (0 when the cap is at or above N: nothing is launched)
+ *   samples_kept       sum of their totals afterwards: <= sum of C */
+typedef struct adanerf_cap_report {
+  float threshold_max;
+  int32_t batches_trimmed;
+  int64_t samples_selected;
+  int64_t samples_kept;
+} adanerf_cap_report;
+int adanerf_sample_cap_report(adanerf_ctx* ctx, adanerf_cap_report* out);
+
 /* The second half of hybrid rendering: per pixel t = 1 - acc (one fp32 subtraction); !(t > 0) gives t = 0 (a NaN too); t > 1 gives t = 1;
  * t == 0: out = rgb, the bits copied (a NaN in the behind image cannot leak); otherwise out_c = rgb_c + t * behind_c, a product, then a
  * sum, each rounded to fp32.
@@ -642,6 +696,16 @@ int adanerf_compact_budget(adanerf_ctx* ctx, const float* d_oracle, int32_t n_ra
 int adanerf_compact_depth_limit(adanerf_ctx* ctx, const float* d_oracle, int32_t n_rays, int32_t n_max, float thr, const float* d_rays,
                                 const float* d_limit_zc, const float pos[3], const float rot_c2w[9], int32_t* d_ray_offsets,
                                 int32_t* d_ray_counts, uint32_t* d_sample_key, float* d_sample_w, int32_t* d_total);
+
+/* adanerf_compact with a sample cap, for tests: the selection at (n_max, thr); the budget trim if d_n_map / d_thr_map is given (either or both
+ * may be NULL); the depth trim if d_limit_zc is given (then d_rays, pos and rot_c2w as in adanerf_compact_depth_limit; all four may be NULL);
+ * the cap of adanerf_set_sample_cap with C = cap_total (>= n_rays, else ADANERF_EINVAL); the compaction.  thr > 0.  Honours
+ * ADANERF_FLAG_WAVE_SELECT and n_max > 16 as adanerf_compact does.  Outputs as adanerf_compact, plus d_tstar [1] fp32 device: the t* the
+ * cap chose, -inf if nothing was trimmed. */
+int adanerf_compact_cap(adanerf_ctx* ctx, const float* d_oracle, int32_t n_rays, int32_t n_max, float thr, const uint8_t* d_n_map,
+                        const float* d_thr_map, const float* d_rays, const float* d_limit_zc, const float pos[3], const float rot_c2w[9],
+                        int64_t cap_total, int32_t* d_ray_offsets, int32_t* d_ray_counts, uint32_t* d_sample_key, float* d_sample_w,
+                        int32_t* d_total, float* d_tstar);
 
 /* Calibrates the band of ADANERF_SAMPLING_GUARDED for the loaded model: n_poses cameras drawn inside the view cell
  * (positions uniform in 90 % of it, any orientation; seeded), 64 x 64 rays covering the field of view each, through both the
