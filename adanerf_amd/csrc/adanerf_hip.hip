@@ -819,6 +819,9 @@ static int create_on(adanerf_ctx* c, const char* model_dir, const adanerf_option
     // the split-precision packing: the ring-streamed kernel's for the 8 x 256 net, the run-time-shaped kernel's otherwise (not with raySampleInput,
     // not above width 256: such nets run the fp32 kernel in every sampling mode)
     if (has_split_sampling(c) && !pack_sampling_net(n0, sh, Elem::F16_SPLIT, &p0s, &err)) return bail(ADANERF_EIO, "model0.onnx: " + err);
+    // a weight outside the fp16 range packs as +-inf: a 16-bit engine can return a finite, wrong row for it (pack.hpp).  Only the fp32 engine runs it.
+    if (has_split_sampling(c) && opt->sampling_mode != ADANERF_SAMPLING_FP32 && !sampling_weights_fit_fp16(n0, &err))
+      return bail(ADANERF_EUNSUPPORTED, "model0.onnx: " + err + " is outside the fp16 range (|w| < 65520) of the 16-bit sampling engines: use ADANERF_SAMPLING_FP32");
   }
   c->sampling_mode = opt->sampling_mode;
   c->model_dir = model_dir;

@@ -7,9 +7,13 @@
 namespace adanerf {
 
 // ---- split-precision sampling MLP: fp16 hi + 2^-11 * fp16 lo', three MFMAs per term --------------
-// x ~= hi + lo' / 2048 with hi = fp16(x), lo' = fp16((x - hi) * 2048): 22 significant bits and no
-// dependence on fp16 subnormals.  W.x = Whi.xhi + (Whi.xlo' + Wlo'.xhi) / 2048 (the lo'.lo' term is
-// 2^-22 relative and dropped).  Main and cross products accumulate in separate fp32 accumulators.
+// x ~= hi + lo' / 2048 with hi = fp16(x), lo' = fp16((x - hi) * 2048): 22 significant bits down to 2^-14.  Below, fp16 subnormals
+// carry the value (both conversions and the matrix pipe keep them; tests/test_gpu_sampling_ranges.py holds every kernel here to that
+// bit for bit): hi is subnormal or 0 and lo' resolves an absolute 2^-35, so |x| <= 2^-36 is 0.  At the top, x >= 65520 is hi = inf (the
+// row goes non-finite and counts in sampling_overflow), every x <= 65520 - 2^-7 is carried finite, and the one fp32 between them,
+// nextafter(65520, 0), is hi = 65504 + lo' = 32768 (a tie, to even): the value 65520, inf after the next layer that reads it with weight 1.
+// W.x = Whi.xhi + (Whi.xlo' + Wlo'.xhi) / 2048 (the lo'.lo' term is 2^-22 relative and dropped); for fp32 x and W the cross sum
+// needs at most 24 bits, so it is exact in the accumulator.  Main and cross products accumulate in separate fp32 accumulators.
 // Measured against an fp64 reference on the shipped weights: max error 1.9e-6 (numpy sgemm: 2.4e-6),
 // identical selections on 100 % of rays -- at 3/16 of the fp32-MFMA cycle count.
 // kSplitScale (2^11) is defined in pack.hpp

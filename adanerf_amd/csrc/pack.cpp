@@ -309,6 +309,19 @@ static bool shape_ok(const NetShape& sh, std::string* err) {
   return true;
 }
 
+bool sampling_weights_fit_fp16(const TensorMap& net0, std::string* which) {
+  for (int i = 0; i < count_layers(net0, "layers."); ++i) {
+    const std::string name = "layers." + std::to_string(i) + ".weight";
+    const Tensor& W = net0.at(name);
+    for (size_t k = 0; k < W.data.size(); ++k)
+      if (!(std::fabs(W.data[k]) < 65520.0f)) {      // the smallest value fp16 rounds to inf; a NaN fails the comparison too
+        if (which) *which = name + "[" + std::to_string(k / std::max(W.cols(), 1)) + "][" + std::to_string(k % std::max(W.cols(), 1)) + "] = " + std::to_string(W.data[k]);
+        return false;
+      }
+  }
+  return true;
+}
+
 bool pack_sampling_net(const TensorMap& net0, const NetShape& sh, Elem elem, PackedNet* out, std::string* err) {
   *out = PackedNet();
   out->elem = elem;

@@ -72,6 +72,11 @@ struct NetShape {
 // only (the wide form), without raySampleInput.
 bool pack_sampling_net(const TensorMap& net0, const NetShape& shape, Elem elem, PackedNet* out, std::string* err);
 
+// The 16-bit sampling engines hold a weight as fp16 (hi, lo') or one fp16: |w| >= 65520 (and a NaN) packs as hi = +-inf, lo' = -+inf, under which
+// a unit with a negative operand and a bias comes out as relu(-inf) = 0 -- finite and wrong, never counted.  adanerf_create refuses such a
+// network for every sampling mode but ADANERF_SAMPLING_FP32 (the packer itself packs what it is given).  false: *which names the first such weight.
+bool sampling_weights_fit_fp16(const TensorMap& net0, std::string* which);
+
 // pts_linears.{0..D-1}, feature_linear(+alpha_linear as row W), views_linears.0, rgb_linear
 // (src/models.py:199-277).  Layer order in the blob: 0..D-1, feature+alpha, views, rgb.  Any topology (any W <= 512, run zero-padded to
 // 64 / 128 / 256 / 512 -- fp32 at 512 in the wide form; D in 1..8, skips anywhere) and encoding layout packs for every element type (16-bit: k_generic16.hip.hpp).

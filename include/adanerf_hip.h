@@ -111,7 +111,22 @@ enum {
 };
 /* Sampling nets of another topology / encoding layout (run-time-shaped kernels): ADANERF_SAMPLING_FP32 runs the exact fp32
  * kernel, every other mode the split-precision one (same arithmetic as ADANERF_SAMPLING_SPLIT_FP16; no plain-fp16 pass);
- * with raySampleInput always the fp32 kernel.  Sampling nets wider than 256 run the fp32 kernel in every mode (its wide form). */
+ * with raySampleInput always the fp32 kernel.  Sampling nets wider than 256 run the fp32 kernel in every mode (its wide form).
+ *
+ * Operand range of the 16-bit sampling engines (tests/range_networks.py states the rule per layer, tests/test_gpu_sampling_ranges.py holds
+ * the kernels to it bit for bit): an operand x -- an encoded input, a ReLU output, a weight -- is hi = fp16(x), lo' = fp16((x - hi) 2^11),
+ * both conversions round to nearest even and keep fp16 subnormals; a layer computes fma(Whi xlo' + Wlo' xhi, 2^-11, bias + Whi xhi) in
+ * fp32 (plain fp16: bias + fp16(W) fp16(x)).  So a value is carried to 22 bits down to 2^-14 and with an absolute step of 2^-35 below
+ * (lo' subnormal): |x| <= 2^-36 is 0, and so is a weight with |w| <= 2^-36.
+ *   Activations: x >= 65520 converts to inf; the row of that ray is then non-finite in every column and the ray counts in
+ *   adanerf_stats.sampling_overflow.  Every x <= 65520 - 2^-7 stays finite.  The one fp32 value between, nextafter(65520, 0), is carried
+ *   as hi = 65504, lo' = 32768 (a tie, to even) -- the value 65520 -- and overflows at the next hidden layer that reads it with weight 1
+ *   (split engine; plain fp16 rounds it to 65504).  A NaN stays a NaN through every ReLU.
+ *   Weights: adanerf_create refuses (ADANERF_EUNSUPPORTED) a sampling net with a weight |w| >= 65520 or NaN in every mode but
+ *   ADANERF_SAMPLING_FP32, where the network runs on the fp32 kernel: packed as +-inf, such a weight times a negative operand is -inf,
+ *   which ReLU turns into a finite 0 whatever the bias -- a wrong row nobody would count.  (Nets that run the fp32 kernel in every
+ *   mode -- raySampleInput, width above 256 -- are not refused.)  Biases are fp32 in every engine.
+ *   ADANERF_SAMPLING_FP32 has no range below fp32's own and never counts.  Its ReLU is fmaxf: a NaN activation becomes 0 there. */
 
 /* sample placement (config.ini rayMarchSampler[1]) */
 enum {

@@ -32,7 +32,9 @@ Instantiations and the cases that reach them:
     sample_mlp16x3_gen_kernel <10, 4 | 2, 2 | 16, 16, W = 64/128/256>  [gen_split_w*_*] (nine cases; sampling="fp16" runs it too)
     sample_mlp_gen_kernel (fp32, raySampleInput)                       [gen_fp32_w128], [gen_fp32_rsi8_w128]
     sample_mlp_gen_wide_kernel <10, 4 | 16, 16>                        [wide_fp32_w320], [wide_fp32_w512_catchall]
-    the fp16-range contract: test_sampling_fp16_range_contract[fixed_split | fixed_fp16 | gen_split_w128]"""
+    the fp16-range contract: test_sampling_fp16_range_contract[fixed_split | fixed_fp16 | gen_split_w128]
+    the operand rounding of every sampling kernel at the edges of its range, bit for bit (fp16 subnormals, hi = 0, ties, the last values
+    below 65520 and the rays within 1 % of that edge, which the contract test above leaves out): test_gpu_sampling_ranges.py"""
 import dataclasses
 import math
 
