@@ -23,9 +23,8 @@ NeuralRenderer::~NeuralRenderer() {
   }
   if (ctx) {
     if (d_gathered) adanerf_free(ctx, d_gathered);
-    if (d_frame) adanerf_free(ctx, d_frame);
-    for (void* p : {d_depth, d_acc, d_warp, d_wmask, d_src_rgb, d_warp_rgb, d_rgb, d_sum, d_hist[0][0], d_hist[0][1], d_hist[0][2], d_hist[1][0], d_hist[1][1], d_hist[1][2], d_up, d_limit, d_behind, d_dmask, d_stage, d_cmask})
-      if (p) adanerf_free(ctx, p);
+    for (const FrameBuffer& b : frameBuffers())
+      if (*b.p) adanerf_free(ctx, *b.p);
     if (d_window) adanerf_free(ctx, d_window);
     adanerf_destroy(ctx);
   }
@@ -192,106 +191,60 @@ bool NeuralRenderer::init() {
   return true;
 }
 
+// The host's frame-sized buffers on rank 0.  The modes that share a buffer agree on its size: d_rgb is the fp32 frame, d_depth / d_acc the aux
+// maps at the render size in all of them.  --taa, --taau and --fovea-temporal are mutually exclusive (settings.cpp), so the history has one
+// size: S w x S h under --taau, the render size under the other two.
+std::vector<NeuralRenderer::FrameBuffer> NeuralRenderer::frameBuffers() {
+  const size_t n = static_cast<size_t>(info_.width) * info_.height;
+  const bool taa = settings.taa_alpha > 0.f, taau = settings.taau_scale > 0, density = !settings.density_stride.empty(),
+             fovea_temporal = density && settings.fovea_temporal_alpha > 0.f, supersample = settings.supersample > 1,
+             contrast = supersample && settings.supersample_contrast >= 0.f, occluder = !settings.occluders.empty(), reproject = settings.reproject > 1,
+             gather = reproject && settings.reproject_gather;
+  const size_t N = taau ? n * settings.taau_scale * settings.taau_scale : n, hist = taa || taau || fovea_temporal ? N : 0;
+  const size_t aux = taa || taau || fovea_temporal || reproject ? n : 0;
+  std::vector<FrameBuffer> table = {
+      {&d_frame, n * 4, RESET_SOURCE},
+      {&d_rgb, taa || taau || density || supersample || occluder ? n * 12 : 0, 0},
+      {&d_depth, aux * 4, RESET_SOURCE | RESET_HISTORY},
+      {&d_acc, (occluder ? n : aux) * 4, RESET_SOURCE | RESET_HISTORY | RESET_OCCLUDER},
+      {&d_up, taau ? N * 4 : 0, 0},
+      {&d_dmask, density ? n : 0, RESET_FOVEA},
+      {&d_sum, supersample ? n * 12 : 0, 0},
+      {&d_stage, contrast ? n * 12 : 0, 0},
+      {&d_cmask, contrast ? n : 0, 0},
+      {&d_limit, occluder ? n * 4 : 0, RESET_OCCLUDER},      // the library drops the limit when rays_local changes
+      {&d_behind, occluder ? n * 12 : 0, RESET_OCCLUDER},
+      {&d_warp, reproject ? n * 4 : 0, 0},
+      {&d_wmask, reproject ? n * 4 : 0, 0},                  // (the mask is a byte per pixel: a quarter of its allocation)
+      {&d_src_rgb, gather ? n * 12 : 0, RESET_SOURCE},
+      {&d_warp_rgb, gather ? n * 12 : 0, 0},
+  };
+  for (int side = 0; side < 2; ++side) {
+    table.push_back({&history.set[side][0], hist * 12, RESET_HISTORY});
+    table.push_back({&history.set[side][1], hist * 4, RESET_HISTORY});
+    table.push_back({&history.set[side][2], hist, RESET_HISTORY});
+  }
+  return table;
+}
+
 bool NeuralRenderer::allocFrameBuffers() {
-  if (d_frame && adanerf_free(ctx, d_frame) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-  d_frame = nullptr;
-  if (adanerf_malloc(ctx, static_cast<size_t>(info_.width) * info_.height * 4, &d_frame) != ADANERF_OK) {
-    err = adanerf_last_error(ctx);
-    return false;
+  int resets = 0;
+  for (const FrameBuffer& b : frameBuffers()) {
+    if (*b.p && adanerf_free(ctx, *b.p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+    *b.p = nullptr;
+    if (b.bytes == 0) continue;
+    if (adanerf_malloc(ctx, b.bytes, b.p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+    resets |= b.resets;
   }
   d_shown = d_frame;
-  if (settings.taa_alpha > 0.f) {      // the aux outputs and the history belong to the frame size
-    const size_t n = static_cast<size_t>(info_.width) * info_.height;
-    taa_have = false;
-    void** bufs[] = {&d_rgb, &d_depth, &d_acc, &d_hist[0][0], &d_hist[0][1], &d_hist[0][2], &d_hist[1][0], &d_hist[1][1], &d_hist[1][2]};
-    const size_t bytes[] = {n * 12, n * 4, n * 4, n * 12, n * 4, n, n * 12, n * 4, n};
-    for (int k = 0; k < 9; ++k) {
-      if (*bufs[k] && adanerf_free(ctx, *bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-      *bufs[k] = nullptr;
-      if (adanerf_malloc(ctx, bytes[k], bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-    }
-    if (adanerf_set_aux_outputs(ctx, static_cast<float*>(d_depth), static_cast<float*>(d_acc)) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-  }
-  if (settings.taau_scale > 0) {      // the render-size frame and aux outputs; the history and the shown frame at S w x S h
-    const size_t n = static_cast<size_t>(info_.width) * info_.height, N = n * settings.taau_scale * settings.taau_scale;
-    taa_have = false;
-    void** bufs[] = {&d_rgb, &d_depth, &d_acc, &d_hist[0][0], &d_hist[0][1], &d_hist[0][2], &d_hist[1][0], &d_hist[1][1], &d_hist[1][2], &d_up};
-    const size_t bytes[] = {n * 12, n * 4, n * 4, N * 12, N * 4, N, N * 12, N * 4, N, N * 4};
-    for (int k = 0; k < 10; ++k) {
-      if (*bufs[k] && adanerf_free(ctx, *bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-      *bufs[k] = nullptr;
-      if (adanerf_malloc(ctx, bytes[k], bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-    }
-    if (adanerf_set_aux_outputs(ctx, static_cast<float*>(d_depth), static_cast<float*>(d_acc)) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-  }
-  if (!settings.density_stride.empty()) {      // the mask and the fp32 frame belong to the frame size
-    const size_t n = static_cast<size_t>(info_.width) * info_.height;
-    fovea_pending = true;
-    void** bufs[] = {&d_rgb, &d_dmask};
-    const size_t bytes[] = {n * 12, n};
-    for (int k = 0; k < 2; ++k) {
-      if (*bufs[k] && adanerf_free(ctx, *bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-      *bufs[k] = nullptr;
-      if (adanerf_malloc(ctx, bytes[k], bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-    }
-    if (settings.fovea_temporal_alpha > 0.f) {      // the aux outputs and the history belong to the frame size too
-      taa_have = false;
-      void** more[] = {&d_depth, &d_acc, &d_hist[0][0], &d_hist[0][1], &d_hist[0][2], &d_hist[1][0], &d_hist[1][1], &d_hist[1][2]};
-      const size_t more_bytes[] = {n * 4, n * 4, n * 12, n * 4, n, n * 12, n * 4, n};
-      for (int k = 0; k < 8; ++k) {
-        if (*more[k] && adanerf_free(ctx, *more[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-        *more[k] = nullptr;
-        if (adanerf_malloc(ctx, more_bytes[k], more[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-      }
-      if (adanerf_set_aux_outputs(ctx, static_cast<float*>(d_depth), static_cast<float*>(d_acc)) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-    }
-  }
-  if (settings.supersample > 1) {
-    for (void** p : {&d_rgb, &d_sum}) {
-      if (*p && adanerf_free(ctx, *p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-      *p = nullptr;
-      if (adanerf_malloc(ctx, static_cast<size_t>(info_.width) * info_.height * 3 * sizeof(float), p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-    }
-    if (settings.supersample_contrast >= 0.f) {      // the staging image and the mask belong to the frame size too
-      const size_t n = static_cast<size_t>(info_.width) * info_.height;
-      void** bufs[] = {&d_stage, &d_cmask};
-      const size_t bytes[] = {n * 12, n};
-      for (int k = 0; k < 2; ++k) {
-        if (*bufs[k] && adanerf_free(ctx, *bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-        *bufs[k] = nullptr;
-        if (adanerf_malloc(ctx, bytes[k], bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-      }
-    }
-  }
-  if (!settings.occluders.empty()) {      // the limit and the acc map belong to the frame size: the library drops them when rays_local changes
-    const size_t n = static_cast<size_t>(info_.width) * info_.height;
-    occ_have = false;
-    void** bufs[] = {&d_rgb, &d_acc, &d_limit, &d_behind};
-    const size_t bytes[] = {n * 12, n * 4, n * 4, n * 12};
-    for (int k = 0; k < 4; ++k) {
-      if (*bufs[k] && adanerf_free(ctx, *bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-      *bufs[k] = nullptr;
-      if (adanerf_malloc(ctx, bytes[k], bufs[k]) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-    }
-    if (adanerf_set_aux_outputs(ctx, nullptr, static_cast<float*>(d_acc)) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-  }
-  if (settings.reproject > 1) {      // the aux outputs belong to the frame size: the library drops them when rays_local changes
-    const size_t n = static_cast<size_t>(info_.width) * info_.height;
-    have_source = false;
-    for (void** p : {&d_depth, &d_acc, &d_warp, &d_wmask}) {      // (the mask is a byte per pixel: a quarter of its allocation)
-      if (*p && adanerf_free(ctx, *p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-      *p = nullptr;
-      if (adanerf_malloc(ctx, n * 4, p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-    }
-    if (settings.reproject_gather) {
-      for (void** p : {&d_src_rgb, &d_warp_rgb}) {
-        if (*p && adanerf_free(ctx, *p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-        *p = nullptr;
-        if (adanerf_malloc(ctx, n * 12, p) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-      }
-    }
-    if (adanerf_set_aux_outputs(ctx, static_cast<float*>(d_depth), static_cast<float*>(d_acc)) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
-  }
+  if (resets & RESET_SOURCE) have_source = false;
+  if (resets & RESET_HISTORY) history.reset();
+  if (resets & RESET_OCCLUDER) occ_have = false;
+  if (resets & RESET_FOVEA) fovea_pending = true;
+  // the aux outputs belong to the frame size (the library drops them when rays_local changes): the depth and acc maps of the temporal and
+  // reprojection stages, the acc map alone under --occluder
+  float* const aux_depth = settings.occluders.empty() ? static_cast<float*>(d_depth) : nullptr;
+  if (d_acc && adanerf_set_aux_outputs(ctx, aux_depth, static_cast<float*>(d_acc)) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
   if (world_ > 1) {
     const size_t payload = static_cast<size_t>(info_.rays_local_max) * 4;
     if (d_gathered && adanerf_free(ctx, d_gathered) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
@@ -333,9 +286,7 @@ bool NeuralRenderer::applyFrameSize() {
             std::to_string(strip_rows_) + " rows over " + std::to_string(world_) + " shares";
       return false;
     }
-    std::vector<adanerf_ctx*> all(1, ctx);
-    all.insert(all.end(), peers.begin(), peers.end());
-    for (adanerf_ctx* c : all)
+    for (adanerf_ctx* c : contexts())
       if (adanerf_set_frame_size(c, w, h) != ADANERF_OK) return err = adanerf_last_error(c), false;
     adanerf_get_info(ctx, &info_);
     if (!allocFrameBuffers()) return false;
@@ -357,8 +308,7 @@ bool NeuralRenderer::applyFovea() {
     gaze_x = 0.5f * static_cast<float>(info_.width);
     gaze_y = 0.5f * static_cast<float>(info_.height);
   }
-  std::vector<adanerf_ctx*> all(1, ctx);
-  all.insert(all.end(), peers.begin(), peers.end());
+  const std::vector<adanerf_ctx*> all = contexts();
   d_fovea_n.resize(all.size(), nullptr);
   d_fovea_thr.resize(all.size(), nullptr);
   for (size_t i = 0; i < all.size(); ++i) {
@@ -416,32 +366,35 @@ bool NeuralRenderer::renderFoveatedTemporal(adanerf_stats* st, const float rot[9
   adanerf_host_density_phase(ft_k, &px, &py);
   ft_k = (ft_k + 1) % 64;
   const uint8_t* mask = static_cast<const uint8_t*>(d_dmask);
-  const int out = taa_have ? 1 - taa_side : 0;
-  void* const* hist = d_hist[taa_side];
-  const bool at_rest = taa_have && std::memcmp(prev_pos, camera.getPosition(), sizeof(prev_pos)) == 0 && std::memcmp(prev_rot, rot, sizeof(prev_rot)) == 0;
+  const History::Inputs h = history.inputs(camera.getPosition(), rot);
   if (adanerf_foveate_density_phased(ctx, gaze_x, gaze_y, static_cast<int32_t>(settings.density_radius.size()), settings.density_radius.data(),
                                      settings.density_stride.data(), px, py, static_cast<uint8_t*>(d_dmask)) != ADANERF_OK ||
       adanerf_render_masked(ctx, mask, 1u, nullptr, static_cast<float*>(d_rgb), st, &m) != ADANERF_OK ||
       adanerf_fill_density_phased(ctx, mask, info_.width, info_.height, px, py, static_cast<float*>(d_rgb), static_cast<float*>(d_depth), static_cast<float*>(d_acc),
                                   nullptr, nullptr) != ADANERF_OK ||
       adanerf_temporal_resolve_sparse(ctx, mask, px, py, static_cast<const float*>(d_rgb), static_cast<const float*>(d_depth), static_cast<const float*>(d_acc),
-                                      camera.getPosition(), rot, taa_have ? static_cast<const float*>(hist[0]) : nullptr,
-                                      taa_have && !at_rest ? static_cast<const float*>(hist[1]) : nullptr,
-                                      taa_have ? static_cast<const uint8_t*>(hist[2]) : nullptr, prev_pos, prev_rot, settings.fovea_temporal_alpha, 0.02f, 0.5f,
-                                      ADANERF_TEMPORAL_CLAMP, static_cast<float*>(d_hist[out][0]), static_cast<float*>(d_hist[out][1]),
-                                      static_cast<uint8_t*>(d_hist[out][2]), d_frame, nullptr, &rejected) != ADANERF_OK) {
+                                      camera.getPosition(), rot, h.rgb, h.depth, h.count, h.prev_pos, h.prev_rot, settings.fovea_temporal_alpha, 0.02f, 0.5f,
+                                      ADANERF_TEMPORAL_CLAMP, h.out_rgb, h.out_depth, h.out_count, d_frame, nullptr, &rejected) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;
   }
-  std::memcpy(prev_pos, camera.getPosition(), sizeof(prev_pos));
-  std::memcpy(prev_rot, rot, sizeof(prev_rot));
-  taa_side = out;
-  taa_have = true;
+  history.commit(camera.getPosition(), rot);
   s_rejected += rejected;
   s_density_rendered += m;
   if (settings.log_camera)
     std::printf("foveated %d phase %d %d rendered %d of %u rejected %d\n", sample_count, static_cast<int>(px), static_cast<int>(py), static_cast<int>(m),
                 settings.total_size, static_cast<int>(rejected));
+  return true;
+}
+
+// a setting every context (--gpus / --sub-shares) gets before this frame.  It shows from this frame on: render it instead of warping the
+// source frame, and --taa does not blend it with frames of the old setting.
+template <class Set>
+bool NeuralRenderer::applyToAll(Set set) {
+  for (adanerf_ctx* c : contexts())
+    if (set(c) != ADANERF_OK) return err = adanerf_last_error(c), false;
+  have_source = false;
+  history.reset();
   return true;
 }
 
@@ -451,31 +404,15 @@ bool NeuralRenderer::render() {
   if (!applyFrameSize()) return false;
   if (selection_pending) {      // script tokens "n" / "thr": every context (--gpus / --sub-shares) gets the same pair before this frame
     selection_pending = false;
-    std::vector<adanerf_ctx*> all(1, ctx);
-    all.insert(all.end(), peers.begin(), peers.end());
-    for (adanerf_ctx* c : all)
-      if (adanerf_set_selection(c, want_samples, want_threshold) != ADANERF_OK) {
-        err = adanerf_last_error(c);
-        return false;
-      }
+    if (!applyToAll([&](adanerf_ctx* c) { return adanerf_set_selection(c, want_samples, want_threshold); })) return false;
     want_samples = 0;
     want_threshold = -1.f;
     adanerf_get_info(ctx, &info_);
-    have_source = false;      // a new selection shows from this frame on: render it
-    taa_have = false;         // and --taa does not blend it with frames of the old one
   }
   if (cap_pending) {      // --sample-cap / script token "cap": every context (--gpus / --sub-shares) gets the same bound before this frame
     cap_pending = false;
-    std::vector<adanerf_ctx*> all(1, ctx);
-    all.insert(all.end(), peers.begin(), peers.end());
-    for (adanerf_ctx* c : all)
-      if (adanerf_set_sample_cap(c, want_cap) != ADANERF_OK) {
-        err = adanerf_last_error(c);
-        return false;
-      }
+    if (!applyToAll([&](adanerf_ctx* c) { return adanerf_set_sample_cap(c, want_cap); })) return false;
     cap_in_force = want_cap;
-    have_source = false;      // the bound shows from this frame on: render it
-    taa_have = false;
   }
   if (!applyFovea()) return false;
   if (!applyFoveaDensity()) return false;
@@ -490,7 +427,7 @@ bool NeuralRenderer::render() {
     }
     sample_count++;
     have_source = false;      // the debug view has no depth to warp
-    taa_have = false;         // nor is it a frame --taa may blend with
+    history.reset();          // nor is it a frame --taa may blend with
     d_shown = d_frame;
     return writeImageToFile();
   }
@@ -585,19 +522,31 @@ bool NeuralRenderer::render() {
   return writeImageToFile();
 }
 
+// One render with the rays through (dx, dy) of their pixels.  The offset goes back to (0, 0) whatever happened; err is the first failure's.
+template <class Render>
+bool NeuralRenderer::renderAtOffset(float dx, float dy, Render render) {
+  const bool ok = adanerf_set_pixel_offset(ctx, dx, dy) == ADANERF_OK && render();
+  if (!ok) err = adanerf_last_error(ctx);      // before the offset goes back: that call succeeds and would not touch the message anyway
+  const bool back = adanerf_set_pixel_offset(ctx, 0.f, 0.f) == ADANERF_OK;
+  if (ok && !back) err = adanerf_last_error(ctx);
+  return ok && back;
+}
+
 // --supersample S: S x S renders of this frame's camera at the offsets of the regular sub-pixel grid, summed on the device; d_frame gets
-// the mean under the viewer's output contract.  The offset goes back to (0, 0).
+// the mean under the viewer's output contract.
 bool NeuralRenderer::renderSupersampled(adanerf_stats* st) {
   if (settings.supersample_contrast >= 0.f) return renderSupersampledAdaptive(st);
   const int S = settings.supersample, renders = S * S, n = info_.width * info_.height;
-  bool ok = true;
-  for (int k = 0; ok && k < renders; ++k) {
+  for (int k = 0; k < renders; ++k) {
     float dx = 0.f, dy = 0.f;
     adanerf_stats sk;
     std::memset(&sk, 0, sizeof(sk));
-    ok = adanerf_host_subpixel_grid(S, k, &dx, &dy) == ADANERF_OK && adanerf_set_pixel_offset(ctx, dx, dy) == ADANERF_OK &&
-         adanerf_render(ctx, nullptr, static_cast<float*>(d_rgb), &sk) == ADANERF_OK &&
-         adanerf_accumulate(ctx, static_cast<const float*>(d_rgb), n, static_cast<float*>(d_sum), k == 0) == ADANERF_OK;
+    if (adanerf_host_subpixel_grid(S, k, &dx, &dy) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+    if (!renderAtOffset(dx, dy, [&] {
+          return adanerf_render(ctx, nullptr, static_cast<float*>(d_rgb), &sk) == ADANERF_OK &&
+                 adanerf_accumulate(ctx, static_cast<const float*>(d_rgb), n, static_cast<float*>(d_sum), k == 0) == ADANERF_OK;
+        }))
+      return false;
     const int64_t samples = st->total_samples + sk.total_samples;
     const float ms[5] = {st->ms_total + sk.ms_total, st->ms_sample_mlp + sk.ms_sample_mlp, st->ms_compact + sk.ms_compact, st->ms_shade_mlp + sk.ms_shade_mlp,
                          st->ms_composite + sk.ms_composite};
@@ -609,11 +558,8 @@ bool NeuralRenderer::renderSupersampled(adanerf_stats* st) {
     st->ms_shade_mlp = ms[3];
     st->ms_composite = ms[4];
   }
-  if (!ok) err = adanerf_last_error(ctx);      // before the offset goes back: that call succeeds and would not touch the message anyway
-  const bool back = adanerf_set_pixel_offset(ctx, 0.f, 0.f) == ADANERF_OK;
-  if (!ok) return false;
   st->total_samples /= renders;      // per rendered frame, as the log's "avg samples ppx" counts
-  if (!back || adanerf_resolve_mean(ctx, static_cast<const float*>(d_sum), n, renders, d_frame, nullptr) != ADANERF_OK || adanerf_sync(ctx) != ADANERF_OK) {
+  if (adanerf_resolve_mean(ctx, static_cast<const float*>(d_sum), n, renders, d_frame, nullptr) != ADANERF_OK || adanerf_sync(ctx) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;
   }
@@ -624,32 +570,35 @@ bool NeuralRenderer::renderSupersampled(adanerf_stats* st) {
 // flagged -- the S x S renders of the grid for the flagged pixels alone, summed and averaged over the centre frame.  A flagged pixel carries
 // the bytes of --supersample S, every other the bytes of a plain render.  No aux or disparity map is installed on this path (--supersample
 // refuses every option that installs one), so there is none to switch off for the masked passes.  *st: the centre frame's record, the
-// stage times summed over all passes.  The offset goes back to (0, 0).
+// stage times summed over all passes.
 bool NeuralRenderer::renderSupersampledAdaptive(adanerf_stats* st) {
   const int S = settings.supersample, renders = S * S, w = info_.width, h = info_.height, n = w * h;
   const uint8_t* mask = static_cast<const uint8_t*>(d_cmask);
   float *rgb = static_cast<float*>(d_rgb), *stage = static_cast<float*>(d_stage), *sum = static_cast<float*>(d_sum);
   int32_t flagged = 0;
-  bool ok = adanerf_set_pixel_offset(ctx, 0.f, 0.f) == ADANERF_OK && adanerf_render(ctx, d_frame, rgb, st) == ADANERF_OK &&
-            adanerf_contrast_mask(ctx, rgb, w, h, settings.supersample_contrast, static_cast<uint8_t*>(d_cmask), &flagged) == ADANERF_OK;
-  for (int k = 0; ok && flagged > 0 && k < renders; ++k) {
+  if (!renderAtOffset(0.f, 0.f, [&] {
+        return adanerf_render(ctx, d_frame, rgb, st) == ADANERF_OK &&
+               adanerf_contrast_mask(ctx, rgb, w, h, settings.supersample_contrast, static_cast<uint8_t*>(d_cmask), &flagged) == ADANERF_OK;
+      }))
+    return false;
+  for (int k = 0; flagged > 0 && k < renders; ++k) {
     float dx = 0.f, dy = 0.f;
     int32_t m = 0;
     adanerf_stats sk;
     std::memset(&sk, 0, sizeof(sk));
-    ok = adanerf_host_subpixel_grid(S, k, &dx, &dy) == ADANERF_OK && adanerf_set_pixel_offset(ctx, dx, dy) == ADANERF_OK &&
-         adanerf_render_masked(ctx, mask, 1u, nullptr, stage, &sk, &m) == ADANERF_OK &&
-         adanerf_accumulate_masked(ctx, stage, mask, 1u, n, sum, k == 0) == ADANERF_OK;
+    if (adanerf_host_subpixel_grid(S, k, &dx, &dy) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+    if (!renderAtOffset(dx, dy, [&] {
+          return adanerf_render_masked(ctx, mask, 1u, nullptr, stage, &sk, &m) == ADANERF_OK &&
+                 adanerf_accumulate_masked(ctx, stage, mask, 1u, n, sum, k == 0) == ADANERF_OK;
+        }))
+      return false;
     st->ms_total += sk.ms_total;
     st->ms_sample_mlp += sk.ms_sample_mlp;
     st->ms_compact += sk.ms_compact;
     st->ms_shade_mlp += sk.ms_shade_mlp;
     st->ms_composite += sk.ms_composite;
   }
-  if (!ok) err = adanerf_last_error(ctx);      // before the offset goes back: that call succeeds and would not touch the message anyway
-  const bool back = adanerf_set_pixel_offset(ctx, 0.f, 0.f) == ADANERF_OK;
-  if (!ok) return false;
-  if (!back || (flagged > 0 && adanerf_resolve_mean_masked(ctx, sum, mask, 1u, n, renders, d_frame, rgb) != ADANERF_OK) || adanerf_sync(ctx) != ADANERF_OK) {
+  if ((flagged > 0 && adanerf_resolve_mean_masked(ctx, sum, mask, 1u, n, renders, d_frame, rgb) != ADANERF_OK) || adanerf_sync(ctx) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;
   }
@@ -698,69 +647,47 @@ bool NeuralRenderer::renderHybrid(adanerf_stats* st, const float rot[9]) {
   return true;
 }
 
-// --taa: one render of this frame's camera at the next offset of the sub-pixel cycle, then adanerf_temporal_resolve against the history
-// (clamp on), which the result replaces; d_frame gets the resolved frame under the viewer's output contract.  The offset goes back to (0, 0).
-// The history's depth is tested only when the pose differs from the history's.
-bool NeuralRenderer::renderTemporal(adanerf_stats* st, const float rot[9]) {
-  const int S = settings.taa_grid;
-  float dx = 0.f, dy = 0.f;
-  const bool ok = adanerf_host_subpixel_grid(S, taa_k % (S * S), &dx, &dy) == ADANERF_OK && adanerf_set_pixel_offset(ctx, dx, dy) == ADANERF_OK &&
-                  adanerf_render(ctx, nullptr, static_cast<float*>(d_rgb), st) == ADANERF_OK;
-  if (!ok) err = adanerf_last_error(ctx);
-  const bool back = adanerf_set_pixel_offset(ctx, 0.f, 0.f) == ADANERF_OK;
-  if (!ok) return false;
+// --taa / --taau: one render of this frame's camera into d_rgb at the next offset (*dx, *dy) of the S x S sub-pixel cycle
+bool NeuralRenderer::renderJittered(int S, adanerf_stats* st, float* dx, float* dy) {
+  if (adanerf_host_subpixel_grid(S, taa_k % (S * S), dx, dy) != ADANERF_OK) return err = adanerf_last_error(ctx), false;
+  if (!renderAtOffset(*dx, *dy, [&] { return adanerf_render(ctx, nullptr, static_cast<float*>(d_rgb), st) == ADANERF_OK; })) return false;
   taa_k = (taa_k + 1) % (S * S);
-  const int out = taa_have ? 1 - taa_side : 0;
-  void* const* hist = d_hist[taa_side];
-  // the camera has not moved since the history was written: nothing can have been uncovered, so no disocclusion test (as renderer.py)
-  const bool at_rest = taa_have && std::memcmp(prev_pos, camera.getPosition(), sizeof(prev_pos)) == 0 && std::memcmp(prev_rot, rot, sizeof(prev_rot)) == 0;
+  return true;
+}
+
+// --taa: one jittered render, then adanerf_temporal_resolve against the history (clamp on), which the result replaces; d_frame gets the
+// resolved frame under the viewer's output contract.  The history's depth is tested only when the pose differs from the history's.
+bool NeuralRenderer::renderTemporal(adanerf_stats* st, const float rot[9]) {
+  float dx = 0.f, dy = 0.f;
+  if (!renderJittered(settings.taa_grid, st, &dx, &dy)) return false;
+  const History::Inputs h = history.inputs(camera.getPosition(), rot);
   int32_t rejected = 0;
-  if (!back || adanerf_temporal_resolve(ctx, static_cast<const float*>(d_rgb), static_cast<const float*>(d_depth), static_cast<const float*>(d_acc),
-                                        camera.getPosition(), rot, taa_have ? static_cast<const float*>(hist[0]) : nullptr,
-                                        taa_have && !at_rest ? static_cast<const float*>(hist[1]) : nullptr, taa_have ? static_cast<const uint8_t*>(hist[2]) : nullptr,
-                                        prev_pos, prev_rot, settings.taa_alpha, settings.taa_tol, 0.5f, ADANERF_TEMPORAL_CLAMP,
-                                        static_cast<float*>(d_hist[out][0]), static_cast<float*>(d_hist[out][1]), static_cast<uint8_t*>(d_hist[out][2]),
-                                        d_frame, nullptr, &rejected) != ADANERF_OK) {
+  if (adanerf_temporal_resolve(ctx, static_cast<const float*>(d_rgb), static_cast<const float*>(d_depth), static_cast<const float*>(d_acc), camera.getPosition(), rot,
+                               h.rgb, h.depth, h.count, h.prev_pos, h.prev_rot, settings.taa_alpha, settings.taa_tol, 0.5f, ADANERF_TEMPORAL_CLAMP, h.out_rgb,
+                               h.out_depth, h.out_count, d_frame, nullptr, &rejected) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;
   }
-  std::memcpy(prev_pos, camera.getPosition(), sizeof(prev_pos));
-  std::memcpy(prev_rot, rot, sizeof(prev_rot));
-  taa_side = out;
-  taa_have = true;
+  history.commit(camera.getPosition(), rot);
   s_rejected += rejected;
   return true;
 }
 
-// --taau S: one render of this frame's camera at the next offset of the S x S cycle, then adanerf_temporal_upsample (clamp on) into the
-// history of S w x S h, which the result replaces; d_up gets the upsampled frame under the viewer's output contract.  The offset goes back
-// to (0, 0).  The history's depth is tested only when the pose differs from the history's.
+// --taau S: one jittered render, then adanerf_temporal_upsample (clamp on) into the history of S w x S h, which the result replaces; d_up
+// gets the upsampled frame under the viewer's output contract.  The history's depth is tested only when the pose differs from the history's.
 bool NeuralRenderer::renderUpsampled(adanerf_stats* st, const float rot[9]) {
   const int S = settings.taau_scale;
   float dx = 0.f, dy = 0.f;
-  const bool ok = adanerf_host_subpixel_grid(S, taa_k % (S * S), &dx, &dy) == ADANERF_OK && adanerf_set_pixel_offset(ctx, dx, dy) == ADANERF_OK &&
-                  adanerf_render(ctx, nullptr, static_cast<float*>(d_rgb), st) == ADANERF_OK;
-  if (!ok) err = adanerf_last_error(ctx);
-  const bool back = adanerf_set_pixel_offset(ctx, 0.f, 0.f) == ADANERF_OK;
-  if (!ok) return false;
-  taa_k = (taa_k + 1) % (S * S);
-  const int out = taa_have ? 1 - taa_side : 0;
-  void* const* hist = d_hist[taa_side];
-  const bool at_rest = taa_have && std::memcmp(prev_pos, camera.getPosition(), sizeof(prev_pos)) == 0 && std::memcmp(prev_rot, rot, sizeof(prev_rot)) == 0;
+  if (!renderJittered(S, st, &dx, &dy)) return false;
+  const History::Inputs h = history.inputs(camera.getPosition(), rot);
   int32_t rejected = 0;
-  if (!back || adanerf_temporal_upsample(ctx, S, static_cast<const float*>(d_rgb), static_cast<const float*>(d_depth), static_cast<const float*>(d_acc), dx, dy,
-                                         camera.getPosition(), rot, taa_have ? static_cast<const float*>(hist[0]) : nullptr,
-                                         taa_have && !at_rest ? static_cast<const float*>(hist[1]) : nullptr,
-                                         taa_have ? static_cast<const uint8_t*>(hist[2]) : nullptr, prev_pos, prev_rot, settings.taau_alpha, settings.taau_tol,
-                                         0.5f, ADANERF_TEMPORAL_CLAMP, static_cast<float*>(d_hist[out][0]), static_cast<float*>(d_hist[out][1]),
-                                         static_cast<uint8_t*>(d_hist[out][2]), d_up, nullptr, &rejected) != ADANERF_OK) {
+  if (adanerf_temporal_upsample(ctx, S, static_cast<const float*>(d_rgb), static_cast<const float*>(d_depth), static_cast<const float*>(d_acc), dx, dy,
+                                camera.getPosition(), rot, h.rgb, h.depth, h.count, h.prev_pos, h.prev_rot, settings.taau_alpha, settings.taau_tol, 0.5f,
+                                ADANERF_TEMPORAL_CLAMP, h.out_rgb, h.out_depth, h.out_count, d_up, nullptr, &rejected) != ADANERF_OK) {
     err = adanerf_last_error(ctx);
     return false;
   }
-  std::memcpy(prev_pos, camera.getPosition(), sizeof(prev_pos));
-  std::memcpy(prev_rot, rot, sizeof(prev_rot));
-  taa_side = out;
-  taa_have = true;
+  history.commit(camera.getPosition(), rot);
   s_rejected += rejected;
   return true;
 }

@@ -2,12 +2,46 @@
 // C ABI of libadanerf_hip.so.  Owns the device framebuffer the viewer's BufferManager would own.
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
 #include "../../include/adanerf_hip.h"
 #include "camera.h"
 #include "settings.h"
+
+// The resolved frames a temporal stage blends with (--taa, --taau, --fovea-temporal; one of them at a time): two sets (rgb float [n*3],
+// depth float [n], count uint8 [n]) that ping-pong, which one was written last and at which pose.
+struct History {
+  void* set[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+  bool have = false;                 // set[side], pos and rot describe a resolved frame of the size in force
+  int side = 0;
+  float pos[3] = {0, 0, 0}, rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  struct Inputs {
+    const float *rgb, *depth;        // the history, or null without one; depth null at rest too
+    const uint8_t* count;
+    const float *prev_pos, *prev_rot;
+    float *out_rgb, *out_depth;      // the set the resolve writes
+    uint8_t* out_count;
+  };
+  int out() const { return have ? 1 - side : 0; }
+  // what a resolve at (pos, rot) reads and writes.  The camera has not moved since the history was written: nothing can have been
+  // uncovered, so no disocclusion test (as renderer.py)
+  Inputs inputs(const float at_pos[3], const float at_rot[9]) const {
+    const bool at_rest = have && std::memcmp(pos, at_pos, sizeof(pos)) == 0 && std::memcmp(rot, at_rot, sizeof(rot)) == 0;
+    void* const* h = set[side];
+    void* const* o = set[out()];
+    return {have ? static_cast<const float*>(h[0]) : nullptr, have && !at_rest ? static_cast<const float*>(h[1]) : nullptr,
+            have ? static_cast<const uint8_t*>(h[2]) : nullptr, pos, rot, static_cast<float*>(o[0]), static_cast<float*>(o[1]), static_cast<uint8_t*>(o[2])};
+  }
+  void commit(const float at_pos[3], const float at_rot[9]) {      // after a successful resolve at (pos, rot)
+    side = out();
+    have = true;
+    std::memcpy(pos, at_pos, sizeof(pos));
+    std::memcpy(rot, at_rot, sizeof(rot));
+  }
+  void reset() { have = false; }     // the next frame is a first frame
+};
 
 class NeuralRenderer {
  public:
@@ -63,7 +97,7 @@ class NeuralRenderer {
     return fovea_pending;
   }
   // --taa / --taau: the next frame is shown as rendered and starts a new history (script token "cut"); without them nothing to drop
-  void cutHistory() { taa_have = false; }
+  void cutHistory() { history.reset(); }
   bool applyFrameSize();             // a pending setFrameSize, now: render() calls it; --dry-run calls it in render()'s place (host only)
   int batchesPerFrame() const;       // ceil(rays / batch_rays)
   bool writeImageToFile();           // out.bmp in the model directory (neuralrenderer.cpp:184-222); --write-window: out_window.bmp too
@@ -75,6 +109,13 @@ class NeuralRenderer {
   Camera& camera;
   adanerf_ctx* ctx = nullptr;        // rank 0: display GPU, owns the frame
   std::vector<adanerf_ctx*> peers;   // ranks 1 .. N-1 (--gpus N), one per GPU, same process
+  std::vector<adanerf_ctx*> contexts() const {      // rank 0, then the peers
+    std::vector<adanerf_ctx*> all(1, ctx);
+    all.insert(all.end(), peers.begin(), peers.end());
+    return all;
+  }
+  template <class Set>
+  bool applyToAll(Set set);          // set(context) on every context, then the source frame and the history are dropped: the change shows from this frame on
   std::vector<void*> d_payload;      // per rank: uchar4 [rays_local_max] on that rank's GPU
   void* d_gathered = nullptr;        // rank 0: uchar4 [N][rays_local_max]
   adanerf_info info_{};
@@ -105,16 +146,16 @@ class NeuralRenderer {
   void* d_cmask = nullptr;
   long long s_refined = 0;           // pixels refined in the running interval's frames
   bool renderSupersampledAdaptive(adanerf_stats* st);   // the centre frame into d_frame / d_rgb, then the S x S masked renders of its flagged pixels over it
-  // --taa: depth_map / acc_map (d_depth, d_acc) and the fp32 frame (d_rgb) of this frame's render; two history sets (rgb float [h*w*3], depth
-  // float [h*w], count uint8 [h*w]) that ping-pong, the pose of the one last written, the place in the offset cycle
-  void* d_hist[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-  bool taa_have = false;             // d_hist[taa_side] and prev_* describe a resolved frame of the size in force
-  int taa_side = 0, taa_k = 0;
-  float prev_pos[3] = {0, 0, 0}, prev_rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+  // --taa: depth_map / acc_map (d_depth, d_acc) and the fp32 frame (d_rgb) of this frame's render; the history, the place in the offset cycle
+  History history;
+  int taa_k = 0;
   long long s_rejected = 0;          // rejected pixels of the running interval's frames
+  template <class Render>
+  bool renderAtOffset(float dx, float dy, Render render);   // render() with the rays through (dx, dy) of their pixels; the offset goes back to (0, 0) whatever happened
+  bool renderJittered(int S, adanerf_stats* st, float* dx, float* dy);   // one render into d_rgb at the next offset of the S x S cycle
   bool renderTemporal(adanerf_stats* st, const float rot[9]);   // one render at the cycle's next offset, resolved against the history into d_frame
-  // --taau S: as --taa, with the two history sets and the shown frame d_up (uchar4) at S w x S h; the state above (taa_have, taa_side, taa_k,
-  // prev_*, s_rejected) is shared, the two being exclusive
+  // --taau S: as --taa, with the two history sets and the shown frame d_up (uchar4) at S w x S h; the state above (history, taa_k,
+  // s_rejected) is shared, the two being exclusive
   void* d_up = nullptr;
   bool renderUpsampled(adanerf_stats* st, const float rot[9]);   // one render at the cycle's next offset, resolved into the S w x S h history and d_up
   // --occluder: the limit (float [h*w]) and the colour behind it (float [h*w*3]) of the spheres at the pose and size they were last filled
@@ -130,13 +171,22 @@ class NeuralRenderer {
   long long s_density_rendered = 0;  // rays rendered in the running interval's frames
   bool applyFoveaDensity();          // the mask filled again: at start, after "gaze", after "size" (fovea_pending, shared with --fovea: the two are exclusive)
   bool renderFoveated(adanerf_stats* st);   // adanerf_render_masked over the lattice, adanerf_fill_density for the rest, into d_frame
-  // --fovea-temporal: the frame number of the phase cycle; the aux maps (d_depth, d_acc), the history sets and their state are --taa's
-  // (d_hist, taa_have, taa_side, prev_*, s_rejected: --fovea-density excludes --taa and --taau)
+  // --fovea-temporal: the frame number of the phase cycle; the aux maps (d_depth, d_acc), the history and the count are --taa's
+  // (history, s_rejected: --fovea-density excludes --taa and --taau)
   int ft_k = 0;
   bool renderFoveatedTemporal(adanerf_stats* st, const float rot[9]);   // phased mask, masked render, phased fill, sparse resolve into d_frame
   void* d_window = nullptr;          // --write-window: uchar4 [window_height*window_width], the frame as adanerf_present shows it
   int world_ = 1, strip_rows_ = 8;   // share layout chosen at init; a live context keeps its strip height
-  bool allocFrameBuffers();          // d_frame, d_gathered, d_payload for the size in info_ (again after a size change)
+  // a frame-sized device buffer of rank 0: its member, the bytes it needs under the settings and the size in force (0: not needed), and the
+  // state that describes its contents and so resets when it is made again
+  enum Resets { RESET_SOURCE = 1, RESET_HISTORY = 2, RESET_OCCLUDER = 4, RESET_FOVEA = 8 };
+  struct FrameBuffer {
+    void** p;
+    size_t bytes;
+    int resets;
+  };
+  std::vector<FrameBuffer> frameBuffers();
+  bool allocFrameBuffers();          // every buffer of frameBuffers(), d_gathered and d_payload for the size in info_ (again after a size change)
   bool writeBmp(const std::string& name, const void* d_image, int w, int h);
   std::string err;
   bool render_oracle = false;

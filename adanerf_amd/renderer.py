@@ -289,6 +289,79 @@ def _ptr(x):
     return int(x)
 
 
+def _pose_ptrs(*arrays):
+    """(pos, rot, pos, rot, ...) -> their C float pointers ([3] and [9] fp32, contiguous); None stays None.  A pointer keeps its array alive."""
+    f = [None if v is None else np.ascontiguousarray(v, dtype=np.float32).reshape(9 if i % 2 else 3) for i, v in enumerate(arrays)]
+    return [None if v is None else v.ctypes.data_as(C.POINTER(C.c_float)) for v in f]
+
+
+def _release(owner, arrays):
+    """Frees device arrays ``owner`` made with empty(): off its list, and ``_last_frame`` cleared if it showed one of them."""
+    for a in arrays:
+        if owner._last_frame is not None and owner._last_frame[0] is a:
+            owner._last_frame = None
+        a.free()
+        owner._own.remove(a)
+
+
+def _check_blend(who: str, alpha, depth_tol):
+    """alpha / depth_tol of a temporal stage as floats; ValueError outside (0, 1] / below 0 (a NaN fails both)."""
+    if not 0.0 < float(alpha) <= 1.0:
+        raise ValueError("%s: alpha must lie in (0, 1], got %r" % (who, alpha))
+    if not float(depth_tol) >= 0.0:
+        raise ValueError("%s: depth_tol must be >= 0, got %r" % (who, depth_tol))
+    return float(alpha), float(depth_tol)
+
+
+class _History:
+    """What a temporal stage keeps on the device between frames: two sets (rgb [n,3] fp32, depth [n] fp32, count [n] uint8) that ping-pong,
+    which one was written last and at which pose -- ``hist`` = (index into ``sets``, pos, rot), None without a history -- and the stage's
+    other buffers of the same pixel count, ``extras`` = ((attribute, columns, dtype), ...).  ``owner`` makes them (empty()) and lists them
+    (_own, _last_frame: see _release)."""
+
+    def __init__(self, owner, extras=()):
+        self.owner, self.extras = owner, tuple(extras)
+        self.n, self.sets, self.hist = None, [], None
+
+    def buffers(self):
+        return [] if self.n is None else [b for st in self.sets for b in st] + [getattr(self, name) for name, _, _ in self.extras]
+
+    def ensure(self, n: int):
+        """Everything for n pixels: made on first use and again, without a history, when n changes."""
+        if self.n == n:
+            return
+        _release(self.owner, self.buffers())
+        e = self.owner.empty
+        self.sets = [(e((n, 3), np.float32), e((n,), np.float32), e((n,), np.uint8)) for _ in range(2)]
+        for name, cols, dtype in self.extras:
+            setattr(self, name, e((n, cols) if cols > 1 else (n,), dtype))
+        self.n, self.hist = n, None
+
+    def _out(self) -> int:
+        return 0 if self.hist is None else 1 - self.hist[0]
+
+    def inputs(self, pose):
+        """For a resolve at ``pose`` = (pos, rot): (hist_rgb, hist_depth, hist_count, prev_pos, prev_rot, out_set), Nones without a
+        history.  The camera has not moved since the history was written: in a static scene nothing can have been uncovered, so there is
+        no disocclusion test (hist_depth None).  The test would compare the depths of two jittered renders of one pose, and where a pixel
+        spans several surfaces the jitter alone moves its depth past any tolerance: those pixels would restart their mean for nothing."""
+        out = self.sets[self._out()]
+        if self.hist is None:
+            return None, None, None, None, None, out
+        side, pos, rot = self.hist
+        rgb, depth, count = self.sets[side]
+        at_rest = np.array_equal(pos, pose[0]) and np.array_equal(rot, pose[1])
+        return rgb, None if at_rest else depth, count, pos, rot, out
+
+    def commit(self, pose):
+        """The resolve at ``pose`` has written inputs()'s out_set: it is the history now."""
+        self.hist = (self._out(), pose[0], pose[1])
+
+    def reset(self):
+        """A cut: the next frame has no history.  The buffers stay."""
+        self.hist = None
+
+
 FOVEA_MAX_RINGS = 8
 
 
@@ -525,11 +598,17 @@ class NeuralRenderer:
         self._rp_on = False           # enable_reprojection(): render_numpy keeps depth, acc and the pose of its frame
         self._rp_frame = None         # (device rgba8, depth, acc, pos, rot, rays) of the last render_numpy since then
         self._ta = None               # enable_temporal(): alpha, depth_tol, clamp, the cycle of sub-pixel offsets and the place in it
-        self._ta_hist = None          # (index of the history's buffer set, pos, rot) of the last render_temporal since then
+        self._ta_history = _History(self, [("mask", 1, np.uint8)])      # render_temporal's history and verdict mask
         self._tu = None               # enable_temporal_upsample(): scale, alpha, depth_tol, clamp, the offset cycle and the place in it
-        self._tu_hist = None          # (index of the history's buffer set, pos, rot) of the last render_upsampled since then
+        self._tu_history = _History(self, [("mask", 1, np.uint8), ("rgba", 4, np.uint8)])      # render_upsampled's, at the output size, and its 8-bit image
         self._ft = None               # enable_foveated_temporal(): alpha, depth_tol, clamp and the frame number k of the phase cycle
-        self._ft_hist = None          # (index of the history's buffer set, pos, rot) of the last render_foveated_temporal since then
+        # render_foveated_temporal's, and the density mask of the phase (render_foveated's own mask stays at phase (0, 0))
+        self._ft_history = _History(self, [("mask", 1, np.uint8), ("rgba", 4, np.uint8), ("dmask", 1, np.uint8)])
+        # device buffers of the renderer's own, made on first use by _buffers() and dropped by _drop_buffers(): render_numpy's outputs, the
+        # budget maps, the aux outputs and warp images of reproject(), the density mask, the depth limit, the sums and masks of the supersamplers
+        for name in ("_o_rgb", "_o_rgba", "_b_n", "_b_thr", "_rp_depth", "_rp_acc", "_rp_rgba", "_rp_mask", "_rp_rgb", "_rp_wrgb", "_fd_mask", "_dl_buf",
+                     "_hy_acc", "_hy_behind", "_hy_limit", "_ss_sum", "_sa_stage", "_sa_mask"):
+            setattr(self, name, None)
         self._dl_in_force = None      # what the last set_depth_limit installed; render_hybrid puts it back
         self._aux_in_force = (None, None)   # (depth_map, acc_map) of the last set_aux_outputs, likewise
         self._disp_in_force = None    # the disp_map of the last set_disp_output; render_supersampled_adaptive puts it back
@@ -581,6 +660,27 @@ class NeuralRenderer:
     def to_device(self, arr: np.ndarray) -> DeviceArray:
         return self.empty(arr.shape, arr.dtype).upload(arr)
 
+    def _buffers(self, *specs) -> bool:
+        """The renderer's own device buffers ``specs`` = (attribute, shape, dtype), ...: made on first use, and made again -- all of them,
+        and True returned -- when the shape of the first has changed."""
+        a = getattr(self, specs[0][0])
+        if a is not None and a.shape == specs[0][1]:
+            return False
+        self._drop_buffers(*[name for name, _, _ in specs])
+        for name, shape, dtype in specs:
+            setattr(self, name, self.empty(shape, dtype))
+        return True
+
+    def _drop_buffers(self, *names):
+        _release(self, [getattr(self, name) for name in names if getattr(self, name) is not None])
+        for name in names:
+            setattr(self, name, None)
+
+    def _out_buffers(self):
+        """``_o_rgb`` / ``_o_rgba``: the fp32 and 8-bit frame of the render size in force"""
+        n = self.info.rays_local
+        self._buffers(("_o_rgb", (n, 3), np.float32), ("_o_rgba", (n, 4), np.uint8))
+
     # -- per frame ---------------------------------------------------------------------------------
     def set_camera(self, pos, rot_c2w):
         p = np.ascontiguousarray(pos, dtype=np.float32).reshape(3)
@@ -610,40 +710,21 @@ class NeuralRenderer:
         if self.info.rays_local != was_rays:      # the library dropped the per-ray buffers of the old rays_local
             self._dl_in_force, self._aux_in_force, self._disp_in_force = None, (None, None), None
         self.settings.width, self.settings.height = self.info.width, self.info.height
-        if hasattr(self, "_b_n") and self._b_n.shape[0] != self.info.rays_local:      # the library dropped the maps with the old rays_local
-            self._drop_budget_buffers()
+        if self._b_n is not None and self._b_n.shape[0] != self.info.rays_local:      # the library dropped the maps with the old rays_local
+            self._drop_buffers("_b_n", "_b_thr")
         self._rp_frame = None      # a frame of the old size cannot be warped with the new size's ray generator
-        self._ta_hist = None       # nor can a history of the old size be gathered from
-        self._tu_hist = None
-        self._ft_hist = None
+        for history in (self._ta_history, self._tu_history, self._ft_history):      # nor can a history of the old size be gathered from
+            history.reset()
         self._fd = None            # the density mask is per frame size: foveate_density() fills it again
-        for name in ("_o_rgb", "_o_rgba"):
-            if hasattr(self, name):
-                a = getattr(self, name)
-                if self._last_frame is not None and self._last_frame[0] is a:
-                    self._last_frame = None
-                a.free()
-                self._own.remove(a)
-                delattr(self, name)
+        self._drop_buffers("_o_rgb", "_o_rgba")
         return self.info
 
     # -- per-ray sample budgets ----------------------------------------------------------------------
-    def _drop_budget_buffers(self):
-        for name in ("_b_n", "_b_thr"):
-            if hasattr(self, name):
-                a = getattr(self, name)
-                a.free()
-                self._own.remove(a)
-                delattr(self, name)
-
     def budget_buffers(self):
         """The renderer's own device maps ([rays_local] uint8 N, [rays_local] fp32 threshold), made on first use and again after a frame
         size that changes rays_local.  Fill them (upload, foveate_device) and install them with set_budget_map."""
         n = self.info.rays_local
-        if not hasattr(self, "_b_n") or self._b_n.shape[0] != n:
-            self._drop_budget_buffers()
-            self._b_n = self.empty((n,), np.uint8)
-            self._b_thr = self.empty((n,), np.float32)
+        self._buffers(("_b_n", (n,), np.uint8), ("_b_thr", (n,), np.float32))
         return self._b_n, self._b_thr
 
     def set_budget_map(self, n_map=None, thr_map=None):
@@ -720,12 +801,9 @@ class NeuralRenderer:
         if isinstance(rings, str):
             rings = parse_fovea_density(rings)
         n = self.info.width * self.info.height
-        if not hasattr(self, "_fd_mask") or self._fd_mask.shape[0] != n:
-            if hasattr(self, "_fd_mask"):
-                self.sync()      # a frame in flight still reads the mask
-                self._fd_mask.free()
-                self._own.remove(self._fd_mask)
-            self._fd_mask = self.empty((n,), np.uint8)
+        if self._fd_mask is not None and self._fd_mask.shape[0] != n:
+            self.sync()      # a frame in flight still reads the mask
+        self._buffers(("_fd_mask", (n,), np.uint8))
         self._fd = None
         self._check(self.foveate_density_device(gaze_xy, rings, self._fd_mask))
         self._fd = ((float(gaze_xy[0]), float(gaze_xy[1])), [tuple(r) for r in rings], self.info.width, self.info.height)
@@ -738,9 +816,7 @@ class NeuralRenderer:
         if self._fd is None or self._fd[2:] != (w, h):
             raise AdaNeRFError("render_foveated: no density mask for %d x %d (call foveate_density first, and again after set_frame_size)" % (w, h))
         n = self.info.rays_local
-        if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
-            self._o_rgb = self.empty((n, 3), np.float32)
-            self._o_rgba = self.empty((n, 4), np.uint8)
+        self._out_buffers()
         rendered, st = self.render_masked(self._fd_mask, 1, self._o_rgba, self._o_rgb)
         rc, _ = self.fill_density_device(self._fd_mask, w, h, self._o_rgb, self._aux_in_force[0], self._aux_in_force[1], self._o_rgba, count=False)
         self._check(rc)
@@ -775,8 +851,7 @@ class NeuralRenderer:
         (they keep the history they have).  out_count is required, and hist_count with a history.  out_mask: 1 the history was used, 2 it
         held only a placeholder, 0 rejected.  Returns the number of rejected pixels (synchronous); with rejected=False nothing is read
         back and the outputs are complete after sync()."""
-        f = [None if v is None else np.ascontiguousarray(v, dtype=np.float32).reshape(k) for v, k in ((cur_pos, 3), (cur_rot, 9), (prev_pos, 3), (prev_rot, 9))]
-        fp = [None if v is None else v.ctypes.data_as(C.POINTER(C.c_float)) for v in f]
+        fp = _pose_ptrs(cur_pos, cur_rot, prev_pos, prev_rot)
         n = C.c_int32(0)
         self._check(self.lib.adanerf_temporal_resolve_sparse(self.handle, _ptr(mask), int(phase_xy[0]), int(phase_xy[1]), _ptr(cur_rgb), _ptr(cur_depth),
                                                              _ptr(cur_acc), fp[0], fp[1], _ptr(hist_rgb), _ptr(hist_depth), _ptr(hist_count), fp[2], fp[3],
@@ -784,23 +859,6 @@ class NeuralRenderer:
                                                              _ptr(out_depth), _ptr(out_count), _ptr(out_rgba8), _ptr(out_mask),
                                                              C.byref(n) if rejected else None))
         return int(n.value) if rejected else None
-
-    def _foveated_temporal_buffers(self):
-        """two history sets (rgb, depth, count) to ping-pong, the verdict mask, the 8-bit image of the resolved frame and the density mask of
-        the phase (render_foveated's own mask stays at phase (0, 0)), made on first use
-        and again after a frame size that changes rays_local; the frame's depth_map / acc_map are the aux buffers reproject() uses too"""
-        n = self.info.rays_local
-        self._reproject_buffers()
-        if not hasattr(self, "_ft_sets") or self._ft_mask.shape[0] != n:
-            if hasattr(self, "_ft_sets"):
-                for a in [b for st in self._ft_sets for b in st] + [self._ft_mask, self._ft_rgba, self._ft_dmask]:
-                    if self._last_frame is not None and self._last_frame[0] is a:
-                        self._last_frame = None
-                    a.free()
-                    self._own.remove(a)
-            self._ft_sets = [(self.empty((n, 3), np.float32), self.empty((n,), np.float32), self.empty((n,), np.uint8)) for _ in range(2)]
-            self._ft_mask, self._ft_rgba, self._ft_dmask = self.empty((n,), np.uint8), self.empty((n, 4), np.uint8), self.empty((n,), np.uint8)
-            self._ft_hist = None
 
     def enable_foveated_temporal(self, alpha: float = 0.1, depth_tol: float = 0.02, clamp: bool = True):
         """Foveated density over time from now on through render_foveated_temporal(): the lattice of foveate_density() -- which must have
@@ -813,18 +871,15 @@ class NeuralRenderer:
             raise AdaNeRFError("foveated density over time needs a whole frame of a model without useNDC")
         if self._fd is None:
             raise AdaNeRFError("enable_foveated_temporal: call foveate_density first (it sets the gaze and the rings)")
-        if not 0.0 < float(alpha) <= 1.0:
-            raise ValueError("enable_foveated_temporal: alpha must lie in (0, 1], got %r" % (alpha,))
-        if not float(depth_tol) >= 0.0:
-            raise ValueError("enable_foveated_temporal: depth_tol must be >= 0, got %r" % (depth_tol,))
-        self._ft = dict(alpha=float(alpha), depth_tol=float(depth_tol), clamp=bool(clamp), k=0)
-        self._ft_hist = None
-        self._foveated_temporal_buffers()
+        alpha, depth_tol = _check_blend("enable_foveated_temporal", alpha, depth_tol)
+        self._ft = dict(alpha=alpha, depth_tol=depth_tol, clamp=bool(clamp), k=0)
+        self._temporal_buffers(self._ft_history, self.info.rays_local)
+        self._ft_history.reset()
 
     def reset_foveated_temporal(self):
         """Drops the history (a cut): the next render_foveated_temporal shows its frame as render_foveated would at that phase.  The
         phase cycle goes on."""
-        self._ft_hist = None
+        self._ft_history.reset()
 
     def render_foveated_temporal(self):
         """One frame at the camera of the last set_camera: frame k takes the phase density_phase(k), fills the mask of foveate_density()'s
@@ -834,38 +889,30 @@ class NeuralRenderer:
         where the history was used, 2 where it held only a placeholder; rejected counts mask 0 (every pixel on the first frame and after
         reset_foveated_temporal / set_frame_size).  While the pose is bit for bit the one of the call before, the history's depth is not
         tested (nothing is uncovered while the camera rests).  render_foveated() and its mask are untouched: the phased mask is a buffer
-        of this path's own (``_ft_dmask``).  present() shows the resolved frame."""
-        if getattr(self, "_ft", None) is None:
+        of this path's own (``_ft_history.dmask``).  present() shows the resolved frame."""
+        if self._ft is None:
             raise AdaNeRFError("render_foveated_temporal: call enable_foveated_temporal first")
         if self._pose is None:
             raise AdaNeRFError("render_foveated_temporal needs the pose of the frame: call set_camera first")
         w, h = self.info.width, self.info.height
         if self._fd is None or self._fd[2:] != (w, h):
             raise AdaNeRFError("render_foveated_temporal: no density mask for %d x %d (call foveate_density first, and again after set_frame_size)" % (w, h))
-        n = self.info.rays_local
-        self._foveated_temporal_buffers()
-        if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
-            self._o_rgb = self.empty((n, 3), np.float32)
-            self._o_rgba = self.empty((n, 4), np.uint8)
-        ft = self._ft
+        ft, hi = self._ft, self._ft_history
+        self._temporal_buffers(hi, self.info.rays_local)
         phase = density_phase(ft["k"])
         ft["k"] += 1
-        self._check(self.foveate_density_phased_device(self._fd[0], self._fd[1], phase, self._ft_dmask))
-        rendered, st = self.render_masked(self._ft_dmask, 1, None, self._o_rgb)
-        rc, _ = self.fill_density_phased_device(self._ft_dmask, w, h, phase, self._o_rgb, self._rp_depth, self._rp_acc, None, count=False)
+        self._check(self.foveate_density_phased_device(self._fd[0], self._fd[1], phase, hi.dmask))
+        rendered, st = self.render_masked(hi.dmask, 1, None, self._o_rgb)
+        rc, _ = self.fill_density_phased_device(hi.dmask, w, h, phase, self._o_rgb, self._rp_depth, self._rp_acc, None, count=False)
         self._check(rc)
-        side = 0 if self._ft_hist is None else 1 - self._ft_hist[0]
-        out = self._ft_sets[side]
-        hist = (None, None, None) if self._ft_hist is None else self._ft_sets[self._ft_hist[0]]
-        prev = (None, None) if self._ft_hist is None else self._ft_hist[1:]
-        at_rest = self._ft_hist is not None and np.array_equal(prev[0], self._pose[0]) and np.array_equal(prev[1], self._pose[1])
-        rejected = self.temporal_resolve_sparse_device(self._ft_dmask, phase, self._o_rgb, self._rp_depth, self._rp_acc, self._pose[0], self._pose[1], hist[0],
-                                                       None if at_rest else hist[1], hist[2], prev[0], prev[1], out[0], out[1], out[2], self._ft_rgba,
-                                                       self._ft_mask, alpha=ft["alpha"], depth_tol=ft["depth_tol"], clamp=ft["clamp"])
-        self._ft_hist = (side, self._pose[0], self._pose[1])
-        self._last_frame = (self._ft_rgba, w, h)
+        hist_rgb, hist_depth, hist_count, prev_pos, prev_rot, out = hi.inputs(self._pose)
+        rejected = self.temporal_resolve_sparse_device(hi.dmask, phase, self._o_rgb, self._rp_depth, self._rp_acc, self._pose[0], self._pose[1], hist_rgb,
+                                                       hist_depth, hist_count, prev_pos, prev_rot, out[0], out[1], out[2], hi.rgba, hi.mask,
+                                                       alpha=ft["alpha"], depth_tol=ft["depth_tol"], clamp=ft["clamp"])
+        hi.commit(self._pose)
+        self._last_frame = (hi.rgba, w, h)
         self._rp_frame = None      # the depth between the rendered pixels is interpolated, not the volume's own
-        return out[0].numpy(), self._ft_rgba.numpy(), self._ft_mask.numpy(), rejected, rendered, st
+        return out[0].numpy(), hi.rgba.numpy(), hi.mask.numpy(), rejected, rendered, st
 
     # -- hybrid rendering: depth limits, the rasterised colour behind --------------------------------------
     def set_depth_limit(self, limit_zc=None):
@@ -876,11 +923,7 @@ class NeuralRenderer:
             n = self.info.rays_local
             if limit_zc.size != n:
                 raise ValueError("set_depth_limit: %d entries for %d local rays" % (limit_zc.size, n))
-            if not hasattr(self, "_dl_buf") or self._dl_buf.shape[0] != n:
-                if hasattr(self, "_dl_buf"):
-                    self._dl_buf.free()
-                    self._own.remove(self._dl_buf)
-                self._dl_buf = self.empty((n,), np.float32)
+            self._buffers(("_dl_buf", (n,), np.float32))
             self.sync()      # frames in flight still read the buffer
             self._dl_buf.upload(limit_zc.reshape(-1).astype(np.float32, copy=False))
             limit_zc = self._dl_buf
@@ -903,19 +946,11 @@ class NeuralRenderer:
         behind = np.ascontiguousarray(behind_rgb, dtype=np.float32).reshape(-1)
         if behind.size != 3 * n:
             raise ValueError("render_hybrid: %d colour values for %d local rays" % (behind.size, n))
-        if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
-            self._o_rgb = self.empty((n, 3), np.float32)
-            self._o_rgba = self.empty((n, 4), np.uint8)
+        self._out_buffers()
         limit = np.ascontiguousarray(limit_zc, dtype=np.float32).reshape(-1)
         if limit.size != n:
             raise ValueError("render_hybrid: %d limits for %d local rays" % (limit.size, n))
-        if not hasattr(self, "_hy_acc") or self._hy_acc.shape[0] != n:
-            for name in ("_hy_acc", "_hy_behind", "_hy_limit"):
-                if hasattr(self, name):
-                    a = getattr(self, name)
-                    a.free()
-                    self._own.remove(a)
-            self._hy_acc, self._hy_behind, self._hy_limit = self.empty((n,), np.float32), self.empty((n, 3), np.float32), self.empty((n,), np.float32)
+        self._buffers(("_hy_acc", (n,), np.float32), ("_hy_behind", (n, 3), np.float32), ("_hy_limit", (n,), np.float32))
         was_limit, was_aux = self._dl_in_force, self._aux_in_force
         self.sync()      # frames in flight still read the buffers
         self._hy_behind.upload(behind)
@@ -964,14 +999,8 @@ class NeuralRenderer:
         that was in force is restored."""
         grid = subpixel_grid(s)
         n = self.info.rays_local
-        if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
-            self._o_rgb = self.empty((n, 3), np.float32)
-            self._o_rgba = self.empty((n, 4), np.uint8)
-        if not hasattr(self, "_ss_sum") or self._ss_sum.shape[0] != n:
-            if hasattr(self, "_ss_sum"):
-                self._ss_sum.free()
-                self._own.remove(self._ss_sum)
-            self._ss_sum = self.empty((n, 3), np.float32)
+        self._out_buffers()
+        self._buffers(("_ss_sum", (n, 3), np.float32))
         was = self.pixel_offset
         total = Stats()
         try:
@@ -1036,21 +1065,9 @@ class NeuralRenderer:
         n, w, h = self.info.rays_local, self.info.width, self.info.height
         if n != w * h:
             raise AdaNeRFError("render_supersampled_adaptive: whole frames only (shard_world must be 1): the contrast rule reads a pixel's neighbours")
-        if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
-            self._o_rgb = self.empty((n, 3), np.float32)
-            self._o_rgba = self.empty((n, 4), np.uint8)
-        if not hasattr(self, "_ss_sum") or self._ss_sum.shape[0] != n:
-            if hasattr(self, "_ss_sum"):
-                self._ss_sum.free()
-                self._own.remove(self._ss_sum)
-            self._ss_sum = self.empty((n, 3), np.float32)
-        if not hasattr(self, "_sa_stage") or self._sa_stage.shape[0] != n:
-            for name in ("_sa_stage", "_sa_mask"):
-                if hasattr(self, name):
-                    a = getattr(self, name)
-                    a.free()
-                    self._own.remove(a)
-            self._sa_stage, self._sa_mask = self.empty((n, 3), np.float32), self.empty((n,), np.uint8)
+        self._out_buffers()
+        self._buffers(("_ss_sum", (n, 3), np.float32))
+        self._buffers(("_sa_stage", (n, 3), np.float32), ("_sa_mask", (n,), np.uint8))
         was, was_aux, was_disp = self.pixel_offset, self._aux_in_force, self._disp_in_force
         try:
             self.set_pixel_offset(0.0, 0.0)
@@ -1126,9 +1143,7 @@ class NeuralRenderer:
         """Convenience for tests/tools: renders and returns (rgb fp32 [R,3], rgba8 [R,4], Stats).  The device copies stay in
         ``_o_rgb`` / ``_o_rgba`` until the next call (the evaluator scores the frame from there)."""
         n = self.info.rays_local
-        if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
-            self._o_rgb = self.empty((n, 3), np.float32)
-            self._o_rgba = self.empty((n, 4), np.uint8)
+        self._out_buffers()
         if self._rp_on:
             self._reproject_buffers()
         st = self.render(self._o_rgba, self._o_rgb, stats=True)
@@ -1144,15 +1159,8 @@ class NeuralRenderer:
         """the renderer's own aux outputs and warp destinations, made on first use and again after a frame size that changes rays_local
         (the library drops the aux outputs then); installed as the context's aux outputs"""
         n = self.info.rays_local
-        if not hasattr(self, "_rp_depth") or self._rp_depth.shape[0] != n:
-            for name in ("_rp_depth", "_rp_acc", "_rp_rgba", "_rp_mask", "_rp_rgb", "_rp_wrgb"):
-                if hasattr(self, name):
-                    a = getattr(self, name)
-                    a.free()
-                    self._own.remove(a)
-            self._rp_depth, self._rp_acc = self.empty((n,), np.float32), self.empty((n,), np.float32)
-            self._rp_rgba, self._rp_mask = self.empty((n, 4), np.uint8), self.empty((n,), np.uint8)
-            self._rp_rgb, self._rp_wrgb = self.empty((n, 3), np.float32), self.empty((n, 3), np.float32)      # the frame's fp32 colour; the gathered one
+        if self._buffers(("_rp_depth", (n,), np.float32), ("_rp_acc", (n,), np.float32), ("_rp_rgba", (n, 4), np.uint8), ("_rp_mask", (n,), np.uint8),
+                         ("_rp_rgb", (n, 3), np.float32), ("_rp_wrgb", (n, 3), np.float32)):      # ... the frame's fp32 colour; the gathered one
             self._rp_frame = None
             self.set_aux_outputs(self._rp_depth, self._rp_acc)
 
@@ -1171,8 +1179,7 @@ class NeuralRenderer:
         (src_pos, src_rot) warped to (dst_pos, dst_rot) into dst_rgba8 and, if given, dst_depth (fp32) / dst_mask (uint8: 1 a source
         pixel, 2 filled from a neighbour, 0 hole_rgba8).  Returns the number of holes (synchronous); with holes=False nothing is read
         back and the outputs are complete after sync()."""
-        f = [np.ascontiguousarray(v, dtype=np.float32).reshape(k) for v, k in ((src_pos, 3), (src_rot, 9), (dst_pos, 3), (dst_rot, 9))]
-        fp = [v.ctypes.data_as(C.POINTER(C.c_float)) for v in f]
+        fp = _pose_ptrs(src_pos, src_rot, dst_pos, dst_rot)
         n = C.c_int32(0)
         self._check(self.lib.adanerf_reproject(self.handle, _ptr(src_rgba8), _ptr(src_depth), _ptr(src_acc), fp[0], fp[1], fp[2], fp[3],
                                                float(acc_min), int(hole_rgba8) & 0xFFFFFFFF, REPROJECT_FILL if fill else 0, _ptr(dst_rgba8),
@@ -1214,8 +1221,7 @@ class NeuralRenderer:
         (src_pos, src_rot) gathered at (dst_pos, dst_rot) into dst_rgb (fp32) and, if given, dst_rgba8 (uchar4) / dst_depth (fp32) /
         dst_mask (uint8: 1 a verified source surface, 2 an unverified one (guess), 0 hole).  Returns the number of holes (synchronous);
         with holes=False nothing is read back and the outputs are complete after sync()."""
-        f = [np.ascontiguousarray(v, dtype=np.float32).reshape(k) for v, k in ((src_pos, 3), (src_rot, 9), (dst_pos, 3), (dst_rot, 9))]
-        fp = [v.ctypes.data_as(C.POINTER(C.c_float)) for v in f]
+        fp = _pose_ptrs(src_pos, src_rot, dst_pos, dst_rot)
         n = C.c_int32(0)
         self._check(self.lib.adanerf_reproject_gather(self.handle, _ptr(src_rgb), _ptr(src_depth), _ptr(src_acc), fp[0], fp[1], fp[2], fp[3],
                                                       float(acc_min), float(depth_tol), int(iterations), int(hole_rgba8) & 0xFFFFFFFF,
@@ -1260,8 +1266,7 @@ class NeuralRenderer:
         into out_rgb and, if given, out_depth / out_count (the next call's history), out_rgba8 and out_mask (uint8: 1 the history was
         used, 0 rejected).  Returns the number of rejected pixels (synchronous); with rejected=False nothing is read back and the outputs
         are complete after sync()."""
-        f = [None if v is None else np.ascontiguousarray(v, dtype=np.float32).reshape(k) for v, k in ((cur_pos, 3), (cur_rot, 9), (prev_pos, 3), (prev_rot, 9))]
-        fp = [None if v is None else v.ctypes.data_as(C.POINTER(C.c_float)) for v in f]
+        fp = _pose_ptrs(cur_pos, cur_rot, prev_pos, prev_rot)
         n = C.c_int32(0)
         self._check(self.lib.adanerf_temporal_resolve(self.handle, _ptr(cur_rgb), _ptr(cur_depth), _ptr(cur_acc), fp[0], fp[1], _ptr(hist_rgb),
                                                       _ptr(hist_depth), _ptr(hist_count), fp[2], fp[3], float(alpha), float(depth_tol), float(acc_min),
@@ -1269,19 +1274,25 @@ class NeuralRenderer:
                                                       _ptr(out_rgba8), _ptr(out_mask), C.byref(n) if rejected else None))
         return int(n.value) if rejected else None
 
-    def _temporal_buffers(self):
-        """two history sets (rgb, depth, count) to ping-pong and the mask, made on first use and again after a frame size that changes
-        rays_local; the frame's depth_map / acc_map are the aux buffers reproject() uses too"""
-        n = self.info.rays_local
+    def _temporal_buffers(self, history: _History, n: int):
+        """what a temporal stage renders into and resolves with: the frame's depth_map / acc_map (the aux buffers reproject() uses too),
+        ``_o_rgb`` / ``_o_rgba``, and its history at n pixels -- each made on first use and again when its size changes"""
         self._reproject_buffers()
-        if not hasattr(self, "_ta_sets") or self._ta_mask.shape[0] != n:
-            if hasattr(self, "_ta_sets"):
-                for a in [b for st in self._ta_sets for b in st] + [self._ta_mask]:
-                    a.free()
-                    self._own.remove(a)
-            self._ta_sets = [(self.empty((n, 3), np.float32), self.empty((n,), np.float32), self.empty((n,), np.uint8)) for _ in range(2)]
-            self._ta_mask = self.empty((n,), np.uint8)
-            self._ta_hist = None
+        self._out_buffers()
+        history.ensure(n)
+
+    def _render_next_offset(self, cycle):
+        """One render into ``_o_rgb`` at the next sub-pixel offset of ``cycle`` (its "offsets" and the place "k" in them); the offset that
+        was in force is restored.  Returns (dx, dy, Stats)."""
+        dx, dy = cycle["offsets"][cycle["k"] % len(cycle["offsets"])]
+        cycle["k"] += 1
+        was = self.pixel_offset
+        try:
+            self.set_pixel_offset(dx, dy)
+            st = self.render(None, self._o_rgb, stats=True)
+        finally:
+            self.set_pixel_offset(*was)
+        return dx, dy, st
 
     def enable_temporal(self, alpha: float = 0.1, depth_tol: float = 0.02, clamp: bool = True, grid: int = 2):
         """Temporal anti-aliasing from now on through render_temporal(): every frame is rendered at the next offset of the grid x grid
@@ -1291,17 +1302,14 @@ class NeuralRenderer:
         without useNDC only.  The depth_map / acc_map aux outputs become the renderer's own (as with enable_reprojection)."""
         if self.info.use_ndc or self.info.rays_local != self.info.width * self.info.height:
             raise AdaNeRFError("temporal anti-aliasing needs a whole frame of a model without useNDC")
-        if not 0.0 < float(alpha) <= 1.0:
-            raise ValueError("enable_temporal: alpha must lie in (0, 1], got %r" % (alpha,))
-        if not float(depth_tol) >= 0.0:
-            raise ValueError("enable_temporal: depth_tol must be >= 0, got %r" % (depth_tol,))
-        self._ta = dict(alpha=float(alpha), depth_tol=float(depth_tol), clamp=bool(clamp), offsets=subpixel_grid(grid), k=0)
-        self._ta_hist = None
-        self._temporal_buffers()
+        alpha, depth_tol = _check_blend("enable_temporal", alpha, depth_tol)
+        self._ta = dict(alpha=alpha, depth_tol=depth_tol, clamp=bool(clamp), offsets=subpixel_grid(grid), k=0)
+        self._temporal_buffers(self._ta_history, self.info.rays_local)
+        self._ta_history.reset()
 
     def reset_temporal(self):
         """Drops the history (a cut): the next render_temporal returns its frame as rendered.  The offset cycle goes on."""
-        self._ta_hist = None
+        self._ta_history.reset()
 
     def render_temporal(self):
         """One frame at the camera of the last set_camera, rendered at the next sub-pixel offset of the cycle and resolved against the
@@ -1314,35 +1322,17 @@ class NeuralRenderer:
             raise AdaNeRFError("render_temporal: call enable_temporal first")
         if self._pose is None:
             raise AdaNeRFError("render_temporal needs the pose of the frame: call set_camera first")
-        n = self.info.rays_local
-        self._temporal_buffers()
-        if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
-            self._o_rgb = self.empty((n, 3), np.float32)
-            self._o_rgba = self.empty((n, 4), np.uint8)
-        ta = self._ta
-        dx, dy = ta["offsets"][ta["k"] % len(ta["offsets"])]
-        ta["k"] += 1
-        was = self.pixel_offset
-        try:
-            self.set_pixel_offset(dx, dy)
-            st = self.render(None, self._o_rgb, stats=True)
-        finally:
-            self.set_pixel_offset(*was)
-        side = 0 if self._ta_hist is None else 1 - self._ta_hist[0]
-        out = self._ta_sets[side]
-        hist = (None, None, None) if self._ta_hist is None else self._ta_sets[self._ta_hist[0]]
-        prev = (None, None) if self._ta_hist is None else self._ta_hist[1:]
-        # The camera has not moved since the history was written: in a static scene nothing can have been uncovered, so there is no
-        # disocclusion test (d_hist_depth NULL).  The test would compare the depths of two jittered renders of one pose, and where a pixel
-        # spans several surfaces the jitter alone moves its depth past any tolerance: those pixels would restart their mean for nothing.
-        at_rest = self._ta_hist is not None and np.array_equal(prev[0], self._pose[0]) and np.array_equal(prev[1], self._pose[1])
-        rejected = self.temporal_resolve_device(self._o_rgb, self._rp_depth, self._rp_acc, self._pose[0], self._pose[1], hist[0], None if at_rest else hist[1], hist[2],
-                                                prev[0], prev[1], out[0], out[1], out[2], self._o_rgba, self._ta_mask, alpha=ta["alpha"],
+        ta, hi = self._ta, self._ta_history
+        self._temporal_buffers(hi, self.info.rays_local)
+        _, _, st = self._render_next_offset(ta)
+        hist_rgb, hist_depth, hist_count, prev_pos, prev_rot, out = hi.inputs(self._pose)
+        rejected = self.temporal_resolve_device(self._o_rgb, self._rp_depth, self._rp_acc, self._pose[0], self._pose[1], hist_rgb, hist_depth, hist_count,
+                                                prev_pos, prev_rot, out[0], out[1], out[2], self._o_rgba, hi.mask, alpha=ta["alpha"],
                                                 depth_tol=ta["depth_tol"], clamp=ta["clamp"])
-        self._ta_hist = (side, self._pose[0], self._pose[1])
+        hi.commit(self._pose)
         self._last_frame = (self._o_rgba, self.info.width, self.info.height)
         self._rp_frame = None      # the aux maps now belong to a jittered frame whose colour was blended: nothing reproject() may warp
-        return out[0].numpy(), self._o_rgba.numpy(), self._ta_mask.numpy(), rejected, st
+        return out[0].numpy(), self._o_rgba.numpy(), hi.mask.numpy(), rejected, st
 
     # -- temporal upsampling: one jittered render at w x h per frame, resolved into a history of s w x s h ----
     def temporal_upsample_device(self, scale: int, cur_rgb, cur_depth, cur_acc, cur_dx: float, cur_dy: float, cur_pos, cur_rot, hist_rgb, hist_depth,
@@ -1354,30 +1344,13 @@ class NeuralRenderer:
         count: each may be None) the previous call wrote at (prev_pos, prev_rot), and out_rgb and, if given, out_depth / out_count (the
         next call's history), out_rgba8 and out_mask (uint8: 1 the history was used, 2 a placeholder replaced, 0 rejected).  Returns the
         number of rejected pixels (synchronous); with rejected=False nothing is read back and the outputs are complete after sync()."""
-        f = [None if v is None else np.ascontiguousarray(v, dtype=np.float32).reshape(k) for v, k in ((cur_pos, 3), (cur_rot, 9), (prev_pos, 3), (prev_rot, 9))]
-        fp = [None if v is None else v.ctypes.data_as(C.POINTER(C.c_float)) for v in f]
+        fp = _pose_ptrs(cur_pos, cur_rot, prev_pos, prev_rot)
         n = C.c_int32(0)
         self._check(self.lib.adanerf_temporal_upsample(self.handle, int(scale), _ptr(cur_rgb), _ptr(cur_depth), _ptr(cur_acc), float(cur_dx), float(cur_dy),
                                                        fp[0], fp[1], _ptr(hist_rgb), _ptr(hist_depth), _ptr(hist_count), fp[2], fp[3], float(alpha),
                                                        float(depth_tol), float(acc_min), TEMPORAL_CLAMP if clamp else 0, _ptr(out_rgb), _ptr(out_depth),
                                                        _ptr(out_count), _ptr(out_rgba8), _ptr(out_mask), C.byref(n) if rejected else None))
         return int(n.value) if rejected else None
-
-    def _upsample_buffers(self):
-        """two history sets (rgb, depth, count) of the output size to ping-pong, its 8-bit image and mask, made on first use and again when
-        the output size changes; the frame's depth_map / acc_map are the aux buffers reproject() uses too"""
-        n = self.info.rays_local * self._tu["scale"] ** 2
-        self._reproject_buffers()
-        if not hasattr(self, "_tu_sets") or self._tu_mask.shape[0] != n:
-            if hasattr(self, "_tu_sets"):
-                for a in [b for st in self._tu_sets for b in st] + [self._tu_mask, self._tu_rgba]:
-                    if self._last_frame is not None and self._last_frame[0] is a:
-                        self._last_frame = None
-                    a.free()
-                    self._own.remove(a)
-            self._tu_sets = [(self.empty((n, 3), np.float32), self.empty((n,), np.float32), self.empty((n,), np.uint8)) for _ in range(2)]
-            self._tu_mask, self._tu_rgba = self.empty((n,), np.uint8), self.empty((n, 4), np.uint8)
-            self._tu_hist = None
 
     def enable_temporal_upsample(self, scale: int = 2, alpha: float = 0.1, depth_tol: float = 0.02, clamp: bool = True):
         """Temporal upsampling from now on through render_upsampled(): every frame is rendered at the context's frame size w x h, at the
@@ -1388,17 +1361,14 @@ class NeuralRenderer:
             raise AdaNeRFError("temporal upsampling needs a whole frame of a model without useNDC")
         if int(scale) != scale or not 1 <= int(scale) <= 4:
             raise ValueError("enable_temporal_upsample: scale must be 1, 2, 3 or 4, got %r" % (scale,))
-        if not 0.0 < float(alpha) <= 1.0:
-            raise ValueError("enable_temporal_upsample: alpha must lie in (0, 1], got %r" % (alpha,))
-        if not float(depth_tol) >= 0.0:
-            raise ValueError("enable_temporal_upsample: depth_tol must be >= 0, got %r" % (depth_tol,))
-        self._tu = dict(scale=int(scale), alpha=float(alpha), depth_tol=float(depth_tol), clamp=bool(clamp), offsets=subpixel_grid(int(scale)), k=0)
-        self._tu_hist = None
-        self._upsample_buffers()
+        alpha, depth_tol = _check_blend("enable_temporal_upsample", alpha, depth_tol)
+        self._tu = dict(scale=int(scale), alpha=alpha, depth_tol=depth_tol, clamp=bool(clamp), offsets=subpixel_grid(int(scale)), k=0)
+        self._temporal_buffers(self._tu_history, self.info.rays_local * int(scale) ** 2)
+        self._tu_history.reset()
 
     def reset_upsample(self):
         """Drops the history (a cut): the next render_upsampled shows every output pixel its nearest sample.  The offset cycle goes on."""
-        self._tu_hist = None
+        self._tu_history.reset()
 
     def render_upsampled(self):
         """One frame at the camera of the last set_camera, rendered at w x h at the next sub-pixel offset of the cycle and resolved into
@@ -1411,32 +1381,17 @@ class NeuralRenderer:
             raise AdaNeRFError("render_upsampled: call enable_temporal_upsample first")
         if self._pose is None:
             raise AdaNeRFError("render_upsampled needs the pose of the frame: call set_camera first")
-        n = self.info.rays_local
-        self._upsample_buffers()
-        if not hasattr(self, "_o_rgb") or self._o_rgb.shape[0] != n:
-            self._o_rgb = self.empty((n, 3), np.float32)
-            self._o_rgba = self.empty((n, 4), np.uint8)
-        tu = self._tu
-        dx, dy = tu["offsets"][tu["k"] % len(tu["offsets"])]
-        tu["k"] += 1
-        was = self.pixel_offset
-        try:
-            self.set_pixel_offset(dx, dy)
-            st = self.render(None, self._o_rgb, stats=True)
-        finally:
-            self.set_pixel_offset(*was)
-        side = 0 if self._tu_hist is None else 1 - self._tu_hist[0]
-        out = self._tu_sets[side]
-        hist = (None, None, None) if self._tu_hist is None else self._tu_sets[self._tu_hist[0]]
-        prev = (None, None) if self._tu_hist is None else self._tu_hist[1:]
-        at_rest = self._tu_hist is not None and np.array_equal(prev[0], self._pose[0]) and np.array_equal(prev[1], self._pose[1])
-        rejected = self.temporal_upsample_device(tu["scale"], self._o_rgb, self._rp_depth, self._rp_acc, dx, dy, self._pose[0], self._pose[1], hist[0],
-                                                 None if at_rest else hist[1], hist[2], prev[0], prev[1], out[0], out[1], out[2], self._tu_rgba,
-                                                 self._tu_mask, alpha=tu["alpha"], depth_tol=tu["depth_tol"], clamp=tu["clamp"])
-        self._tu_hist = (side, self._pose[0], self._pose[1])
-        self._last_frame = (self._tu_rgba, self.info.width * tu["scale"], self.info.height * tu["scale"])
+        tu, hi = self._tu, self._tu_history
+        self._temporal_buffers(hi, self.info.rays_local * tu["scale"] ** 2)
+        dx, dy, st = self._render_next_offset(tu)
+        hist_rgb, hist_depth, hist_count, prev_pos, prev_rot, out = hi.inputs(self._pose)
+        rejected = self.temporal_upsample_device(tu["scale"], self._o_rgb, self._rp_depth, self._rp_acc, dx, dy, self._pose[0], self._pose[1], hist_rgb,
+                                                 hist_depth, hist_count, prev_pos, prev_rot, out[0], out[1], out[2], hi.rgba, hi.mask,
+                                                 alpha=tu["alpha"], depth_tol=tu["depth_tol"], clamp=tu["clamp"])
+        hi.commit(self._pose)
+        self._last_frame = (hi.rgba, self.info.width * tu["scale"], self.info.height * tu["scale"])
         self._rp_frame = None      # the aux maps now belong to a jittered frame: nothing reproject() may warp
-        return out[0].numpy(), self._tu_rgba.numpy(), self._tu_mask.numpy(), rejected, st
+        return out[0].numpy(), hi.rgba.numpy(), hi.mask.numpy(), rejected, st
 
     # -- the frame at the window's size ---------------------------------------------------------------
     def present_device(self, src_rgba8, src_w: int, src_h: int, dst_rgba8, dst_w: int, dst_h: int, flip_y: bool = False,
@@ -1552,22 +1507,16 @@ class NeuralRenderer:
                             sample_w, total) -> int:
         """adanerf_compact_depth_limit: the selection at (n_max, thr), the depth trim of ray r to limit_zc[r] under the pose (pos, rot_c2w)
         with the ray records ``rays`` [n_rays,8], then the compaction.  Returns the library's code instead of raising: tests look at both."""
-        fp = C.POINTER(C.c_float)
-        p = np.ascontiguousarray(pos, dtype=np.float32).reshape(3)
-        r = np.ascontiguousarray(rot_c2w, dtype=np.float32).reshape(9)
-        return self.lib.adanerf_compact_depth_limit(self.handle, _ptr(oracle), n_rays, n_max, thr, _ptr(rays), _ptr(limit_zc), p.ctypes.data_as(fp),
-                                                    r.ctypes.data_as(fp), _ptr(ray_offsets), _ptr(ray_counts), _ptr(sample_key), _ptr(sample_w), _ptr(total))
+        p, r = _pose_ptrs(pos, rot_c2w)
+        return self.lib.adanerf_compact_depth_limit(self.handle, _ptr(oracle), n_rays, n_max, thr, _ptr(rays), _ptr(limit_zc), p, r, _ptr(ray_offsets), _ptr(ray_counts), _ptr(sample_key), _ptr(sample_w), _ptr(total))
 
     def compact_cap(self, oracle, n_rays: int, n_max: int, thr: float, cap_total: int, ray_offsets, ray_counts, sample_key, sample_w, total, tstar,
                     n_map=None, thr_map=None, rays=None, limit_zc=None, pos=None, rot_c2w=None) -> int:
         """adanerf_compact_cap: the selection at (n_max, thr), the budget trim (n_map / thr_map) and the depth trim (rays, limit_zc, pos,
         rot_c2w) where given, the sample cap at C = cap_total, then the compaction; ``tstar`` [1] fp32 on the device gets t* (-inf: nothing
         trimmed).  Returns the library's code instead of raising: tests look at both."""
-        fp = C.POINTER(C.c_float)
-        p = None if pos is None else np.ascontiguousarray(pos, dtype=np.float32).reshape(3)
-        r = None if rot_c2w is None else np.ascontiguousarray(rot_c2w, dtype=np.float32).reshape(9)
-        return self.lib.adanerf_compact_cap(self.handle, _ptr(oracle), n_rays, n_max, thr, _ptr(n_map), _ptr(thr_map), _ptr(rays), _ptr(limit_zc),
-                                            None if p is None else p.ctypes.data_as(fp), None if r is None else r.ctypes.data_as(fp), int(cap_total),
+        p, r = _pose_ptrs(pos, rot_c2w)
+        return self.lib.adanerf_compact_cap(self.handle, _ptr(oracle), n_rays, n_max, thr, _ptr(n_map), _ptr(thr_map), _ptr(rays), _ptr(limit_zc), p, r, int(cap_total),
                                             _ptr(ray_offsets), _ptr(ray_counts), _ptr(sample_key), _ptr(sample_w), _ptr(total), _ptr(tstar))
 
     def compact_budget(self, oracle, n_rays: int, n_max: int, thr: float, n_map, thr_map, ray_offsets, ray_counts, sample_key, sample_w, total):
@@ -1663,3 +1612,11 @@ class NeuralRenderer:
     def disp_map(self, depth, acc, n: int, disp_out):
         """disp_out[i] = 1 / max(1e-10, depth[i] / acc[i]) over n fp32 values (NaN stays NaN)"""
         self._check(self.lib.adanerf_disp_map(self.handle, _ptr(depth), _ptr(acc), n, _ptr(disp_out)))
+
+
+# The names tests and tools read the histories by (``_ta_sets``, ``_ta_hist``, ``_tu_rgba``, ``_ft_dmask``, ...): read-only views of the
+# members of the history objects.
+for _mode, _members in (("ta", ("sets", "hist", "mask")), ("tu", ("sets", "hist", "mask", "rgba")), ("ft", ("sets", "hist", "mask", "rgba", "dmask"))):
+    for _member in _members:
+        setattr(NeuralRenderer, "_%s_%s" % (_mode, _member),
+                property(lambda self, _h="_%s_history" % _mode, _m=_member: getattr(getattr(self, _h), _m)))
