@@ -42,7 +42,7 @@ struct StageScratch {
   double flip_ppd = 0.0;                      // what flip_tab holds (0: nothing yet)
   FlipParams flip_params{};
   bool flip_lds_raised = false;               // flip_kernel may use more than 64 KB of dynamic LDS
-  DevBuf zbuf;                                // adanerf_reproject: [width*height] uint64 z-buffer
+  DevBuf zbuf;                                // adanerf_reproject: [width*height] uint64 z-buffer; adanerf_reproject_pair: two of them, one behind the other
   DevBuf gather_surface;                      // adanerf_reproject_gather: [width*height] float4 (surface point, source camera depth)
   DevBuf count;                               // the one int32 a stage counts in (stages.hip stage_count)
   DevBuf upsample_zp;                         // adanerf_temporal_upsample / _resolve_sparse: [width*height] fp32 depths at the previous pose

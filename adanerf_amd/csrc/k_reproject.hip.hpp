@@ -11,7 +11,8 @@
 // Every floating-point operation is a single rounded fp32 operation in a fixed order (the library is built with -ffp-contract=off), so
 // the stage is exact against a numpy float32 restatement (tests/reproject_reference.py).  The source reads are coalesced, the scatter is
 // what it is: one 8-byte atomic per source pixel, 5.1 MB of them for an 800 x 800 frame.
-// The rotation into the destination camera, the image coordinates and the block's count are k_pose_core.hip.hpp's.
+// The rotation into the destination camera, the image coordinates and the block's count are k_pose_core.hip.hpp's.  The splat of one source
+// pixel is reproject_splat_pixel, which adanerf_reproject_pair's splat (k_reproject_pair.hip.hpp) calls per source as well.
 // Device code only (gfx950, wave64); part of stages.hip.
 #pragma once
 #include "k_pose_core.hip.hpp"
@@ -35,11 +36,10 @@ __global__ __launch_bounds__(256) void reproject_clear_kernel(unsigned long long
   if (j < n) zbuf[j] = kReprojectEmpty;
 }
 
-__global__ __launch_bounds__(256) void reproject_splat_kernel(ReprojectParams p, const float* __restrict__ depth, const float* __restrict__ acc,
-                                                              unsigned long long* __restrict__ zbuf) {
+// the splat of source pixel i (the caller's i < w * h) into zbuf: adanerf_reproject's, and per source adanerf_reproject_pair's
+__device__ __forceinline__ void reproject_splat_pixel(const ReprojectParams& p, int i, const float* __restrict__ depth, const float* __restrict__ acc,
+                                                      unsigned long long* __restrict__ zbuf) {
   const int w = p.g.w, h = p.g.h;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;      // w * h < 2^25 (frame_geometry)
-  if (i >= w * h) return;
   const int row = i / w, col = i - row * w;
   float nds[3], o[3];
   gen_ray(p.g, col, row, nds, o);
@@ -66,6 +66,13 @@ __global__ __launch_bounds__(256) void reproject_splat_kernel(ReprojectParams p,
   const unsigned long long key =
       (static_cast<unsigned long long>(near ? __float_as_uint(zc) : kReprojectFarBits) << 32) | static_cast<unsigned long long>(static_cast<uint32_t>(i));
   atomicMin(zbuf + (Y * w + X), key);
+}
+
+__global__ __launch_bounds__(256) void reproject_splat_kernel(ReprojectParams p, const float* __restrict__ depth, const float* __restrict__ acc,
+                                                              unsigned long long* __restrict__ zbuf) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;      // w * h < 2^25 (frame_geometry)
+  if (i >= p.g.w * p.g.h) return;
+  reproject_splat_pixel(p, i, depth, acc, zbuf);
 }
 
 // fill != 0: a hole takes the largest key among its 8 neighbours' splats.  holes: += the pixels left with mask 0, one atomicAdd per block.

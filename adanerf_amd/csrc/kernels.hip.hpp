@@ -9,12 +9,13 @@
 //   A5+A6     shade_mlp16x2_kernel / shade_mlp32_kernel   fused PE + 8x256 shading MLP (bf16/f16/f32 MFMA)
 //   A7        composite_kernel       sigmoid + alpha * oracle weight, front-to-back
 //   N8        mask_bits_kernel / mask_scatter_kernel   a byte mask as bit words for refine_list_kernel; the pixels of a listed batch to their places (masked rendering)
-// stages.hip (k_flip, k_present, k_reproject, k_reproject_gather, k_accumulate, k_temporal, k_upsample, k_blend, k_density, k_sparse_temporal, k_contrast;
-// k_pose_core: the arithmetic N4, N13, N6, N7 and N12 share):
+// stages.hip (k_flip, k_present, k_reproject, k_reproject_gather, k_reproject_pair, k_accumulate, k_temporal, k_upsample, k_blend, k_density, k_sparse_temporal, k_contrast;
+// k_pose_core: the arithmetic N4, N13, N14, N6, N7 and N12 share):
 //   N1        flip_kernel / flip_mean_kernel   FLIP error map and mean of an image pair (the evaluator's second metric)
 //   N3        present_kernel / present_area_kernel   the frame at the window's size (the viewer's blit: linear / nearest, y flip; exact area filter)
 //   N4        reproject_clear_kernel / reproject_splat_kernel / reproject_resolve_kernel   a rendered frame warped to another pose by its depth
 //   N13       gather_surface_kernel / gather_warp_kernel   the same warp as a gather: each destination pixel iterates along its ray to the source surface
+//   N14       reproject_pair_splat_kernel / reproject_pair_resolve_kernel   two rendered frames warped to a pose between them: N4's splat per source, one resolve over both z-buffers
 //   N5        accumulate_kernel / resolve_mean_kernel   sum and mean of several sub-pixel frames (supersampling in time)
 //   N6        temporal_resolve_kernel   a history image carried to the pose of the moment, clamped and blended with the new frame (temporal anti-aliasing)
 //   N7        upsample_depth_kernel / upsample_resolve_kernel   a frame rendered at w x h resolved into a history of s w x s h (temporal upsampling)

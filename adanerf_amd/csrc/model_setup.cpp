@@ -530,6 +530,27 @@ int adanerf_host_contrast_mask(const float* rgb, int32_t width, int32_t height, 
   return ADANERF_OK;
 }
 
+int adanerf_host_pair_weight(const float dst_pos[3], const float a_pos[3], const float b_pos[3], float* weight_b) {
+  if (!dst_pos || !a_pos || !b_pos || !weight_b) return fail(ADANERF_EINVAL, "adanerf_host_pair_weight: NULL argument");
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(dst_pos[i]) || !std::isfinite(a_pos[i]) || !std::isfinite(b_pos[i])) return fail(ADANERF_EINVAL, "adanerf_host_pair_weight: every value must be finite");
+  // every intermediate goes through a volatile, as in adanerf_host_sphere_zc: one rounded float64 operation per step, never fused
+  volatile double d[2];
+  for (int s = 0; s < 2; ++s) {
+    const float* from = s ? b_pos : a_pos;
+    volatile double e0 = static_cast<double>(dst_pos[0]) - static_cast<double>(from[0]);
+    volatile double e1 = static_cast<double>(dst_pos[1]) - static_cast<double>(from[1]);
+    volatile double e2 = static_cast<double>(dst_pos[2]) - static_cast<double>(from[2]);
+    volatile double m0 = e0 * e0, m1 = e1 * e1, m2 = e2 * e2;
+    volatile double sum = m0 + m1;
+    volatile double sq = sum + m2;
+    d[s] = std::sqrt(sq);
+  }
+  volatile double both = d[0] + d[1];
+  *weight_b = both == 0.0 ? 0.5f : static_cast<float>(d[0] / both);
+  return ADANERF_OK;
+}
+
 int adanerf_host_depth_table(const char* model_dir, const adanerf_options* opt, float* ztab128) {
   if (!model_dir || !opt || !ztab128) return fail(ADANERF_EINVAL, "NULL argument");
   ModelSetup ms;

@@ -15,6 +15,7 @@
 #include "k_present.hip.hpp"
 #include "k_reproject.hip.hpp"
 #include "k_reproject_gather.hip.hpp"
+#include "k_reproject_pair.hip.hpp"
 #include "k_accumulate.hip.hpp"
 #include "k_temporal.hip.hpp"
 #include "k_upsample.hip.hpp"
@@ -404,6 +405,66 @@ int adanerf_reproject_gather(adanerf_ctx* c, const float* d_src_rgb, const float
   const dim3 grid((w + kGatherTileW - 1) / kGatherTileW, (h + kGatherTileH - 1) / kGatherTileH);
   hipLaunchKernelGGL(gather_warp_kernel, grid, dim3(256), 0, c->stream, pw, surface, d_src_rgb, d_dst_rgb, static_cast<uchar4*>(d_dst_rgba8), d_dst_depth,
                      d_dst_mask, holes);
+  HIP_TRY(c, hipGetLastError());
+  return read_count(c, holes, holes_out);
+}
+
+int adanerf_reproject_pair(adanerf_ctx* c, const float* d_a_rgb, const float* d_a_depth_map, const float* d_a_acc_map, const float a_pos[3],
+                           const float a_rot_c2w[9], const float* d_b_rgb, const float* d_b_depth_map, const float* d_b_acc_map, const float b_pos[3],
+                           const float b_rot_c2w[9], const float dst_pos[3], const float dst_rot_c2w[9], float weight_b, float acc_min, float depth_tol,
+                           uint32_t hole_rgba8, int32_t flags, float* d_dst_rgb, void* d_dst_rgba8, float* d_dst_depth, uint8_t* d_dst_mask,
+                           uint8_t* d_dst_source, int32_t* holes_out) {
+  constexpr const char* who = "adanerf_reproject_pair";
+  if (!c) return ADANERF_EINVAL;
+  if (!d_a_rgb || !d_a_depth_map || !d_a_acc_map || !d_b_rgb || !d_b_depth_map || !d_b_acc_map || !d_dst_rgb) return reject(c, ADANERF_EINVAL, who, "NULL image");
+  if (int rc = check_poses(c, who, a_pos, a_rot_c2w, b_pos, b_rot_c2w, true)) return rc;
+  if (int rc = check_poses(c, who, dst_pos, dst_rot_c2w, nullptr, nullptr, false)) return rc;
+  if (!(weight_b >= 0.f && weight_b <= 1.f)) return reject(c, ADANERF_EINVAL, who, "weight_b must lie in [0, 1]");      // every comparison also refuses a NaN
+  if (!(acc_min >= 0.f)) return reject(c, ADANERF_EINVAL, who, "acc_min must be >= 0");
+  if (!(depth_tol >= 0.f)) return reject(c, ADANERF_EINVAL, who, "depth_tol must be >= 0");
+  if (flags & ~ADANERF_REPROJECT_FILL) return reject(c, ADANERF_EINVAL, who, "flags must be 0 or ADANERF_REPROJECT_FILL");
+  if (misaligned4({d_a_rgb, d_a_depth_map, d_a_acc_map, d_b_rgb, d_b_depth_map, d_b_acc_map, d_dst_rgb, d_dst_rgba8, d_dst_depth}))
+    return reject(c, ADANERF_EINVAL, who, "fp32 and uchar4 images must be 4-byte aligned");
+  const int w = c->ms.info.width, h = c->ms.info.height, n = w * h;
+  const size_t b1 = static_cast<size_t>(n) * sizeof(float);
+  struct Range { const void* p; size_t bytes; };
+  const Range in[6] = {{d_a_rgb, 3 * b1}, {d_a_depth_map, b1}, {d_a_acc_map, b1}, {d_b_rgb, 3 * b1}, {d_b_depth_map, b1}, {d_b_acc_map, b1}};
+  const Range out[5] = {{d_dst_rgb, 3 * b1}, {d_dst_rgba8, b1}, {d_dst_depth, b1}, {d_dst_mask, static_cast<size_t>(n)}, {d_dst_source, static_cast<size_t>(n)}};
+  for (int a = 0; a < 5; ++a) {      // the resolve reads both sources' colour while it writes; A and B may be the same images
+    if (!out[a].p) continue;
+    for (const Range& r : in)
+      if (ranges_overlap(out[a].p, out[a].bytes, r.p, r.bytes)) return reject(c, ADANERF_EINVAL, who, "an output overlaps a source image");
+    for (int b = a + 1; b < 5; ++b)
+      if (out[b].p && ranges_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes)) return reject(c, ADANERF_EINVAL, who, "two outputs overlap");
+  }
+  if (int rc = check_depth_frames(c, who)) return rc;
+  BIND(c);
+  if (int rc = grow_in_use(c, &c->stages.zbuf, static_cast<size_t>(n) * 2 * sizeof(uint64_t))) return rc;      // adanerf_reproject's scratch: its z-buffer, and a second behind it
+  int32_t* holes = nullptr;
+  if (int rc = stage_count(c, &holes)) return rc;
+  PairSplatParams ps{};
+  const float* const pos[2] = {a_pos, b_pos};
+  const float* const rot[2] = {a_rot_c2w, b_rot_c2w};
+  for (int s = 0; s < 2; ++s) {
+    ps.s[s].g = c->ms.rg;
+    copy_pose(ps.s[s].g.pos, ps.s[s].g.rot, pos[s], rot[s]);
+    copy_pose(ps.s[s].dst_pos, ps.s[s].dst_rot, dst_pos, dst_rot_c2w);
+    ps.s[s].acc_min = acc_min;
+    ps.s[s].origin_is_camera = c->ms.coarse_fine ? 1 : 0;      // what the render path writes to ADANERF_BUF_RAYS (camera_rays_kernel)
+  }
+  ps.depth[0] = d_a_depth_map;
+  ps.depth[1] = d_b_depth_map;
+  ps.acc[0] = d_a_acc_map;
+  ps.acc[1] = d_b_acc_map;
+  const PairResolveParams pr{{d_a_rgb, d_b_rgb}, w, h, (flags & ADANERF_REPROJECT_FILL) ? 1 : 0, weight_b, depth_tol, hole_rgba8};
+  unsigned long long* zbuf = reinterpret_cast<unsigned long long*>(c->stages.zbuf.p);
+  const unsigned blocks = static_cast<unsigned>((n + 255) / 256);
+  hipLaunchKernelGGL(reproject_clear_kernel, dim3((2 * n + 255) / 256), dim3(256), 0, c->stream, zbuf, 2 * n, holes);      // both z-buffers; zeroes the count as well
+  HIP_TRY(c, hipGetLastError());
+  hipLaunchKernelGGL(reproject_pair_splat_kernel, dim3(blocks, 2), dim3(256), 0, c->stream, ps, zbuf);
+  HIP_TRY(c, hipGetLastError());
+  hipLaunchKernelGGL(reproject_pair_resolve_kernel, dim3(blocks), dim3(256), 0, c->stream, pr, zbuf, d_dst_rgb, static_cast<uchar4*>(d_dst_rgba8), d_dst_depth,
+                     d_dst_mask, d_dst_source, holes);
   HIP_TRY(c, hipGetLastError());
   return read_count(c, holes, holes_out);
 }

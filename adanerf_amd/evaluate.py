@@ -8,7 +8,7 @@ reference's second default metric (``metrics = ["flip", "psnr"]`` :613-615): the
                                    [--metrics psnr flip] [--sweep-thresholds T ...] [--sweep-samples N ...] [--sweep-scales S ...]
                                    [--reproject-stride K [--reproject-warp splat|gather] [--rerender holes|unsourced]] [--supersample S] [--present-filter nearest|linear|area]
                                    [--fovea-density R:S[,R:S...],S [--fovea-temporal ALPHA] [--fovea-temporal-still K]] [--supersample-contrast T]
-                                   [--sweep-sample-caps C ...]
+                                   [--sweep-sample-caps C ...] [--interpolate-stride K [--rerender holes|unsourced]]
 
 ``--sweep-sample-caps`` renders the set once per sample cap on one context (``NeuralRenderer.set_sample_cap``: a hard bound on the mean
 samples per ray of every frame, met on the device by raising the threshold): the quality a frame-time guarantee costs; the summary's
@@ -26,6 +26,10 @@ dataset's ``w x h`` on the GPU (``adanerf_present``, the viewer's blit) and scor
 the same ground truth.  ``--rerender holes|unsourced`` scores every warped frame once more with its holes (unsourced: the filled pixels too)
 rendered at its own pose (``adanerf_render_masked``).  ``--reproject-warp gather`` makes the warped frames with ``adanerf_reproject_gather``
 (``--reproject-iterations N``, ``--reproject-tol T``: its two dials) instead of the splat.
+
+``--interpolate-stride K`` renders the poses with ``i % K == 0`` and the last one as keyframes and makes every other pose from the
+keyframe before it AND the keyframe after it (``adanerf_reproject_pair``, weight from ``adanerf_host_pair_weight``, fill on): what a host
+that knows its path, or shows its frames K late, shows in between.  ``--rerender`` applies to those frames as it does to warped ones.
 
 ``--supersample S`` makes every image the mean of S x S renders at the sub-pixel offsets of ``adanerf_host_subpixel_grid``, accumulated
 and resolved on the GPU (``NeuralRenderer.render_supersampled``) and scored from the fp32 mean: anti-aliasing in time, against the
@@ -121,7 +125,7 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
              video: Optional[str] = None, fps: int = 30, metrics=("psnr",), fovea=None, sweep_thresholds=None, sweep_samples=None, reproject_stride=None,
              supersample=None, present_filter=None, temporal=None, temporal_still=None, temporal_upsample=None, temporal_upsample_frames=None,
              rerender=None, fovea_density=None, reproject_warp="splat", reproject_iterations=None, reproject_tol=None, sweep_sample_caps=None,
-             fovea_temporal=None, fovea_temporal_still=None, supersample_contrast=None, sweep_scales=None):
+             interpolate_stride=None, fovea_temporal=None, fovea_temporal_still=None, supersample_contrast=None, sweep_scales=None):
     """metrics: "psnr" (always reported where a ground-truth image exists) and / or "flip": each record gains ``flip``, the summary
     ``mean_flip``, and with out_dir the error map is written as an 8-bit greyscale ``%05d_flip.png``.
 
@@ -148,6 +152,16 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     reproject_warp ("splat", the default, or "gather"; gather needs reproject_stride): the warped frames come from
     NeuralRenderer.reproject_gather (adanerf_reproject_gather; reproject_iterations / reproject_tol: its two dials, None = the renderer's
     defaults) and rerender uses reproject_gather_rerender.  Warped records carry ``warp``; the summary keys are unchanged.
+
+    interpolate_stride (K >= 1 or None): the poses with i % K == 0, and the last pose, are rendered as keyframes
+    (NeuralRenderer.render_keyframe); every other pose is made from the keyframe before it and the keyframe after it
+    (NeuralRenderer.interpolate: adanerf_reproject_pair, the weight from pair_weight, fill on) and scored from the fp32 result.  Records
+    gain ``interpolated`` and, for an interpolated frame, ``hole_fraction`` and ``blended_fraction`` (pixels both keyframes agreed on, of
+    w h) in place of samples_per_ray / ms; the summary gains ``mean_psnr_rendered``, ``mean_psnr_interpolated``, ``mean_hole_fraction``,
+    ``mean_blended_fraction`` and, with "flip", ``mean_flip_rendered`` / ``mean_flip_interpolated``.  With rerender every interpolated
+    frame is scored a second time with its holes rendered at its own pose (NeuralRenderer.interpolate_rerender): ``psnr_rerendered`` /
+    ``mse_rerendered`` / ``rerendered_fraction`` in the records, ``mean_psnr_interpolated_rerendered`` / ``mean_rerendered_fraction`` in
+    the summary.  Not with reproject_stride or any other frame-to-frame option, the sweeps or fovea_density.
 
     supersample (S in 1..8 or None): every image is the mean of S x S renders at the offsets of the regular sub-pixel grid
     (NeuralRenderer.render_supersampled), scored from the fp32 mean; ms is the sum over the S x S renders, samples_per_ray is per rendered
@@ -207,6 +221,13 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
     ``mean_cap_threshold`` is the mean over the trimmed frames of the largest threshold the cap chose (None if no frame was trimmed);
     records carry ``sample_cap`` and ``cap_threshold`` (None: not trimmed); out_dir gets ``cap<C>/``.  With metrics and fovea only; the cap
     is removed afterwards."""
+    ip = int(interpolate_stride) if interpolate_stride is not None else 0
+    if interpolate_stride is not None and (ip != interpolate_stride or ip < 1):
+        raise ValueError("interpolate_stride must be an integer >= 1, got %s" % (interpolate_stride,))
+    if ip and (reproject_stride is not None or supersample is not None or temporal is not None or temporal_still is not None or temporal_upsample is not None or
+               fovea_density is not None or sweep_scales or sweep_thresholds or sweep_samples or sweep_sample_caps):
+        raise ValueError("interpolate_stride makes frames from two keyframes at the dataset's resolution: not together with reproject_stride, supersample, "
+                         "the temporal options, fovea_density or a sweep")
     if sweep_sample_caps and (sweep_thresholds or sweep_samples or sweep_scales or reproject_stride is not None or supersample is not None or
                               temporal is not None or temporal_still is not None or temporal_upsample is not None or fovea_density is not None):
         raise ValueError("sweep_sample_caps goes with metrics and fovea only")
@@ -233,7 +254,7 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
         raise ValueError("reproject_warp / reproject_iterations / reproject_tol choose how warped frames are made: they need reproject_stride")
     gather_kw = dict(iterations=GATHER_ITERATIONS if reproject_iterations is None else int(reproject_iterations),
                      depth_tol=GATHER_DEPTH_TOL if reproject_tol is None else float(reproject_tol))
-    if rerender and not stride:
+    if rerender and not stride and not ip:
         raise ValueError("rerender re-renders the holes of warped frames: it needs reproject_stride")
     if stride and sweep_scales:
         raise ValueError("reproject_stride warps at the dataset's resolution: not together with sweep_scales")
@@ -295,9 +316,11 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
         vid = Y4mWriter(video, w, h, fps) if video else None
         d_ref = r.empty((w * h, 3), np.float32) if want_flip else None
         d_map = r.empty((w * h,), np.float32) if want_flip and out_dir else None
-        d_pres = r.empty((w * h, 3), np.float32) if want_flip and (sweep_scales or stride or ta or tu or ft) else None      # (the foveated frame is scored in place)
+        d_pres = r.empty((w * h, 3), np.float32) if want_flip and (sweep_scales or stride or ta or tu or ft or ip) else None      # (the foveated frame is scored in place)
         if stride:
             r.enable_reprojection()
+        if ip:
+            r.enable_interpolation()
         if ta:
             r.enable_temporal(alpha=ta, grid=2)
         if tu:
@@ -318,10 +341,29 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                 r.foveate_density((0.5 * rw, 0.5 * rh), fovea_density)
             if ft:      # a pass over the set is one sequence, from a cut
                 r.enable_foveated_temporal(alpha=ft)
-            for i, fr in enumerate(frames):
+            keys = [i for i in range(len(frames)) if i % ip == 0 or i == len(frames) - 1] if ip else []
+            order = list(range(len(frames)))
+            if ip:      # every keyframe ahead of the poses it closes: the frame after an in-between pose is rendered before that pose is made
+                order = sorted(order, key=lambda i: (min(k for k in keys if k >= i) if i else 0, i not in keys, i))
+            for i in order:
+                fr = frames[i]
                 ref = None
                 warped = bool(stride) and i % stride != 0
-                if warped:      # the last rendered frame at this pose: what a host that renders every K-th frame shows here
+                interpolated = bool(ip) and i not in keys
+                if interpolated:      # between the keyframe before this pose and the keyframe after it
+                    rgb, rgba, _, source, holes = r.interpolate(fr["pose"], fr["rot"])
+                    rec = dict(extra, frame=i, image=fr["image"], interpolated=True, hole_fraction=holes / float(w * h),
+                               blended_fraction=int(np.count_nonzero(source == 3)) / float(w * h))
+                    if rerender:
+                        rr_rgb, rr_rgba, _, _, _, rerendered = r.interpolate_rerender(fr["pose"], fr["rot"], rerender)
+                        rec.update(rerendered_fraction=rerendered / float(w * h))
+                        if out_dir:
+                            write_png(os.path.join(out_dir, "%05d_rerendered.png" % i), rr_rgba[:, :3].reshape(h, w, 3))
+                elif ip:
+                    r.set_camera(fr["pose"], fr["rot"])
+                    rgb, rgba, st = r.render_keyframe()
+                    rec = dict(extra, frame=i, image=fr["image"], samples_per_ray=st.total_samples / float(rw * rh), ms=st.ms_total, interpolated=False)
+                elif warped:      # the last rendered frame at this pose: what a host that renders every K-th frame shows here
                     if reproject_warp == "gather":
                         _, rgba, _, holes = r.reproject_gather(fr["pose"], fr["rot"], **gather_kw)
                     else:
@@ -333,6 +375,7 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                             rr_rgba, _, _, rerendered = r.reproject_gather_rerender(fr["pose"], fr["rot"], rerender, **gather_kw)
                         else:
                             rr_rgba, _, _, rerendered = r.reproject_rerender(fr["pose"], fr["rot"], rerender)
+                        rr_rgb = rr_rgba[:, :3].astype(np.float32) / 255.0
                         rec.update(rerendered_fraction=rerendered / float(w * h))
                         if out_dir:
                             os.makedirs(out_dir, exist_ok=True)
@@ -363,11 +406,11 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                     ref = gt[:, :, :3].astype(np.float32).reshape(-1, 3) / 255.0        # datasets.py:286-287
                     mse = float(np.mean((rgb.astype(np.float64) - ref) ** 2))
                     rec.update(mse=mse, psnr=psnr_from_mse(mse))
-                    if warped and rerender:
-                        rr_mse = float(np.mean(((rr_rgba[:, :3].astype(np.float32) / 255.0).astype(np.float64) - ref) ** 2))
+                    if (warped or interpolated) and rerender:
+                        rr_mse = float(np.mean((rr_rgb.astype(np.float64) - ref) ** 2))
                         rec.update(mse_rerendered=rr_mse, psnr_rerendered=psnr_from_mse(rr_mse))
                     if want_flip:       # the rendered frame is still on the device (render_numpy); argument order of src/evaluate.py:144
-                        d_test = r._o_rgb if not presented and not warped else d_pres.upload(rgb)
+                        d_test = r._o_rgb if not presented and not warped and not ip else d_pres.upload(rgb)
                         rec.update(flip=r.flip_device(d_test, d_ref.upload(ref), w, h, error_map=d_map))
                         if d_map is not None:
                             fm = np.nan_to_num(d_map.numpy().reshape(h, w), nan=1.0)      # the map lies in [0, 1]
@@ -428,7 +471,7 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
                 if not quiet:
                     print("frame %d: %s" % (i, ", ".join("%s=%s" % (k, ("%.4f" % v) if isinstance(v, float) else v)
                                                           for k, v in rec.items() if k not in ("frame", "image"))))
-            return recs
+            return sorted(recs, key=lambda x: x["frame"]) if ip else recs
 
         sweep = []
         if sweep_thresholds or sweep_samples or sweep_scales:
@@ -466,7 +509,7 @@ def evaluate(model_dir: str, dataset_dir: str, set_name: str = "test", out_dir: 
 
 def summarise(results: List[dict], want_flip: bool) -> dict:
     with_gt = [x for x in results if "psnr" in x]
-    rendered = [x for x in results if not x.get("warped")]
+    rendered = [x for x in results if not x.get("warped") and not x.get("interpolated")]
     summary = dict(frames=len(results), mean_samples_per_ray=float(np.mean([x["samples_per_ray"] for x in rendered])) if rendered else 0.0,
                    mean_ms=float(np.mean([x["ms"] for x in rendered])) if rendered else 0.0)
     if with_gt:
@@ -484,6 +527,19 @@ def summarise(results: List[dict], want_flip: bool) -> dict:
         if any("rerendered_fraction" in x for x in results):      # rerender: the warped frames once more, their holes rendered
             part = [x["psnr_rerendered"] for x in results if "psnr_rerendered" in x]
             summary["mean_psnr_warped_rerendered"] = float(np.mean(part)) if part else None
+            summary["mean_rerendered_fraction"] = float(np.mean([x["rerendered_fraction"] for x in results if "rerendered_fraction" in x]))
+    if any("interpolated" in x for x in results):      # interpolate_stride: the keyframes and the frames made between them apart
+        for kind, flag in (("rendered", False), ("interpolated", True)):
+            part = [x for x in with_gt if bool(x.get("interpolated")) == flag]
+            summary["mean_psnr_" + kind] = float(np.mean([x["psnr"] for x in part])) if part else None
+            if want_flip:
+                summary["mean_flip_" + kind] = float(np.mean([x["flip"] for x in part])) if part else None
+        made = [x for x in results if x.get("interpolated")]
+        summary["mean_hole_fraction"] = float(np.mean([x["hole_fraction"] for x in made])) if made else 0.0
+        summary["mean_blended_fraction"] = float(np.mean([x["blended_fraction"] for x in made])) if made else 0.0
+        if any("rerendered_fraction" in x for x in results):
+            part = [x["psnr_rerendered"] for x in results if "psnr_rerendered" in x]
+            summary["mean_psnr_interpolated_rerendered"] = float(np.mean(part)) if part else None
             summary["mean_rerendered_fraction"] = float(np.mean([x["rerendered_fraction"] for x in results if "rerendered_fraction" in x]))
     if any("temporal_upsample" in x for x in results):      # temporal_upsample: the upsampled frames beside the enlarged small ones
         part = [x for x in results if "psnr_upsampled" in x]
@@ -548,6 +604,10 @@ def build_parser():
     ap.add_argument("--reproject-iterations", type=int, default=None, metavar="N", help="with --reproject-warp gather: steps per pixel, 1..8 (default %d)" % GATHER_ITERATIONS)
     ap.add_argument("--reproject-tol", type=float, default=None, metavar="T",
                     help="with --reproject-warp gather: relative depth tolerance of the consistency test (default %g)" % GATHER_DEPTH_TOL)
+    ap.add_argument("--interpolate-stride", type=int, default=None, metavar="K",
+                    help="render the poses with i %% K == 0 and the last one as keyframes and make the others from the keyframe before AND the keyframe "
+                         "after them (adanerf_reproject_pair); the summary gains mean_psnr_rendered / mean_psnr_interpolated / mean_hole_fraction / "
+                         "mean_blended_fraction (and mean_flip_* with --metrics flip); --rerender applies to those frames")
     ap.add_argument("--rerender", default=None, choices=["holes", "unsourced"],
                     help="with --reproject-stride: score every warped frame once more with its holes (unsourced: the filled pixels too) rendered at "
                          "its own pose (adanerf_render_masked); the summary gains mean_psnr_warped_rerendered / mean_rerendered_fraction")
@@ -595,8 +655,12 @@ def main(argv=None):
     a = ap.parse_args(argv)
     if (a.reproject_warp is not None or a.reproject_iterations is not None or a.reproject_tol is not None) and a.reproject_stride is None:
         ap.error("--reproject-warp / --reproject-iterations / --reproject-tol need --reproject-stride")
-    if a.rerender is not None and a.reproject_stride is None:
+    if a.rerender is not None and a.reproject_stride is None and a.interpolate_stride is None:
         ap.error("--rerender needs --reproject-stride")
+    if a.interpolate_stride is not None and (a.reproject_stride is not None or a.supersample is not None or a.temporal is not None or a.temporal_still is not None or
+                                             a.temporal_upsample is not None or a.fovea_density is not None or a.sweep_scales or a.sweep_thresholds or
+                                             a.sweep_samples or a.sweep_sample_caps):
+        ap.error("--interpolate-stride cannot be combined with --reproject-stride, --supersample, the --temporal options, --fovea-density or a sweep")
     if a.supersample is not None and a.reproject_stride is not None:
         ap.error("--supersample cannot be combined with --reproject-stride")
     if (a.temporal is not None or a.temporal_still is not None) and (a.supersample is not None or a.reproject_stride is not None or a.sweep_scales):
@@ -632,7 +696,7 @@ def main(argv=None):
                           temporal=a.temporal, temporal_still=a.temporal_still, temporal_upsample=a.temporal_upsample,
                           temporal_upsample_frames=a.temporal_upsample_frames, fovea_density=a.fovea_density,
                           supersample_contrast=a.supersample_contrast, fovea_temporal=a.fovea_temporal, fovea_temporal_still=a.fovea_temporal_still,
-                          sweep_sample_caps=a.sweep_sample_caps)
+                          sweep_sample_caps=a.sweep_sample_caps, interpolate_stride=a.interpolate_stride)
     print(json.dumps(summary))
 
 

@@ -161,6 +161,10 @@ bool NeuralRenderer::init() {
     err = world > 1 ? "--reproject warps whole frames of one context; use it with --gpus 1" : "--reproject: the depth of a useNDC model is NDC depth";
     return false;
   }
+  if (settings.interpolate > 1 && (world > 1 || info_.use_ndc)) {
+    err = world > 1 ? "--interpolate warps whole frames of one context; use it with --gpus 1" : "--interpolate: the depth of a useNDC model is NDC depth";
+    return false;
+  }
   if (settings.taa_alpha > 0.f && (world > 1 || settings.render_oracle || info_.use_ndc)) {
     err = world > 1 ? "--taa resolves whole frames of one context; use it with --gpus 1"
                     : (settings.render_oracle ? "--taa blends rendered frames; not with --oracle" : "--taa: the depth of a useNDC model is NDC depth");
@@ -199,7 +203,7 @@ std::vector<NeuralRenderer::FrameBuffer> NeuralRenderer::frameBuffers() {
   const bool taa = settings.taa_alpha > 0.f, taau = settings.taau_scale > 0, density = !settings.density_stride.empty(),
              fovea_temporal = density && settings.fovea_temporal_alpha > 0.f, supersample = settings.supersample > 1,
              contrast = supersample && settings.supersample_contrast >= 0.f, occluder = !settings.occluders.empty(), reproject = settings.reproject > 1,
-             gather = reproject && settings.reproject_gather;
+             gather = reproject && settings.reproject_gather, pair = settings.interpolate > 1;
   const size_t N = taau ? n * settings.taau_scale * settings.taau_scale : n, hist = taa || taau || fovea_temporal ? N : 0;
   const size_t aux = taa || taau || fovea_temporal || reproject ? n : 0;
   std::vector<FrameBuffer> table = {
@@ -214,11 +218,17 @@ std::vector<NeuralRenderer::FrameBuffer> NeuralRenderer::frameBuffers() {
       {&d_cmask, contrast ? n : 0, 0},
       {&d_limit, occluder ? n * 4 : 0, RESET_OCCLUDER},      // the library drops the limit when rays_local changes
       {&d_behind, occluder ? n * 12 : 0, RESET_OCCLUDER},
-      {&d_warp, reproject ? n * 4 : 0, 0},
-      {&d_wmask, reproject ? n * 4 : 0, 0},                  // (the mask is a byte per pixel: a quarter of its allocation)
+      {&d_warp, reproject || pair ? n * 4 : 0, 0},
+      {&d_wmask, reproject || pair ? n * 4 : 0, 0},          // (the mask is a byte per pixel: a quarter of its allocation)
       {&d_src_rgb, gather ? n * 12 : 0, RESET_SOURCE},
-      {&d_warp_rgb, gather ? n * 12 : 0, 0},
+      {&d_warp_rgb, gather || pair ? n * 12 : 0, 0},
   };
+  for (Keyframe& k : ip_key) {      // --interpolate: the two keyframes
+    table.push_back({&k.rgba, pair ? n * 4 : 0, RESET_SOURCE});
+    table.push_back({&k.rgb, pair ? n * 12 : 0, RESET_SOURCE});
+    table.push_back({&k.depth, pair ? n * 4 : 0, RESET_SOURCE});
+    table.push_back({&k.acc, pair ? n * 4 : 0, RESET_SOURCE});
+  }
   for (int side = 0; side < 2; ++side) {
     table.push_back({&history.set[side][0], hist * 12, RESET_HISTORY});
     table.push_back({&history.set[side][1], hist * 4, RESET_HISTORY});
@@ -237,7 +247,7 @@ bool NeuralRenderer::allocFrameBuffers() {
     resets |= b.resets;
   }
   d_shown = d_frame;
-  if (resets & RESET_SOURCE) have_source = false;
+  if (resets & RESET_SOURCE) have_source = false, ip_keys = 0;
   if (resets & RESET_HISTORY) history.reset();
   if (resets & RESET_OCCLUDER) occ_have = false;
   if (resets & RESET_FOVEA) fovea_pending = true;
@@ -394,6 +404,7 @@ bool NeuralRenderer::applyToAll(Set set) {
   for (adanerf_ctx* c : contexts())
     if (set(c) != ADANERF_OK) return err = adanerf_last_error(c), false;
   have_source = false;
+  ip_keys = 0;
   history.reset();
   return true;
 }
@@ -427,11 +438,13 @@ bool NeuralRenderer::render() {
     }
     sample_count++;
     have_source = false;      // the debug view has no depth to warp
+    ip_keys = 0;
     history.reset();          // nor is it a frame --taa may blend with
     d_shown = d_frame;
     return writeImageToFile();
   }
   if (settings.reproject > 1 && have_source && since_render + 1 < settings.reproject) return warp(rot);
+  if (settings.interpolate > 1) return interpolate(rot);
   adanerf_stats st;
   std::memset(&st, 0, sizeof(st));
   if (!peers.empty()) {
@@ -728,11 +741,82 @@ bool NeuralRenderer::warp(const float rot[9]) {
   return writeImageToFile();
 }
 
+// one render at this frame's camera into keyframe slot `into`, its depth_map and acc_map with it
+bool NeuralRenderer::renderKeyframe(int into, adanerf_stats* st, const float rot[9]) {
+  Keyframe& k = ip_key[into];
+  if (adanerf_set_aux_outputs(ctx, static_cast<float*>(k.depth), static_cast<float*>(k.acc)) != ADANERF_OK ||
+      adanerf_render(ctx, k.rgba, static_cast<float*>(k.rgb), st) != ADANERF_OK)
+    return err = adanerf_last_error(ctx), false;
+  std::memcpy(k.pos, camera.getPosition(), sizeof(k.pos));
+  std::memcpy(k.rot, rot, sizeof(k.rot));
+  return true;
+}
+
+// --interpolate K: the frames are shown K calls late.  On the calls with ip_call % K == 0 a keyframe is rendered at the camera of the moment:
+// it becomes B, the one that was B becomes A and is shown.  On the K - 1 calls in between the frame is adanerf_reproject_pair(A, B) at the
+// camera queued K calls earlier (fill on, the weight of adanerf_host_pair_weight).  Until two keyframes exist every call renders and shows
+// its own frame.
+bool NeuralRenderer::interpolate(const float rot[9]) {
+  const int K = settings.interpolate;
+  if (ip_keys == 0) ip_call = 0;
+  if (static_cast<int>(ip_ring.size()) != K) ip_ring.assign(K, Pose());
+  Pose& slot = ip_ring[ip_call % K];
+  const Pose late = slot;      // the camera of K calls ago
+  std::memcpy(slot.pos, camera.getPosition(), sizeof(slot.pos));
+  std::memcpy(slot.rot, rot, sizeof(slot.rot));
+  const bool key = ip_call % K == 0;
+  if (key || ip_keys < 2) {
+    adanerf_stats st;
+    std::memset(&st, 0, sizeof(st));
+    const int into = ip_keys == 0 ? 0 : 1 - ip_newer;      // the older keyframe's slot; before there are two, frames in between borrow it too
+    if (!renderKeyframe(into, &st, rot)) return false;
+    d_shown = ip_key[into].rgba;
+    if (key) {
+      ip_newer = into;
+      ip_keys = std::min(ip_keys + 1, 2);
+      if (ip_keys == 2) d_shown = ip_key[1 - ip_newer].rgba;      // A: the keyframe of K calls ago
+    }
+    s_inference1 += st.ms_sample_mlp;
+    s_inference2 += st.ms_shade_mlp;
+    s_fc2 += st.ms_compact;
+    s_rm += st.ms_composite;
+    s_total += st.ms_total;
+    s_num_total_samples += st.total_samples;
+    s_rendered++;
+  } else {
+    const Keyframe &A = ip_key[1 - ip_newer], &B = ip_key[ip_newer];
+    float weight_b = 0.5f;
+    int32_t holes = 0;
+    if (adanerf_host_pair_weight(late.pos, A.pos, B.pos, &weight_b) != ADANERF_OK ||
+        adanerf_reproject_pair(ctx, static_cast<const float*>(A.rgb), static_cast<const float*>(A.depth), static_cast<const float*>(A.acc), A.pos, A.rot,
+                               static_cast<const float*>(B.rgb), static_cast<const float*>(B.depth), static_cast<const float*>(B.acc), B.pos, B.rot, late.pos,
+                               late.rot, weight_b, 0.5f, 0.05f, 0xFF000000u, ADANERF_REPROJECT_FILL, static_cast<float*>(d_warp_rgb), d_warp, nullptr,
+                               static_cast<uint8_t*>(d_wmask), nullptr, &holes) != ADANERF_OK)
+      return err = adanerf_last_error(ctx), false;
+    int32_t m = 0;
+    if (!settings.rerender.empty()) {
+      // --rerender: the holes (unsourced: the filled pixels too) at the camera of K calls ago; the aux maps belong to the keyframes: off for this call
+      const bool ok = adanerf_set_camera(ctx, late.pos, late.rot) == ADANERF_OK && adanerf_set_aux_outputs(ctx, nullptr, nullptr) == ADANERF_OK &&
+                      adanerf_render_masked(ctx, static_cast<const uint8_t*>(d_wmask), settings.rerender == "holes" ? 1u : 5u, d_warp, nullptr, nullptr, &m) == ADANERF_OK;
+      if (!ok) return err = adanerf_last_error(ctx), false;
+      s_rerendered += m;
+    }
+    if (settings.log_camera) std::printf("interpolated %d holes %d rerendered %d weight %g\n", sample_count, static_cast<int>(holes), static_cast<int>(m), weight_b);
+    s_warped++;
+    s_holes += holes;
+    d_shown = d_warp;
+  }
+  ip_call++;
+  sample_count++;
+  logInterval();
+  return writeImageToFile();
+}
+
 void NeuralRenderer::logInterval() {
   if (sample_count % logging_interval != 0) return;
   // same fields as the reference's log line; fc1 (ray/oracle features) is fused into "Inference 1".  --reproject K > 1: the averages are
   // over the rendered frames of the interval, and the line gains the holes per warped frame
-  const int rendered = settings.reproject > 1 ? std::max(s_rendered, 1) : logging_interval;
+  const int rendered = settings.reproject > 1 || settings.interpolate > 1 ? std::max(s_rendered, 1) : logging_interval;
   std::cout << "Inference 1:" << s_inference1 / rendered << ", 2:" << s_inference2 / rendered << " | fc1: 0"
             << ", fc2: " << s_fc2 / rendered << ", rm: " << s_rm / rendered
             << ", avg samples ppx: " << s_num_total_samples / static_cast<double>(rendered) / settings.total_size
@@ -745,6 +829,7 @@ void NeuralRenderer::logInterval() {
   if (settings.taau_scale > 0)
     std::cout << ", taau rejected: " << s_rejected / static_cast<double>(logging_interval) / settings.total_size / (settings.taau_scale * settings.taau_scale);
   if (settings.reproject > 1) std::cout << ", holes: " << s_holes / static_cast<double>(std::max(s_warped, 1)) << " (" << s_warped << " warped frames)";
+  if (settings.interpolate > 1) std::cout << ", holes: " << s_holes / static_cast<double>(std::max(s_warped, 1)) << " (" << s_warped << " interpolated frames)";
   if (settings.fovea_temporal_alpha > 0.f) std::cout << ", fovea-temporal rejected: " << s_rejected / static_cast<double>(logging_interval) / settings.total_size;
   if (!settings.density_stride.empty()) std::cout << ", rendered fraction: " << s_density_rendered / static_cast<double>(logging_interval) / settings.total_size;
   if (cap_in_force > 0.f)

@@ -97,7 +97,10 @@ class NeuralRenderer {
     return fovea_pending;
   }
   // --taa / --taau: the next frame is shown as rendered and starts a new history (script token "cut"); without them nothing to drop
-  void cutHistory() { history.reset(); }
+  void cutHistory() {      // --interpolate: both keyframes go too, the next frame is the first of a new sequence
+    history.reset();
+    ip_keys = 0;
+  }
   bool applyFrameSize();             // a pending setFrameSize, now: render() calls it; --dry-run calls it in render()'s place (host only)
   int batchesPerFrame() const;       // ceil(rays / batch_rays)
   bool writeImageToFile();           // out.bmp in the model directory (neuralrenderer.cpp:184-222); --write-window: out_window.bmp too
@@ -132,6 +135,25 @@ class NeuralRenderer {
   int since_render = 0;              // warped frames since it
   float src_pos[3] = {0, 0, 0}, src_rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
   bool warp(const float rot[9]);     // this frame = the source frame at the camera of the moment
+  // --interpolate K: two keyframes (uchar4 frame, fp32 colour, depth_map, acc_map, pose) that ping-pong, the ring of the last K cameras and
+  // the interpolated frame (d_warp, d_warp_rgb, d_wmask)
+  struct Keyframe {
+    void* rgba = nullptr;
+    void* rgb = nullptr;
+    void* depth = nullptr;
+    void* acc = nullptr;
+    float pos[3], rot[9];
+  };
+  struct Pose {
+    float pos[3], rot[9];
+  };
+  Keyframe ip_key[2];
+  int ip_keys = 0;                   // keyframes held (0, 1 or 2) of the size and selection in force; dropped with the --reproject source
+  int ip_newer = 0;                  // which of ip_key is B, the keyframe rendered last
+  int ip_call = 0;                   // frames since the first keyframe of this sequence
+  std::vector<Pose> ip_ring;         // the cameras of the last K frames: slot ip_call % K
+  bool renderKeyframe(int into, adanerf_stats* st, const float rot[9]);
+  bool interpolate(const float rot[9]);      // this frame of --interpolate K: a keyframe, or the frame between two at the camera of K frames ago
   void logInterval();                // the per-100-frame line of the single-context path
   long long s_rerendered = 0;        // --rerender: pixels rendered into the warped frames of the running interval
   long long s_holes = 0;             // holes of the warped frames / rendered and warped frames of the running interval

@@ -38,6 +38,9 @@ const char* Settings::usage() {
          "                                    tolerance of its consistency test (default 0.05)\n"
          "               [--rerender holes|unsourced]     with --reproject K: render the warped frames' holes (unsourced: the pixels filled from a\n"
          "                                    neighbour, or gathered but unverified, too) at their own camera instead of leaving them\n"
+         "               [--interpolate K]    show the same frames K frames late: of every K frames render the first as a keyframe and make the\n"
+         "                                    K - 1 before it from the keyframe behind and the keyframe ahead (adanerf_reproject_pair, K >= 2);\n"
+         "                                    --rerender applies to those frames\n"
          "               [--supersample S]    every shown frame is S x S renders (S in 1..8) at the offsets of a regular sub-pixel grid, summed and\n"
          "                                    averaged on the device (anti-aliasing in time); -w / --write-window write the resolved image\n"
          "               [--supersample-contrast T]   with --supersample S >= 2: one render at the pixel centres, then the S x S renders only for\n"
@@ -257,6 +260,15 @@ bool Settings::init(int argc, char** argv, std::string* err) {
         return false;
       }
       reproject = static_cast<int>(k);
+    } else if (a == "--interpolate") {
+      if (!need(i, 1)) return false;
+      char* end = nullptr;
+      const long k = std::strtol(argv[++i], &end, 10);
+      if (end == argv[i] || *end != 0 || k < 2 || k > 1000000) {
+        *err = "--interpolate K: K must be an integer >= 2";
+        return false;
+      }
+      interpolate = static_cast<int>(k);
     } else if (a == "--reproject-warp") {
       if (!need(i, 1)) return false;
       const std::string v = argv[++i];
@@ -397,7 +409,22 @@ bool Settings::init(int argc, char** argv, std::string* err) {
     *err = "window size must be positive";
     return false;
   }
-  if (!rerender.empty() && reproject <= 1) {
+  if (interpolate > 1) {      // two keyframes of one context, rendered plainly and shown K frames late
+    const char* why = reproject > 1 ? "--interpolate makes the frames between two keyframes; not with --reproject, which warps the last one"
+                      : taa_alpha > 0.f ? "--interpolate shows keyframes as rendered; not with --taa"
+                      : taau_scale > 0 ? "--interpolate shows keyframes as rendered; not with --taau"
+                      : supersample > 1 ? "--interpolate: the mean of jittered frames has no depth map to warp by; not with --supersample"
+                      : !density_stride.empty() ? "--interpolate: the lattice is not coupled to the other stages; not with --fovea-density"
+                      : !occluders.empty() ? "--interpolate: the reprojection stages take no depth limit; not with --occluder"
+                      : gpus > 1 ? "--interpolate warps whole frames of one context; use it with --gpus 1"
+                      : render_oracle ? "--interpolate warps rendered frames; not with --oracle"
+                                      : nullptr;
+    if (why) {
+      *err = why;
+      return false;
+    }
+  }
+  if (!rerender.empty() && reproject <= 1 && interpolate <= 1) {
     *err = "--rerender re-renders the holes of warped frames; only with --reproject K, K > 1";
     return false;
   }

@@ -59,6 +59,8 @@ class Settings {
                                 // of its own) are rendered at the frame's camera (adanerf_render_masked); empty: they stay filled from neighbours
   int reproject = 1;            // --reproject K: of every K frames the first is rendered, the next K - 1 are that frame warped to their own camera
                                 // (adanerf_reproject, fill on); 1: every frame is rendered
+  int interpolate = 0;          // --interpolate K (K >= 2): frames are shown K calls late; of every K the first is rendered as a keyframe, the K - 1 before
+                                // it come from the keyframe behind and the keyframe ahead (adanerf_reproject_pair, fill on); 0: off
   bool reproject_warp_set = false;      // --reproject-warp / --reproject-iterations / --reproject-tol was given (an error without --reproject K > 1)
   bool reproject_gather = false;        // --reproject-warp gather: the warped frames come from adanerf_reproject_gather; splat (the default): adanerf_reproject
   int reproject_iterations = 4;         // --reproject-iterations N (1..8) and --reproject-tol T (>= 0): the gather's two dials

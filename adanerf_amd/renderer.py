@@ -80,7 +80,7 @@ class CapReport(C.Structure):
 
 
 EXPORTS = ["adanerf_create", "adanerf_destroy", "adanerf_get_info", "adanerf_last_error", "adanerf_abi_version", "adanerf_struct_sizes", "adanerf_set_camera", "adanerf_set_selection", "adanerf_set_frame_size", "adanerf_present", "adanerf_reproject",
-           "adanerf_reproject_gather",
+           "adanerf_reproject_gather", "adanerf_reproject_pair", "adanerf_host_pair_weight",
            "adanerf_set_budget_map", "adanerf_foveate", "adanerf_compact_budget",
            "adanerf_render", "adanerf_set_aux_outputs", "adanerf_set_disp_output", "adanerf_assemble_strips", "adanerf_sync", "adanerf_set_stream", "adanerf_set_profiling",
            "adanerf_collect_stats", "adanerf_ray_features", "adanerf_sample_mlp",
@@ -152,6 +152,9 @@ def load_library(path: Optional[str] = None):
     fp = C.POINTER(C.c_float)
     lib.adanerf_reproject.argtypes = [vp, vp, vp, vp, fp, fp, fp, fp, C.c_float, C.c_uint32, i32, vp, vp, vp, C.POINTER(i32)]
     lib.adanerf_reproject_gather.argtypes = [vp, vp, vp, vp, fp, fp, fp, fp, C.c_float, C.c_float, i32, C.c_uint32, i32, vp, vp, vp, vp, C.POINTER(i32)]
+    lib.adanerf_reproject_pair.argtypes = [vp, vp, vp, vp, fp, fp, vp, vp, vp, fp, fp, fp, fp, C.c_float, C.c_float, C.c_float, C.c_uint32, i32,
+                                           vp, vp, vp, vp, vp, C.POINTER(i32)]
+    lib.adanerf_host_pair_weight.argtypes = [fp, fp, fp, fp]
     lib.adanerf_temporal_resolve.argtypes = [vp, vp, vp, vp, fp, fp, vp, vp, vp, fp, fp, C.c_float, C.c_float, C.c_float, i32, vp, vp, vp, vp, vp,
                                              C.POINTER(i32)]
     lib.adanerf_temporal_upsample.argtypes = [vp, i32, vp, vp, vp, C.c_float, C.c_float, fp, fp, vp, vp, vp, fp, fp, C.c_float, C.c_float, C.c_float, i32,
@@ -363,6 +366,17 @@ class _History:
 
 
 FOVEA_MAX_RINGS = 8
+
+
+def pair_weight(dst_pos, a_pos, b_pos) -> float:
+    """The weight_b of adanerf_reproject_pair for a destination between the keyframes at a_pos and b_pos (adanerf_host_pair_weight): its
+    distance from A over the sum of its distances from A and B, 0.5 where both are 0 (a pure rotation).  No device needed.  ValueError on
+    a position that is not finite."""
+    fp = _pose_ptrs(dst_pos, None, a_pos, None, b_pos, None)
+    out = C.c_float(0)
+    if load_library().adanerf_host_pair_weight(fp[0], fp[2], fp[4], C.byref(out)) != 0:
+        raise ValueError("adanerf_host_pair_weight(%r, %r, %r) refused: every value must be finite" % (dst_pos, a_pos, b_pos))
+    return float(out.value)
 
 
 def subpixel_grid(s: int):
@@ -597,6 +611,8 @@ class NeuralRenderer:
         self._pose = None             # (pos [3], rot [9]) of the last set_camera
         self._rp_on = False           # enable_reprojection(): render_numpy keeps depth, acc and the pose of its frame
         self._rp_frame = None         # (device rgba8, depth, acc, pos, rot, rays) of the last render_numpy since then
+        self._ip_on = False           # enable_interpolation(): render_keyframe keeps two frames for interpolate()
+        self._ip_keys = []            # [(set 0 / 1, pos, rot)] of the keyframes kept, the older first
         self._ta = None               # enable_temporal(): alpha, depth_tol, clamp, the cycle of sub-pixel offsets and the place in it
         self._ta_history = _History(self, [("mask", 1, np.uint8)])      # render_temporal's history and verdict mask
         self._tu = None               # enable_temporal_upsample(): scale, alpha, depth_tol, clamp, the offset cycle and the place in it
@@ -606,7 +622,8 @@ class NeuralRenderer:
         self._ft_history = _History(self, [("mask", 1, np.uint8), ("rgba", 4, np.uint8), ("dmask", 1, np.uint8)])
         # device buffers of the renderer's own, made on first use by _buffers() and dropped by _drop_buffers(): render_numpy's outputs, the
         # budget maps, the aux outputs and warp images of reproject(), the density mask, the depth limit, the sums and masks of the supersamplers
-        for name in ("_o_rgb", "_o_rgba", "_b_n", "_b_thr", "_rp_depth", "_rp_acc", "_rp_rgba", "_rp_mask", "_rp_rgb", "_rp_wrgb", "_fd_mask", "_dl_buf",
+        for name in ("_o_rgb", "_o_rgba", "_b_n", "_b_thr", "_rp_depth", "_rp_acc", "_rp_rgba", "_rp_mask", "_rp_rgb", "_rp_wrgb", "_ip_rgb0", "_ip_depth0", "_ip_acc0", "_ip_rgb1", "_ip_depth1", "_ip_acc1", "_ip_wrgb", "_ip_rgba", "_ip_mask",
+                     "_ip_source", "_fd_mask", "_dl_buf",
                      "_hy_acc", "_hy_behind", "_hy_limit", "_ss_sum", "_sa_stage", "_sa_mask"):
             setattr(self, name, None)
         self._dl_in_force = None      # what the last set_depth_limit installed; render_hybrid puts it back
@@ -713,6 +730,7 @@ class NeuralRenderer:
         if self._b_n is not None and self._b_n.shape[0] != self.info.rays_local:      # the library dropped the maps with the old rays_local
             self._drop_buffers("_b_n", "_b_thr")
         self._rp_frame = None      # a frame of the old size cannot be warped with the new size's ray generator
+        self._ip_keys = []         # nor can keyframes of the old size
         for history in (self._ta_history, self._tu_history, self._ft_history):      # nor can a history of the old size be gathered from
             history.reset()
         self._fd = None            # the density mask is per frame size: foveate_density() fills it again
@@ -1256,6 +1274,97 @@ class NeuralRenderer:
         finally:
             self.set_aux_outputs(self._rp_depth, self._rp_acc)
         return self._rp_rgba.numpy(), mask, holes, rerendered
+
+    # -- two keyframes warped to a pose between them (adanerf_reproject_pair) ----------------------------------
+    def reproject_pair_device(self, a_rgb, a_depth, a_acc, a_pos, a_rot, b_rgb, b_depth, b_acc, b_pos, b_rot, dst_pos, dst_rot, dst_rgb, dst_rgba8=None,
+                              dst_depth=None, dst_mask=None, dst_source=None, weight_b: float = 0.5, acc_min: float = 0.5, depth_tol: float = 0.05,
+                              hole_rgba8: int = 0xFF000000, fill: bool = True, holes: bool = True) -> Optional[int]:
+        """adanerf_reproject_pair on device images of the context's frame size: the frames (fp32 rgb, depth_map, acc_map) rendered at
+        (a_pos, a_rot) and (b_pos, b_rot) warped to (dst_pos, dst_rot) into dst_rgb (fp32) and, if given, dst_rgba8 (uchar4) / dst_depth
+        (fp32) / dst_mask (uint8: 1 a source pixel, 2 filled from a neighbour, 0 hole) / dst_source (uint8: 1 A, 2 B, 3 both blended,
+        0 none).  Returns the number of holes (synchronous); with holes=False nothing is read back and the outputs are complete after
+        sync()."""
+        fp = _pose_ptrs(a_pos, a_rot, b_pos, b_rot, dst_pos, dst_rot)
+        n = C.c_int32(0)
+        self._check(self.lib.adanerf_reproject_pair(self.handle, _ptr(a_rgb), _ptr(a_depth), _ptr(a_acc), fp[0], fp[1], _ptr(b_rgb), _ptr(b_depth),
+                                                    _ptr(b_acc), fp[2], fp[3], fp[4], fp[5], float(weight_b), float(acc_min), float(depth_tol),
+                                                    int(hole_rgba8) & 0xFFFFFFFF, REPROJECT_FILL if fill else 0, _ptr(dst_rgb), _ptr(dst_rgba8),
+                                                    _ptr(dst_depth), _ptr(dst_mask), _ptr(dst_source), C.byref(n) if holes else None))
+        return int(n.value) if holes else None
+
+    def _interpolation_buffers(self):
+        """the two source sets (fp32 colour, depth_map, acc_map) and the interpolated images, made on first use and again after a frame
+        size that changes rays_local"""
+        n = self.info.rays_local
+        if self._buffers(("_ip_rgb0", (n, 3), np.float32), ("_ip_depth0", (n,), np.float32), ("_ip_acc0", (n,), np.float32),
+                         ("_ip_rgb1", (n, 3), np.float32), ("_ip_depth1", (n,), np.float32), ("_ip_acc1", (n,), np.float32),
+                         ("_ip_wrgb", (n, 3), np.float32), ("_ip_rgba", (n, 4), np.uint8), ("_ip_mask", (n,), np.uint8), ("_ip_source", (n,), np.uint8)):
+            self._ip_keys = []
+
+    def _ip_set(self, k: int):
+        return (self._ip_rgb0, self._ip_depth0, self._ip_acc0) if k == 0 else (self._ip_rgb1, self._ip_depth1, self._ip_acc1)
+
+    def enable_interpolation(self):
+        """From now on render_keyframe() keeps the last two frames it rendered on the device -- fp32 colour, depth_map, acc_map and pose,
+        in two sets that ping-pong -- and interpolate() warps both to a pose between them (adanerf_reproject_pair).  Whole frames of
+        models without useNDC only.  The aux outputs point at the set being written during render_keyframe() and at what was in force
+        before it afterwards."""
+        if self.info.use_ndc or self.info.rays_local != self.info.width * self.info.height:
+            raise AdaNeRFError("interpolation needs a whole frame of a model without useNDC")
+        self._ip_on = True
+        self._interpolation_buffers()
+
+    def render_keyframe(self):
+        """One render at the camera in force into the older of the two source sets (after enable_interpolation): it becomes the newer
+        keyframe B, the one that was B becomes A.  Returns what render_numpy returns."""
+        if not self._ip_on:
+            raise AdaNeRFError("render_keyframe: call enable_interpolation() first")
+        if self._pose is None:
+            raise AdaNeRFError("interpolation needs the pose of the frame: call set_camera before render_keyframe")
+        self._interpolation_buffers()
+        self._out_buffers()
+        k = 1 - self._ip_keys[-1][0] if self._ip_keys else 0
+        rgb, depth, acc = self._ip_set(k)
+        was = self._aux_in_force
+        self.set_aux_outputs(depth, acc)
+        try:
+            st = self.render(self._o_rgba, rgb, stats=True)
+        finally:
+            self.set_aux_outputs(*was)
+        self._ip_keys = self._ip_keys[-1:] + [(k, self._pose[0], self._pose[1])]
+        return rgb.numpy(), self._o_rgba.numpy(), st
+
+    def interpolate(self, dst_pos, dst_rot, weight_b: Optional[float] = None, fill: bool = True, acc_min: float = 0.5, depth_tol: float = 0.05):
+        """The last two render_keyframe frames, A the older and B the newer, warped to the pose (dst_pos, dst_rot) between them: returns
+        (rgb [R,3] float32, rgba8 [R,4] uint8, mask [R] uint8, source [R] uint8, holes).  ``weight_b``: the share of B where both see
+        the same surface; None: pair_weight(dst_pos, A's position, B's).  Holes come out opaque black.  The camera in force does not
+        change."""
+        if len(self._ip_keys) < 2 or self._ip_mask is None or self._ip_mask.shape[0] != self.info.rays_local:
+            raise AdaNeRFError("interpolate: needs two keyframes -- enable_interpolation(), then set_camera and render_keyframe twice")
+        (ka, a_pos, a_rot), (kb, b_pos, b_rot) = self._ip_keys
+        if weight_b is None:
+            weight_b = pair_weight(dst_pos, a_pos, b_pos)
+        holes = self.reproject_pair_device(*self._ip_set(ka), a_pos, a_rot, *self._ip_set(kb), b_pos, b_rot, dst_pos, dst_rot, self._ip_wrgb, self._ip_rgba,
+                                           None, self._ip_mask, self._ip_source, weight_b=weight_b, acc_min=acc_min, depth_tol=depth_tol, fill=fill)
+        return self._ip_wrgb.numpy(), self._ip_rgba.numpy(), self._ip_mask.numpy(), self._ip_source.numpy(), holes
+
+    def interpolate_rerender(self, dst_pos, dst_rot, rerender: str = "holes", weight_b: Optional[float] = None, fill: bool = True, acc_min: float = 0.5,
+                             depth_tol: float = 0.05):
+        """interpolate(), then the pixels neither keyframe could source rendered at the destination pose into both colour images, as
+        reproject_rerender does for the one-source warp: ``rerender="holes"`` the mask-0 pixels, ``"unsourced"`` the neighbour-filled
+        ones (mask 2) as well.  The camera moves to (dst_pos, dst_rot) and stays there; the keyframes are untouched (the aux outputs are
+        off for the masked call).  Returns (rgb, rgba8, mask, source, holes, rerendered)."""
+        if rerender not in ("holes", "unsourced"):
+            raise AdaNeRFError("interpolate_rerender: rerender must be 'holes' or 'unsourced'")
+        _, _, mask, source, holes = self.interpolate(dst_pos, dst_rot, weight_b=weight_b, fill=fill, acc_min=acc_min, depth_tol=depth_tol)
+        self.set_camera(dst_pos, dst_rot)
+        was = self._aux_in_force
+        self.set_aux_outputs(None, None)
+        try:
+            rerendered, _ = self.render_masked(self._ip_mask, RERENDER_VALUES[rerender], rgba8=self._ip_rgba, rgb=self._ip_wrgb)
+        finally:
+            self.set_aux_outputs(*was)
+        return self._ip_wrgb.numpy(), self._ip_rgba.numpy(), mask, source, holes, rerendered
 
     # -- temporal anti-aliasing: one jittered render per frame, resolved against a history ------------------
     def temporal_resolve_device(self, cur_rgb, cur_depth, cur_acc, cur_pos, cur_rot, hist_rgb, hist_depth, hist_count, prev_pos, prev_rot,

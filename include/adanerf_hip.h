@@ -20,6 +20,7 @@
  *   adanerf_reproject                    none: the viewer presents the frame it rendered (src/neuralrenderer.cpp:146-182 ->
  *                                        src/interoprenderbuffer.cpp:87); this stage sits in front of that step
  *   adanerf_reproject_gather             none, as adanerf_reproject: the same warp as a gather, without cracks
+ *   adanerf_reproject_pair               none, as adanerf_reproject: two rendered frames warped to a pose between them
  *   adanerf_temporal_resolve             none: the viewer shows each frame as rendered, without a history (src/neuralrenderer.cpp:146-182 ->
  *                                        src/interoprenderbuffer.cpp:87); temporal anti-aliasing between the render and that step
  *   adanerf_temporal_upsample            none: the viewer blits the frame it rendered (src/interoprenderbuffer.cpp:87), at whatever size it
@@ -1053,6 +1054,59 @@ int adanerf_reproject_gather(adanerf_ctx* ctx, const float* d_src_rgb, const flo
                              float acc_min, float depth_tol, int32_t iterations, uint32_t hole_rgba8, int32_t flags, float* d_dst_rgb,
                              void* d_dst_rgba8, float* d_dst_depth, uint8_t* d_dst_mask, int32_t* holes_out);
 
+/* Two-source reprojection (bidirectional frame interpolation): two rendered frames A and B warped to a pose between them.  A disocclusion
+ * is a region ONE source frame never saw, so no single-source warp can fill it with real data; a frame behind and a frame ahead uncover
+ * each other's.  For a host that has the frame after the in-between pose already: one that replays a script, evaluates a pose list, or
+ * shows its frames K calls late.  Inputs are what two adanerf_render calls of this context wrote.
+ *   d_a_rgb / d_b_rgb [height*width,3] fp32 (d_rgb_f32_out), d_*_depth_map / d_*_acc_map [height*width] fp32 (adanerf_set_aux_outputs);
+ *                           a_pos / a_rot_c2w, b_pos / b_rot_c2w: the pose of each render.  A and B may be the same buffers
+ *   dst_pos / dst_rot_c2w   the pose to warp to (conventions of adanerf_set_camera; the camera in force is neither read nor changed)
+ *   weight_b                in [0, 1]: the share of B where both sources see the same surface (adanerf_host_pair_weight)
+ *   acc_min, hole_rgba8     as adanerf_reproject's; depth_tol >= 0: relative tolerance of the agreement test
+ *   flags                   0 or ADANERF_REPROJECT_FILL
+ *   d_dst_rgb [height*width,3] fp32; d_dst_rgba8 [height*width] uchar4, d_dst_depth [height*width] fp32, d_dst_mask and d_dst_source
+ *                           [height*width] uint8: each of the four may be NULL
+ *   holes_out               as adanerf_reproject's: the number of pixels with mask 0; non-NULL makes the call synchronous
+ * All images have the context's CURRENT frame size and are indexed as adanerf_render's output is; fp32 and uchar4 images are 4-byte aligned;
+ * no output may overlap a source image or another output.
+ * Definition (every operation a single rounded fp32 operation in this order; the same inputs give the same bits on every call):
+ *   splat, per source s in {A, B}: adanerf_reproject's splat verbatim on that source's maps and pose (the far test, the direction-only
+ *               far pixels, v, zc, u, vv, the key bits(zc) << 32 | i under a 64-bit integer minimum), each source into its own z-buffer
+ *               Z_s, bit for bit what adanerf_reproject builds for that source.
+ *   resolve, destination pixel j: k_s = Z_s[j], z_s the float in its high word (+inf for a far winner), i_s its low word.
+ *     both have a winner   they agree iff both are far, or both are near and |zA - zB| <= depth_tol * min(zA, zB) (a subtraction, fabs,
+ *               fmin, a multiplication, a comparison).  Agreement: per channel c = cA + weight_b * (cB - cA) (a subtraction, a
+ *               multiplication, an addition) with c_s the colour of source pixel i_s; depth the same expression on zA, zB, +inf when both
+ *               are far; mask 1, source 3.  Disagreement (one far and one near winner too): the source with the smaller high word wins --
+ *               in a static scene the nearer surface occludes the other in the destination view -- its colour and depth, mask 1, source 1
+ *               (A) or 2 (B).
+ *     one has a winner     that source's colour and depth, mask 1, source 1 or 2.
+ *     neither, with ADANERF_REPROJECT_FILL   the candidates are the winners in the 8 neighbours of j in both z-buffers, up to 16 keys,
+ *               never filled results; the LARGEST key (the farthest surface, as in adanerf_reproject) gives colour and depth; B's largest is
+ *               taken iff it is larger than A's largest, so A wins on equal keys; mask 2, source 1 or 2.
+ *     otherwise            fp32 (0, 0, 0), hole_rgba8, depth 0, mask 0, source 0.
+ *   d_dst_rgba8 of a mask 1 / 2 pixel follows adanerf_resolve_mean's byte contract.
+ * The mask bytes mean exactly what adanerf_reproject's mean (0 hole, 1 own source pixel, 2 neighbour-filled), so
+ * adanerf_render_masked(d_dst_mask, 1 or 5, ..) works on the result unchanged; provenance is in d_dst_source for that reason.
+ * What it does not do: the scene is static (a moving object is warped as if it stood still); view-dependent colour is a blend of the two
+ * source poses'; a host that uses it lags K frames or knows its path in advance; a splat covers one pixel, as adanerf_reproject's; no
+ * useNDC models, no shards.  Against the one-source warp on a trained network's depth (profiles/reproject_pair_measured.md: two renders a
+ * tenth of the view cell apart, the two poses between them, 800 x 800): 0.5 % holes against 5.2 / 9.8 %, 25.3 / 25.5 dB against 20.3 / 19.6 dB
+ * as shown, 26.0 / 26.1 against 21.7 / 22.1 dB with the holes re-rendered; one pair call takes 0.6 of the time of two adanerf_reproject calls.
+ * Unlike the gather, it helps on that depth: its data is a second real frame, not a better search of the first.
+ * Runs on the context's stream in three launches (one clear over both z-buffers and the hole count, one splat of both sources side by
+ * side, one resolve); the second z-buffer lives in the context-owned scratch that holds adanerf_reproject's, grown on demand (the stream
+ * is synchronised only then), never shrunk, freed by adanerf_destroy; adanerf_render never allocates it.
+ * ADANERF_EINVAL, with nothing written: a NULL source image, pose or d_dst_rgb; a pose entry that is not finite; weight_b NaN or outside
+ * [0, 1]; acc_min or depth_tol NaN or negative; an unknown flag; a misaligned fp32 or uchar4 pointer; an output overlapping a source image
+ * or another output.
+ * ADANERF_EUNSUPPORTED, with nothing written: a useNDC model (its depth_map is NDC depth); a context with shard_world != 1. */
+int adanerf_reproject_pair(adanerf_ctx* ctx, const float* d_a_rgb, const float* d_a_depth_map, const float* d_a_acc_map, const float a_pos[3],
+                           const float a_rot_c2w[9], const float* d_b_rgb, const float* d_b_depth_map, const float* d_b_acc_map,
+                           const float b_pos[3], const float b_rot_c2w[9], const float dst_pos[3], const float dst_rot_c2w[9], float weight_b,
+                           float acc_min, float depth_tol, uint32_t hole_rgba8, int32_t flags, float* d_dst_rgb, void* d_dst_rgba8,
+                           float* d_dst_depth, uint8_t* d_dst_mask, uint8_t* d_dst_source, int32_t* holes_out);
+
 /* adanerf_temporal_resolve flags */
 enum { ADANERF_TEMPORAL_CLAMP = 1 }; /* the history colour is clamped to the min / max of the current colour over the pixel's 3 x 3 neighbourhood */
 
@@ -1326,6 +1380,13 @@ int adanerf_host_density_phase(int32_t k, int32_t* phase_x, int32_t* phase_y);
  * byte what the device writes.  rgb [height*width,3] fp32 and mask [height*width] uint8 in host memory; n_flagged may be NULL.
  * ADANERF_EINVAL, with nothing written: everything adanerf_contrast_mask refuses. */
 int adanerf_host_contrast_mask(const float* rgb, int32_t width, int32_t height, float threshold, uint8_t* mask, int32_t* n_flagged);
+
+/* The weight_b of adanerf_reproject_pair both hosts use, so that they blend alike: the destination's distance from A over the sum of its
+ * distances from A and from B.  In float64 from the fp32 positions, each step one rounded operation: e_i = dst_i - a_i,
+ * dA = sqrt((e_0 e_0 + e_1 e_1) + e_2 e_2), dB alike from b; *weight_b = (float)(dA / (dA + dB)), and 0.5 when dA + dB == 0 (a pure
+ * rotation weighs both frames alike).  dst == a gives 0, dst == b gives 1.
+ * ADANERF_EINVAL, with nothing written: a NULL pointer; a position entry that is not finite. */
+int adanerf_host_pair_weight(const float dst_pos[3], const float a_pos[3], const float b_pos[3], float* weight_b);
 
 #ifdef __cplusplus
 }
